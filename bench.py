@@ -238,8 +238,9 @@ class Env:
             shutil.rmtree(self.ref_dir, ignore_errors=True)
 
 
-def run_workload(E, name, wl, args):
-    """Times K steps of one workload; returns its result block (rank 0) incl. roofline, cpu_baseline, parity_check."""
+def run_workload(E, name, wl, args, leg=None):
+    """Times K steps of one workload; returns its result block (rank 0) incl. roofline, cpu_baseline, parity_check.  `leg` names
+    the leg in the files of --dump-outputs."""
     from ma_amd.shard import reduce_timing_and_counts, shard_range, weak_shard_first_index
     torch, ma_amd, L, dev, dist = E.torch, E.ma, E.L, E.dev, E.dist
     rank, world = E.rank, E.world
@@ -468,8 +469,15 @@ def run_workload(E, name, wl, args):
     # cpu_baseline_and_parity covers; this ties the overlapped / host-to-host records to it byte for byte (a race between
     # concurrent batches -- shared DP scratch, result arrays re-allocated mid-run -- would show here).
     xleg = None
-    if (NB > 1 or host_io) and n_reads > 0 and not os.environ.get("MA_BENCH_NO_XLEG") and not h2h_only:
-        xleg = cross_leg_parity(batches, hout, acc, host_io, hs, B, K, codes, offs, offs_h)
+    want_xleg = (NB > 1 or host_io) and n_reads > 0 and not os.environ.get("MA_BENCH_NO_XLEG") and not h2h_only
+    want_dump = bool(args.dump_outputs) and rank == 0 and n_reads > 0 and not h2h_only
+    last = last_step_results(batches, hout, acc, host_io, hs, B) if want_xleg or want_dump else []
+    if want_dump:
+        k, kr, off, al, ops, _, _ = max(last, key=lambda g: g[0])  # step K - 1, whichever batch object ran it
+        leg = leg or ("host_to_host" if host_io else ("overlapped" if NB > 1 else "single_stream"))
+        dump_outputs(args.dump_outputs, "%s.%s" % (name, leg), off, al, ops, B, args.dump_budget)
+    if want_xleg:
+        xleg = cross_leg_parity(batches, last, B, codes, offs, offs_h)
     kms = sum(a["kms"] for a in acc)
     walls = [w for a in acc for w in a["wall"]]
     ctr = sum(a["ctr"] for a in acc)
@@ -600,10 +608,10 @@ def run_workload(E, name, wl, args):
     return res
 
 
-def cross_leg_parity(batches, hout, acc, host_io, hs, B, K, codes, offs, offs_h):
-    """The MappingQuality records (offsets, every header byte, every op) of the LAST step each batch object ran inside the timed
-    region -- with the other batches in flight beside it, host to host or device resident -- against the same reads aligned
-    again with nothing else running (device resident, on batch object 0)."""
+def last_step_results(batches, hout, acc, host_io, hs, B):
+    """The MappingQuality records (offsets, alignment headers, ops) of the LAST step each batch object ran inside the timed region,
+    as the caller of the leg receives them: from the page-locked result arrays (host to host) or downloaded from the batch object
+    (device resident).  Read before anything else runs on the batch objects."""
     got = []
     for i, (bt, _) in enumerate(batches):
         k = acc[i]["last"]
@@ -625,6 +633,12 @@ def cross_leg_parity(batches, hout, acc, host_io, hs, B, K, codes, offs, offs_h)
             ops = ops[:2 * nops]
             k_reads = k
         got.append((k, k_reads, off, al, ops, na, nops))
+    return got
+
+
+def cross_leg_parity(batches, got, B, codes, offs, offs_h):
+    """The last step of every batch object (last_step_results) -- run with the other batches in flight beside it, host to host or
+    device resident -- against the same reads aligned again with nothing else running (device resident, on batch object 0)."""
     bad_steps, n_al, n_ops = 0, 0, 0
     bt0 = batches[0][0]
     for k, kr, off, al, ops, na, nops in got:
@@ -641,6 +655,41 @@ def cross_leg_parity(batches, hout, acc, host_io, hs, B, K, codes, offs, offs_h)
     return {"steps_compared": len(got), "reads": len(got) * B, "alignments": n_al, "ops": n_ops, "mismatching_steps": bad_steps,
             "what": "the last step of every batch in flight vs the same reads aligned alone (single stream, device resident): MappingQuality "
                     "records byte for byte"}
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: every file of one run together
+DUMP_FIELDS = ("begin_ref", "end_ref", "begin_q", "end_q", "score", "soc_index", "n_ops", "secondary", "supplementary", "mapq")
+
+
+def dump_outputs(dirpath, tag, off, al, ops, B, budget):
+    """--dump-outputs: the MappingQuality records of one leg's last timed step, as its caller receives them, for a fixed sample of
+    the step's reads: reads in the order of a seeded permutation of 0 .. B - 1 while their records fit `budget` bytes, then
+    sorted.  Writes float64 arrays <tag>.<x>.npy: `read` (index in the step), `n_alignments` (per sampled read), one array per
+    alignment field (DUMP_FIELDS, the alignments of the sampled reads in read order) and `ops` (their ops, n x 2, in the same
+    order; an alignment's `n_ops` rows).  Returns the bytes written."""
+    off = np.asarray(off[:B + 1], dtype=np.int64)
+    na = off[1:] - off[:-1]
+    ops_end = np.zeros(int(off[B]) + 1, dtype=np.int64)
+    ops_end[1:] = np.cumsum(al["n_ops"][:int(off[B])].astype(np.int64))
+    read_ops = ops_end[off[1:]] - ops_end[off[:-1]]
+    files = 3 + len(DUMP_FIELDS)
+    cost = 16 + 8 * len(DUMP_FIELDS) * na + 16 * read_ops  # read + n_alignments, the header fields, the ops of a read
+    order = np.random.default_rng(20240531).permutation(B)
+    room = budget - 128 * files  # an .npy header is 128 bytes for these arrays
+    sel = np.sort(order[:int(np.searchsorted(np.cumsum(cost[order]), room, side="right"))])
+    rows = np.concatenate([np.arange(off[r], off[r + 1]) for r in sel]) if sel.size else np.zeros(0, dtype=np.int64)
+    a = al[rows]
+    op_rows = np.concatenate([np.arange(2 * int(o), 2 * int(o) + 2 * int(n)) for o, n in zip(a["ops_off"], a["n_ops"])]) if rows.size \
+        else np.zeros(0, dtype=np.int64)
+    arrays = {"read": sel, "n_alignments": na[sel], "ops": np.asarray(ops)[op_rows].reshape(-1, 2)}
+    arrays.update({f: a[f] for f in DUMP_FIELDS})
+    os.makedirs(dirpath, exist_ok=True)
+    n = 0
+    for key, v in arrays.items():
+        path = os.path.join(dirpath, "%s.%s.npy" % (tag, key))
+        np.save(path, np.asarray(v, dtype=np.float64))
+        n += os.path.getsize(path)
+    return n
 
 
 def cpu_baseline_and_parity(E, name, wl, args, codes, offs_h, B, n_reads, step, batches, roofline):
@@ -984,7 +1033,7 @@ def run_legs(E, name, wl, args):
     import copy
     a1 = copy.copy(args)
     a1.inflight, a1.host_io = 1, 0
-    r = run_workload(E, name, wl, a1)
+    r = run_workload(E, name, wl, a1, "single_stream")
     nfl = args.overlap if wl["read_len"] <= 1000 else min(args.overlap, args.overlap_long)
     # batches in flight of the host-to-host leg: a workload may ask for its own number (WORKLOADS[..]["h2h_inflight"]: 10 kb reads run
     # best with ONE batch object whose uploads and downloads run beside its own kernels -- a second batch's seeding crawls beside the
@@ -993,12 +1042,11 @@ def run_legs(E, name, wl, args):
     if nfl > 1 and not wl.get("single_only"):
         for key, hio in (("overlapped", 0), ("host_to_host", 1)):
             nfl_leg = nfl_h2h if hio else nfl
-            wl2 = dict(wl)
-            wl2["steps"] = max(wl["steps"], 2 * nfl_leg)  # every batch object gets at least two timed steps
             a2 = copy.copy(args)
             a2.inflight, a2.cpu_sample, a2.host_io = nfl_leg, 0, hio
             try:
-                r2, err = run_workload(E, name, wl2, a2), None
+                # the leg's timed steps are the workload's (--steps): with fewer steps than batches, fewer batches are in flight
+                r2, err = run_workload(E, name, wl, a2, key), None
             except RuntimeError as e:  # e.g. not enough HBM for that many long-read batches
                 r2, err = None, str(e)
                 for bt in E.live:
@@ -1015,8 +1063,8 @@ def run_legs(E, name, wl, args):
                 continue
             rf2 = dict(r2["roofline"])
             rf2["leg"] = ("%d batches in flight, %s: a kernel's launch time includes the share of the chip the other batches' kernels "
-                          "took meanwhile" % (nfl_leg, r2["io"]))
-            r[key] = {"batches_in_flight": nfl_leg, "io": r2["io"], "value": r2["value"], "unit": r2["unit"], "steps": r2["steps"],
+                          "took meanwhile" % (r2["batches_in_flight"], r2["io"]))
+            r[key] = {"batches_in_flight": r2["batches_in_flight"], "io": r2["io"], "value": r2["value"], "unit": r2["unit"], "steps": r2["steps"],
                       "ms_per_step": r2["ms_per_step"], "step_ms_min": r2["step_ms_min"], "step_ms_max": r2["step_ms_max"],
                       "gbases_per_s": r2["gbases_per_s"], "aligned_reads": r2["aligned_reads"],
                       "kernel_ms_per_step_under_overlap": r2["roofline"]["kernel_ms_per_step"], "roofline": rf2,
@@ -1030,8 +1078,10 @@ def run_legs(E, name, wl, args):
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=10,
+                    help="timed steps of every leg of the 150bp workload, or of the one workload --workload / --read-len selects "
+                         "(the other workloads of the default run keep their own counts: WORKLOADS)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps on every batch object before a leg's timed steps")
     ap.add_argument("--workload", default="all", choices=["all", "150bp", "10kb", "50kb", "illumina", "10kb_pacbio", "50kb_nanopore"])
     ap.add_argument("--reads-per-step", type=int, default=0, help="override the workload's reads per step")
     ap.add_argument("--read-len", type=int, default=0, help="custom single workload with --sub/--ins/--dele")
@@ -1051,15 +1101,13 @@ def build_parser():
                     help="run ONE leg only, with this many batches in flight per GPU (own stream + host thread each; profiling runs)")
     ap.add_argument("--host-io", type=int, default=0, help="with --inflight: that leg host to host (1) or device resident (0)")
     ap.add_argument("--detail-file", default="", help="where the per-workload blocks go (default: gpurun_out/bench_detail.json)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after each leg's timed steps, write the records of its last step for a seeded sample of its reads to "
+                         "DIR/<workload>.<leg>.<array>.npy (float64, at most 64 MB in all)")
     return ap
 
 
 def main():
-    # A batch of long reads runs its DP classes on up to four streams beside its I/O stream, and the runtime maps streams onto
-    # GPU_MAX_HW_QUEUES hardware queues (default 4): streams that share a queue run one after the other.  After the 150 bp legs of this
-    # process had created and dropped a dozen streams, the 10 kb batch's main stream and its k_ksw_pk<5> stream landed on ONE queue and
-    # the DP stage took 196 instead of 148 ms (profiles/r06_hw_queues.txt).  Must be set before the first HIP call of the process.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     args = build_parser().parse_args()
     self_launch_or_check(args, sys.argv[1:])
     if os.environ.get("MA_BENCH_DRY_RUN") == "1":
@@ -1084,6 +1132,8 @@ def main():
             if args.reads_per_step > 0 and (wl["read_len"] <= 1000 or args.workload != "all"):
                 wl["reads_per_step"] = args.reads_per_step
             wls.append((name, wl))
+    # --dump-outputs: every leg that can run gets an equal share of the 64 MB (three legs per workload, one with --inflight)
+    args.dump_budget = DUMP_BYTES // (len(wls) * (1 if args.inflight > 0 else 3))
     results = []
     for name, wl in wls:
         if args.inflight > 0:  # one explicit leg (what a rocprofv3 run of a single leg uses)
@@ -1206,7 +1256,6 @@ def compose_line(E, args, results, boundary, anchor):
             E.world, args.scaling, top.get("batches_in_flight", 1)),
         "detail_file": os.path.relpath(dpath, ROOT) if os.path.isabs(dpath) else dpath,
         "kernel_source_hash": kernel_source_hash(),
-        "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
     }
     # The top-level roofline is the SINGLE-STREAM leg's (one batch at a time: a launch's duration is the kernel's own, and
     # avg_launch_ms <= that leg's ms_per_step); under overlap a kernel's launch time includes the share of the chip the other

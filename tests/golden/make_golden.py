@@ -12,7 +12,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-from ma_testlib import (sample_inversion_reads, sample_pairs, rand_genome, sample_reads, write_case, write_ksw_cases, rand_ksw_cases, run_ref, have_ref)  # noqa
+from ma_testlib import (sample_inversion_reads, sample_pairs, rand_genome, sample_reads, write_case, write_ksw_cases, rand_ksw_cases, run_ref, have_ref,  # noqa
+                        direct_parity_case, high_error_50kb_case)
 
 
 def gz(path):
@@ -115,6 +116,34 @@ def f4_goldens():
     gz("f4.case")
 
 
+def gpu_test_goldens():
+    """The reference's pipeline dumps for the GPU tests that compare the GPU path with it directly (no oracle in the loop)."""
+    g, reads = direct_parity_case()
+    write_case("gpu_direct.case", g, reads)
+    for preset in ("default", "illumina", "default+mems"):
+        run_ref("pipe", "gpu_direct.case", preset, 3, "gpu_direct.%s.pipe" % preset)
+        gz("gpu_direct.%s.pipe" % preset)
+    os.remove("gpu_direct.case")
+    g, reads = high_error_50kb_case()
+    write_case("gpu_c50k.case", g, reads)
+    run_ref("pipe", "gpu_c50k.case", "default", 3, "gpu_c50k.default.pipe")
+    gz("gpu_c50k.default.pipe")
+    os.remove("gpu_c50k.case")
+    # C1: ecoli_like (the device generator, restated in numpy) and the 1 000 reads ma_synth_reads_device(seed 11) cut from it,
+    # stored in c1.reads.npz because reads are only synthesised on the device
+    from make_large_index_hashes import synth_genome
+    import numpy as np
+    d = np.load("c1.reads.npz")
+    codes, offs = d["codes"], d["offs"]
+    reads = [codes[offs[i]:offs[i + 1]].copy() for i in range(len(offs) - 1)]
+    reads += [reads[0][:12].copy(), np.full(150, 4, dtype=np.uint8)]  # as test_c1_ecoli_like_vs_compiled_reference
+    write_case("c1.case", [synth_genome(1, 4641652, repeats=False)], reads)
+    for preset in ("default", "illumina"):
+        run_ref("pipe", "c1.case", preset, 1, "c1.%s.pipe" % preset)
+        gz("c1.%s.pipe" % preset)
+    os.remove("c1.case")
+
+
 def main():
     if not have_ref():
         sys.exit("oracle/_ref/ref_dump missing: run `make -C oracle ref` where /root/reference exists")
@@ -142,6 +171,7 @@ def main():
     run_ref("ksw", "ksw.case", "ksw_ref.out")
     ksw_scoring_goldens()
     f4_goldens()
+    gpu_test_goldens()
     for f in ("small_ref.ext", "small_ref.default.pipe", "small_ref.illumina.pipe", "small_ref.default.seed7.pipe",
               "small_ref.mems.pipe", "ksw_ref.out", "small.case", "ksw.case", "small_ref.bwt", "small_ref.sa", "small_ref.pac"):
         gz(f)

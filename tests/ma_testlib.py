@@ -45,6 +45,24 @@ def rand_genome(seed, contig_lens, repeat_unit=0, repeat_copies=0, repeat_div=0.
     return contigs
 
 
+def direct_parity_case():
+    """Genome and reads of test_gpu_parity.test_pipeline_vs_compiled_reference_direct (golden: gpu_direct.<preset>.pipe.gz): large
+    enough for the heuristics (> 10 Mnt doubled), with repeats, N bases and long reads."""
+    g = rand_genome(19, [2700000, 1400000, 1000000], repeat_unit=300, repeat_copies=250, repeat_div=0.08)
+    reads = (sample_reads(g, 2500, 150, 131, sub=0.01) + sample_reads(g, 300, 150, 132, sub=0.06, n_rate=0.01)
+             + sample_reads(g, 20, 5000, 133, sub=0.005, ins=0.003, dele=0.003) + sample_reads(g, 40, 150, 135, random_frac=1.0)
+             + sample_reads(g, 200, 100, 136, sub=0.03) + sample_reads(g, 2, 25000, 134, sub=0.03, ins=0.03, dele=0.04))
+    return g, reads
+
+
+def high_error_50kb_case():
+    """Genome and reads of test_gpu_round2.test_50kb_high_error_reads_vs_compiled_reference (golden: gpu_c50k.default.pipe.gz)."""
+    g = rand_genome(23, [3100000, 1700000, 1200000], repeat_unit=300, repeat_copies=300, repeat_div=0.08)
+    reads = sample_reads(g, 5, 50000, 141, sub=0.03, ins=0.03, dele=0.04) + sample_reads(g, 1, 50000, 142, sub=0.01, ins=0.005,
+                                                                                      dele=0.005)
+    return g, reads
+
+
 def revcomp(a):
     a = np.asarray(a, dtype=np.uint8)
     out = a[::-1].copy()

@@ -37,3 +37,42 @@ def test_world_size_must_equal_the_gpus_flag():
     assert r.returncode != 0 and "refusing" in r.stderr
     r = _run(["--gpus", "1"], WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     assert r.returncode == 0
+
+
+def test_dump_outputs_writes_a_fixed_float_sample_within_its_budget(tmp_path):
+    """--dump-outputs: the same records give the same files, every array is float64, the files fit the budget, and the sampled
+    reads' alignments and ops are the records of those reads."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from ma_amd.api import ALIGNMENT_DT
+    rng = np.random.default_rng(5)
+    B = 5000
+    na = rng.integers(0, 4, B)
+    off = np.zeros(B + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(na)
+    al = np.zeros(int(off[B]), dtype=ALIGNMENT_DT)
+    al["begin_ref"] = rng.integers(0, 6 * 10 ** 9, al.size)
+    al["score"] = rng.integers(-50, 300, al.size)
+    al["n_ops"] = rng.integers(1, 40, al.size)
+    al["mapq"] = rng.random(al.size)
+    al["ops_off"] = np.concatenate([[0], np.cumsum(al["n_ops"][:-1])])
+    ops = rng.integers(0, 200, 2 * int(al["n_ops"].sum()) + 2).astype(np.uint64)
+    budget = 200000
+    n = bench.dump_outputs(str(tmp_path / "a"), "w.leg", off, al, ops, B, budget)
+    assert 0 < n <= budget
+    assert bench.dump_outputs(str(tmp_path / "b"), "w.leg", off, al, ops, B, budget) == n
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and len(names) == 3 + len(bench.DUMP_FIELDS)
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    d = {f[len("w.leg."):-4]: np.load(tmp_path / "a" / f) for f in names}
+    sel = d["read"].astype(np.int64)
+    assert 0 < sel.size < B and np.all(np.diff(sel) > 0)
+    assert np.array_equal(d["n_alignments"], na[sel])
+    rows = np.concatenate([np.arange(off[r], off[r + 1]) for r in sel]).astype(np.int64)
+    for f in bench.DUMP_FIELDS:
+        assert np.array_equal(d[f], al[f][rows].astype(np.float64)), f
+    want = np.concatenate([ops[2 * int(o):2 * int(o + k)] for o, k in zip(al["ops_off"][rows], al["n_ops"][rows])])
+    assert np.array_equal(d["ops"].ravel(), want.astype(np.float64))

@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 
 from ma_testlib import (ROOT, gunzip_to, read_case, read_ksw_cases, parse_pipe_dump, parse_ksw_dump, OrIndex, or_params,
-                        rand_genome, sample_reads, rand_ksw_cases, or_ksw, revcomp, write_case, KSW_EXTZ, KSW_RIGHT, KSW_REV)
+                        rand_genome, sample_reads, rand_ksw_cases, or_ksw, revcomp, write_case, direct_parity_case, KSW_EXTZ, KSW_RIGHT,
+                        KSW_REV)
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(ROOT, "tests", "golden")
@@ -327,23 +328,14 @@ def test_ksw_other_scoring_schemes(gpu_device, scoring):
 
 
 @pytest.mark.parametrize("preset", ["default", "illumina", "default+mems"])
-def test_pipeline_vs_compiled_reference_direct(gpu_device, tmp_path, preset):
-    """No oracle in the loop: when the compiled reference travelled with the repository (oracle/_ref, built from
-    /root/reference by oracle/Makefile.ref), its own modules and the GPU path align the same reads of a genome large enough
+def test_pipeline_vs_compiled_reference_direct(gpu_device, preset):
+    """No oracle in the loop: the compiled reference's own modules (oracle/Makefile.ref; their output on these reads is
+    tests/golden/gpu_direct.<preset>.pipe.gz, make_golden.py) and the GPU path align the same reads of a genome large enough
     for the heuristics (> 10 Mnt doubled), with repeats, N bases, long reads: every stage record must be identical."""
-    import subprocess
     import ma_amd
-    ref_dump = os.path.join(ROOT, "oracle", "_ref", "ref_dump")
-    if not os.path.exists(ref_dump):
-        pytest.skip("oracle/_ref not present on this box")
-    g = rand_genome(19, [2700000, 1400000, 1000000], repeat_unit=300, repeat_copies=250, repeat_div=0.08)
-    reads = (sample_reads(g, 2500, 150, 131, sub=0.01) + sample_reads(g, 300, 150, 132, sub=0.06, n_rate=0.01)
-             + sample_reads(g, 20, 5000, 133, sub=0.005, ins=0.003, dele=0.003) + sample_reads(g, 40, 150, 135, random_frac=1.0)
-             + sample_reads(g, 200, 100, 136, sub=0.03) + sample_reads(g, 2, 25000, 134, sub=0.03, ins=0.03, dele=0.04))
-    case = str(tmp_path / "c.case")
-    write_case(case, g, reads)
-    subprocess.check_call([ref_dump, "pipe", case, preset, "3", str(tmp_path / "ref.pipe")], stdout=subprocess.DEVNULL)
-    want = parse_pipe_dump(str(tmp_path / "ref.pipe"))
+    g, reads = direct_parity_case()
+    want = parse_pipe_dump(os.path.join(G, "gpu_direct.%s.pipe.gz" % preset))
+    assert len(want) == len(reads) and all(w["len"] == len(r) for w, r in zip(want, reads))
     got, counters, counts = gpu_pipeline(ma_amd.Index.build(g), preset, 3, reads)
     compare_reads(got, want)
     assert counts["aligned_reads"] == sum(1 for w in want if w["mq"])

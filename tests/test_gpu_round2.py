@@ -13,29 +13,22 @@ import threading
 import numpy as np
 import pytest
 
-from ma_testlib import ROOT, gunzip_to, parse_pipe_dump, rand_genome, read_case, sample_reads, write_case
+from ma_testlib import ROOT, gunzip_to, high_error_50kb_case, parse_pipe_dump, rand_genome, read_case, sample_reads, write_case
 from test_gpu_parity import compare_reads, gpu_pipeline
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(ROOT, "tests", "golden")
 
 
-def test_50kb_high_error_reads_vs_compiled_reference(gpu_device, tmp_path):
+def test_50kb_high_error_reads_vs_compiled_reference(gpu_device):
     """BASELINE config 5's shape (50 kb reads, 3 / 3 / 4 % substitutions / insertions / deletions): every stage record
-    of the GPU path equals the reference's own modules (oracle/_ref, compiled from /root/reference), Default preset and
-    the nanopore-like settings (SMEM seeding, min 5 SoCs, 100 supplementaries)."""
+    of the GPU path equals the reference's own modules (oracle/Makefile.ref; their output on these reads is
+    tests/golden/gpu_c50k.default.pipe.gz, make_golden.py), Default preset."""
     import ma_amd
-    ref_dump = os.path.join(ROOT, "oracle", "_ref", "ref_dump")
-    if not os.path.exists(ref_dump):
-        pytest.skip("oracle/_ref not present on this box")
-    g = rand_genome(23, [3100000, 1700000, 1200000], repeat_unit=300, repeat_copies=300, repeat_div=0.08)
-    reads = sample_reads(g, 5, 50000, 141, sub=0.03, ins=0.03, dele=0.04) + sample_reads(g, 1, 50000, 142, sub=0.01, ins=0.005,
-                                                                                      dele=0.005)
-    case = str(tmp_path / "c50k.case")
-    write_case(case, g, reads)
+    g, reads = high_error_50kb_case()
+    want = parse_pipe_dump(os.path.join(G, "gpu_c50k.default.pipe.gz"))
+    assert len(want) == len(reads) and all(w["len"] == len(r) for w, r in zip(want, reads))
     idx = ma_amd.Index.build(g)
-    subprocess.check_call([ref_dump, "pipe", case, "default", "3", str(tmp_path / "ref.pipe")], stdout=subprocess.DEVNULL)
-    want = parse_pipe_dump(str(tmp_path / "ref.pipe"))
     got, counters, counts = gpu_pipeline(idx, "default", 3, reads)
     compare_reads(got, want)
     assert counts["aligned_reads"] == sum(1 for w in want if w["mq"])
@@ -314,7 +307,7 @@ def test_bench_two_ranks_partition_one_read_set(gpu_device):
     assert 1.9 * w1["aligned_reads"] < ww["aligned_reads"] < 2.1 * w1["aligned_reads"]
     # every leg of the line: one batch at a time, batches in flight, host to host (reads from / results into page-locked host
     # memory) -- the same reads, so the same number of aligned reads per step
-    for key in ("overlapped", "host_to_host"):  # (these legs run more steps, of other reads of the same kind)
+    for key in ("overlapped", "host_to_host"):
         assert abs(w1[key]["aligned_reads"] / w1[key]["steps"] - w1["aligned_reads"] / w1["steps"]) < 0.01 * 30000, key
         assert ww[key]["value"] > 0
     assert w1["host_to_host"]["aligned_reads"] == w1["overlapped"]["aligned_reads"]  # the same reads through both I/O paths

@@ -195,17 +195,15 @@ def test_index_pinned_at_grch38_scale(gpu_device):
     idx.close()
 
 
-def test_c1_ecoli_like_vs_compiled_reference(gpu_device, tmp_path):
+def test_c1_ecoli_like_vs_compiled_reference(gpu_device):
     """configs[0] (C1) at its stated size: 1 k x 150 bp reads (0.5 % substitutions, seed 11) vs `ecoli_like` (one contig of
     4 641 652 nt, seed 1).  The doubled text (9.28 Mnt) lies just BELOW the 10 Mnt switch, so the drop-all and SoC-score
     heuristics are off (binarySeeding.cpp:172-175, stripOfConsideration.cpp:21-23).  The compiled reference builds ITS OWN index
-    of the contig; every stage record of every read must equal the GPU path's."""
-    import torch
+    of the contig; every stage record of every read must equal the GPU path's.  The reference's output on these reads is
+    tests/golden/c1.<preset>.pipe.gz (make_golden.py), the reads it saw are tests/golden/c1.reads.npz."""
     import ma_amd
+    import torch
     from test_gpu_parity import compare_reads, gpu_pipeline
-    ref_dump = os.path.join(ROOT, "oracle", "_ref", "ref_dump")
-    if not os.path.exists(ref_dump):
-        pytest.skip("oracle/_ref not present on this box")
     L = ma_amd.lib()
     F = 4641652
     g = torch.empty(F, dtype=torch.uint8, device="cuda")
@@ -215,13 +213,12 @@ def test_c1_ecoli_like_vs_compiled_reference(gpu_device, tmp_path):
     codes, offs, nb = _synth_reads(L, idx, 11, 1000, 150, sub=0.005)
     oh = offs.cpu().numpy()
     ch = codes.cpu().numpy()
+    stored = np.load(os.path.join(ROOT, "tests", "golden", "c1.reads.npz"))
+    assert np.array_equal(ch[:nb], stored["codes"]) and np.array_equal(oh[:1001], stored["offs"])  # the reads the reference aligned
     reads = [ch[int(oh[i]):int(oh[i + 1])].copy() for i in range(1000)]
     reads += [reads[0][:12].copy(), np.full(150, 4, dtype=np.uint8)]  # shorter than a seed, all N
-    case = str(tmp_path / "c1.case")
-    write_case(case, [g.cpu().numpy()], reads)
     for preset in ("default", "illumina"):
-        subprocess.check_call([ref_dump, "pipe", case, preset, "1", str(tmp_path / "ref.pipe")], stdout=subprocess.DEVNULL)
-        want = parse_pipe_dump(str(tmp_path / "ref.pipe"))
+        want = parse_pipe_dump(os.path.join(ROOT, "tests", "golden", "c1.%s.pipe.gz" % preset))
         got, counters, counts = gpu_pipeline(idx, preset, 1, reads)
         compare_reads(got, want)
         assert counts["aligned_reads"] == sum(1 for w in want if w["mq"]) >= 990

@@ -190,25 +190,27 @@ def test_bench_cross_leg_parity_and_line_hygiene(gpu_device):
         assert rf["peak"] == 1228.8 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 2e-3 and rf["mix_ceiling"]["peak"] < rf["peak"]
 
 
-def test_eight_ranks_share_one_device_without_starving_the_host(gpu_device):
-    """bench.py with 8 ranks x 3 batches in flight = 24 waiting host threads.  Under the pool's 16-core
+def test_ranks_share_one_device_without_starving_the_host(gpu_device):
+    """bench.py with 4 ranks x 5 batches in flight = 20 waiting host threads.  Under the pool's 16-core
     CFS quota spinning stream waits would throttle the whole process group, so bench.py switches the batches to blocking
-    (event) waits when ranks x batches exceeds the cores the quota grants.  All 8 ranks run on GPU 0 here (MA_BENCH_ONE_DEVICE,
-    gloo); they share one GPU, so the AGGREGATE rate is what must hold: at least 1 / 1.2 of one rank's."""
+    (event) waits when ranks x batches exceeds the cores the quota grants.  All 4 ranks run on GPU 0 here (MA_BENCH_ONE_DEVICE,
+    gloo; with this process and the launcher, at most six processes have the device open); they share one GPU, so the AGGREGATE
+    rate is what must hold: at least 1 / 1.2 of one rank's."""
     from test_gpu_round2 import _bench
+    R, NB = 4, 5
     common = ["--workload", "150bp", "--genome-scale", "0.01", "--steps", "6", "--warmup", "1", "--reads-per-step", "100000",
-              "--cpu-sample", "0", "--boundary-reads", "0"]
+              "--cpu-sample", "0", "--boundary-reads", "0", "--overlap", str(NB)]
     one = _bench(common + ["--gpus", "1"])
-    eight = _bench(common + ["--gpus", "8"], nproc=8, env={"MA_BENCH_ONE_DEVICE": "1"}, self_launch=True)
-    assert eight["n_gpus"] == 8
-    w8 = eight["config"]["workloads"][0]
-    assert w8["host_to_host"]["aligned_reads"] > 0.95 * 8 * 6 * 100000
-    quota = w8["host_cores"]
-    assert w8["host_to_host"]["stream_waits"].startswith("blocking" if 8 * 3 > quota else "spinning"), (quota, w8["host_to_host"]["stream_waits"])
-    print("1 rank: %.0f reads/s host to host; 8 ranks on one device: %.0f reads/s, waits %s, cfs throttled %s" % (
-        one["value"], eight["value"], w8["host_to_host"]["stream_waits"], eight.get("cfs_throttled_150bp")))
-    assert eight["value"] >= one["value"] / 1.2, (one["value"], eight["value"])
-    assert eight["parity_150bp_h2h"].startswith("0 mismatching")
+    many = _bench(common + ["--gpus", str(R)], nproc=R, env={"MA_BENCH_ONE_DEVICE": "1"}, self_launch=True)
+    assert many["n_gpus"] == R
+    wr = many["config"]["workloads"][0]
+    assert wr["host_to_host"]["aligned_reads"] > 0.95 * R * 6 * 100000
+    quota = wr["host_cores"]
+    assert wr["host_to_host"]["stream_waits"].startswith("blocking" if R * NB > quota else "spinning"), (quota, wr["host_to_host"]["stream_waits"])
+    print("1 rank: %.0f reads/s host to host; %d ranks on one device: %.0f reads/s, waits %s, cfs throttled %s" % (
+        one["value"], R, many["value"], wr["host_to_host"]["stream_waits"], many.get("cfs_throttled_150bp")))
+    assert many["value"] >= one["value"] / 1.2, (one["value"], many["value"])
+    assert many["parity_150bp_h2h"].startswith("0 mismatching")
 
 
 def short_extension_cases(n, seed):
