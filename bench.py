@@ -3,8 +3,13 @@
 
 A "step" is one pass of the whole hot path (FMD seeding -> seed extraction -> SoC/harmonization ->
 banded-DP gap fill/extension -> mapping quality) over one batch of synthetic reads that is already
-resident in HBM.  The metric is quoted on "150bp & 10kb" reads, so the default invocation runs, against ONE
-GRCh38-sized synthetic genome (24 contigs, 3.09 Gnt, planted repeat families) and in one process per GPU:
+resident in HBM.
+
+A plain run measures the headline alone: against ONE GRCh38-sized synthetic genome (24 contigs, 3.09 Gnt, planted repeat
+families) it runs only the leg `value` comes from -- C2 below, host to host -- with --warmup untimed and --steps timed steps,
+and prints the line; everything else runs under --full only.  With --dump-outputs it writes, after the timed leg, the files of
+every leg of a --full run: each leg's last timed step aligned once more, one batch at a time (dump_other_legs).  The metric
+is quoted on "150bp & 10kb" reads, so `--full` runs, against the same genome and in one process per GPU:
 
   C2  150 bp Illumina-like reads (0.5 % substitutions), 1 M reads per step            -> `value` (headline, history)
   C3  10 kb CCS-like reads (0.4 / 0.3 / 0.3 % sub / ins / del), 5 steps of 200 k reads = the 1 M reads of configs[2]
@@ -21,10 +26,12 @@ with its own timed region (barrier + synchronize on both sides, MAX over ranks):
                      (offsets, alignment headers, ops) end in page-locked HOST memory, several batches in flight so that
                      the copies of one batch hide behind the kernels of another
 
-The line's top-level value / ms_per_step / roofline are those of the HOST-TO-HOST leg of C2 (config.value_is says so);
-value_150bp_device_resident, value_10kb, value_50kb, value_150bp_illumina ... are top-level scalars of the same line; the
-full per-workload blocks (and the boundary leg) go to a side file (config.detail_file) and to stderr, so that the printed
-line stays short.  --workload {150bp,10kb,50kb,illumina} or an explicit --read-len runs a single workload.
+The line's top-level value / ms_per_step are those of the HOST-TO-HOST leg of C2 (config.value_is says so), with or without
+--full.  With --full, value_150bp_device_resident, value_10kb, value_50kb, value_150bp_illumina ... are top-level scalars of
+the same line, the roofline and CPU baseline are the single-stream leg's, and the full per-workload blocks (and the boundary
+leg) go to a side file (config.detail_file) and to stderr, so that the printed line stays short.  --workload
+{150bp,10kb,50kb,illumina} or an explicit --read-len runs a single workload; a plain run runs only the leg of it that `value`
+would come from under --full.
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL, used only for the barrier and the
 max-over-ranks time); the index is replicated, there is no data-path collective.  --scaling weak (default): every rank
@@ -34,6 +41,7 @@ environment starts the N ranks itself (python -m torch.distributed.run ... bench
 and exits with their status; inside a torchrun environment WORLD_SIZE must equal --gpus.
 """
 import argparse
+import copy
 import ctypes as C
 import json
 import os
@@ -238,16 +246,15 @@ class Env:
             shutil.rmtree(self.ref_dir, ignore_errors=True)
 
 
-def run_workload(E, name, wl, args, leg=None):
-    """Times K steps of one workload; returns its result block (rank 0) incl. roofline, cpu_baseline, parity_check.  `leg` names
-    the leg in the files of --dump-outputs."""
-    from ma_amd.shard import reduce_timing_and_counts, shard_range, weak_shard_first_index
-    torch, ma_amd, L, dev, dist = E.torch, E.ma, E.L, E.dev, E.dist
+def make_reads(E, wl, args):
+    """The reads of all steps of one workload on this rank, in HBM: (codes, offs, offs_h, B, n_global) -- B reads per step on this
+    rank, n_global reads over all ranks."""
+    from ma_amd.shard import shard_range, weak_shard_first_index
+    torch, L, dev = E.torch, E.L, E.dev
     rank, world = E.rank, E.world
-    read_len, preset = wl["read_len"], wl.get("preset") or args.preset
-    host_io = bool(args.host_io)
-    K, W = wl["steps"], wl["warmup"]
-    B_total = wl["reads_per_step"]  # reads per step and GPU (weak) / per step over all GPUs (strong)
+    read_len = wl["read_len"]
+    K = wl["steps"]
+    B_total = wl["reads_per_step"]
     if args.scaling == "strong":
         lo, hi = shard_range(B_total, world, rank)
         B = hi - lo  # this rank's share of every step
@@ -274,6 +281,26 @@ def run_workload(E, name, wl, args, leg=None):
         o = offs[k * (B + 1):k * (B + 1) + B + 1].cpu().numpy().astype(np.uint64)
         offs_h[k * B:k * B + B + 1] = o + np.uint64(nb_total)
         nb_total += int(nb.value)
+    return codes, offs, offs_h, B, n_global
+
+
+def staging_steps(K, max_bases):
+    """Steps whose reads the page-locked staging of the host-to-host leg holds (at most ~6 GB); step k uses slot k mod this."""
+    return int(max(1, min(K, 6e9 // max(max_bases, 1))))
+
+
+def run_workload(E, name, wl, args, leg=None):
+    """Times K steps of one workload; returns its result block (rank 0) incl. roofline, cpu_baseline, parity_check.  `leg` names
+    the leg in the files of --dump-outputs."""
+    from ma_amd.shard import reduce_timing_and_counts
+    torch, ma_amd, dev, dist = E.torch, E.ma, E.dev, E.dist
+    rank, world = E.rank, E.world
+    read_len, preset = wl["read_len"], wl.get("preset") or args.preset
+    host_io = bool(args.host_io)
+    K, W = wl["steps"], wl["warmup"]
+    B_total = wl["reads_per_step"]  # reads per step and GPU (weak) / per step over all GPUs (strong)
+    codes, offs, offs_h, B, n_global = make_reads(E, wl, args)
+    n_reads = B * K
     P = ma_amd.Params.preset(preset)
     max_bases = int((offs_h[B::B] - offs_h[:-1:B]).max()) if K > 0 and B > 0 else 0
     NB = max(1, min(args.inflight, K))
@@ -286,7 +313,7 @@ def run_workload(E, name, wl, args, leg=None):
     hout = []
     hs = 0
     if host_io and n_reads > 0:
-        hs = int(max(1, min(K, 6e9 // max(max_bases, 1))))
+        hs = staging_steps(K, max_bases)
         hstride = max_bases + 64
         hcodes = ma_amd.HostArray(hs * hstride, np.uint8)
         hoffs = ma_amd.HostArray(hs * (B + 1), np.uint64)
@@ -467,9 +494,9 @@ def run_workload(E, name, wl, args, leg=None):
     # ---- the results of a leg with several batches in flight (and of the host-to-host leg) against the same steps run ALONE,
     # one batch at a time, device resident -- after the timed region.  The single-stream path is what the oracle check of
     # cpu_baseline_and_parity covers; this ties the overlapped / host-to-host records to it byte for byte (a race between
-    # concurrent batches -- shared DP scratch, result arrays re-allocated mid-run -- would show here).
+    # concurrent batches -- shared DP scratch, result arrays re-allocated mid-run -- would show here).  --full only.
     xleg = None
-    want_xleg = (NB > 1 or host_io) and n_reads > 0 and not os.environ.get("MA_BENCH_NO_XLEG") and not h2h_only
+    want_xleg = args.full and (NB > 1 or host_io) and n_reads > 0 and not os.environ.get("MA_BENCH_NO_XLEG") and not h2h_only
     want_dump = bool(args.dump_outputs) and rank == 0 and n_reads > 0 and not h2h_only
     last = last_step_results(batches, hout, acc, host_io, hs, B) if want_xleg or want_dump else []
     if want_dump:
@@ -551,9 +578,9 @@ def run_workload(E, name, wl, args, leg=None):
                                         "handed_on_otherwise": int(bd[6]), "proved_frac": round(float(bd[1]) / float(bd[0]), 4),
                                         "diagonals_per_job": round(float(bd[7]) / float(bd[0]), 1)}
 
-    # ---- CPU baseline (rank 0, N = 1): the compiled reference and the oracle on this host's cores, then parity ---------
+    # ---- CPU baseline (rank 0, N = 1, --full): the compiled reference and the oracle on this host's cores, then parity ---------
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample != 0 and n_reads > 0 and not host_io:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample != 0 and n_reads > 0 and not host_io:
         pinned = os.sched_getaffinity(0)
         try:  # the host threads were pinned next to the GPU for the GPU legs (one socket); the CPU baseline gets every CPU the process had
             os.sched_setaffinity(0, E.cpus_at_start)
@@ -690,6 +717,51 @@ def dump_outputs(dirpath, tag, off, al, ops, B, budget):
         np.save(path, np.asarray(v, dtype=np.float64))
         n += os.path.getsize(path)
     return n
+
+
+def dumped_legs(wl, args):
+    """(leg, batches in flight, host to host) of every leg of one workload that --full runs: leg_plan's, or the one --inflight asks
+    for, named as run_workload names it in the files of --dump-outputs."""
+    if args.inflight > 0:
+        nb = max(1, min(args.inflight, wl["steps"]))
+        return [("host_to_host" if args.host_io else ("overlapped" if nb > 1 else "single_stream"), args.inflight, args.host_io)]
+    return leg_plan(wl, args)
+
+
+def dump_other_legs(E, wls, ran, args):
+    """--dump-outputs of a plain run: the files of every leg of `wls` that a --full run dumps, but `ran` ((workload, leg) of the leg
+    that ran and wrote its own), so that a plain run writes the files of a --full run.  A leg's files hold the records of the reads
+    its last timed step aligned: step K - 1 or, host to host, the staging slot that step used ((K - 1) mod staging_steps).  The
+    records of a step do not depend on the leg that aligned it (--full checks that: cross_leg_parity), so each such step is aligned
+    once here, one batch at a time, device resident, after the timed leg."""
+    if E.rank != 0 or os.environ.get("MA_BENCH_H2H"):
+        return
+    for name, wl in wls:
+        legs = [(key, hio) for key, _, hio in dumped_legs(wl, args) if (name, key) != ran]
+        if not legs or wl["steps"] <= 0:
+            continue
+        K = wl["steps"]
+        codes, offs, offs_h, B, _ = make_reads(E, wl, args)
+        if B > 0:
+            max_bases = int((offs_h[B::B] - offs_h[:-1:B]).max())
+            steps = {}
+            for key, hio in legs:
+                steps.setdefault((K - 1) % staging_steps(K, max_bases) if hio else K - 1, []).append(key)
+            bt = E.ma.Batch(E.idx, E.ma.Params.preset(wl.get("preset") or args.preset), B, max_bases + 64)
+            try:
+                bt.set_stream(E.torch.cuda.current_stream().cuda_stream)
+                for k, keys in sorted(steps.items()):
+                    bt.set_reads_device(codes.data_ptr() + int(offs_h[k * B]), offs.data_ptr() + 8 * k * (B + 1), B,
+                                        int(offs_h[k * B + B] - offs_h[k * B]))
+                    bt.align()
+                    bt.sync()
+                    off, al, ops = bt.mapq_alignments()
+                    for key in keys:
+                        dump_outputs(args.dump_outputs, "%s.%s" % (name, key), off, al, ops, B, args.dump_budget)
+            finally:
+                bt.close()
+        del codes, offs
+        E.torch.cuda.empty_cache()
 
 
 def cpu_baseline_and_parity(E, name, wl, args, codes, offs_h, B, n_reads, step, batches, roofline):
@@ -1028,50 +1100,87 @@ def c1_anchor(E, args):
     return out
 
 
-def run_legs(E, name, wl, args):
-    """The three legs of one workload (module docstring); returns the single-stream block with the other legs attached."""
-    import copy
-    a1 = copy.copy(args)
-    a1.inflight, a1.host_io = 1, 0
-    r = run_workload(E, name, wl, a1, "single_stream")
+def leg_plan(wl, args):
+    """The legs of one workload in the order run_legs runs them, as (key, batches in flight, host to host): one batch at a time,
+    then -- with --overlap > 1 -- device resident and host to host with batches in flight.  `value` comes from the last leg that
+    runs (compose_line)."""
     nfl = args.overlap if wl["read_len"] <= 1000 else min(args.overlap, args.overlap_long)
     # batches in flight of the host-to-host leg: a workload may ask for its own number (WORKLOADS[..]["h2h_inflight"]: 10 kb reads run
     # best with ONE batch object whose uploads and downloads run beside its own kernels -- a second batch's seeding crawls beside the
     # first one's persistent DP waves, profiles/r06_h2h_inflight.txt); --overlap 0 / 1 still means: single-stream leg only
     nfl_h2h = min(nfl, wl.get("h2h_inflight", nfl)) if nfl > 1 else nfl
+    legs = [("single_stream", 1, 0)]
     if nfl > 1 and not wl.get("single_only"):
-        for key, hio in (("overlapped", 0), ("host_to_host", 1)):
-            nfl_leg = nfl_h2h if hio else nfl
-            a2 = copy.copy(args)
-            a2.inflight, a2.cpu_sample, a2.host_io = nfl_leg, 0, hio
-            try:
-                # the leg's timed steps are the workload's (--steps): with fewer steps than batches, fewer batches are in flight
-                r2, err = run_workload(E, name, wl, a2, key), None
-            except RuntimeError as e:  # e.g. not enough HBM for that many long-read batches
-                r2, err = None, str(e)
-                for bt in E.live:
-                    bt.close()
-                E.live.clear()
-                for h in E.live_host:
-                    h.close()
-                E.live_host = []
-                E.torch.cuda.empty_cache()
-            if r is None:
-                continue
-            if r2 is None:
-                r[key] = {"batches_in_flight": nfl_leg, "error": err}
-                continue
-            rf2 = dict(r2["roofline"])
-            rf2["leg"] = ("%d batches in flight, %s: a kernel's launch time includes the share of the chip the other batches' kernels "
-                          "took meanwhile" % (r2["batches_in_flight"], r2["io"]))
-            r[key] = {"batches_in_flight": r2["batches_in_flight"], "io": r2["io"], "value": r2["value"], "unit": r2["unit"], "steps": r2["steps"],
-                      "ms_per_step": r2["ms_per_step"], "step_ms_min": r2["step_ms_min"], "step_ms_max": r2["step_ms_max"],
-                      "gbases_per_s": r2["gbases_per_s"], "aligned_reads": r2["aligned_reads"],
-                      "kernel_ms_per_step_under_overlap": r2["roofline"]["kernel_ms_per_step"], "roofline": rf2,
-                      "cross_leg_parity": r2.get("cross_leg_parity"), "stream_waits": r2.get("stream_waits"),
-                      "cfs_throttled": r2.get("cfs_throttled")}
-            if r2.get("host_phases_ms_per_step"):
-                r[key]["host_phases_ms_per_step"] = r2["host_phases_ms_per_step"]
+        legs += [("overlapped", nfl, 0), ("host_to_host", nfl_h2h, 1)]
+    return legs
+
+
+def drop_live(E):
+    """Closes what a leg that failed half-way left open."""
+    for bt in E.live:
+        bt.close()
+    E.live.clear()
+    for h in E.live_host:
+        h.close()
+    E.live_host = []
+    E.torch.cuda.empty_cache()
+
+
+def run_headline_leg(E, name, wl, args):
+    """A plain run: only the leg `value` comes from (the last of leg_plan), set up as run_legs sets it up; returns (leg, result
+    block).  If that leg fails
+    (e.g. not enough HBM for that many batches), the one before it runs instead, as `value` would then come from that one."""
+    legs = leg_plan(wl, args)[::-1]
+    # A leg with batches in flight takes their streams from torch's pool (run_workload), and which hardware queue a stream shares
+    # with the others depends on the streams the process made before it.  Under --full the legs before this one take theirs first:
+    # take as many here, so that the timed steps run on the streams they run on under --full (on the 150 bp leg, without this the
+    # plain run's value came out 1-2 % below that of --full).
+    K = wl["steps"]
+    for _ in range(sum(min(n, K) for _, n, _ in legs[1:] if min(n, K) > 1)):
+        E.torch.cuda.Stream()
+    for at, (key, nfl_leg, hio) in enumerate(legs):
+        a = copy.copy(args)
+        a.inflight, a.host_io = nfl_leg, hio
+        try:
+            return key, run_workload(E, name, wl, a, key)
+        except RuntimeError as e:
+            if at + 1 == len(legs):
+                raise
+            print("bench.py: the %s leg of workload %s failed (%s); running the %s leg instead" % (key, name, e, legs[at + 1][0]),
+                  file=sys.stderr, flush=True)
+            drop_live(E)
+
+
+def run_legs(E, name, wl, args):
+    """The legs of one workload (module docstring, leg_plan); returns the single-stream block with the other legs attached."""
+    a1 = copy.copy(args)
+    a1.inflight, a1.host_io = 1, 0
+    r = run_workload(E, name, wl, a1, "single_stream")
+    for key, nfl_leg, hio in leg_plan(wl, args)[1:]:
+        a2 = copy.copy(args)
+        a2.inflight, a2.cpu_sample, a2.host_io = nfl_leg, 0, hio
+        try:
+            # the leg's timed steps are the workload's (--steps): with fewer steps than batches, fewer batches are in flight
+            r2, err = run_workload(E, name, wl, a2, key), None
+        except RuntimeError as e:  # e.g. not enough HBM for that many long-read batches
+            r2, err = None, str(e)
+            drop_live(E)
+        if r is None:
+            continue
+        if r2 is None:
+            r[key] = {"batches_in_flight": nfl_leg, "error": err}
+            continue
+        rf2 = dict(r2["roofline"])
+        rf2["leg"] = ("%d batches in flight, %s: a kernel's launch time includes the share of the chip the other batches' kernels "
+                      "took meanwhile" % (r2["batches_in_flight"], r2["io"]))
+        r[key] = {"batches_in_flight": r2["batches_in_flight"], "io": r2["io"], "value": r2["value"], "unit": r2["unit"], "steps": r2["steps"],
+                  "ms_per_step": r2["ms_per_step"], "step_ms_min": r2["step_ms_min"], "step_ms_max": r2["step_ms_max"],
+                  "gbases_per_s": r2["gbases_per_s"], "aligned_reads": r2["aligned_reads"],
+                  "kernel_ms_per_step_under_overlap": r2["roofline"]["kernel_ms_per_step"], "roofline": rf2,
+                  "cross_leg_parity": r2.get("cross_leg_parity"), "stream_waits": r2.get("stream_waits"),
+                  "cfs_throttled": r2.get("cfs_throttled")}
+        if r2.get("host_phases_ms_per_step"):
+            r[key]["host_phases_ms_per_step"] = r2["host_phases_ms_per_step"]
     return r
 
 
@@ -1080,7 +1189,7 @@ def build_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10,
                     help="timed steps of every leg of the 150bp workload, or of the one workload --workload / --read-len selects "
-                         "(the other workloads of the default run keep their own counts: WORKLOADS)")
+                         "(the other workloads of a --full run keep their own counts: WORKLOADS)")
     ap.add_argument("--warmup", type=int, default=1, help="untimed steps on every batch object before a leg's timed steps")
     ap.add_argument("--workload", default="all", choices=["all", "150bp", "10kb", "50kb", "illumina", "10kb_pacbio", "50kb_nanopore"])
     ap.add_argument("--reads-per-step", type=int, default=0, help="override the workload's reads per step")
@@ -1100,7 +1209,10 @@ def build_parser():
     ap.add_argument("--inflight", type=int, default=0,
                     help="run ONE leg only, with this many batches in flight per GPU (own stream + host thread each; profiling runs)")
     ap.add_argument("--host-io", type=int, default=0, help="with --inflight: that leg host to host (1) or device resident (0)")
-    ap.add_argument("--detail-file", default="", help="where the per-workload blocks go (default: gpurun_out/bench_detail.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="run everything besides the leg `value` comes from: every workload and leg, the CPU baselines, parity "
+                         "checks and roofline, the C1 anchor, the boundary leg, the detail file (off: the headline alone)")
+    ap.add_argument("--detail-file", default="", help="with --full: where the per-workload blocks go (default: see compose_line)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after each leg's timed steps, write the records of its last step for a seeded sample of its reads to "
                          "DIR/<workload>.<leg>.<array>.npy (float64, at most 64 MB in all)")
@@ -1108,7 +1220,10 @@ def build_parser():
 
 
 def main():
-    args = build_parser().parse_args()
+    ap = build_parser()
+    args = ap.parse_args()
+    if args.detail_file and not args.full:
+        ap.error("--detail-file: the per-workload blocks are written by a --full run only")
     self_launch_or_check(args, sys.argv[1:])
     if os.environ.get("MA_BENCH_DRY_RUN") == "1":
         return dry_run(args)
@@ -1132,27 +1247,34 @@ def main():
             if args.reads_per_step > 0 and (wl["read_len"] <= 1000 or args.workload != "all"):
                 wl["reads_per_step"] = args.reads_per_step
             wls.append((name, wl))
-    # --dump-outputs: every leg that can run gets an equal share of the 64 MB (three legs per workload, one with --inflight)
+    # --dump-outputs: every leg that can run under --full gets an equal share of the 64 MB (three legs per workload, one with
+    # --inflight); a plain run writes the same files (dump_other_legs)
     args.dump_budget = DUMP_BYTES // (len(wls) * (1 if args.inflight > 0 else 3))
     results = []
-    for name, wl in wls:
+    for name, wl in (wls if args.full else wls[:1]):  # a plain run: the workload `value` comes from
         if args.inflight > 0:  # one explicit leg (what a rocprofv3 run of a single leg uses)
             r = run_workload(E, name, wl, args)
-        else:
+            ran = (name, dumped_legs(wl, args)[0][0])
+        elif args.full:
             r = run_legs(E, name, wl, args)
+        else:
+            key, r = run_headline_leg(E, name, wl, args)
+            ran = (name, key)
         if r is not None:
             results.append(r)
+    if args.dump_outputs and not args.full:
+        dump_other_legs(E, wls, ran, args)
     boundary = anchor = None
-    full = E.rank == 0 and E.world == 1 and args.cpu_sample != 0 and args.read_len == 0 and args.inflight == 0
-    if full and args.workload == "all":
+    extras = args.full and E.rank == 0 and E.world == 1 and args.cpu_sample != 0 and args.read_len == 0 and args.inflight == 0
+    if extras and args.workload == "all":
         try:
             anchor = c1_anchor(E, args)
         except Exception as e:  # noqa: BLE001
             anchor = {"error": repr(e)[:300]}
-    if full and args.boundary_reads > 0:
+    if extras and args.boundary_reads > 0:
         boundary = boundary_leg(E, args)
     if E.rank == 0:
-        print(compose_line(E, args, results, boundary, anchor))
+        print(compose_line(E, args, results, boundary, anchor) if args.full else plain_line(E, args, results[0]))
     E.close()
     if E.dist is not None:
         E.dist.destroy_process_group()
@@ -1162,6 +1284,39 @@ def leg_of(block, key):
     """(value, ms_per_step, batches in flight) of a workload's leg, or Nones"""
     leg = block if key is None else (block.get(key) or {})
     return leg.get("value"), leg.get("ms_per_step"), leg.get("batches_in_flight")
+
+
+def headline_fields(E, args, top, warmup):
+    """The fields every line starts with, of the leg `value` comes from."""
+    return {
+        "metric": "aligned reads/sec (whole node), 150bp & 10kb synthetic vs GRCh38",
+        "value": top["value"], "unit": "aligned reads/s", "n_gpus": E.world, "steps": top["steps"], "warmup": warmup,
+        "ms_per_step": top["ms_per_step"], "higher_is_better": True, "scaling": args.scaling,
+        "vs_baseline": None, "dtype": "u8/int8 (2-bit BWT ranks, int8 DP differences, int16/32 scores)",
+        "data": "synthetic",
+    }
+
+
+def genome_of(E, args):
+    return "GRCh38-like synthetic genome (%d contigs, %d nt%s)" % (len(E.lens), E.F, "" if args.no_repeats else ", planted repeats")
+
+
+def plain_line(E, args, r):
+    """The line of a plain run: compose_line's headline fields, from the one leg that ran (run_headline_leg, or --inflight)."""
+    out = headline_fields(E, args, r, r["warmup"])
+    out["config"] = {
+        "workload": r["workload"] + " vs " + genome_of(E, args),
+        "value_is": "workload '%s' (%s), %d batch(es) in flight per GPU, %s%s" % (
+            r["name"], r["baseline_config"], r["batches_in_flight"], r["io"],
+            " (the one leg --inflight / --host-io asked for)" if args.inflight > 0 else ""),
+        "index_build_s": round(E.t_index, 2),
+        "parallelism": "reads partitioned over %d GPU(s) (%s scaling), index replicated, no collective; %d batch(es) in flight per GPU" % (
+            E.world, args.scaling, r["batches_in_flight"]),
+        "kernel_source_hash": kernel_source_hash(),
+        "mode": "plain: this leg alone; --full adds the other workloads and legs, the CPU baselines, parity checks, roofline, C1 "
+                "anchor and boundary leg",
+    }
+    return json.dumps(out)
 
 
 def compose_line(E, args, results, boundary, anchor):
@@ -1180,13 +1335,7 @@ def compose_line(E, args, results, boundary, anchor):
     except OSError as e:
         dpath = "not written (%s)" % e
     print("bench detail: " + json.dumps(detail), file=sys.stderr, flush=True)
-    out = {
-        "metric": "aligned reads/sec (whole node), 150bp & 10kb synthetic vs GRCh38",
-        "value": top["value"], "unit": "aligned reads/s", "n_gpus": E.world, "steps": top["steps"], "warmup": head["warmup"],
-        "ms_per_step": top["ms_per_step"], "higher_is_better": True, "scaling": args.scaling,
-        "vs_baseline": None, "dtype": "u8/int8 (2-bit BWT ranks, int8 DP differences, int16/32 scores)",
-        "data": "synthetic",
-    }
+    out = headline_fields(E, args, top, head["warmup"])
     # every workload as top-level scalars: host to host (the timed region of BASELINE.md section 3), device resident with the same
     # batches in flight, and one batch at a time (the leg the per-kernel roofline is measured on)
     for r in results:
@@ -1242,8 +1391,7 @@ def compose_line(E, args, results, boundary, anchor):
             out["dropin_graph_reads_per_s"] = g.get("reads_per_s")
             out["dropin_graph_threads"] = g.get("threads")
     out["config"] = {
-        "workload": head["workload"] + " vs GRCh38-like synthetic genome (%d contigs, %d nt%s)" % (
-            len(E.lens), E.F, "" if args.no_repeats else ", planted repeats"),
+        "workload": head["workload"] + " vs " + genome_of(E, args),
         "value_is": "workload '%s' (%s), %s" % (
             head["name"], head["baseline_config"],
             ( "%d batch(es) in flight per GPU, %s (the one leg --inflight / --host-io asked for)" % (head.get("batches_in_flight", 1), head.get("io", ""))

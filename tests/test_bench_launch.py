@@ -76,3 +76,58 @@ def test_dump_outputs_writes_a_fixed_float_sample_within_its_budget(tmp_path):
         assert np.array_equal(d[f], al[f][rows].astype(np.float64)), f
     want = np.concatenate([ops[2 * int(o):2 * int(o + k)] for o, k in zip(al["ops_off"][rows], al["n_ops"][rows])])
     assert np.array_equal(d["ops"].ravel(), want.astype(np.float64))
+
+
+def test_detail_file_goes_with_full():
+    """The per-workload blocks are a --full run's: a plain run refuses --detail-file instead of leaving the file unwritten."""
+    r = _run(["--gpus", "1", "--detail-file", "d.json"])
+    assert r.returncode == 2 and "--full" in r.stderr
+    assert _run(["--gpus", "1", "--full", "--detail-file", "d.json"]).returncode == 0
+
+
+def test_plain_run_runs_only_the_leg_value_comes_from(monkeypatch):
+    """Without --full one leg of the workload runs: the one `value` comes from under --full (the last of leg_plan), with the
+    batches in flight and I/O --full gives it; if it fails to set up, the leg before it runs instead.  --dump-outputs names the
+    legs of a --full run (dumped_legs) as run_legs runs them."""
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    calls = []
+
+    def fake_run_workload(E, name, wl, args, leg=None):
+        calls.append((leg, args.inflight, args.host_io))
+        if leg in E.failing:
+            raise RuntimeError("no HBM for %s" % leg)
+        return {"name": name, "leg": leg, "roofline": {"kernel_ms_per_step": {}}, "batches_in_flight": args.inflight, "io": "",
+                "value": 1.0, "unit": "", "steps": 1, "ms_per_step": 1.0, "step_ms_min": 1.0, "step_ms_max": 1.0, "gbases_per_s": 0,
+                "aligned_reads": 1}
+
+    monkeypatch.setattr(bench, "run_workload", fake_run_workload)
+    streams = []
+    torch = types.SimpleNamespace(cuda=types.SimpleNamespace(empty_cache=lambda: None, Stream=lambda: streams.append(1)))
+    E = types.SimpleNamespace(live=[], live_host=[], torch=torch, failing=())
+    # (workload, the leg `value` comes from, streams the legs before it take from torch's pool under --full)
+    for name, want, n_streams in (("150bp", ("host_to_host", 3, 1), 3), ("10kb", ("host_to_host", 1, 1), 2),
+                                  ("50kb", ("host_to_host", 2, 1), 2), ("10kb_pacbio", ("single_stream", 1, 0), 0)):
+        args = bench.build_parser().parse_args(["--workload", name])
+        wl = dict(bench.WORKLOADS[name], steps=10, warmup=1)
+        calls.clear()
+        bench.run_legs(E, name, wl, args)
+        assert calls[-1] == want, name  # the leg `value` comes from under --full
+        assert [c[0] for c in calls] == [leg for leg, _, _ in bench.dumped_legs(wl, args)], name
+        calls.clear()
+        streams.clear()
+        assert bench.run_headline_leg(E, name, wl, args)[0] == want[0]
+        assert calls == [want] and len(streams) == n_streams, name
+    wl = dict(bench.WORKLOADS["150bp"], steps=2, warmup=1)  # fewer steps than batches: fewer batches in flight
+    calls.clear()
+    streams.clear()
+    bench.run_headline_leg(E, "150bp", wl, bench.build_parser().parse_args([]))
+    assert calls == [("host_to_host", 3, 1)] and len(streams) == 2
+    calls.clear()
+    bench.run_headline_leg(E, "150bp", wl, bench.build_parser().parse_args(["--overlap", "0"]))
+    assert calls == [("single_stream", 1, 0)]
+    E.failing = ("host_to_host",)
+    calls.clear()
+    assert bench.run_headline_leg(E, "150bp", wl, bench.build_parser().parse_args([]))[0] == "overlapped"
+    assert calls == [("host_to_host", 3, 1), ("overlapped", 3, 0)]

@@ -266,7 +266,7 @@ def test_unknown_seeding_technique_is_rejected(gpu_device, tmp_path):
 
 
 def _bench(args, nproc=1, env=None, self_launch=False):
-    """Runs bench.py and returns its line with the per-workload blocks of the detail file put back under config.workloads.
+    """Runs bench.py --full and returns its line with the per-workload blocks of the detail file put back under config.workloads.
     nproc > 1: under an outer torchrun as the driver starts it -- or, self_launch, by bench.py's own --gpus N."""
     import sys
     import tempfile
@@ -278,7 +278,7 @@ def _bench(args, nproc=1, env=None, self_launch=False):
         e.pop("WORLD_SIZE", None)
     with tempfile.TemporaryDirectory() as td:
         detail = os.path.join(td, "detail.json")
-        out = subprocess.check_output(base + [os.path.join(ROOT, "bench.py")] + args + ["--detail-file", detail], env=e,
+        out = subprocess.check_output(base + [os.path.join(ROOT, "bench.py"), "--full"] + args + ["--detail-file", detail], env=e,
                                       stderr=subprocess.DEVNULL).decode()
         line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
         with open(detail) as f:
@@ -313,6 +313,30 @@ def test_bench_two_ranks_partition_one_read_set(gpu_device):
     assert w1["host_to_host"]["aligned_reads"] == w1["overlapped"]["aligned_reads"]  # the same reads through both I/O paths
     assert one["value"] == w1["host_to_host"]["value"] and "host to host" in one["config"]["value_is"]
     assert one["value_150bp_device_resident"] == w1["overlapped"]["value"] and one["value_150bp_single_stream"] == w1["value"]
+
+
+def test_bench_plain_run_is_the_headline_leg_of_a_full_run(gpu_device, tmp_path):
+    """Without --full the bench times the leg `value` comes from and nothing else: the same reads aligned as that leg of a --full
+    run; --dump-outputs writes the files of the --full run, every leg's, byte for byte."""
+    import sys
+    common = ["--workload", "150bp", "--genome-scale", "0.01", "--steps", "3", "--warmup", "1", "--reads-per-step", "30000",
+              "--cpu-sample", "0", "--boundary-reads", "0", "--gpus", "1"]
+    full = _bench(common + ["--dump-outputs", str(tmp_path / "full")])
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py")] + common + ["--dump-outputs", str(tmp_path / "plain")],
+                                  stderr=subprocess.DEVNULL).decode()
+    plain = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    h2h = full["config"]["workloads"][0]["host_to_host"]
+    assert plain["steps"] == full["steps"] == 3 and plain["warmup"] == full["warmup"] == 1 and plain["n_gpus"] == 1
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["config"]["value_is"].startswith("workload '150bp' (configs[1] (C2)), 3 batch(es) in flight per GPU, host to host")
+    assert abs(plain["value"] * plain["ms_per_step"] * plain["steps"] / 1e3 - h2h["aligned_reads"]) < 2e-3 * h2h["aligned_reads"]
+    assert "roofline" not in plain and "cpu_baseline" not in plain and "parity_150bp_h2h" not in plain
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert len(names) == 3 * 13 and names == sorted(os.listdir(tmp_path / "full"))
+    for f in names:
+        assert (tmp_path / "plain" / f).read_bytes() == (tmp_path / "full" / f).read_bytes(), f
 
 
 def test_bench_gpus_flag_starts_the_ranks_itself(gpu_device):

@@ -4,7 +4,7 @@
 import ctypes as C, os, runpy, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.argv = ["bench.py"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full"] + sys.argv[1:]
 import ma_amd
 try:
     runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")

@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["MA_AMD_LIB"] = os.path.join(ROOT, "tools", "_prof", "libma_amd_chainprof.so")
 os.environ.setdefault("MA_LANES_PER_WAVE", "1")
 sys.path.insert(0, ROOT)
-sys.argv = ["bench.py", "--steps", "1", "--warmup", "0", "--cpu-sample", "0", "--boundary-reads", "0", "--overlap", "0"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full", "--steps", "1", "--warmup", "0", "--cpu-sample", "0", "--boundary-reads", "0", "--overlap", "0"] + sys.argv[1:]
 import runpy
 import ma_amd
 try:

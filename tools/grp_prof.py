@@ -5,7 +5,7 @@ import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["MA_AMD_LIB"] = os.path.join(ROOT, "tools", "_prof", "libma_amd_prof.so")
 sys.path.insert(0, ROOT)
-sys.argv = ["bench.py", "--steps", "2", "--warmup", "0", "--cpu-sample", "0"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full", "--steps", "2", "--warmup", "0", "--cpu-sample", "0"] + sys.argv[1:]
 import runpy
 import ma_amd
 try:

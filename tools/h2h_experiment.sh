@@ -9,7 +9,7 @@ OUT=gpurun_out/h2h_experiment.txt
 : > $OUT
 run() {
     tag=$1; nfl=$2; hio=$3; shift 3
-    env "$@" python bench.py --workload 150bp --steps $K --warmup 2 --cpu-sample 0 --boundary-reads 0 --inflight $nfl --host-io $hio \
+    env "$@" python bench.py --full --workload 150bp --steps $K --warmup 2 --cpu-sample 0 --boundary-reads 0 --inflight $nfl --host-io $hio \
         --detail-file gpurun_out/h2h_$tag.json > gpurun_out/h2h_$tag.line 2> gpurun_out/h2h_$tag.err
     python - "$tag" >> $OUT <<'P'
 import json, sys

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Everything the round's committed numbers come from, in one GPU call (≈38 min of box time in round 6; the part before QUICK's exit ≈23 min): parity tests, rocprofv3
-# kernel stats + PMC passes of the four workloads, the bench line (all workloads, three legs each, C1 anchor, boundary), the
+# kernel stats + PMC passes of the four workloads, the --full bench line (all workloads, three legs each, C1 anchor, boundary), the
 # kernel trace of the leg `value` comes from and its concurrency timeline, the overlap matrix, the phase profile of
 # k_ksw_pk<5>, SQ counters of the 10 kb DP stage, launch timelines.  tools/evidence_to_profiles.sh copies what is to be judged
 # from gpurun_out/ into profiles/ (profiles/README.md).
@@ -24,11 +24,12 @@ hipcc --offload-arch=gfx950 -O3 tools/valu_mix.hip -o tools/_prof/valu_mix 2>/de
 tools/_prof/valu_mix > gpurun_out/calib_$TAG/valu_mix.txt 2>&1; tools/_prof/gups > gpurun_out/calib_$TAG/gups.txt 2>&1
 python3 tools/calibration_json.py gpurun_out/calib_$TAG > gpurun_out/${TAG}_calibration.json
 cp gpurun_out/${TAG}_calibration.json profiles/${TAG}_calibration.json
-# the driver's line (all workloads incl. the Illumina preset and the C1 anchor); its per-workload blocks go to the detail file
-# (the driver's own command line)
+# the driver's command with --full (all workloads incl. the Illumina preset, their legs, CPU baselines and parity checks, the C1
+# anchor, the boundary leg); the line and its per-workload blocks (the detail file) go straight into profiles/, as the PMC passes
+# and the calibration above do
 T0=$(date +%s)
-python bench.py --gpus 1 --steps 20 --warmup 5 --detail-file gpurun_out/${TAG}_bench_detail.json > gpurun_out/${TAG}_bench_default.json 2> gpurun_out/${TAG}_bench_default.err
-echo "python bench.py --gpus 1 --steps 20 --warmup 5: $(( $(date +%s) - T0 )) s wall" > gpurun_out/${TAG}_bench_default_wall.txt
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail-file profiles/${TAG}_bench_detail.json > profiles/${TAG}_bench_default.json 2> "$TMPDIR/${TAG}_bench_default.err"
+echo "python bench.py --full --gpus 1 --steps 20 --warmup 5: $(( $(date +%s) - T0 )) s wall" > profiles/${TAG}_bench_default_wall.txt
 [ -n "$QUICK" ] && exit 0   # QUICK=1: only what depends on the kernel sources' hash (tests, PMC passes, calibration, the bench line)
 make -s -C ma_amd/csrc prof > /dev/null 2>&1   # the diagnostics build of THESE sources (phase profiles below)
 # where the host-to-host leg stands against the device-resident one: one direction only, serial instead of double-buffered I/O,
@@ -64,7 +65,7 @@ for wl in 50kb_nanopore 50kb 10kb; do echo "== $wl"; python3 tools/chain_prof.py
 python3 tools/ksw_prof.py --workload 150bp --boundary-reads 0 --overlap 0 2>&1 | grep -v "^{" | grep -v "^bench detail:" | grep -v amdgpu.ids > gpurun_out/${TAG}_ext_pairing_bound.txt
 python3 - <<PY
 import json
-d = json.loads(open("gpurun_out/${TAG}_bench_default.json").read().strip().splitlines()[-1])
+d = json.loads(open("profiles/${TAG}_bench_default.json").read().strip().splitlines()[-1])
 print("value", d["value"], d["ms_per_step"], d["config"]["value_is"])
 for k in sorted(d):
     if k.startswith(("value_", "parity_", "c1_", "cpu_reference_", "dropin_", "roofline_")):

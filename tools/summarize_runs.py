@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One line per bench detail file (bench.py --detail-file): leg, batches in flight, reads/s, ms per step, per-stage kernel times,
+"""One line per bench detail file (bench.py --full --detail-file): leg, batches in flight, reads/s, ms per step, per-stage kernel times,
 seeding fraction of the gather ceiling, parity.  The experiment tables under profiles/ (r06_seed_task_leaf.txt, r06_smem_tasks_tuning.txt,
 r06_h2h_inflight.txt ...) are this script's output over the detail files of one gpurun call.
 usage: summarize_runs.py <glob of detail files> [<glob> ...]"""
