@@ -5,7 +5,7 @@
 //   ma_align <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam|stdout> [preset] [mates.fa|fq[.gz]]
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_align.cpp -Lma_amd -lma_amd [-lz] -lpthread
-#include "ma_sam.h"
+#include "ma_batch_nodes.h"
 #include <cstdio>
 
 using namespace libMA;
@@ -61,7 +61,9 @@ int main( int argc, char** argv )
         {
             PairedFileReader xPairedReader( xParams );
             auto pStreams = std::make_shared<PairedFileStream>( pIn, fileStreamFromPath( argv[ 5 ] ) );
-            PairedFileWriter xWriter( xParams, std::string( argv[ 3 ] ), pPack );
+            // the flat paired path: mates paired on the device, SAM text straight from the pair records (with "Detect Small
+            // Inversions" executePairedFlat itself goes through containers); the bytes are PairedFileWriter's
+            BatchPairedFileWriter xWriter( xParams, std::make_shared<PairedFileWriter>( xParams, std::string( argv[ 3 ] ), pPack ), pPack );
             while( true )
             {
                 auto pMates = std::make_shared<ReadVec>( );
@@ -75,9 +77,9 @@ int main( int argc, char** argv )
                 }
                 if( pMates->empty( ) )
                     break;
-                auto pRes = xAligner.executePaired( pFM, pMates );
-                for( size_t k = 0; k < pRes->size( ); k++ )
-                    xWriter.execute( ( *pMates )[ 2 * k ], ( *pMates )[ 2 * k + 1 ], ( *pRes )[ k ], pPack );
+                auto pFlat = xAligner.executePairedFlat( pFM, pMates );
+                for( auto& pBatch : *pFlat )
+                    xWriter.execute( *pBatch );
             }
         }
     }

@@ -16,6 +16,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 using namespace libMA;
 using namespace libMS;
@@ -235,7 +236,7 @@ int main( int argc, char** argv )
 {
     if( argc < 6 )
     {
-        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads]\n" );
+        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats]]\n" );
         return 2;
     }
     try
@@ -246,7 +247,7 @@ int main( int argc, char** argv )
         maCheck( ma_set_device( atoi( argv[ 5 ] ) ) );
         maCheck( ma_host_bind_thread( atoi( argv[ 5 ] ), 0, nullptr ) ); // this thread and all it starts: the CPUs next to the GPU
         const unsigned uiHw = std::max( 1u, std::thread::hardware_concurrency( ) );
-        const int iGraphThreads = argc >= 7 ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
+        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         double t0 = now( );
@@ -264,6 +265,99 @@ int main( int argc, char** argv )
             uiState ^= uiState << 13, uiState ^= uiState >> 7, uiState ^= uiState << 17;
             return uiState;
         };
+        if( argc >= 7 && !strcmp( argv[ 6 ], "paired" ) )
+        {
+            // ---- the paired leg: n mates (n / 2 pairs, outer distance 340 .. 460, every second pair seen from the other strand)
+            // host to host INCLUDING SAM text through (a) BatchAligner::executePaired + PairedFileWriter -- Alignment
+            // containers, PairedReads on one host thread -- and (b) executePairedFlat + BatchPairedFileWriter -- paired on the
+            // device, text from the flat pair records; alternating, <repeats> times each after one warm-up of each
+            const int iRepeats = argc >= 8 ? std::max( 1, atoi( argv[ 7 ] ) ) : 5;
+            auto pMates = std::make_shared<ReadVec>( );
+            auto window = [ & ]( uint64_t uiPos, bool bRev, size_t uiName ) {
+                auto pQ = std::make_shared<NucSeq>( );
+                pQ->sName = "r" + std::to_string( uiName );
+                pQ->xCodes.resize( uiLen );
+                for( size_t j = 0; j < uiLen; j++ )
+                {
+                    const uint64_t p = uiPos + j;
+                    uint8_t b = ( vPac[ p >> 2 ] >> ( ( ~p & 3 ) << 1 ) ) & 3;
+                    if( rnd( ) % 200 == 0 )
+                        b = ( b + 1 + rnd( ) % 3 ) & 3;
+                    pQ->xCodes[ j ] = b;
+                }
+                if( bRev )
+                {
+                    std::reverse( pQ->xCodes.begin( ), pQ->xCodes.end( ) );
+                    for( auto& b : pQ->xCodes )
+                        b = 3 - b;
+                }
+                return pQ;
+            };
+            for( size_t k = 0; 2 * k + 1 < n; k++ )
+            {
+                const uint64_t uiDist = std::max<uint64_t>( uiLen + 1, 340 + rnd( ) % 121 );
+                const uint64_t uiPos = rnd( ) % ( uiF - uiDist - 1 );
+                if( k & 1 )
+                {
+                    pMates->push_back( window( uiPos + uiDist - uiLen, true, 2 * k ) );
+                    pMates->push_back( window( uiPos, false, 2 * k + 1 ) );
+                }
+                else
+                {
+                    pMates->push_back( window( uiPos, false, 2 * k ) );
+                    pMates->push_back( window( uiPos + uiDist - uiLen, true, 2 * k + 1 ) );
+                }
+            }
+            std::vector<uint8_t>( ).swap( vPac );
+            BatchAligner xAligner( xParams );
+            xAligner.uiBatchReads = std::min<size_t>( pMates->size( ), 1u << 18 );
+            xAligner.uiInflight = 3;
+            xAligner.warmUp( pFM, pMates );
+            uint64_t uiBytesContainer = 0, uiBytesFlat = 0, uiHostPairs = 0;
+            auto container = [ & ]( ) {
+                auto pSink = std::make_shared<CountingSink>( );
+                PairedFileWriter xWriter( xParams, std::static_pointer_cast<OutStream>( pSink ), pPack );
+                const double t = now( );
+                auto pPairs = xAligner.executePaired( pFM, pMates );
+                for( size_t k = 0; k < pPairs->size( ); k++ )
+                    xWriter.execute( ( *pMates )[ 2 * k ], ( *pMates )[ 2 * k + 1 ], ( *pPairs )[ k ], pPack );
+                const double f = now( ) - t;
+                uiBytesContainer = pSink->uiBytes.load( );
+                return f;
+            };
+            auto flat = [ & ]( ) {
+                auto pSink = std::make_shared<CountingSink>( );
+                BatchPairedFileWriter xWriter( xParams, std::static_pointer_cast<OutStream>( pSink ), pPack );
+                xWriter.uiFormatThreads = std::min( 16u, uiHw );
+                const double t = now( );
+                uiHostPairs = 0;
+                auto pFlat = xAligner.executePairedFlat( pFM, pMates );
+                for( auto& pB : *pFlat )
+                {
+                    xWriter.execute( *pB );
+                    uiHostPairs += pB->pResult->uiPairsOnHost;
+                }
+                const double f = now( ) - t;
+                uiBytesFlat = pSink->uiBytes.load( );
+                return f;
+            };
+            container( ), flat( ); // warm-up of both
+            std::vector<double> vC, vF;
+            for( int r = 0; r < iRepeats; r++ )
+                vC.push_back( pMates->size( ) / container( ) ), vF.push_back( pMates->size( ) / flat( ) );
+            auto list = []( std::vector<double> v ) {
+                std::sort( v.begin( ), v.end( ) );
+                std::string s = "{\"median\": " + std::to_string( v[ v.size( ) / 2 ] ) + ", \"min\": " + std::to_string( v.front( ) ) +
+                                ", \"max\": " + std::to_string( v.back( ) ) + "}";
+                return s;
+            };
+            printf( "{\"paired\": {\"mates\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_reads\": %zu, \"in_flight\": 3, "
+                    "\"execute_paired_reads_per_s\": %s, \"execute_paired_flat_reads_per_s\": %s, \"sam_bytes_container\": %llu, "
+                    "\"sam_bytes_flat\": %llu, \"pairs_finished_on_host\": %llu}}\n",
+                    pMates->size( ), uiLen, iRepeats, xAligner.uiBatchReads, list( vC ).c_str( ), list( vF ).c_str( ),
+                    (unsigned long long)uiBytesContainer, (unsigned long long)uiBytesFlat, (unsigned long long)uiHostPairs );
+            return uiBytesContainer == uiBytesFlat ? 0 : 1;
+        }
         for( size_t i = 0; i < n; i++ )
         {
             auto pQ = std::make_shared<NucSeq>( );

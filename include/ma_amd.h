@@ -60,12 +60,14 @@ typedef struct
     int32_t report_n_best; /* 0                                  xReportN */
     int32_t max_supplementary; /* 1                              xMaxSupplementaryPerPrim */
     double max_overlap_supplementary; /* 0.1                     xMaxOverlapSupplementary */
-    /* read by the host modules SmallInversions / PairedReads */
+    /* read by the host module SmallInversions */
     int32_t search_inversions; /* 0                              xSearchInversions */
     int32_t zdrop_inversion; /* 100                              xZDropInversion */
-    int32_t use_paired_reads; /* 0                               xUsePairedReads */
+    int32_t use_paired_reads; /* 0                               xUsePairedReads (read by the host layer only: it selects the
+                                                                 paired graph; ma_pair_batch pairs whenever it is called) */
     int32_t libm_probe; /* 0. Diagnostics only (tests): != 0 nudges every tan / sin / atan / log result of the chaining
                            stage by one ulp (ma_amd/csrc/chain.h LibmProbe); results must not change */
+    /* read by ma_pair_batch (with `match`) and by the host module PairedReads */
     double mean_paired_dist; /* 400                              xMeanPairedReadDistance */
     double std_paired_dist; /* 150                               xStdPairedReadDistance */
     double paired_bonus; /* 1.25                                 xPairedBonus */
@@ -75,7 +77,7 @@ typedef struct
  * "pacbio" 1096-1098, "nanopore" 1101-1104. */
 void ma_params_default( ma_params* p );
 void ma_params_illumina( ma_params* p );
-void ma_params_illuminapaired( ma_params* p ); /* illumina + xUsePairedReads (read by the host module PairedReads) */
+void ma_params_illuminapaired( ma_params* p ); /* illumina + xUsePairedReads (selects the paired graph of the host layer) */
 void ma_params_pacbio( ma_params* p ); /* default + xMaxSupplementaryPerPrim 100, xMinNumSoC 5 */
 void ma_params_nanopore( ma_params* p ); /* pacbio + SMEM seeding */
 /* ParameterSetManager::setSelected (parameter.h:1163-1170) by key, case-insensitive like the reference's map keys are
@@ -267,6 +269,30 @@ int ma_batch_stage_reads( ma_batch*, const uint8_t* codes, const uint64_t* offse
 int ma_batch_use_staged_reads( ma_batch* );
 int ma_batch_start_mapq_download( ma_batch*, uint64_t* aln_off /*n+1*/, ma_alignment* alns, uint64_t* ops );
 int ma_batch_finish_download( ma_batch* );
+/* ---- paired reads: PairedReads::execute (pairedReads.cpp:14-131) on the device ----
+ * Reads 2k and 2k+1 of the batch are the mates of pair k.  ma_pair_batch runs after ma_dp_batch / ma_align_batch on the batch's
+ * stream and picks, per pair, one alignment of each mate out of the two MappingQuality lists: the best combined score, times
+ * paired_bonus when the two lie on opposite strands mean_paired_dist +- 3 std_paired_dist apart (ties like the reference's
+ * std::sort leaves them); the picked records lose secondary / supplementary and may get the pair's mapping quality.  A pair with
+ * one empty list yields the other mate's whole list, unchanged.  It reads mean_paired_dist, std_paired_dist, paired_bonus and
+ * match of the batch's parameters and does not look at use_paired_reads.  It waits for the stream (the one read-back that
+ * sizes the download) and fails -- with a message, launching nothing -- for an odd number of reads or without a MappingQuality
+ * output, and with "PairedReads: no alignment of non-zero length to pair" when both lists of a pair hold alignments of length
+ * 0 only.  The MappingQuality records themselves stay as they are (ma_batch_get_mapq_alignments still serves them).
+ *   ma_batch_pair_counts           pairs, records and ops (pairs of words) of the download; n_host_pairs = pairs whose pick the
+ *                                  library finished on the host (several candidates share the best key among more than the 32
+ *                                  the kernel sorts on chip; same result, any pointer may be NULL)
+ *   ma_batch_get_pairs             pair k's records are alns[pair_off[k] .. pair_off[k+1]), records and ops in the layout of
+ *                                  ma_batch_get_mapq_alignments; mate[i] = 1: record of the first mate; other[i] = index of the
+ *                                  partner's record WITHIN the pair, -1 for none (any pointer may be NULL)
+ *   ma_batch_start_pair_download   the same without the wait, completed by ma_batch_finish_download (cf.
+ *                                  ma_batch_start_mapq_download; one download can be pending per object) */
+int ma_pair_batch( ma_batch* );
+int ma_batch_pair_counts( ma_batch*, uint64_t* n_pairs, uint64_t* n_records, uint64_t* n_ops, uint64_t* n_host_pairs );
+int ma_batch_get_pairs( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, ma_alignment* alns, uint64_t* ops /*2*n_ops*/, int32_t* mate,
+                        int32_t* other );
+int ma_batch_start_pair_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, ma_alignment* alns, uint64_t* ops, int32_t* mate,
+                                  int32_t* other );
 /* work counters for the roofline model (same meaning as the oracle's): [0] extend_backward steps,
  * [1] distinct occ blocks touched, [2] bwt_sa LF steps, [3] SA rows, [4] DP band cells, [5] ksw jobs */
 int ma_batch_counters( ma_batch*, uint64_t out[ 8 ] );

@@ -465,6 +465,40 @@ class Batch:
     def finish_download(self):
         _chk(lib().ma_batch_finish_download(self.h))
 
+    # ---- paired reads (ma_pair_batch): reads 2k and 2k+1 of the batch are the mates of pair k
+    def pair(self):
+        """PairedReads::execute for every pair on the device, after align() / dp()."""
+        _chk(lib().ma_pair_batch(self.h))
+
+    def pair_counts(self):
+        v = [C.c_uint64() for _ in range(4)]
+        _chk(lib().ma_batch_pair_counts(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("pairs", "records", "ops", "host_pairs"), [x.value for x in v]))
+
+    def pairs(self):
+        """(pair_off, alns, ops, mate, other): pair k's records are alns[pair_off[k]:pair_off[k + 1]] (ALIGNMENT_DT, ops as
+        (type, length) pairs from ops_off on); mate 1 = record of the first mate, other = index of the partner's record
+        within the pair or -1."""
+        c = self.pair_counts()
+        off = np.zeros(c["pairs"] + 1, dtype=np.uint64)
+        alns = np.zeros(c["records"], dtype=ALIGNMENT_DT)
+        ops = np.zeros(2 * c["ops"] + 2, dtype=np.uint64)
+        mate = np.zeros(c["records"], dtype=np.int32)
+        other = np.zeros(c["records"], dtype=np.int32)
+        _chk(lib().ma_batch_get_pairs(self.h, _ptr(off), _ptr(alns), _ptr(ops), _ptr(mate), _ptr(other)))
+        return off, alns, ops, mate, other
+
+    def start_pair_download(self, off, alns, ops, mate, other):
+        """pairs() into caller-owned HostArrays (u64[pairs + 1], ALIGNMENT_DT[records], u64[2 * ops], i32[records] twice)
+        without the wait: None when they are too small, else pair_counts(); complete after finish_download()."""
+        c = self.pair_counts()
+        if (off.n < c["pairs"] + 1 or alns.n < c["records"] or ops.n < 2 * c["ops"] or mate.n < c["records"]
+                or other.n < c["records"]):
+            return None
+        _chk(lib().ma_batch_start_pair_download(self.h, C.c_void_p(off.ptr), C.c_void_p(alns.ptr), C.c_void_p(ops.ptr),
+                                                C.c_void_p(mate.ptr), C.c_void_p(other.ptr)))
+        return c
+
     def close(self):
         if self.h:
             lib().ma_batch_destroy(self.h)

@@ -57,7 +57,11 @@ enum : int
     CTR_NEXT_BIG = 88, // 4 x u32 job queues of the second (few waves, large scratch) launch of a class (2 words)
     CTR_N_1X1 = 90, // 1 x 1 gap fills answered by k_dp_enum itself (counted as ksw calls of one cell each)
     CTR_MAX_BANDL = 91, // largest min(qlen, tlen) of the long jobs on the band of 120 (scratch rows of their launch)
-    CTR_COUNT = 92
+    CTR_PAIR_RECS = 92, // ma_pair_batch: records / ops of the picked pairs (exact sizes of the pair download) ...
+    CTR_PAIR_OPS = 93,
+    CTR_PAIR_OVER = 94, // ... pairs k_pair_pick left to the host, pairs without any candidate (stage_pair.h)
+    CTR_PAIR_ERR = 95,
+    CTR_COUNT = 96
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -72,6 +76,9 @@ enum : int
 #include "stage_dp.h"
 
 #include "stage_output.h"
+
+#include "../host/ma_pair_flat.h"
+#include "stage_pair.h"
 
 // ------------------------------------------------------------------------------------------------
 // batch object
@@ -107,6 +114,9 @@ struct ma_batch
     DevBuf jobs, info, ez, cigOff, cigPool, kswScratch, clsLists, opsCap, opsOff, ops, hdr, order, mqOrder, mqCnt;
     DevBuf outCnt, outOps, outAlnOff, outOpsOff, outAlns, outOpsPairs; // packed results (get_alns)
     DevBuf sortKey, sortKey2, sortVal2; // longest-job-first order of the DP job lists
+    // pairing (ma_pair_batch): per pair its pick and sizes, the pairs left to the host and their round trip, the packed columns
+    DevBuf pairPick, pairCnt, pairOps, pairOver, pairHostOff, pairHostLists, pairHostPick, pairMate, pairOther;
+    u64 pairRecs = 0, pairNOps = 0, pairOnHost = 0;
     u64 cigPoolCap = 0, cigPoolMin = 0, nOpsCap = 0, nJobSlots = 0;
     KswSide kswSide; // created on first use
 #if defined( MA_EXP_DP_PRIO ) // experiment build: the DP kernels of a batch on a stream of the lowest priority (launch_dp.h)
@@ -121,7 +131,7 @@ struct ma_batch
     bool stagedPending = false, downPending = false;
     u64 stN = 0, stBases = 0;
     u32 stMaxQ = 0;
-    int stage_done = 0; // 0 none, 1 seeded, 2 extracted, 3 chained, 4 dp
+    int stage_done = 0; // 0 none, 1 seeded, 2 extracted, 3 chained, 4 dp, 5 paired
     bool timing = false;
     bool blocking = false; // batch_wait: sleep on an event instead of spinning
     hipEvent_t waitEv = nullptr;
@@ -1116,3 +1126,5 @@ int ma_debug_seed_prof( unsigned long long* out )
 #endif
 
 } // extern "C"
+
+#include "launch_pair.h"

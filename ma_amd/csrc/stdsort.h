@@ -206,6 +206,47 @@ template <typename T, typename C> MA_HD_OUTLINE void sort( T* a, i64 n, C comp )
         insertion_sort( a, (i64)0, n, comp );
 }
 
+// std::sort(a, a+n, comp) for n <= 32, without the stack of deferred ranges (no dynamically indexed locals: nothing for the
+// compiler to put into scratch memory).  A partition splits a range of at most 32 elements into two that are disjoint, of
+// which at most one is longer than 16: only that one is partitioned again (both halves inherit the same depth budget),
+// the other waits for the final insertion sort like in sort().  Same comparisons on the same elements => same permutation.
+template <typename T, typename C> MA_HD void sort_upto32( T* a, i64 n, C comp )
+{
+    if( n <= 0 )
+        return;
+    i64 first = 0, last = n, depth = 0;
+    {
+        u64 m = (u64)n; // __lg(n) * 2
+        while( m >>= 1 )
+            depth++;
+        depth *= 2;
+    }
+    while( last - first > 16 )
+    {
+        if( depth == 0 )
+        {
+            heap_sort_range( a, first, last, comp );
+            break;
+        }
+        --depth;
+        const i64 mid = first + ( last - first ) / 2;
+        move_median_to_first( a, first, first + 1, mid, last - 1, comp );
+        const i64 cut = unguarded_partition( a, first + 1, last, first, comp );
+        if( last - cut > 16 )
+            first = cut;
+        else
+            last = cut;
+    }
+    if( n > 16 )
+    {
+        insertion_sort( a, (i64)0, (i64)16, comp );
+        for( i64 i = 16; i != n; ++i )
+            unguarded_linear_insert( a, i, comp );
+    }
+    else
+        insertion_sort( a, (i64)0, n, comp );
+}
+
 // The part of std::sort that is left of a range [first, last) once __introsort_loop has come down to it with `depth`
 // levels of its budget left -- the rest of the loop on that range, then the final insertion sort's share of it (the blocks
 // the loop leaves are sorted in place, see wave_sort.h) -- by one thread.

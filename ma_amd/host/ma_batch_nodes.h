@@ -260,4 +260,83 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
         return false; // serialises its own output
     }
 };
+
+// SAM records of a whole PAIRED batch (BatchAligner::executePairedFlat): PairedFileWriter::execute (fileWriter.cpp:158-383)
+// per pair, formatted from the flat pair records (ma_flat_sam.h formatPair) by uiFormatThreads threads into one arena each and
+// written in input order under one acquisition of the writer's lock.  The NGMLR tags are refused like PairedFileWriter does.
+class BatchPairedFileWriter
+{
+    std::shared_ptr<PairedFileWriter> pPerPair; // owns stream + lock, writes the header
+    ma_amd::flat::SamFormat xFormat;
+    ma_amd::flat::Contigs xContigs;
+
+  public:
+    size_t uiFormatThreads = 8;
+    std::atomic<uint64_t> uiBytes{ 0 }, uiReads{ 0 };
+
+    BatchPairedFileWriter( const ParameterSetManager& rParameters, std::shared_ptr<OutStream> pOut, std::shared_ptr<Pack> pPack )
+        : BatchPairedFileWriter( rParameters, std::make_shared<PairedFileWriter>( rParameters, pOut, pPack ), pPack )
+    {}
+    // on the stream (and behind the header) of a PairedFileWriter that exists already
+    BatchPairedFileWriter( const ParameterSetManager& rParameters, std::shared_ptr<PairedFileWriter> pWriter, std::shared_ptr<Pack> pPack )
+        : pPerPair( pWriter )
+    {
+        const SamOptions& rO = rParameters.xSam;
+        xFormat.bNoSecondary = rO.bNoSecondary, xFormat.bNoSupplementary = rO.bNoSupplementary;
+        xFormat.bOutputMCigar = rO.bOutputMCigar, xFormat.bCGTag = rO.bCGTag, xFormat.bSoftClip = rO.bSoftClip;
+        xContigs.vNames = pPack->vNames, xContigs.vStarts = pPack->vStarts, xContigs.vLengths = pPack->vLengths;
+    }
+
+    void execute( const AlignedBatch& rBatch )
+    {
+        if( !rBatch.paired( ) )
+            throw std::runtime_error( "BatchPairedFileWriter: not a paired batch" );
+        const size_t n = rBatch.pairs( );
+        const size_t uiThreads = std::max<size_t>( 1, std::min<size_t>( uiFormatThreads, n / 1024 + 1 ) );
+        std::vector<ma_amd::flat::Arena> vArenas( uiThreads );
+        std::string sFailure;
+        std::mutex xFailure;
+        auto view = []( const NucSeq& rQ ) {
+            ma_amd::flat::ReadView xQ;
+            xQ.sName = rQ.sName.data( ), xQ.uiNameLen = rQ.sName.size( );
+            xQ.pCodes = rQ.xCodes.data( ), xQ.uiLength = rQ.xCodes.size( );
+            xQ.pQuality = rQ.xQuality.empty( ) ? nullptr : rQ.xQuality.data( );
+            return xQ;
+        };
+        auto format = [ & ]( size_t t ) {
+            try
+            {
+                const uint64_t* pOff = rBatch.pairOffsets( );
+                for( size_t k = n * t / uiThreads; k < n * ( t + 1 ) / uiThreads; k++ )
+                    ma_amd::flat::formatPair( vArenas[ t ], xFormat, xContigs, view( *rBatch.read( 2 * k ) ), view( *rBatch.read( 2 * k + 1 ) ),
+                                              rBatch.pairAlignments( ) + pOff[ k ], pOff[ k + 1 ] - pOff[ k ], rBatch.pairOps( ),
+                                              rBatch.pairMate( ) + pOff[ k ], rBatch.pairOther( ) + pOff[ k ] );
+            }
+            catch( const std::exception& rE )
+            {
+                std::lock_guard<std::mutex> xGuard( xFailure );
+                if( sFailure.empty( ) )
+                    sFailure = rE.what( );
+            }
+        };
+        std::vector<std::thread> vT;
+        for( size_t t = 1; t < uiThreads; t++ )
+            vT.emplace_back( format, t );
+        format( 0 );
+        for( auto& rT : vT )
+            rT.join( );
+        if( !sFailure.empty( ) )
+            throw std::runtime_error( sFailure );
+        uint64_t uiTotal = 0;
+        {
+            std::lock_guard<std::mutex> xGuard( *pPerPair->pLock );
+            for( const auto& rArena : vArenas )
+            {
+                pPerPair->pOut->write( rArena.data( ), rArena.size( ) );
+                uiTotal += rArena.size( );
+            }
+        }
+        uiBytes += uiTotal, uiReads += 2 * n;
+    }
+};
 } // namespace libMA

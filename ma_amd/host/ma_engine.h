@@ -187,6 +187,15 @@ struct BatchResult
     HostBuf<uint64_t> vMqOps; // (type, length) pairs
     uint64_t uiMqAlignments = 0, uiMqOps = 0;
     uint64_t uiAlignedReads = 0;
+    // Paired batches (Engine::run with bPairs: reads 2k, 2k + 1 are the mates of pair k): INSTEAD of the MappingQuality
+    // records the records PairedReads leaves per pair (ma_pair_batch / ma_batch_get_pairs), CSR by pair, with the two columns
+    // mate (1 = record of the first mate) and other (index of the partner's record within the pair, -1: none)
+    bool bPairs = false;
+    HostBuf<uint64_t> vPairOff; // uiReads / 2 + 1
+    HostBuf<ma_alignment> vPair;
+    HostBuf<uint64_t> vPairOps;
+    HostBuf<int32_t> vPairMate, vPairOther;
+    uint64_t uiPairRecords = 0, uiPairOps = 0, uiPairsOnHost = 0; // (uiPairsOnHost: pairs the library finished on the host)
     double fPack = 0, fH2D = 0, fKernels = 0, fD2H = 0; // seconds: gathering the reads, upload, all stages, download
     float aStageMs[ 8 ] = { 0, 0, 0, 0, 0, 0, 0, 0 }; // host wall time of seed / extract / chain / dp (ma_batch_host_ms)
 };
@@ -283,7 +292,7 @@ class Engine
             vRefs.emplace_back( *pRead );
         return run( vRefs, bStages );
     }
-    std::shared_ptr<BatchResult> run( const std::vector<ReadRef>& vReads, bool bStages )
+    std::shared_ptr<BatchResult> run( const std::vector<ReadRef>& vReads, bool bStages, bool bPairs = false )
     {
         const size_t n = vReads.size( );
         auto tPack = std::chrono::steady_clock::now( );
@@ -311,18 +320,20 @@ class Engine
                 rT.join( );
         }
         const double fPack = secondsSince( tPack );
-        auto pRes = runFlat( pCodes, pOff, n, bStages );
+        auto pRes = runFlat( pCodes, pOff, n, bStages, bPairs );
         pRes->fPack = fPack;
         return pRes;
     }
     // reads that already are one array of codes + CSR offsets (n + 1), e.g. in page-locked memory the caller filled
-    std::shared_ptr<BatchResult> runFlat( const uint8_t* pCodes, const uint64_t* pOff, size_t n, bool bStages )
+    // bPairs: the reads are mate pairs (2k, 2k + 1); the result carries the pair records instead of the MappingQuality ones
+    std::shared_ptr<BatchResult> runFlat( const uint8_t* pCodes, const uint64_t* pOff, size_t n, bool bStages, bool bPairs = false )
     {
         auto pRes = freshResult( );
         BatchResult& R = *pRes;
         R.uiReads = n;
         R.bStages = bStages;
         R.bSocQueues = false;
+        R.bPairs = bPairs;
         R.fPack = 0;
         fit( n, pOff[ n ] );
         auto t0 = std::chrono::steady_clock::now( );
@@ -367,7 +378,18 @@ class Engine
             engineCheck( ma_batch_get_alignments( pBatch, R.vAlnOff.data( ), R.vAlns.data( ), R.vAlnOps.data( ) ) );
         }
         uint64_t* pMqOff = R.vMqOff.need( n + 1 );
-        engineCheck( ma_batch_get_mapq_alignments( pBatch, pMqOff, R.vMq.need( nAln + 1 ), R.vMqOps.need( 2 * nOps + 2 ) ) );
+        if( bPairs )
+        {
+            uint64_t nPairs = 0;
+            engineCheck( ma_pair_batch( pBatch ) );
+            engineCheck( ma_batch_pair_counts( pBatch, &nPairs, &R.uiPairRecords, &R.uiPairOps, &R.uiPairsOnHost ) );
+            engineCheck( ma_batch_get_pairs( pBatch, R.vPairOff.need( nPairs + 1 ), R.vPair.need( R.uiPairRecords + 1 ),
+                                             R.vPairOps.need( 2 * R.uiPairOps + 2 ), R.vPairMate.need( R.uiPairRecords + 1 ),
+                                             R.vPairOther.need( R.uiPairRecords + 1 ) ) );
+            memset( pMqOff, 0, ( n + 1 ) * sizeof( uint64_t ) ); // no per-read records in a paired result
+        }
+        else
+            engineCheck( ma_batch_get_mapq_alignments( pBatch, pMqOff, R.vMq.need( nAln + 1 ), R.vMqOps.need( 2 * nOps + 2 ) ) );
         R.uiMqAlignments = n ? pMqOff[ n ] : 0;
         R.uiMqOps = 0;
         if( R.uiMqAlignments )

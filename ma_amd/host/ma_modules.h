@@ -1412,6 +1412,37 @@ class AlignedBatch : public libMS::Container
     {
         return pResult == nullptr ? 0 : pResult->uiAlignedReads;
     }
+    // A PAIRED batch (BatchAligner::executePairedFlat): reads 2k, 2k + 1 are the mates of pair k; instead of per-read records
+    // it holds what PairedReads leaves per pair: records [pairOffsets()[k], pairOffsets()[k+1]) of pairAlignments(), ops in
+    // pairOps(), pairMate()[r] = 1: record of the first mate, pairOther()[r] = the partner's index within the pair or -1
+    bool paired( ) const
+    {
+        return pResult != nullptr && pResult->bPairs;
+    }
+    size_t pairs( ) const
+    {
+        return size( ) / 2;
+    }
+    const uint64_t* pairOffsets( ) const
+    {
+        return pResult->vPairOff.data( );
+    }
+    const ma_alignment* pairAlignments( ) const
+    {
+        return pResult->vPair.data( );
+    }
+    const uint64_t* pairOps( ) const
+    {
+        return pResult->vPairOps.data( );
+    }
+    const int32_t* pairMate( ) const
+    {
+        return pResult->vPairMate.data( );
+    }
+    const int32_t* pairOther( ) const
+    {
+        return pResult->vPairOther.data( );
+    }
     std::shared_ptr<AlignmentVector> alignmentsOf( size_t uiRead ) const
     {
         auto pV = std::make_shared<AlignmentVector>( );
@@ -1496,14 +1527,16 @@ class BatchAligner
     // Alignment containers (rOut[ i ]).  pPerIndex: phase times per replica.
     void alignRangeOn( const std::vector<const ma_index*>& vIndices, const libMS::ContainerVector<std::shared_ptr<NucSeq>>& rQueries,
                        size_t uiFrom, size_t uiTo, TP_RESULT* pOut, AlignerTiming& rT, TP_FLAT* pFlat = nullptr,
-                       std::shared_ptr<ReadVector> pReadsOfFlat = nullptr, std::vector<AlignerTiming>* pPerIndex = nullptr ) const
+                       std::shared_ptr<ReadVector> pReadsOfFlat = nullptr, std::vector<AlignerTiming>* pPerIndex = nullptr,
+                       bool bPairs = false ) const
     {
         if( vIndices.empty( ) )
             throw std::runtime_error( "BatchAligner: no index" );
         std::mutex xNext;
         size_t uiNext = uiFrom;
         std::string sFailure;
-        const size_t uiBatch = std::max<size_t>( uiBatchReads, 1 );
+        // bPairs: reads 2k, 2k + 1 are mates that are paired on the device, so no batch boundary may fall between them
+        const size_t uiBatch = std::max<size_t>( uiBatchReads, 1 ) + ( bPairs ? std::max<size_t>( uiBatchReads, 1 ) % 2 : 0 );
         const size_t uiBatchesAll = ( uiTo - uiFrom + uiBatch - 1 ) / uiBatch;
         const size_t uiFlatBase = pFlat ? pFlat->size( ) : 0;
         if( pFlat )
@@ -1516,7 +1549,7 @@ class BatchAligner
             vReads.reserve( hi - lo );
             for( size_t i = lo; i < hi; i++ )
                 vReads.emplace_back( rQueries[ i ]->xCodes );
-            auto pRes = xEngine.run( vReads, false );
+            auto pRes = xEngine.run( vReads, false, bPairs );
             const auto t0 = std::chrono::steady_clock::now( );
             if( pFlat )
             {
@@ -1721,6 +1754,82 @@ class BatchAligner
         }
         return pRet;
     }
+
+    // Paired mode with the results left FLAT and the pick made on the DEVICE (ma_pair_batch): both mates of all pairs go
+    // through the device in batches of whole pairs, uiInflight of them in flight like executeFlat; one AlignedBatch per device
+    // batch, in input order, holding the pair records (AlignedBatch::paired) -- no Alignment container, no per-read download.
+    // With "Detect Small Inversions" the inversions have to be found BEFORE pairing and SmallInversions needs containers:
+    // then this takes the container path (executePaired) and flattens what it returns into one batch of the same shape.
+    std::shared_ptr<TP_FLAT> executePairedFlat( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<ReadVector> vMates )
+    {
+        if( vMates->size( ) % 2 )
+            throw std::runtime_error( "BatchAligner::executePairedFlat: odd number of reads" );
+        if( xP.search_inversions )
+            return flattenPairs( executePaired( pFM_index, vMates ), vMates );
+        return executePairedFlatOn( pFM_index->pDev->all( ), vMates, &vLastPerIndex );
+    }
+    std::shared_ptr<TP_FLAT> executePairedFlatOn( const std::vector<const ma_index*>& vIndices, std::shared_ptr<ReadVector> vMates,
+                                                  std::vector<AlignerTiming>* pPerIndex )
+    {
+        if( vMates->size( ) % 2 )
+            throw std::runtime_error( "BatchAligner::executePairedFlat: odd number of reads" );
+        auto pRet = std::make_shared<TP_FLAT>( );
+        xLast = AlignerTiming( );
+        const auto t0 = std::chrono::steady_clock::now( );
+        if( !vMates->empty( ) )
+            alignRangeOn( vIndices, *vMates, 0, vMates->size( ), nullptr, xLast, pRet.get( ), vMates, pPerIndex, true );
+        xLast.fWall = detail::secondsSince( t0 );
+        return pRet;
+    }
+    // the pairs of executePaired as ONE paired AlignedBatch (host memory; the records keep PairedReads' changes)
+    static std::shared_ptr<TP_FLAT> flattenPairs( std::shared_ptr<TP_RESULT> pPairs, std::shared_ptr<ReadVector> vMates )
+    {
+        auto pRes = std::make_shared<detail::BatchResult>( );
+        detail::BatchResult& R = *pRes;
+        R.uiReads = vMates->size( );
+        R.bPairs = true;
+        uint64_t uiRecords = 0, uiOps = 0;
+        for( auto& pV : *pPairs )
+            for( auto& pA : *pV )
+                uiRecords++, uiOps += pA->data.size( );
+        uint64_t* pOff = R.vPairOff.need( pPairs->size( ) + 1 );
+        ma_alignment* pAlns = R.vPair.need( uiRecords + 1 );
+        uint64_t* pOps = R.vPairOps.need( 2 * uiOps + 2 );
+        int32_t *pMate = R.vPairMate.need( uiRecords + 1 ), *pOther = R.vPairOther.need( uiRecords + 1 );
+        memset( R.vMqOff.need( R.uiReads + 1 ), 0, ( R.uiReads + 1 ) * sizeof( uint64_t ) );
+        uint64_t r = 0, o = 0;
+        pOff[ 0 ] = 0;
+        for( size_t k = 0; k < pPairs->size( ); k++ )
+        {
+            const AlignmentVector& rV = *( *pPairs )[ k ];
+            for( size_t i = 0; i < rV.size( ); i++, r++ )
+            {
+                const Alignment& rA = *rV[ i ];
+                ma_alignment& rF = pAlns[ r ];
+                rF.begin_ref = (int64_t)rA.uiBeginOnRef, rF.end_ref = (int64_t)rA.uiEndOnRef;
+                rF.begin_q = (int64_t)rA.uiBeginOnQuery, rF.end_q = (int64_t)rA.uiEndOnQuery;
+                rF.score = rA.iScore, rF.soc_index = rA.index_of_strip, rF.n_ops = (uint32_t)rA.data.size( ), rF.ops_off = o;
+                rF.secondary = rA.bSecondary ? 1 : 0, rF.supplementary = rA.bSupplementary ? 1 : 0, rF.mapq = rA.fMappingQuality;
+                for( auto& rD : rA.data )
+                    pOps[ 2 * o ] = (uint64_t)rD.first, pOps[ 2 * o + 1 ] = rD.second, o++;
+                pMate[ r ] = rA.xStats.bFirst ? 1 : 0;
+                pOther[ r ] = -1;
+                auto pPartner = rA.xStats.pOther.lock( );
+                for( size_t j = 0; pPartner != nullptr && j < rV.size( ); j++ )
+                    if( rV[ j ] == pPartner )
+                        pOther[ r ] = (int32_t)j;
+            }
+            pOff[ k + 1 ] = r;
+        }
+        R.uiPairRecords = uiRecords, R.uiPairOps = uiOps;
+        auto pB = std::make_shared<AlignedBatch>( );
+        pB->pReads = vMates;
+        pB->uiFirst = 0;
+        pB->pResult = pRes;
+        auto pRet = std::make_shared<TP_FLAT>( );
+        pRet->push_back( pB );
+        return pRet;
+    }
 };
 
 // Throughput API, several GPUs of one node: reads are independent, the index is replicated, the device batches
@@ -1840,6 +1949,21 @@ class MultiDeviceAligner
         if( !pQueries->empty( ) )
             xAligner.alignRangeOn( vIndices, *pQueries, 0, pQueries->size( ), nullptr, xLast, pRet.get( ), pQueries, &vLast );
         xLast.fWall = detail::secondsSince( t0 );
+        for( auto& rT : vLast )
+            rT.fWall = xLast.fWall;
+        return pRet;
+    }
+
+    // BatchAligner::executePairedFlat over all replicas: batches of whole pairs rotate over them, paired on the device that
+    // aligned them.  (search_inversions: use BatchAligner::executePairedFlat, which takes the container path.)
+    std::shared_ptr<BatchAligner::TP_FLAT> executePairedFlat( std::shared_ptr<ReadVector> vMates )
+    {
+        if( xParams.getSelected( )->search_inversions )
+            throw std::runtime_error( "MultiDeviceAligner::executePairedFlat: not with 'Detect Small Inversions' (SmallInversions needs containers)" );
+        configure( );
+        vLast.assign( vIndices.size( ), AlignerTiming( ) );
+        auto pRet = xAligner.executePairedFlatOn( vIndices, vMates, &vLast );
+        xLast = xAligner.xLast;
         for( auto& rT : vLast )
             rT.fWall = xLast.fWall;
         return pRet;
