@@ -53,8 +53,9 @@ MA_HD int ksw_grp_size( const KswScoring& SC, i32 qlen, i32 tlen, i32 w, i32 zdr
         return 0;
     if( zdrop > 16000 )
         return 0; // the z-drop threshold is kept as a packed int16
-    // 4 / 2 jobs per wave with two rows per lane; 1 = two jobs per wave with FOUR rows per lane (MA_KSW_GRP=1 leaves those to k_ksw_ext<1>)
-    return qlen <= 32 ? 4 : ( qlen <= 64 ? 2 : ( qlen <= 128 && SC.grp == 2 ? 1 : 0 ) );
+    // 4 / 2 jobs per wave with two rows per lane (queries of 65..128 bases with FOUR rows per lane, NR = 2, measured slower than
+    // k_ksw_ext<1>: DESIGN.md section 3.4; no kernel is built for them)
+    return qlen <= 32 ? 4 : ( qlen <= 64 ? 2 : 0 );
 }
 
 template <int LANES> __device__ __forceinline__ i32 grp_max_i32( i32 v ) // maximum over the 64 / G lanes of a group, in every lane
@@ -713,7 +714,7 @@ __device__ void ksw_grp_set( const FETCH& F, const KswScoring& SC, const u32* li
 #endif
 }
 
-// six job lists: G = 1 left / right (MA_KSW_GRP=2 only), G = 2 left / right, G = 4 left / right
+// six job lists (KSW_CLS_GRP0 + list): the narrow band of ksw_band.h left / right, G = 2 left / right, G = 4 left / right
 #define KSW_GRP_LISTS 6
 // One kernel per (G, direction): a single instantiation of ksw_grp_set per kernel keeps the register allocation of each below
 // the budget (all six in one kernel: 128 VGPRs and scratch traffic inside the diagonal loop).

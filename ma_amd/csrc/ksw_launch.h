@@ -1,11 +1,13 @@
 // ksw_launch.h -- persistent-wave driver around ksw_wave_core: every 64-thread workgroup (= one
-// wavefront) pulls DP job slots from an atomic counter until none are left.
+// wavefront) pulls DP job slots from an atomic counter until none are left.  Also the kernel classes of the DP jobs (KSW_CLS_*), the
+// one router that assigns them (ksw_route_job), the sizing of the launches (KswSizing) and the launches themselves (ksw_run_all).
 #pragma once
 #include "internal.h"
 #include "ksw_wave.h"
 #include "ksw_reg.h"
 #include "ksw_ext.h"
 #include "ksw_pk.h"
+#include "nw.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -55,24 +57,53 @@ __device__ __forceinline__ u32 ksw_fetch_size( u32 n )
     return n / gridDim.x >= 32u ? KSW_JOBS_PER_FETCH : 1u;
 }
 
-// job classes by the number of 128-cell ring slots they need (ksw_pk_slots): 1, 2, 3, <=5, else LDS kernel (class 3
-// shares the launch slot of the widest ring; class 4 = ksw_wave.h)
+// exact jobs by the number of 128-cell ring slots they need (ksw_pk_slots): 1, 2, 3, <= 5, else the LDS kernel
 #define KSW_S0 1
 #define KSW_S1 2
 #define KSW_S2 3
 #define KSW_S3 5
-#define KSW_N_CLASSES 15 // 0..3 exact register kernel (ksw_pk.h), 4 LDS kernel, 5 / 6 extension kernel (ksw_ext.h) with 1 / 2 slots,
-                         // 7..12 the query-stationary extension kernel (ksw_grp.h): 4 jobs of up to 254 query bases on the proven narrow band
-                         // (ksw_band.h) / 2 of up to 64 / 4 of up to 32 per wave, left / right; 13 / 14 LONG extension jobs on the proven band
-                         // of 120, one per wave, left / right (ksw_band.h, G = 1)
-#define KSW_CLS_GRP0 7
-#define KSW_CLS_BANDL 13
+// Kernel classes of the DP jobs.  A job list, a launch and a word of every per-class counter bank (KswSizing, CTR_CLS0 /
+// CTR_MAX_PC0 / CTR_MAX_CIGC0 of the pipeline) are indexed by these.
+enum : int
+{
+    KSW_CLS_PK0 = 0, // exact register kernel k_ksw_pk<S> (ksw_pk.h), S = KSW_S0 .. KSW_S3 ring slots
+    KSW_CLS_PK1 = 1,
+    KSW_CLS_PK2 = 2,
+    KSW_CLS_PK3 = 3,
+    KSW_CLS_LDS = 4, // exact kernel with its state in LDS / HBM, k_ksw (ksw_wave.h): whatever fits no register kernel
+    KSW_CLS_EXT1 = 5, // extension kernel k_ksw_ext<R> (ksw_ext.h) with R = 1 / 2 slots
+    KSW_CLS_EXT2 = 6,
+    KSW_CLS_GRP0 = 7, // first of the KSW_GRP_LISTS lists of extensions that share a wavefront; from here on the scratch per wave is fixed
+    KSW_CLS_NARROW_L = 7, // the proven narrow band k_ksw_band (ksw_band.h): 4 jobs of up to 254 query bases per wave, left / right
+    KSW_CLS_NARROW_R = 8,
+    KSW_CLS_GRP2_L = 9, // query-stationary k_ksw_grp<2> (ksw_grp.h): 2 jobs of up to 64 query bases per wave, left / right
+    KSW_CLS_GRP2_R = 10,
+    KSW_CLS_GRP4_L = 11, // k_ksw_grp<4>: 4 jobs of up to 32 query bases per wave, left / right
+    KSW_CLS_GRP4_R = 12,
+    KSW_CLS_BANDL = 13, // LONG extension jobs on the proven band of 120, k_ksw_band<.., 1>: one per wave, left / right
+    KSW_CLS_BANDL_L = 13,
+    KSW_CLS_BANDL_R = 14,
+    KSW_N_CLASSES = 15
+};
+// Words of `next`, the zeroed u32 counters of ksw_run_all: one job queue per launch, and the lengths of the lists the kernels append to
+enum : int
+{
+    KSW_NX_CLS = 0, // + class, KSW_CLS_PK0 .. KSW_CLS_EXT2: queue of the class's own launch
+    KSW_NX_REDO = 7, // + k: queue of k_ksw_pk<k> over the jobs handed back to the exact kernels (second pass)
+    KSW_NX_GRP = 11, // + list, 0 .. KSW_GRP_LISTS - 1: queues of the wavefront-sharing launches
+    KSW_NX_BAND_EXT = 17, // + 0 / 1: jobs the narrow band appended to the lists of KSW_CLS_EXT1 / EXT2
+    KSW_NX_BANDL = 19, // + 0 / 1: queues of the two launches on the band of 120
+    KSW_NX_REDOL = 21, // + k: queue of k_ksw_pk<k> over the long jobs the band of 120 handed back (when they have a stream of their own)
+    KSW_NX_N_REDOL = 25, // ... and the number of those jobs
+    KSW_N_NEXT = 28, // words of `next` (the last two are spare)
+    KSW_N_NEXT_BIG = 4 // words of `nextBig`: + k, queue of the huge tier of class k
+};
 MA_HD int ksw_job_class( i32 qlen, i32 tlen, i32 w )
 {
     if( qlen > 150000 )
-        return 4; // the register kernels keep the reversed query in LDS (160 KB per CU)
+        return KSW_CLS_LDS; // the register kernels keep the reversed query in LDS (160 KB per CU)
     const i32 n = ksw_pk_slots( qlen, tlen, w ); // 128-cell slots of the two-cells-per-lane kernel (ksw_pk.h)
-    return n <= KSW_S0 ? 0 : ( n <= KSW_S1 ? 1 : ( n <= KSW_S2 ? 2 : ( n <= KSW_S3 ? 3 : 4 ) ) );
+    return n <= KSW_S0 ? KSW_CLS_PK0 : ( n <= KSW_S1 ? KSW_CLS_PK1 : ( n <= KSW_S2 ? KSW_CLS_PK2 : ( n <= KSW_S3 ? KSW_CLS_PK3 : KSW_CLS_LDS ) ) );
 }
 // per-wave scratch of one job: direction bytes of the exact kernels (n_col bytes per diagonal) / of the extension kernel
 // (one ring row per diagonal)
@@ -185,21 +216,78 @@ __device__ __forceinline__ bool ksw_next( unsigned int* nextSlot, u32 n, u32& cu
 #include "ksw_band.h"
 namespace ma
 {
-// MA_KSW_GRP=0 (A/B and test hook) keeps the short extensions on the one-job-per-wavefront kernel.  The switch travels in
-// KswScoring (a kernel argument of everything that classifies jobs), so host and device classify alike.
-#define ksw_grp_enabled( ) ( SC.grp != 0 )
-// pipeline mode: extensions whose callers read only max_q / max_t / cigar go to the extension kernel
+// pipeline mode: extensions whose callers read only max_q / max_t / cigar go to the extension kernels.  KswScoring carries the
+// switches (grp: MA_KSW_GRP, 0 keeps the short extensions on the one-job-per-wavefront kernel; band_long: MA_KSW_BANDL) as a kernel
+// argument of everything that classifies jobs, so host and device classify alike.
 MA_HD int ksw_job_class_pipe( const KswScoring& SC, i32 qlen, i32 tlen, i32 w, i32 zdrop, i32 flag )
 {
     const int e = ksw_ext_slots( SC, qlen, tlen, w, zdrop, flag );
+    const int right = ( flag & KSW_EZ_RIGHT ) ? 1 : 0;
     if( e && SC.grp >= 1000 && ksw_band_ok( SC, qlen, tlen, w, zdrop, flag, SC.grp - 1000 ) )
-        return KSW_CLS_GRP0 + ( ( flag & KSW_EZ_RIGHT ) ? 1 : 0 ); // the proven narrow band: four jobs per wave (ksw_band.h)
-    if( e == 1 && ksw_grp_enabled( ) )
+        return KSW_CLS_NARROW_L + right;
+    if( e == 1 && SC.grp != 0 )
         if( const int G = ksw_grp_size( SC, qlen, tlen, w, zdrop, flag ) )
-            return KSW_CLS_GRP0 + ( G == 4 ? 4 : ( G == 2 ? 2 : 0 ) ) + ( ( flag & KSW_EZ_RIGHT ) ? 1 : 0 );
+            return ( G == 4 ? KSW_CLS_GRP4_L : KSW_CLS_GRP2_L ) + right;
     if( !e && SC.band_long && ksw_bandl_ok( SC, qlen, tlen, w, zdrop, flag ) )
-        return KSW_CLS_BANDL + ( ( flag & KSW_EZ_RIGHT ) ? 1 : 0 ); // the proven band of 120, one long job per wave (ksw_band.h)
-    return e ? 4 + e : ksw_job_class( qlen, tlen, w );
+        return KSW_CLS_BANDL_L + right;
+    return e ? KSW_CLS_EXT1 + ( e - 1 ) : ksw_job_class( qlen, tlen, w );
+}
+
+// THE routing of a pipeline job: its final class, and what the sizing of the launches takes from it.  k_dp_enum (through
+// ksw_route_slot) and the host path of ma_ksw_ext_batch (prims.hip) both come here.
+struct KswRoute
+{
+    int cls; // class after both demotions
+    u32 cig; // cigar words of the job's scratch
+    u64 p; // direction bytes in its class's kernel (0 from KSW_CLS_GRP0 on: fixed scratch per wave)
+    u64 pk; // direction bytes in the exact kernels (ksw_p_bytes) ...
+    bool redo; // ... which count when its kernel may hand it back to them (pRedo / cigRedo)
+    u32 bandlN; // a job on the band of 120: its min(qlen, tlen), else 0
+    int ext; // a job on the narrow band: the extension class it goes on to if it fails its checks, else 0 ...
+    u64 pExt; // ... and its direction bytes there
+};
+// qf / tf: base i of the query / target in DP order.  tryAll (MA_KSW_BAND_ALL, host only): no pre-filters, every eligible job is tried
+// on its band.
+template <typename QF, typename TF>
+MA_HD KswRoute ksw_route_job( const KswScoring& SC, i32 qlen, i32 tlen, i32 w, i32 zdrop, i32 flag, const QF& qf, const TF& tf, bool tryAll )
+{
+    KswRoute R;
+    R.cls = ksw_job_class_pipe( SC, qlen, tlen, w, zdrop, flag );
+    // the narrow band is tried on the jobs whose query follows the target's main diagonal, the band of 120 on the long extensions whose
+    // first bases follow the target with few edits; the others go to the kernels they would go to without the band
+    if( !tryAll && SC.grp >= 1000 && ( R.cls == KSW_CLS_NARROW_L || R.cls == KSW_CLS_NARROW_R ) && !ksw_band_likely( qf, tf, qlen, tlen, SC.band_mis ) )
+    {
+        KswScoring S1 = SC;
+        S1.grp = 1;
+        R.cls = ksw_job_class_pipe( S1, qlen, tlen, w, zdrop, flag );
+    }
+    if( !tryAll && ( R.cls == KSW_CLS_BANDL_L || R.cls == KSW_CLS_BANDL_R ) && !ksw_bandl_likely( qf, tf, qlen, tlen ) )
+    {
+        KswScoring S1 = SC;
+        S1.band_long = 0;
+        R.cls = ksw_job_class_pipe( S1, qlen, tlen, w, zdrop, flag );
+    }
+    R.cig = (u32)( qlen + tlen + 2 );
+    R.pk = ksw_p_bytes( qlen, tlen, w );
+    R.p = R.cls >= KSW_CLS_GRP0 ? 0 : ( R.cls >= KSW_CLS_EXT1 ? ksw_ext_p_bytes( qlen, tlen, R.cls - KSW_CLS_EXT1 + 1 ) : R.pk );
+    R.redo = R.cls >= KSW_CLS_EXT1;
+    R.bandlN = R.cls == KSW_CLS_BANDL_L || R.cls == KSW_CLS_BANDL_R ? (u32)( qlen < tlen ? qlen : tlen ) : 0u;
+    R.ext = 0, R.pExt = 0;
+    if( SC.grp >= 1000 && ( R.cls == KSW_CLS_NARROW_L || R.cls == KSW_CLS_NARROW_R ) )
+    {
+        const int e = ksw_ext_slots( SC, qlen, tlen, w, zdrop, flag );
+        R.ext = KSW_CLS_EXT1 + ( e - 1 );
+        R.pExt = ksw_ext_p_bytes( qlen, tlen, e );
+    }
+    return R;
+}
+// ... of a job slot of the pipeline: the bases come from the batch's reads and the packed reference
+MA_HD KswRoute ksw_route_slot( const KswScoring& SC, const IndexView& X, const uint8_t* reads, const DpJob& j )
+{
+    const uint8_t* qb = reads + j.read_off;
+    auto qf = [ & ]( i32 i ) -> u32 { return j.rev ? qb[ j.q_to - 1 - (u32)i ] : qb[ j.q_from + (u32)i ]; };
+    auto tf = [ & ]( i32 i ) -> u32 { return text_base( X, j.win_begin + ( j.rev ? j.r_to - 1 - (u32)i : j.r_from + (u32)i ) ); };
+    return ksw_route_job( SC, (i32)( j.q_to - j.q_from ), (i32)( j.r_to - j.r_from ), j.w, j.zdrop, j.flag, qf, tf, false );
 }
 
 // job source of a launch: mode 0 = list[0..n), 1 = every slot 0..n that is valid and of class cls,
@@ -396,7 +484,7 @@ __global__ void __launch_bounds__( 64 ) k_ksw( FETCH F, KswScoring SC, KswJobs J
         if( JB.mode == 1 && !F.valid( slot ) )
             continue;
         const KswJobView J = F.view( slot );
-        if( JB.mode != 0 && ksw_job_class( J.qlen, J.tlen, J.w ) != 4 )
+        if( JB.mode != 0 && ksw_job_class( J.qlen, J.tlen, J.w ) != KSW_CLS_LDS )
             continue; // handled by a register-resident launch
         M.L = ( ( J.tlen + 15 ) / 16 ) * 16;
         KswEz ez;
@@ -416,18 +504,11 @@ __global__ void __launch_bounds__( 64 ) k_ksw( FETCH F, KswScoring SC, KswJobs J
 inline i32 ksw_grp_env( ) // KswScoring::grp (read on every call: the tests switch it inside one process)
 {
     const char* e = getenv( "MA_KSW_GRP" );
-    // 2 (experiment build -DMA_EXP_GRP_NR2 only): also the jobs of 65..128 query bases, two per wave with four rows per lane -- measured slower than k_ksw_ext<1> (150 bp:
-    // DP 19.1 -> 20.0 ms): a register set's recurrence is 76 of the ~91 instructions of a diagonal, so sharing the rest buys 16 % per
-    // job at best, and 128 VGPRs leave 4 waves per SIMD where k_ksw_ext runs 8
-    // 3 (or 1000 + n): extensions of 65 (n) .. 254 query bases on the proven narrow band, four per wave (ksw_band.h).  Default: 1033
-    // (150 bp: DP 19.0 ms with 1, 16.4 with 3, 15.7 with 1033)
+    // 0: one job per wavefront; 1: queries of up to 64 bases share a wavefront (2, once the four-rows-per-lane experiment of DESIGN.md
+    // section 3.4, reads as 1); 3 (or 1000 + n): extensions of 65 (n) .. 254 query bases on the proven narrow band, four per wave
+    // (ksw_band.h).  Default: 1033 (150 bp: DP 19.0 ms with 1, 16.4 with 3, 15.7 with 1033)
     const i32 v = e ? std::max( 0, atoi( e ) ) : 1033;
-#if defined( MA_EXP_GRP_NR2 )
-    const i32 top = 2;
-#else
-    const i32 top = 1; // the shipped library has no four-rows-per-lane kernels (measured slower): 2 means 1
-#endif
-    return v == 3 ? 1065 : ( v >= 1000 ? std::min( v, 1000 + KSW_BAND_QMAX ) : std::min( v, top ) );
+    return v == 3 ? 1065 : ( v >= 1000 ? std::min( v, 1000 + KSW_BAND_QMAX ) : std::min( v, 1 ) );
 }
 inline i32 ksw_bandl_env( ) // KswScoring::band_long
 {
@@ -468,6 +549,24 @@ inline void ksw_size_job( KswSizing& S, i32 qlen, i32 tlen, i32 w )
     const u64 c = (u64)qlen + tlen + 2;
     S.cig = S.cig > c ? S.cig : c;
 }
+// ... and what a routed pipeline job adds to the per-class part (k_dp_enum does the same with atomics on the batch's counters)
+inline void ksw_size_route( KswSizing& S, const KswRoute& R )
+{
+    S.cls[ R.cls ]++;
+    S.pc[ R.cls ] = std::max( S.pc[ R.cls ], R.p );
+    S.cigc[ R.cls ] = std::max<u64>( S.cigc[ R.cls ], R.cig );
+    S.bandlN = std::max<u64>( S.bandlN, R.bandlN );
+    if( R.redo )
+    {
+        S.pRedo = std::max( S.pRedo, R.pk );
+        S.cigRedo = std::max<u64>( S.cigRedo, R.cig );
+    }
+    if( R.ext )
+    {
+        S.pc[ R.ext ] = std::max( S.pc[ R.ext ], R.pExt );
+        S.cigc[ R.ext ] = std::max<u64>( S.cigc[ R.ext ], R.cig );
+    }
+}
 
 // Plans the launch: fills WS (without base) and returns waves + dynamic LDS bytes
 struct KswPlan
@@ -505,12 +604,9 @@ inline KswPlan ksw_plan( const KswSizing& S, u64 nJobs, u64 scratch_budget_bytes
     return P;
 }
 
-// Launches every class that has jobs.  `next` = 28 zeroed counters (one per launch; [11..16]: the six lists of k_ksw_grp, [17], [18]:
-// jobs the narrow band appended to the extension kernels' lists, [19], [20]: the two lists of long jobs on the band of 120, [21..24]:
-// the launches that take the long jobs the band handed back when they have a stream of their own, [25]: the number of those jobs),
-// `nextBig` = 4 more.  `lists`
+// Launches every class that has jobs.  `next` = KSW_N_NEXT zeroed counters (KSW_NX_*), `nextBig` = KSW_N_NEXT_BIG more.  `lists`
 // (device, or null) holds the job slots of class k at lists + k * list_stride, SZ.cls[k] entries, and room for the jobs
-// the extension kernel hands back at lists + KSW_N_CLASSES * list_stride (counted in *nRedo); without lists every
+// the extension kernels hand back at lists + KSW_N_CLASSES * list_stride (counted in *nRedo); without lists every
 // launch scans nSlots and there are no extension-kernel classes.
 //
 // Scratch: every wave owns `stride` bytes (direction bytes + cigar of the job it is working on) of one allocation that
@@ -572,6 +668,21 @@ struct KswSide
 // LDS bytes of a job's query window (ksw_q_lds) up to which it runs in the class's first tier: the register kernels'
 // minimum per-wave LDS, so that 16 waves take 96 KB of a CU's 160 KB and the extension kernels' waves still fit beside them
 #define KSW_Q_SPLIT KSW_REG_LDS
+// the instantiations a launch picks from by a run-time index: exact class k, list k of the wavefront-sharing classes, direction
+template <typename FETCH> auto ksw_pk_kernel( int k ) -> decltype( &k_ksw_pk<FETCH, KSW_S0> )
+{
+    return k == KSW_CLS_PK0 ? k_ksw_pk<FETCH, KSW_S0>
+                            : ( k == KSW_CLS_PK1 ? k_ksw_pk<FETCH, KSW_S1> : ( k == KSW_CLS_PK2 ? k_ksw_pk<FETCH, KSW_S2> : k_ksw_pk<FETCH, KSW_S3> ) );
+}
+template <typename FETCH> auto ksw_grp_kernel( int cls ) -> decltype( &k_ksw_grp<FETCH, 2, 1, true> )
+{
+    return cls == KSW_CLS_GRP2_L ? k_ksw_grp<FETCH, 2, 1, true>
+                                 : ( cls == KSW_CLS_GRP2_R ? k_ksw_grp<FETCH, 2, 1, false> : ( cls == KSW_CLS_GRP4_L ? k_ksw_grp<FETCH, 4, 1, true> : k_ksw_grp<FETCH, 4, 1, false> ) );
+}
+template <typename FETCH, int G> auto ksw_band_kernel( bool left ) -> decltype( &k_ksw_band<FETCH, true, G> )
+{
+    return left ? k_ksw_band<FETCH, true, G> : k_ksw_band<FETCH, false, G>;
+}
 template <typename FETCH>
 int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizing& SZ, DevBuf& scratch,
                  unsigned int* next, KswOut O, hipStream_t stream, u32* lists = nullptr, u64 list_stride = 0,
@@ -583,12 +694,14 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
         nJobs += SZ.cls[ k ];
     if( nJobs == 0 )
         return 0;
-    const u64 nGrp = SZ.cls[ 7 ] + SZ.cls[ 8 ] + SZ.cls[ 9 ] + SZ.cls[ 10 ] + SZ.cls[ 11 ] + SZ.cls[ 12 ];
+    u64 nGrp = 0;
+    for( int k = 0; k < KSW_GRP_LISTS; k++ )
+        nGrp += SZ.cls[ KSW_CLS_GRP0 + k ];
     // jobs on the proven narrow band (ksw_band.h): those that fail a check are appended to the lists of k_ksw_ext<1> / <2>, which
-    // run after them (next[ 17 ], next[ 18 ] count them)
-    const u64 nBand = SC.grp >= 1000 ? SZ.cls[ 7 ] + SZ.cls[ 8 ] : 0;
-    const u64 nBandL = SZ.cls[ KSW_CLS_BANDL ] + SZ.cls[ KSW_CLS_BANDL + 1 ]; // long jobs on the band of 120; those that fail go to `redo`
-    const u64 nExt = SZ.cls[ 5 ] + SZ.cls[ 6 ] + nGrp + nBandL;
+    // run after them (next[ KSW_NX_BAND_EXT + 0 / 1 ] count them)
+    const u64 nBand = SC.grp >= 1000 ? SZ.cls[ KSW_CLS_NARROW_L ] + SZ.cls[ KSW_CLS_NARROW_R ] : 0;
+    const u64 nBandL = SZ.cls[ KSW_CLS_BANDL_L ] + SZ.cls[ KSW_CLS_BANDL_R ]; // long jobs on the band of 120; those that fail go to `redo`
+    const u64 nExt = SZ.cls[ KSW_CLS_EXT1 ] + SZ.cls[ KSW_CLS_EXT2 ] + nGrp + nBandL;
     const bool conc = side && side->ready( ) && lists; // classes on their own streams
     u64 perCu = 32; // waves per CU of the persistent ksw launches (MA_KSW_WAVES_PER_CU: tuning hook)
     if( const char* e = getenv( "MA_KSW_WAVES_PER_CU" ) )
@@ -597,23 +710,30 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
     // Concurrent launches each own a scratch region, so each asks only for the waves that can be RESIDENT (registers:
     // k_ksw_pk<1> 74 VGPRs = 6 waves per SIMD, <2> 99, <3> 122, <5> 128 = 4; the extension kernels 7 / 4): a persistent wave
     // beyond that would only start when another one retires and its scratch would sit idle until then.
-    const u64 resident[ 7 ] = { 256 * 24, 256 * 16, 256 * 16, 256 * 16, 0, 256 * 28, 256 * 16 };
+    const u64 resident[ KSW_CLS_GRP0 ] = { 256 * 24, 256 * 16, 256 * 16, 256 * 16, 0, 256 * 28, 256 * 16 };
     auto wantOf = [ & ]( int k ) { return conc ? std::min<u64>( wantWaves, resident[ k ] ) : wantWaves; };
     // budgets of the scratch regions: lane 0 / 1 / 2 (sequential launches of a lane share its region)
     const u64 B = KSW_SCRATCH_BUDGET; // one reading per call
-    const u64 budgetOf[ 7 ] = { conc ? B / 3 : B, conc ? B / 3 : B, conc ? B / 3 : B, conc ? 5 * B / 12 : B, B, conc ? B / 4 : B, conc ? B / 4 : B };
+    const u64 budgetOf[ KSW_CLS_GRP0 ] = { conc ? B / 3 : B, conc ? B / 3 : B, conc ? B / 3 : B, conc ? 5 * B / 12 : B, B, conc ? B / 4 : B, conc ? B / 4 : B };
     auto ldsOf = []( u64 qBytes ) { return std::max<u32>( (u32)( ( ( std::min<u64>( qBytes, 150000 + 64 ) + 15 ) / 16 ) * 16 ), KSW_REG_LDS ); };
-    // pass 0 launches of the register kernels: classes 0..3 (exact), 5 / 6 (extension); [7..10]: classes 0..3 of the
-    // second pass (jobs handed back), [11..14]: the huge tier of classes 0..3
-    KswLaunchPlan LP[ 15 ];
+    // launch plans of the register kernels, in three banks: the classes' own launches (pass 0: KSW_CLS_PK0 .. PK3 exact,
+    // KSW_CLS_EXT1 / EXT2 extension), the exact classes' second pass over the jobs handed back, their huge tiers
+    enum : int
+    {
+        LP_CLS = 0, // + class
+        LP_REDO = KSW_CLS_GRP0, // + k
+        LP_BIG = LP_REDO + 4, // + k
+        LP_N = LP_BIG + 4
+    };
+    KswLaunchPlan LP[ LP_N ];
     u64 pSplit[ 4 ] = { 0, 0, 0, 0 };
     // k_ksw_grp: fixed scratch per wave (KSW_GRP_ROWS direction rows; the cigars stay in LDS), 5 waves per SIMD
     KswLaunchPlan LG;
     if( nGrp )
     {
-        const u64 sets = ( SZ.cls[ 7 ] + 1 ) / ( SC.grp >= 1000 ? 4 : 2 ) + ( SZ.cls[ 8 ] + 1 ) / ( SC.grp >= 1000 ? 4 : 2 ) + ( SZ.cls[ 9 ] + 1 ) / 2 + ( SZ.cls[ 10 ] + 1 ) / 2 + ( SZ.cls[ 11 ] + 3 ) / 4 + ( SZ.cls[ 12 ] + 3 ) / 4;
-        // (direction rows of 256 B when the four-rows-per-lane lists have jobs)
-        LG = ksw_plan_launch( (u64)KSW_GRP_ROWS * ( SC.grp < 1000 && SZ.cls[ 7 ] + SZ.cls[ 8 ] ? 256 : 128 ), 0, sets, std::min<u64>( wantWaves, 256 * 20 ), conc ? B / 4 : B );
+        const u64 sets = ( SZ.cls[ KSW_CLS_NARROW_L ] + 1 ) / ( SC.grp >= 1000 ? 4 : 2 ) + ( SZ.cls[ KSW_CLS_NARROW_R ] + 1 ) / ( SC.grp >= 1000 ? 4 : 2 ) +
+                         ( SZ.cls[ KSW_CLS_GRP2_L ] + 1 ) / 2 + ( SZ.cls[ KSW_CLS_GRP2_R ] + 1 ) / 2 + ( SZ.cls[ KSW_CLS_GRP4_L ] + 3 ) / 4 + ( SZ.cls[ KSW_CLS_GRP4_R ] + 3 ) / 4;
+        LG = ksw_plan_launch( (u64)KSW_GRP_ROWS * 128, 0, sets, std::min<u64>( wantWaves, 256 * 20 ), conc ? B / 4 : B );
     }
     KswLaunchPlan LBL; // k_ksw_band<.., 1>: KSW_BANDL_ROWS direction rows per wave, 5 waves per SIMD
     // The few long jobs the band hands back (0.1 % of a 10 kb batch, and the long ones among them: queries AND targets of thousands of
@@ -636,16 +756,17 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
         LPR = ksw_plan_launch( SZ.pRedo ? SZ.pRedo : SZ.p, SZ.cigRedo ? SZ.cigRedo : SZ.cig, std::min<u64>( nBandL / 4 + 64, 256 * 8 ), wantWaves, B / 4 );
         LPR.lds = ldsOf( std::min<u64>( SZ.qlen, SZ.cigRedo ? SZ.cigRedo : SZ.qlen ) + 48 );
     }
-    for( int k = 0; k < 7; k++ )
+    for( int k = 0; k < KSW_CLS_GRP0; k++ )
     {
-        if( k == 4 || ( SZ.cls[ k ] == 0 && !( k >= 5 && nBand ) ) )
+        const bool isExt = k >= KSW_CLS_EXT1;
+        if( k == KSW_CLS_LDS || ( SZ.cls[ k ] == 0 && !( isExt && nBand ) ) )
             continue;
-        const u64 pk = SZ.pc[ k ] ? SZ.pc[ k ] : ( k >= 5 ? std::max( SZ.p, ksw_ext_p_bytes( 256, 2048, k - 4 ) ) : SZ.p );
+        const u64 pk = SZ.pc[ k ] ? SZ.pc[ k ] : ( isExt ? std::max( SZ.p, ksw_ext_p_bytes( 256, 2048, k - KSW_CLS_EXT1 + 1 ) ) : SZ.p );
         const u64 cg = SZ.cigc[ k ] ? SZ.cigc[ k ] : SZ.cig;
         // (the narrow band hands on a few per cent of its jobs: the extension kernels' waves are planned for their own jobs plus a
         // sixteenth of the band's -- more of them would only wait their turn)
-        LP[ k ] = ksw_plan_launch( pk, cg, SZ.cls[ k ] + ( k >= 5 && nBand ? nBand / 16 + 64 : 0 ), wantOf( k ), budgetOf[ k ] );
-        if( k >= 5 )
+        LP[ k ] = ksw_plan_launch( pk, cg, SZ.cls[ k ] + ( isExt && nBand ? nBand / 16 + 64 : 0 ), wantOf( k ), budgetOf[ k ] );
+        if( isExt )
         {
             LP[ k ].lds = KSW_EXT_LDS;
             continue;
@@ -675,12 +796,12 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
         }
         if( nextBig && ( splitP || splitQ ) )
         {
-            LP[ 11 + k ] = LP[ k ]; // the huge jobs: what the small tier leaves
-            LP[ 11 + k ].tier = 2;
+            LP[ LP_BIG + k ] = LP[ k ]; // the huge jobs: what the small tier leaves
+            LP[ LP_BIG + k ].tier = 2;
             if( conc ) // their region is a fixed quarter of the budget (a region that follows the largest job of every batch
                        // would be re-allocated -- seconds, device-wide -- whenever a later batch brings a larger one)
-                LP[ 11 + k ].waves = (u32)std::max<u64>( 1, std::min<u64>( std::min<u32>( LP[ 11 + k ].waves, KSW_SIDE_WAVES ),
-                                                                        ( B / 4 ) / std::max<u64>( LP[ 11 + k ].stride, 1 ) ) );
+                LP[ LP_BIG + k ].waves = (u32)std::max<u64>( 1, std::min<u64>( std::min<u32>( LP[ LP_BIG + k ].waves, KSW_SIDE_WAVES ),
+                                                                        ( B / 4 ) / std::max<u64>( LP[ LP_BIG + k ].stride, 1 ) ) );
             const u64 cgSmall = splitP ? std::min<u64>( cg, pSmall / 16 + 3 ) : cg;
             LP[ k ] = ksw_plan_launch( pSmall, cgSmall, SZ.cls[ k ], wantOf( k ), budgetOf[ k ] );
             LP[ k ].tier = 1;
@@ -689,30 +810,30 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
         }
     }
     if( nExt )
-        for( int k = 0; k < 4; k++ )
+        for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
         {
             // (the band of 120 proves nearly all of its jobs: a quarter of them as waves of the second pass is plenty)
-            LP[ 7 + k ] = ksw_plan_launch( SZ.pRedo ? SZ.pRedo : SZ.p, SZ.cigRedo ? SZ.cigRedo : SZ.cig,
+            LP[ LP_REDO + k ] = ksw_plan_launch( SZ.pRedo ? SZ.pRedo : SZ.p, SZ.cigRedo ? SZ.cigRedo : SZ.cig,
                                            std::min<u64>( nExt, 256 * 4 ) + std::min<u64>( nBandL / 4, 256 * 12 ), wantWaves, conc ? B / 4 : B );
-            LP[ 7 + k ].lds = ldsOf( std::min<u64>( SZ.qlen, SZ.cigRedo ? SZ.cigRedo : SZ.qlen ) + 48 );
+            LP[ LP_REDO + k ].lds = ldsOf( std::min<u64>( SZ.qlen, SZ.cigRedo ? SZ.cigRedo : SZ.qlen ) + 48 );
         }
-    KswPlan plan = ksw_plan( SZ, SZ.cls[ 4 ] ? SZ.cls[ 4 ] : 1, conc ? B / 4 : B );
+    KswPlan plan = ksw_plan( SZ, SZ.cls[ KSW_CLS_LDS ] ? SZ.cls[ KSW_CLS_LDS ] : 1, conc ? B / 4 : B );
     // scratch regions.  Sequential mode: one region for all launches (+ one for the huge tiers when they have a stream).
-    // Concurrent mode: lane 0 = extension classes, handed-back jobs, LDS kernel; lane 1 = class 3; lane 2 = classes 0..2;
+    // Concurrent mode: lane 0 = extension classes, handed-back jobs, LDS kernel; lane 1 = KSW_CLS_PK3; lane 2 = KSW_CLS_PK0 .. PK2;
     // lane 3 = huge tiers.
     auto laneOf = [ & ]( int i ) -> int {
         if( !conc )
-            return i >= 11 && side && side->stream[ 2 ] ? 3 : 0;
-        if( i >= 11 )
+            return i >= LP_BIG && side && side->stream[ 2 ] ? 3 : 0;
+        if( i >= LP_BIG )
             return 3;
-        if( i == 3 )
+        if( i == LP_CLS + KSW_CLS_PK3 )
             return 1;
-        if( i <= 2 )
+        if( i <= LP_CLS + KSW_CLS_PK2 )
             return 2;
         return 0;
     };
-    u64 needLane[ 4 ] = { std::max<u64>( std::max<u64>( SZ.cls[ 4 ] ? plan.ws.stride * plan.waves : 0, LG.stride * LG.waves ), LBL.stride * LBL.waves ), 0, 0, 0 };
-    for( int i = 0; i < 15; i++ )
+    u64 needLane[ 4 ] = { std::max<u64>( std::max<u64>( SZ.cls[ KSW_CLS_LDS ] ? plan.ws.stride * plan.waves : 0, LG.stride * LG.waves ), LBL.stride * LBL.waves ), 0, 0, 0 };
+    for( int i = 0; i < LP_N; i++ )
         if( LP[ i ].waves )
             needLane[ laneOf( i ) ] = std::max<u64>( needLane[ laneOf( i ) ], LP[ i ].stride * LP[ i ].waves );
     if( ownRedo )
@@ -737,23 +858,19 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
     if( scratch.reserve( total ) )
         return 1;
     u32 ldsMax = LPR.lds;
-    for( int i = 0; i < 15; i++ )
-        if( i != 5 && i != 6 )
+    for( int i = 0; i < LP_N; i++ )
+        if( i != LP_CLS + KSW_CLS_EXT1 && i != LP_CLS + KSW_CLS_EXT2 )
             ldsMax = std::max( ldsMax, LP[ i ].lds );
     if( ldsMax > 48 * 1024 )
-    {
-        MA_HIP( hipFuncSetAttribute( (const void*)k_ksw_pk<FETCH, KSW_S0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsMax ) );
-        MA_HIP( hipFuncSetAttribute( (const void*)k_ksw_pk<FETCH, KSW_S1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsMax ) );
-        MA_HIP( hipFuncSetAttribute( (const void*)k_ksw_pk<FETCH, KSW_S2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsMax ) );
-        MA_HIP( hipFuncSetAttribute( (const void*)k_ksw_pk<FETCH, KSW_S3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsMax ) );
-    }
+        for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
+            MA_HIP( hipFuncSetAttribute( (const void*)ksw_pk_kernel<FETCH>( k ), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsMax ) );
     uint8_t* base = scratch.as<uint8_t>( );
     u32* redo = lists ? lists + (u64)KSW_N_CLASSES * list_stride : nullptr;
     u32* redoL = lists ? lists + (u64)( KSW_N_CLASSES + 1 ) * list_stride : nullptr; // (ownRedo: the long jobs the band of 120 handed back)
     hipStream_t laneStream[ 4 ] = { stream, conc ? side->stream[ 0 ] : stream, conc ? side->stream[ 1 ] : stream,
                                     side && side->stream[ 2 ] ? side->stream[ 2 ] : stream };
     bool laneUsed[ 4 ] = { true, false, false, false };
-    for( int i = 0; i < 15; i++ )
+    for( int i = 0; i < LP_N; i++ )
         if( LP[ i ].waves && laneStream[ laneOf( i ) ] != stream )
             laneUsed[ laneOf( i ) ] = true;
     if( ownRedo )
@@ -769,7 +886,7 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
     // pass 0: the classes' own jobs; pass 1: whatever the extension kernel handed back (usually nothing); pass 2: the huge
     // tier of a class that was split
     auto launchPk = [ & ]( int pass, int k ) {
-        const int i = pass == 0 ? k : ( pass == 1 ? 7 + k : 11 + k );
+        const int i = pass == 0 ? LP_CLS + k : ( pass == 1 ? LP_REDO + k : LP_BIG + k );
         const KswLaunchPlan& L = LP[ i ];
         if( L.waves == 0 )
             return;
@@ -782,29 +899,16 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
         JB.tier = pass == 1 ? 0 : L.tier;
         JB.pSplit = pSplit[ k ];
         JB.qSplit = KSW_Q_SPLIT;
-        unsigned int* nx = pass == 0 ? next + k : ( pass == 1 ? next + 7 + k : nextBig + k );
+        unsigned int* nx = pass == 0 ? next + KSW_NX_CLS + k : ( pass == 1 ? next + KSW_NX_REDO + k : nextBig + k );
         hipStream_t st = laneStream[ laneOf( i ) ];
         uint8_t* sbase = base + laneBase[ laneOf( i ) ];
-        switch( k )
-        {
-        case 0:
-            hipLaunchKernelGGL( ( k_ksw_pk<FETCH, KSW_S0> ), dim3( L.waves ), dim3( 64 ), L.lds, st, F, SC, JB, nx, sbase, L.stride, L.p_cap, L.lds, O );
-            break;
-        case 1:
-            hipLaunchKernelGGL( ( k_ksw_pk<FETCH, KSW_S1> ), dim3( L.waves ), dim3( 64 ), L.lds, st, F, SC, JB, nx, sbase, L.stride, L.p_cap, L.lds, O );
-            break;
-        case 2:
-            hipLaunchKernelGGL( ( k_ksw_pk<FETCH, KSW_S2> ), dim3( L.waves ), dim3( 64 ), L.lds, st, F, SC, JB, nx, sbase, L.stride, L.p_cap, L.lds, O );
-            break;
-        default:
-            hipLaunchKernelGGL( ( k_ksw_pk<FETCH, KSW_S3> ), dim3( L.waves ), dim3( 64 ), L.lds, st, F, SC, JB, nx, sbase, L.stride, L.p_cap, L.lds, O );
-        }
+        hipLaunchKernelGGL( ksw_pk_kernel<FETCH>( k ), dim3( L.waves ), dim3( 64 ), L.lds, st, F, SC, JB, nx, sbase, L.stride, L.p_cap, L.lds, O );
     };
     // longest jobs first: the huge tiers, then the wide classes; the extension kernels' small jobs fill the tails
-    for( int k = 3; k >= 0; k-- )
+    for( int k = KSW_CLS_PK3; k >= KSW_CLS_PK0; k-- )
         launchPk( 2, k );
     if( conc )
-        for( int k = 3; k >= 0; k-- )
+        for( int k = KSW_CLS_PK3; k >= KSW_CLS_PK0; k-- )
             launchPk( 0, k );
     if( nBandL ) // the long extensions on the band of 120 first: they are the longest jobs of lane 0
         for( int k = 0; k < 2; k++ )
@@ -815,43 +919,27 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
             const u32* lk = lists + (u64)( KSW_CLS_BANDL + k ) * list_stride;
             const u32 waves = (u32)std::max<u64>( 1, std::min<u64>( LBL.waves, nk ) );
             uint8_t* sb = base + laneBase[ 0 ];
-            if( k == 0 )
-                hipLaunchKernelGGL( ( k_ksw_band<FETCH, true, 1> ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + 19 + k, sb, LBL.stride, O,
-                                    ownRedo ? redoL : redo, 0u, (u32*)nullptr, 0u, ownRedo ? next + 25 : nRedo );
-            else
-                hipLaunchKernelGGL( ( k_ksw_band<FETCH, false, 1> ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + 19 + k, sb, LBL.stride, O,
-                                    ownRedo ? redoL : redo, 0u, (u32*)nullptr, 0u, ownRedo ? next + 25 : nRedo );
+            hipLaunchKernelGGL( ( ksw_band_kernel<FETCH, 1>( k == 0 ) ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + KSW_NX_BANDL + k, sb, LBL.stride, O,
+                                ownRedo ? redoL : redo, 0u, (u32*)nullptr, 0u, ownRedo ? next + KSW_NX_N_REDOL : nRedo );
         }
     if( ownRedo )
     {
         MA_HIP( hipEventRecord( side->band, stream ) );
         MA_HIP( hipStreamWaitEvent( laneStream[ 3 ], side->band, 0 ) );
-        for( int k = 3; k >= 0; k-- )
+        for( int k = KSW_CLS_PK3; k >= KSW_CLS_PK0; k-- )
         {
             KswJobs JB;
             JB.list = redoL;
             JB.n = 0;
-            JB.nDev = next + 25;
+            JB.nDev = next + KSW_NX_N_REDOL;
             JB.mode = 2;
             JB.cls = k;
             JB.tier = 0;
             JB.pSplit = 0;
             JB.qSplit = KSW_Q_SPLIT;
             uint8_t* sb = base + laneBase[ 3 ];
-            switch( k )
-            {
-            case 0:
-                hipLaunchKernelGGL( ( k_ksw_pk<FETCH, KSW_S0> ), dim3( LPR.waves ), dim3( 64 ), LPR.lds, laneStream[ 3 ], F, SC, JB, next + 21 + k, sb, LPR.stride, LPR.p_cap, LPR.lds, O );
-                break;
-            case 1:
-                hipLaunchKernelGGL( ( k_ksw_pk<FETCH, KSW_S1> ), dim3( LPR.waves ), dim3( 64 ), LPR.lds, laneStream[ 3 ], F, SC, JB, next + 21 + k, sb, LPR.stride, LPR.p_cap, LPR.lds, O );
-                break;
-            case 2:
-                hipLaunchKernelGGL( ( k_ksw_pk<FETCH, KSW_S2> ), dim3( LPR.waves ), dim3( 64 ), LPR.lds, laneStream[ 3 ], F, SC, JB, next + 21 + k, sb, LPR.stride, LPR.p_cap, LPR.lds, O );
-                break;
-            default:
-                hipLaunchKernelGGL( ( k_ksw_pk<FETCH, KSW_S3> ), dim3( LPR.waves ), dim3( 64 ), LPR.lds, laneStream[ 3 ], F, SC, JB, next + 21 + k, sb, LPR.stride, LPR.p_cap, LPR.lds, O );
-            }
+            hipLaunchKernelGGL( ksw_pk_kernel<FETCH>( k ), dim3( LPR.waves ), dim3( 64 ), LPR.lds, laneStream[ 3 ], F, SC, JB, next + KSW_NX_REDOL + k, sb,
+                                LPR.stride, LPR.p_cap, LPR.lds, O );
         }
     }
     if( nGrp ) // the short extensions, several per wavefront (lane 0 of the streams, like the other extension kernels); longest first
@@ -864,62 +952,36 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
             const u32 Gk = k < 2 && SC.grp >= 1000 ? 4u : ( k < 4 ? 2u : 4u );
             const u32 waves = (u32)std::max<u64>( 1, std::min<u64>( LG.waves, ( nk + Gk - 1 ) / Gk ) );
             uint8_t* sb = base + laneBase[ 0 ];
-            switch( k )
-            {
-            case 0:
-                if( SC.grp >= 1000 )
-                {
-                    hipLaunchKernelGGL( ( k_ksw_band<FETCH, true> ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + 11 + k, sb, LG.stride, O,
-                                        lists + 5 * list_stride, (u32)SZ.cls[ 5 ], lists + 6 * list_stride, (u32)SZ.cls[ 6 ], next + 17 );
-                    break;
-                }
-#if defined( MA_EXP_GRP_NR2 ) // experiment build only (make expx X=-DMA_EXP_GRP_NR2): two jobs of 65..128 bases per wave, four rows per lane
-                hipLaunchKernelGGL( ( k_ksw_grp<FETCH, 2, 2, true> ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + 11 + k, sb, LG.stride, O, redo, nRedo );
-#endif
-                break;
-            case 1:
-                if( SC.grp >= 1000 )
-                {
-                    hipLaunchKernelGGL( ( k_ksw_band<FETCH, false> ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + 11 + k, sb, LG.stride, O,
-                                        lists + 5 * list_stride, (u32)SZ.cls[ 5 ], lists + 6 * list_stride, (u32)SZ.cls[ 6 ], next + 17 );
-                    break;
-                }
-#if defined( MA_EXP_GRP_NR2 )
-                hipLaunchKernelGGL( ( k_ksw_grp<FETCH, 2, 2, false> ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + 11 + k, sb, LG.stride, O, redo, nRedo );
-#endif
-                break;
-            case 2:
-                hipLaunchKernelGGL( ( k_ksw_grp<FETCH, 2, 1, true> ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + 11 + k, sb, LG.stride, O, redo, nRedo );
-                break;
-            case 3:
-                hipLaunchKernelGGL( ( k_ksw_grp<FETCH, 2, 1, false> ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + 11 + k, sb, LG.stride, O, redo, nRedo );
-                break;
-            case 4:
-                hipLaunchKernelGGL( ( k_ksw_grp<FETCH, 4, 1, true> ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + 11 + k, sb, LG.stride, O, redo, nRedo );
-                break;
-            default:
-                hipLaunchKernelGGL( ( k_ksw_grp<FETCH, 4, 1, false> ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + 11 + k, sb, LG.stride, O, redo, nRedo );
-            }
+            u32* const ext1 = lists + (u64)KSW_CLS_EXT1 * list_stride;
+            u32* const ext2 = lists + (u64)KSW_CLS_EXT2 * list_stride;
+            if( k >= 2 )
+                hipLaunchKernelGGL( ksw_grp_kernel<FETCH>( KSW_CLS_GRP0 + k ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + KSW_NX_GRP + k, sb,
+                                    LG.stride, O, redo, nRedo );
+            else if( SC.grp >= 1000 ) // (without the narrow band its two lists stay empty)
+                hipLaunchKernelGGL( ( ksw_band_kernel<FETCH, 4>( k == 0 ) ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + KSW_NX_GRP + k, sb, LG.stride, O,
+                                    ext1, (u32)SZ.cls[ KSW_CLS_EXT1 ], ext2, (u32)SZ.cls[ KSW_CLS_EXT2 ], next + KSW_NX_BAND_EXT );
         }
-    if( SZ.cls[ 5 ] || nBand )
-        hipLaunchKernelGGL( ( k_ksw_ext<FETCH, 1> ), dim3( LP[ 5 ].waves ), dim3( 64 ), KSW_EXT_LDS, stream, F, SC,
-                            lists + 5 * list_stride, (u32)SZ.cls[ 5 ], next + 5, base + laneBase[ 0 ], LP[ 5 ].stride, LP[ 5 ].p_cap, KSW_EXT_LDS,
-                            O, redo, nRedo, nBand ? next + 17 : nullptr );
-    if( SZ.cls[ 6 ] || nBand )
-        hipLaunchKernelGGL( ( k_ksw_ext<FETCH, 2> ), dim3( LP[ 6 ].waves ), dim3( 64 ), KSW_EXT_LDS, stream, F, SC,
-                            lists + 6 * list_stride, (u32)SZ.cls[ 6 ], next + 6, base + laneBase[ 0 ], LP[ 6 ].stride, LP[ 6 ].p_cap, KSW_EXT_LDS,
-                            O, redo, nRedo, nBand ? next + 18 : nullptr );
+    for( int e = 0; e < 2; e++ ) // k_ksw_ext<1>, k_ksw_ext<2>
+    {
+        const int c = KSW_CLS_EXT1 + e;
+        if( !( SZ.cls[ c ] || nBand ) )
+            continue;
+        const auto kernel = e == 0 ? k_ksw_ext<FETCH, 1> : k_ksw_ext<FETCH, 2>;
+        hipLaunchKernelGGL( kernel, dim3( LP[ LP_CLS + c ].waves ), dim3( 64 ), KSW_EXT_LDS, stream, F, SC, lists + (u64)c * list_stride, (u32)SZ.cls[ c ],
+                            next + KSW_NX_CLS + c, base + laneBase[ 0 ], LP[ LP_CLS + c ].stride, LP[ LP_CLS + c ].p_cap, KSW_EXT_LDS, O, redo, nRedo,
+                            nBand ? next + KSW_NX_BAND_EXT + e : nullptr );
+    }
     if( !conc )
-        for( int k = 0; k < 4; k++ )
+        for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
             launchPk( 0, k );
-    if( SZ.cls[ 4 ] ) // a handed-back job always fits a register kernel
+    if( SZ.cls[ KSW_CLS_LDS ] ) // a handed-back job always fits a register kernel
     {
         KswJobs JB;
-        JB.list = lists ? lists + (u64)4 * list_stride : nullptr;
-        JB.n = lists ? (u32)SZ.cls[ 4 ] : nSlots;
+        JB.list = lists ? lists + (u64)KSW_CLS_LDS * list_stride : nullptr;
+        JB.n = lists ? (u32)SZ.cls[ KSW_CLS_LDS ] : nSlots;
         JB.nDev = nRedo;
         JB.mode = lists ? 0 : 1;
-        JB.cls = 4;
+        JB.cls = KSW_CLS_LDS;
         JB.tier = 0;
         JB.pSplit = 0;
         JB.qSplit = 0;
@@ -927,11 +989,11 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
         if( plan.lds_bytes > 48 * 1024 )
             MA_HIP( hipFuncSetAttribute( (const void*)k_ksw<FETCH>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)plan.lds_bytes ) );
-        hipLaunchKernelGGL( k_ksw<FETCH>, dim3( plan.waves ), dim3( 64 ), plan.lds_bytes, stream, F, SC, JB, next + 4,
+        hipLaunchKernelGGL( k_ksw<FETCH>, dim3( plan.waves ), dim3( 64 ), plan.lds_bytes, stream, F, SC, JB, next + KSW_NX_CLS + KSW_CLS_LDS,
                             plan.ws, plan.lds_bytes, O );
     }
     if( nExt )
-        for( int k = 0; k < 4; k++ )
+        for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
             launchPk( 1, k ); // on the batch's stream, behind the extension kernels that fill the list
     if( forked )
         for( int l = 1; l < 4; l++ )

@@ -26,8 +26,8 @@ static __device__ unsigned long long g_ksw_prof[ 16 ]; // phase cycle counters (
 struct KswScoring
 {
     i32 match, mismatch, q, e, q2, e2; // KswCppParam<5> (kswcpp.h:44-129)
-    // not a score: short extensions may share a wavefront (ksw_grp.h; ksw_job_class_pipe).  0 off, 1 queries up to 64 bases, 2 also
-    // 65..128 with four rows per lane (A/B), 1000 + n: extensions of n..254 query bases on the proven narrow band (ksw_band.h)
+    // not a score: short extensions may share a wavefront (ksw_grp.h; ksw_job_class_pipe).  0 off, 1 queries up to 64 bases,
+    // 1000 + n: extensions of n..254 query bases on the proven narrow band (ksw_band.h)
     i32 grp = 1;
     i32 band_mis = 5; // mismatches on the main diagonal up to which a job is tried on the narrow band (ksw_band_likely; MA_KSW_BAND_MAXMIS: tuning hook)
     i32 band_long = 1; // long extension jobs (queries beyond 254 bases) one per wavefront on the proven band of 120 (ksw_band.h; MA_KSW_BANDL=0: A/B hook)

@@ -182,32 +182,6 @@ int ma_dp_batch( ma_batch* b )
             O.cig_words = c + CTR_CIG_WORDS;
             {
                 EvTimer t( b, 4 );
-                hipStream_t dpStream = b->stream;
-#if defined( MA_EXP_DP_PRIO )
-                // Experiment (round 6): with several batches in flight the persistent DP waves of one batch keep another batch's seeding
-                // kernel out of the SIMDs.  On a stream of the lowest priority the dispatcher should prefer the other batches' kernels
-                // whenever a DP launch ends and wave slots come free.
-                if( !b->dpLow )
-                {
-                    int lo = 0, hi = 0;
-                    MA_HIP( hipDeviceGetStreamPriorityRange( &lo, &hi ) );
-                    MA_HIP( hipStreamCreateWithPriority( &b->dpLow, hipStreamNonBlocking, lo ) );
-                    MA_HIP( hipEventCreateWithFlags( &b->dpFork, hipEventDisableTiming ) );
-                    MA_HIP( hipEventCreateWithFlags( &b->dpJoin, hipEventDisableTiming ) );
-                }
-                dpStream = b->dpLow;
-                MA_HIP( hipEventRecord( b->dpFork, b->stream ) );
-                MA_HIP( hipStreamWaitEvent( dpStream, b->dpFork, 0 ) );
-                struct Rejoin
-                {
-                    ma_batch* b;
-                    ~Rejoin( )
-                    {
-                        (void)hipEventRecord( b->dpJoin, b->dpLow );
-                        (void)hipStreamWaitEvent( b->stream, b->dpJoin, 0 );
-                    }
-                } xRejoin{ b };
-#endif
                 // long reads: every kernel class on its own stream (ksw_launch.h), longest jobs first
                 const bool longReads = b->max_qlen > 254 && !dp_one_stream( );
                 if( longReads && !b->kswSide.ready( ) )
@@ -221,7 +195,7 @@ int ma_dp_batch( ma_batch* b )
                     }
                 }
                 if( longReads )
-                    for( int k : { 0, 1, 2, 3, KSW_CLS_BANDL, KSW_CLS_BANDL + 1 } )
+                    for( int k : { KSW_CLS_PK0, KSW_CLS_PK1, KSW_CLS_PK2, KSW_CLS_PK3, KSW_CLS_BANDL_L, KSW_CLS_BANDL_R } )
                     {
                         const u64 nk = S.cls[ k ];
                         if( nk < 2048 )
@@ -229,16 +203,16 @@ int ma_dp_batch( ma_batch* b )
                         u32* list = b->clsLists.as<u32>( ) + (u64)k * nSlots;
                         if( b->sortKey.reserve( nk * 4 ) || b->sortKey2.reserve( nk * 4 ) || b->sortVal2.reserve( nk * 4 ) )
                             return 1;
-                        hipLaunchKernelGGL( k_job_cost, dim3( (unsigned)( ( nk + 255 ) / 256 ) ), dim3( 256 ), 0, dpStream, F, list, (u32)nk,
+                        hipLaunchKernelGGL( k_job_cost, dim3( (unsigned)( ( nk + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream, F, list, (u32)nk,
                                             b->sortKey.as<u32>( ) );
                         size_t tb = 0;
                         MA_HIP( hipcub::DeviceRadixSort::SortPairsDescending( nullptr, tb, b->sortKey.as<u32>( ), b->sortKey2.as<u32>( ), list,
-                                                                              b->sortVal2.as<u32>( ), (int)nk, 0, 32, dpStream ) );
+                                                                              b->sortVal2.as<u32>( ), (int)nk, 0, 32, b->stream ) );
                         if( b->cubTmp.reserve( tb + 256 ) )
                             return 1;
                         MA_HIP( hipcub::DeviceRadixSort::SortPairsDescending( b->cubTmp.p, tb, b->sortKey.as<u32>( ), b->sortKey2.as<u32>( ), list,
-                                                                              b->sortVal2.as<u32>( ), (int)nk, 0, 32, dpStream ) );
-                        MA_HIP( hipMemcpyAsync( list, b->sortVal2.p, nk * 4, hipMemcpyDeviceToDevice, dpStream ) );
+                                                                              b->sortVal2.as<u32>( ), (int)nk, 0, 32, b->stream ) );
+                        MA_HIP( hipMemcpyAsync( list, b->sortVal2.p, nk * 4, hipMemcpyDeviceToDevice, b->stream ) );
                     }
                 // the wavefront-sharing classes: sets of about equally long jobs (MA_KSW_GRP_SORT=0: A/B hook)
                 if( []( ) { const char* e = getenv( "MA_KSW_GRP_SORT" ); return !e || atoi( e ) != 0; }( ) )
@@ -264,13 +238,13 @@ int ma_dp_batch( ma_batch* b )
                             at += G.n[ k ];
                         }
                         G.hist = b->sortKey.as<u32>( );
-                        MA_HIP( hipMemsetAsync( G.hist, 0, KSW_GRP_SORT_LISTS * 2 * KSW_GRP_BINS * 4, dpStream ) );
+                        MA_HIP( hipMemsetAsync( G.hist, 0, KSW_GRP_SORT_LISTS * 2 * KSW_GRP_BINS * 4, b->stream ) );
                         const dim3 grid( (unsigned)std::min<u64>( 1024, ( most + 255 ) / 256 ), KSW_GRP_SORT_LISTS );
-                        hipLaunchKernelGGL( k_grp_hist, grid, dim3( 256 ), 0, dpStream, F, G );
-                        hipLaunchKernelGGL( k_grp_scatter, grid, dim3( 256 ), 0, dpStream, F, G );
+                        hipLaunchKernelGGL( k_grp_hist, grid, dim3( 256 ), 0, b->stream, F, G );
+                        hipLaunchKernelGGL( k_grp_scatter, grid, dim3( 256 ), 0, b->stream, F, G );
                     }
                 }
-                if( ksw_run_all( F, SC, (u32)nSlots, S, b->kswScratch, (unsigned int*)( c + CTR_NEXT_SLOTS ), O, dpStream,
+                if( ksw_run_all( F, SC, (u32)nSlots, S, b->kswScratch, (unsigned int*)( c + CTR_NEXT_SLOTS ), O, b->stream,
                                  b->clsLists.as<u32>( ), nSlots, (unsigned int*)( c + CTR_N_REDO ), (unsigned int*)( c + CTR_NEXT_BIG ),
                                  longReads ? &b->kswSide : nullptr ) )
                     return 1;
@@ -284,7 +258,7 @@ int ma_dp_batch( ma_batch* b )
             MA_HIP( hipMemsetAsync( c + CTR_ERR, 0, ( CTR_KSW_JOBS - CTR_ERR + 1 ) * 8, b->stream ) ); // ERR, CIG_USED, CELLS, KSW_JOBS
             MA_HIP( hipMemsetAsync( c + CTR_PATH_BYTES, 0, 8, b->stream ) );
             MA_HIP( hipMemsetAsync( c + CTR_NEXT_SLOTS, 0, ( CTR_NEXT_SEED - CTR_NEXT_SLOTS ) * 8, b->stream ) ); // queues, N_REDO, CIG_WORDS
-            MA_HIP( hipMemsetAsync( c + CTR_NEXT_BIG, 0, 16, b->stream ) );
+            MA_HIP( hipMemsetAsync( c + CTR_NEXT_BIG, 0, KSW_N_NEXT_BIG * 4, b->stream ) );
             // (the result records are NOT cleared: every listed job writes its own again, and the records of the 1 x 1 gap
             // fills, which the enumeration wrote, must stay)
         }

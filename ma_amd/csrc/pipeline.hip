@@ -41,28 +41,29 @@ enum : int
     CTR_N_ALIGNED = 17,
     CTR_SEQ_BYTES = 18, // sum of qlen+tlen over DP jobs
     CTR_PATH_BYTES = 19, // back-trace steps (direction bytes read back)
-    CTR_CLS0 = 20, // DP jobs per kernel class (KSW_N_CLASSES = 15 consecutive words)
-    CTR_MAX_QLEN = 35,
-    CTR_NEXT_SLOTS = 36, // 28 x u32 job queues / list counters of the ksw launches (14 words; ksw_run_all: `next`)
-    CTR_N_REDO = 50, // u32: jobs the extension kernels (and the band of 120) handed back
-    CTR_CIG_WORDS = 51, // cigar words written (CTR_CIG_USED counts pool words reserved)
-    CTR_NEXT_SEED = 52, // queue of k_lf_walk
-    CTR_OPS_ALL = 53, // alignment ops of all alignments / of the MappingQuality selection (exact sizes of the downloads)
-    CTR_OPS_MQ = 54,
-    CTR_ALN_MQ = 55, // alignments MappingQuality keeps
-    CTR_MAX_PC0 = 56, // per kernel class: largest direction-byte scratch of a job (15 words) ...
-    CTR_MAX_CIGC0 = 71, // ... and largest cigar scratch in words (15 words)
-    CTR_MAX_P_REDO = 86, // the same two for the extension kernels' jobs if they are handed back to the exact kernel
-    CTR_MAX_CIG_REDO = 87,
-    CTR_NEXT_BIG = 88, // 4 x u32 job queues of the second (few waves, large scratch) launch of a class (2 words)
-    CTR_N_1X1 = 90, // 1 x 1 gap fills answered by k_dp_enum itself (counted as ksw calls of one cell each)
-    CTR_MAX_BANDL = 91, // largest min(qlen, tlen) of the long jobs on the band of 120 (scratch rows of their launch)
-    CTR_PAIR_RECS = 92, // ma_pair_batch: records / ops of the picked pairs (exact sizes of the pair download) ...
-    CTR_PAIR_OPS = 93,
-    CTR_PAIR_OVER = 94, // ... pairs k_pair_pick left to the host, pairs without any candidate (stage_pair.h)
-    CTR_PAIR_ERR = 95,
-    CTR_COUNT = 96
+    CTR_CLS0 = 20, // DP jobs per kernel class (KSW_N_CLASSES consecutive words, indexed by KSW_CLS_*)
+    CTR_MAX_QLEN = CTR_CLS0 + KSW_N_CLASSES,
+    CTR_NEXT_SLOTS, // KSW_N_NEXT x u32 job queues / list counters of the ksw launches (ksw_run_all: `next`, KSW_NX_*)
+    CTR_N_REDO = CTR_NEXT_SLOTS + KSW_N_NEXT / 2, // u32: jobs the extension kernels (and the band of 120) handed back
+    CTR_CIG_WORDS, // cigar words written (CTR_CIG_USED counts pool words reserved)
+    CTR_NEXT_SEED, // queue of k_lf_walk
+    CTR_OPS_ALL, // alignment ops of all alignments / of the MappingQuality selection (exact sizes of the downloads)
+    CTR_OPS_MQ,
+    CTR_ALN_MQ, // alignments MappingQuality keeps
+    CTR_MAX_PC0, // per kernel class: largest direction-byte scratch of a job (KSW_N_CLASSES words) ...
+    CTR_MAX_CIGC0 = CTR_MAX_PC0 + KSW_N_CLASSES, // ... and largest cigar scratch in words (KSW_N_CLASSES words)
+    CTR_MAX_P_REDO = CTR_MAX_CIGC0 + KSW_N_CLASSES, // the same two for the extension kernels' jobs if they are handed back to the exact kernel
+    CTR_MAX_CIG_REDO,
+    CTR_NEXT_BIG, // KSW_N_NEXT_BIG x u32 job queues of the second (few waves, large scratch) launch of a class
+    CTR_N_1X1 = CTR_NEXT_BIG + KSW_N_NEXT_BIG / 2, // 1 x 1 gap fills answered by k_dp_enum itself (counted as ksw calls of one cell each)
+    CTR_MAX_BANDL, // largest min(qlen, tlen) of the long jobs on the band of 120 (scratch rows of their launch)
+    CTR_PAIR_RECS, // ma_pair_batch: records / ops of the picked pairs (exact sizes of the pair download) ...
+    CTR_PAIR_OPS,
+    CTR_PAIR_OVER, // ... pairs k_pair_pick left to the host, pairs without any candidate (stage_pair.h)
+    CTR_PAIR_ERR,
+    CTR_COUNT
 };
+static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0, "the counter block is 96 words; the u32 queues fill whole words" );
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -119,10 +120,6 @@ struct ma_batch
     u64 pairRecs = 0, pairNOps = 0, pairOnHost = 0;
     u64 cigPoolCap = 0, cigPoolMin = 0, nOpsCap = 0, nJobSlots = 0;
     KswSide kswSide; // created on first use
-#if defined( MA_EXP_DP_PRIO ) // experiment build: the DP kernels of a batch on a stream of the lowest priority (launch_dp.h)
-    hipStream_t dpLow = nullptr;
-    hipEvent_t dpFork = nullptr, dpJoin = nullptr;
-#endif
     // double-buffered I/O (ma_batch_stage_reads / ma_batch_start_mapq_download): the next reads are uploaded into reads2 / roff2
     // and the packed results of the last step downloaded on ioStream while the batch's own stream runs kernels
     DevBuf reads2, roff2;

@@ -116,6 +116,19 @@ struct ByteFetchPipe : ByteFetch
 };
 } // namespace
 
+// the 64-bit device counters of one call
+enum : int
+{
+    PC_CIG_USED = 0,
+    PC_CELLS,
+    PC_NJOBS,
+    PC_ERR,
+    PC_NEXT, // ksw_run_all's `next`: KSW_N_NEXT x u32
+    PC_N_REDO = PC_NEXT + KSW_N_NEXT / 2,
+    PC_NEXT_BIG, // KSW_N_NEXT_BIG x u32
+    PC_COUNT = PC_NEXT_BIG + KSW_N_NEXT_BIG / 2
+};
+
 // FETCH::EARLY selects the pipeline semantics (extension kernel + early stop, see ksw_ext.h)
 template <typename FETCH>
 static int ksw_batch_impl( const ma_params* P, const ma_ksw_job* jobs, uint64_t n, const uint8_t* q_bytes, uint64_t q_len,
@@ -133,7 +146,7 @@ static int ksw_batch_impl( const ma_params* P, const ma_ksw_job* jobs, uint64_t 
     KswSizing S;
     for( uint64_t i = 0; i < n; i++ )
         ksw_size_job( S, jobs[ i ].qlen, jobs[ i ].tlen, jobs[ i ].w );
-    // pipeline semantics: per-class job lists as k_dp_enum builds them on the device
+    // pipeline semantics: per-class job lists and sizes by the router k_dp_enum builds them with on the device (ksw_route_job)
     std::vector<u32> lists;
     DevBuf dlists;
     if( FETCH::EARLY )
@@ -141,54 +154,18 @@ static int ksw_batch_impl( const ma_params* P, const ma_ksw_job* jobs, uint64_t 
         for( int k = 0; k < KSW_N_CLASSES; k++ )
             S.cls[ k ] = S.pc[ k ] = S.cigc[ k ] = 0;
         lists.assign( (size_t)( KSW_N_CLASSES + 2 ) * n, 0u );
+        const bool tryAll = getenv( "MA_KSW_BAND_ALL" ) != nullptr; // the tests try every eligible job on its band: no pre-filters
         for( uint64_t i = 0; i < n; i++ )
         {
-            const i32 ql = jobs[ i ].qlen, tl = jobs[ i ].tlen;
-            if( ql <= 0 || tl <= 0 )
+            const ma_ksw_job& j = jobs[ i ];
+            if( j.qlen <= 0 || j.tlen <= 0 )
                 continue;
-            int c = ksw_job_class_pipe( SC, ql, tl, jobs[ i ].w, jobs[ i ].zdrop, jobs[ i ].flag );
-            if( SC.grp >= 1000 && ( c == KSW_CLS_GRP0 || c == KSW_CLS_GRP0 + 1 ) && !getenv( "MA_KSW_BAND_ALL" ) )
-            {
-                // (k_dp_enum's pre-filter of the narrow band; MA_KSW_BAND_ALL=1: the tests try every eligible job)
-                const uint8_t *qp = q_bytes + jobs[ i ].q_off, *tp = t_bytes + jobs[ i ].t_off;
-                auto qf = [ & ]( i32 k ) -> u32 { return qp[ k ]; };
-                auto tf = [ & ]( i32 k ) -> u32 { return tp[ k ]; };
-                if( !ksw_band_likely( qf, tf, ql, tl, SC.band_mis ) )
-                {
-                    KswScoring S1 = SC;
-                    S1.grp = 1;
-                    c = ksw_job_class_pipe( S1, ql, tl, jobs[ i ].w, jobs[ i ].zdrop, jobs[ i ].flag );
-                }
-            }
-            if( ( c == KSW_CLS_BANDL || c == KSW_CLS_BANDL + 1 ) && !getenv( "MA_KSW_BAND_ALL" ) )
-            {
-                const uint8_t *qp = q_bytes + jobs[ i ].q_off, *tp = t_bytes + jobs[ i ].t_off;
-                auto qf = [ & ]( i32 k ) -> u32 { return qp[ k ]; };
-                auto tf = [ & ]( i32 k ) -> u32 { return tp[ k ]; };
-                if( !ksw_bandl_likely( qf, tf, ql, tl ) )
-                {
-                    KswScoring S1 = SC;
-                    S1.band_long = 0;
-                    c = ksw_job_class_pipe( S1, ql, tl, jobs[ i ].w, jobs[ i ].zdrop, jobs[ i ].flag );
-                }
-            }
-            lists[ (size_t)c * n + S.cls[ c ]++ ] = (u32)i;
-            const u64 pk = ksw_p_bytes( ql, tl, jobs[ i ].w ), cg = (u64)ql + tl + 2;
-            S.pc[ c ] = std::max( S.pc[ c ], c >= KSW_CLS_GRP0 ? 0 : ( c >= 5 ? ksw_ext_p_bytes( ql, tl, c - 4 ) : pk ) );
-            S.cigc[ c ] = std::max( S.cigc[ c ], cg );
-            if( c == KSW_CLS_BANDL || c == KSW_CLS_BANDL + 1 )
-                S.bandlN = std::max<u64>( S.bandlN, (u64)std::min( ql, tl ) );
-            if( c >= 5 )
-            {
-                S.pRedo = std::max( S.pRedo, pk );
-                S.cigRedo = std::max( S.cigRedo, cg );
-            }
-            if( SC.grp >= 1000 && ( c == KSW_CLS_GRP0 || c == KSW_CLS_GRP0 + 1 ) )
-            {
-                const int e = ksw_ext_slots( SC, ql, tl, jobs[ i ].w, jobs[ i ].zdrop, jobs[ i ].flag ); // its extension kernel, should it fail its checks
-                S.pc[ 4 + e ] = std::max( S.pc[ 4 + e ], ksw_ext_p_bytes( ql, tl, e ) );
-                S.cigc[ 4 + e ] = std::max( S.cigc[ 4 + e ], cg );
-            }
+            const uint8_t *qp = q_bytes + j.q_off, *tp = t_bytes + j.t_off;
+            auto qf = [ & ]( i32 k ) -> u32 { return qp[ k ]; };
+            auto tf = [ & ]( i32 k ) -> u32 { return tp[ k ]; };
+            const KswRoute R = ksw_route_job( SC, j.qlen, j.tlen, j.w, j.zdrop, j.flag, qf, tf, tryAll );
+            lists[ (size_t)R.cls * n + S.cls[ R.cls ] ] = (u32)i;
+            ksw_size_route( S, R );
         }
         if( dlists.reserve( lists.size( ) * 4 + 16 ) )
             return 1;
@@ -197,12 +174,12 @@ static int ksw_batch_impl( const ma_params* P, const ma_ksw_job* jobs, uint64_t 
     DevBuf dj, dq, dt, dez, doff, dpool, dscr, dctr;
     if( dj.reserve( n * sizeof( ma_ksw_job ) ) || dq.reserve( q_len + 16 ) || dt.reserve( t_len + 16 ) ||
         dez.reserve( n * sizeof( ma_ez ) ) || doff.reserve( ( n + 1 ) * 8 ) || dpool.reserve( cigar_cap * 4 + 16 ) ||
-        dctr.reserve( 256 ) )
+        dctr.reserve( PC_COUNT * 8 ) )
         return 1;
     MA_HIP( hipMemcpy( dj.p, jobs, n * sizeof( ma_ksw_job ), hipMemcpyHostToDevice ) );
     MA_HIP( hipMemcpy( dq.p, q_bytes, q_len, hipMemcpyHostToDevice ) );
     MA_HIP( hipMemcpy( dt.p, t_bytes, t_len, hipMemcpyHostToDevice ) );
-    MA_HIP( hipMemset( dctr.p, 0, 256 ) );
+    MA_HIP( hipMemset( dctr.p, 0, PC_COUNT * 8 ) );
     MA_HIP( hipMemset( dez.p, 0, n * sizeof( ma_ez ) ) );
     MA_HIP( hipMemset( doff.p, 0, ( n + 1 ) * 8 ) );
     KswOut O;
@@ -211,34 +188,34 @@ static int ksw_batch_impl( const ma_params* P, const ma_ksw_job* jobs, uint64_t 
     O.cig_off = doff.as<u64>( );
     O.cig_pool = dpool.as<u32>( );
     O.cig_pool_cap = cigar_cap;
-    O.cig_used = ctr + 0;
-    O.cells = ctr + 1;
-    O.njobs = ctr + 2;
-    O.err = (u32*)( ctr + 3 );
+    O.cig_used = ctr + PC_CIG_USED;
+    O.cells = ctr + PC_CELLS;
+    O.njobs = ctr + PC_NJOBS;
+    O.err = (u32*)( ctr + PC_ERR );
     O.path = nullptr;
     O.cig_words = nullptr;
     O.cig_chunk = 0; // dense pool: cigar_off[n] is the total
-    unsigned int* next = (unsigned int*)( ctr + 4 ); // 28 x u32 launch queues (ctr[4..17])
+    unsigned int* next = (unsigned int*)( ctr + PC_NEXT );
     FETCH F;
     F.jobs = dj.as<ma_ksw_job>( );
     F.qb = dq.as<uint8_t>( );
     F.tb = dt.as<uint8_t>( );
     if( ksw_run_all( F, SC, (u32)n, S, dscr, next, O, 0, FETCH::EARLY ? dlists.as<u32>( ) : nullptr, n,
-                     (unsigned int*)( ctr + 18 ), (unsigned int*)( ctr + 19 ) ) )
+                     (unsigned int*)( ctr + PC_N_REDO ), (unsigned int*)( ctr + PC_NEXT_BIG ) ) )
         return 1;
     MA_HIP( hipDeviceSynchronize( ) );
-    unsigned long long h[ 8 ];
-    MA_HIP( hipMemcpy( h, dctr.p, 64, hipMemcpyDeviceToHost ) );
+    unsigned long long h[ PC_NEXT ];
+    MA_HIP( hipMemcpy( h, dctr.p, sizeof( h ), hipMemcpyDeviceToHost ) );
     int rc = 0;
-    if( ( (u32)h[ 3 ] ) & MA_ERR_CIGAR_OVERFLOW )
+    if( ( (u32)h[ PC_ERR ] ) & MA_ERR_CIGAR_OVERFLOW )
         rc = fail( "ma_ksw_batch: cigar capacity too small" );
     else
     {
         MA_HIP( hipMemcpy( ez, dez.p, n * sizeof( ma_ez ), hipMemcpyDeviceToHost ) );
         MA_HIP( hipMemcpy( cigar_off, doff.p, n * 8, hipMemcpyDeviceToHost ) );
-        cigar_off[ n ] = h[ 0 ];
-        if( cigar && h[ 0 ] )
-            MA_HIP( hipMemcpy( cigar, dpool.p, h[ 0 ] * 4, hipMemcpyDeviceToHost ) );
+        cigar_off[ n ] = h[ PC_CIG_USED ];
+        if( cigar && h[ PC_CIG_USED ] )
+            MA_HIP( hipMemcpy( cigar, dpool.p, h[ PC_CIG_USED ] * 4, hipMemcpyDeviceToHost ) );
     }
     return rc;
 }

@@ -1,6 +1,7 @@
 // stage_dp.h -- kernels of the NeedlemanWunsch stage around the kswcpp kernels of ksw_launch.h (needlemanWunsch.cpp:82-877,
-// mappingQuality.cpp:11-131): k_dp_enum (job enumeration), k_job_cost, k_ops_caps, k_stitch / k_stitch_wave (the walk that
-// assembles the alignments), k_finish (sort + MappingQuality).  Textually part of pipeline.hip.
+// mappingQuality.cpp:11-131): k_dp_enum (job enumeration; the kernel classes come from ksw_route_slot of ksw_launch.h), k_job_cost,
+// k_ops_caps, k_stitch / k_stitch_wave (the walk that assembles the alignments), k_finish (sort + MappingQuality).  Textually part of
+// pipeline.hip.
 struct SetInfo // per harmonized set, filled by the enumeration pass
 {
     u64 win_begin, win_end;
@@ -155,84 +156,23 @@ __global__ void __launch_bounds__( 64 ) k_dp_enum( DpKernelArgs A )
 #pragma unroll
         for( int c = 0; c < KSW_CLS_GRP0; c++ )
             pcl[ c ] = cgl[ c ] = 0;
-        auto classOf = [ & ]( u32 k, u32& pj, u32& cj, u32& pk8, bool second ) -> int {
-            const DpJob& j = A.jobs[ sink.slot0 + k ];
-            const i32 ql = (i32)( j.q_to - j.q_from ), tl = (i32)( j.r_to - j.r_from );
-            pj = cj = pk8 = 0;
-            if( A.one_by_one && ql == 1 && tl == 1 && j.flag == 0 && j.zdrop < 0 )
-                return -2; // answered here (first pass)
-            int cls = second ? (int)A.cls_cache[ sink.slot0 + k ] : ksw_job_class_pipe( A.SC, ql, tl, j.w, j.zdrop, j.flag );
-            if( !second && A.SC.grp >= 1000 && ( cls == KSW_CLS_GRP0 || cls == KSW_CLS_GRP0 + 1 ) )
-            {
-                // the proven narrow band (ksw_band.h) is tried on the jobs whose query follows the target's main diagonal
-                const uint8_t* qb = A.reads + j.read_off;
-                auto qf = [ & ]( i32 i ) -> u32 { return j.rev ? qb[ j.q_to - 1 - (u32)i ] : qb[ j.q_from + (u32)i ]; };
-                auto tf = [ & ]( i32 i ) -> u32 { return text_base( A.X, j.win_begin + ( j.rev ? j.r_to - 1 - (u32)i : j.r_from + (u32)i ) ); };
-                if( !ksw_band_likely( qf, tf, ql, tl, A.SC.band_mis ) )
-                {
-                    KswScoring S1 = A.SC;
-                    S1.grp = 1;
-                    cls = ksw_job_class_pipe( S1, ql, tl, j.w, j.zdrop, j.flag );
-                }
-            }
-            if( !second && ( cls == KSW_CLS_BANDL || cls == KSW_CLS_BANDL + 1 ) )
-            {
-                // the band of 120 is tried on the long extensions whose first bases follow the target with few edits (ksw_bandl_likely)
-                const uint8_t* qb = A.reads + j.read_off;
-                auto qf = [ & ]( i32 i ) -> u32 { return j.rev ? qb[ j.q_to - 1 - (u32)i ] : qb[ j.q_from + (u32)i ]; };
-                auto tf = [ & ]( i32 i ) -> u32 { return text_base( A.X, j.win_begin + ( j.rev ? j.r_to - 1 - (u32)i : j.r_from + (u32)i ) ); };
-                if( !ksw_bandl_likely( qf, tf, ql, tl ) )
-                {
-                    KswScoring S1 = A.SC;
-                    S1.band_long = 0;
-                    cls = ksw_job_class_pipe( S1, ql, tl, j.w, j.zdrop, j.flag );
-                }
-            }
-            if( !second )
-                A.cls_cache[ sink.slot0 + k ] = (uint8_t)cls;
-            const u64 pk = ksw_p_bytes( ql, tl, j.w );
-            // 256-byte units (the query-stationary classes from KSW_CLS_GRP0 on have a fixed scratch per wave: ksw_grp.h)
-            pj = cls >= KSW_CLS_GRP0 ? 0u : (u32)( ( ( cls >= 5 ? ksw_ext_p_bytes( ql, tl, cls - 4 ) : pk ) + 255 ) >> 8 );
-            cj = (u32)( ql + tl + 2 );
-            pk8 = (u32)( ( pk + 255 ) >> 8 );
-            return cls;
+        // a 1 x 1 gap fill the enumeration answers itself (class -2: no list, no cached class)
+        auto oneByOne = [ & ]( const DpJob& j ) -> bool {
+            return A.one_by_one && j.q_to - j.q_from == 1 && j.r_to - j.r_from == 1 && j.flag == 0 && j.zdrop < 0;
         };
+        auto units = []( u64 bytes ) -> u32 { return (u32)( ( bytes + 255 ) >> 8 ); }; // the lanes' maxima are kept in 256-byte units
         u32 cntV = 0; // lane c: jobs of class c among this wave's
         u32 n11 = 0; // this lane's 1 x 1 gap fills
         for( u32 k = 0; k < rounds; k++ )
         {
             int cls = -1;
-            u32 pj = 0, cj = 0, pk8 = 0;
+            u32 pj = 0, cj = 0;
             if( k < mine )
             {
-                cls = classOf( k, pj, cj, pk8, false );
-                if( cls >= 5 )
+                const DpJob& j = A.jobs[ sink.slot0 + k ];
+                if( oneByOne( j ) )
                 {
-                    pRedo = max( pRedo, pk8 );
-                    cgRedo = max( cgRedo, cj );
-                }
-                if( cls == KSW_CLS_BANDL || cls == KSW_CLS_BANDL + 1 )
-                {
-                    const DpJob& jj = A.jobs[ sink.slot0 + k ];
-                    bandlN = max( bandlN, min( jj.q_to - jj.q_from, jj.r_to - jj.r_from ) );
-                }
-                if( A.SC.grp >= 1000 && ( cls == KSW_CLS_GRP0 || cls == KSW_CLS_GRP0 + 1 ) )
-                {
-                    // a job on the narrow band that fails its checks goes on to k_ksw_ext<1> / <2>: their launches are sized for it too
-                    const DpJob& jj = A.jobs[ sink.slot0 + k ];
-                    const i32 ql = (i32)( jj.q_to - jj.q_from ), tl = (i32)( jj.r_to - jj.r_from );
-                    const int e = ksw_ext_slots( A.SC, ql, tl, jj.w, jj.zdrop, jj.flag );
-                    const u32 pe = (u32)( ( ksw_ext_p_bytes( ql, tl, e ) + 255 ) >> 8 );
-#pragma unroll
-                    for( int c = 5; c < 7; c++ )
-                        if( c == 4 + e )
-                        {
-                            pcl[ c ] = max( pcl[ c ], pe );
-                            cgl[ c ] = max( cgl[ c ], cj );
-                        }
-                }
-                if( cls == -2 )
-                {
+                    cls = -2;
                     ma_ez rz; // what a global kswcpp call leaves (kswcpp_core.h:328-338, 796-835): only the cigar is set
                     rz.max = 0, rz.zdropped = 0, rz.max_q = rz.max_t = rz.mqe_t = rz.mte_q = -1;
                     rz.mqe = rz.mte = rz.score = (i32)0x80000000;
@@ -240,6 +180,29 @@ __global__ void __launch_bounds__( 64 ) k_dp_enum( DpKernelArgs A )
                     A.ez[ sink.slot0 + k ] = rz;
                     A.cig_off[ sink.slot0 + k ] = 0; // pool word 0 = 1M
                     n11++;
+                }
+                else
+                {
+                    // (the pre-filters of the band kernels walk the job's first bases: the second pass reads the class from cls_cache)
+                    const KswRoute R = ksw_route_slot( A.SC, A.X, A.reads, j );
+                    cls = R.cls;
+                    A.cls_cache[ sink.slot0 + k ] = (uint8_t)cls;
+                    pj = units( R.p );
+                    cj = R.cig;
+                    if( R.redo )
+                    {
+                        pRedo = max( pRedo, units( R.pk ) );
+                        cgRedo = max( cgRedo, cj );
+                    }
+                    bandlN = max( bandlN, R.bandlN );
+                    // a job on the narrow band that fails its checks goes on to k_ksw_ext<1> / <2>: their launches are sized for it too
+#pragma unroll
+                    for( int c = KSW_CLS_EXT1; c <= KSW_CLS_EXT2; c++ )
+                        if( c == R.ext )
+                        {
+                            pcl[ c ] = max( pcl[ c ], units( R.pExt ) );
+                            cgl[ c ] = max( cgl[ c ], cj );
+                        }
                 }
             }
 #pragma unroll
@@ -271,9 +234,8 @@ __global__ void __launch_bounds__( 64 ) k_dp_enum( DpKernelArgs A )
         for( u32 k = 0; k < rounds; k++ )
         {
             int cls = -1;
-            u32 pj, cj, pk8;
             if( k < mine )
-                cls = classOf( k, pj, cj, pk8, true );
+                cls = oneByOne( A.jobs[ sink.slot0 + k ] ) ? -2 : (int)A.cls_cache[ sink.slot0 + k ];
             unsigned long long todo = __ballot( cls >= 0 );
             while( todo )
             {

@@ -269,7 +269,7 @@ def test_short_extensions_that_share_a_wavefront(gpu_device, scoring, monkeypatc
         long_cases = [(np.concatenate([q, q[::-1], q])[:int(65 + (i * 7) % 64)], t, w, zd, fl) for i, (q, t, w, zd, fl) in enumerate(cases[:400]) if len(q) >= 33]
         monkeypatch.setenv("MA_KSW_GRP", "1")
         ez, cigs = ma_amd.ksw_batch(P, cases, pipeline_semantics=True)
-        monkeypatch.setenv("MA_KSW_GRP", "2")  # experiment builds (-DMA_EXP_GRP_NR2): queries of 65..128 bases two per wavefront; the shipped library reads it as 1 and the 65..128-base cases run on k_ksw_ext
+        monkeypatch.setenv("MA_KSW_GRP", "2")  # reads as 1: the 65..128-base cases run on k_ksw_ext
         ez2, cigs2 = ma_amd.ksw_batch(P, cases + long_cases, pipeline_semantics=True)
         monkeypatch.setenv("MA_KSW_GRP", "0")
         ez0, cigs0 = ma_amd.ksw_batch(P, cases, pipeline_semantics=True)
