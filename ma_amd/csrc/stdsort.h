@@ -5,7 +5,10 @@
 // libstdc++ is not part of /root/reference; the algorithm restated here is bits/stl_algo.h
 // (__introsort_loop, __unguarded_partition_pivot, __move_median_to_first, __final_insertion_sort,
 // threshold 16) and bits/stl_heap.h (__adjust_heap, __push_heap, __make_heap, __pop_heap) of
-// GCC 11.4; tests/test_stdsort.py pins it against the real std::sort on inputs full of ties.
+// GCC 11.4; pinned against the real std::sort / make_heap / pop_heap on inputs full of ties and on McIlroy's adversary, whose
+// lists exhaust the depth budget (tests/emul/host_emul.cpp sortcheck, run by tests/test_host_logic.py), and -- finish_range
+// included -- on the list set of tests/chain_lists.py (tests/emul/sort_census.cpp, run by tests/test_chain_seeds_host.py;
+// on a device: tests/test_gpu_chain_seeds.py).
 #pragma once
 #include "ma_common.h"
 

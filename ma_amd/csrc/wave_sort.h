@@ -10,14 +10,17 @@
 //     latter.  Both stopper sequences can be read off the UNPARTITIONED range (a swap only touches positions both scans have
 //     passed), so: list the stoppers of both sides with wave ballots, count the pairs K that still cross, swap them all at
 //     once; the cut is the (K+1)-th left stopper if that lies below the K-th right one, else the K-th right stopper (where
-//     the serial left scan runs into the element the last swap put there).  tools-checked against the serial loop on 2*10^5
-//     random ranges with heavy ties, and against stdsort.h / libstdc++ by tests/test_host_logic.py + the GPU parity tests.
+//     the serial left scan runs into the element the last swap put there).  Checked against libstdc++ on a device by
+//     tests/test_gpu_chain_seeds.py (tie-heavy and adversarial lists of tests/chain_lists.py, both forms of the kernel) and by
+//     tests/test_gpu_round6.py (sampled reads); the split at WS_SERIAL around ss::finish_range on the host by
+//     tests/test_chain_seeds_host.py (tests/emul/sort_census.cpp).
 //   __final_insertion_sort: after the introsort loop the array consists of blocks of <= 16 elements, every element of a
 //     block <= every element of the next; the one insertion sort over everything is a stable sort of each block in place
 //     (strict comparisons never move an element across a block boundary) -- so it can be done range by range.
 //   ranges of <= WS_SERIAL elements: the rest of the loop and the insertion sort of 64 such ranges at a time, one per lane.
 // What stays serial (wave-uniform, all lanes redundantly): the loop over the large ranges, median-of-three, the recursion
-// stack; the heap sort of a range whose depth budget ran out (lane 0; practically never).
+// stack; the heap sort of a range whose depth budget ran out (lane 0; practically never on seeds of real reads -- the
+// adversarial lists of tests/chain_lists.py are there to reach it).
 // Elements are u64 with the order LESS( a, b ); the caller packs (key << 20 | index).
 #pragma once
 #include "internal.h"

@@ -388,6 +388,107 @@ uint64_t ma_or_res_n_aligned( const ma_or_result* r )
     return r->nAligned;
 }
 
+// ---- the chain stage alone, from given seeds (tests of the product's sorts on chosen input orders) ----
+struct ma_or_chain_result
+{
+    std::vector<u64> seedOff, socOff, hsetOff, hseedOff;
+    std::vector<ma_or_seed> sorted, hseeds;
+    std::vector<ma_or_soc> heap, pops;
+    std::vector<uint32_t> hsetSoc;
+};
+
+static ma_or_soc toSocRec( const SoCEntry& e )
+{
+    ma_or_soc r;
+    r.acc_len = e.sc.accLen;
+    r.ambiguity = e.sc.amb;
+    r.n_seeds = e.sc.cnt;
+    r.begin = (uint32_t)e.b;
+    r.end = (uint32_t)e.e;
+    return r;
+}
+
+ma_or_chain_result* ma_or_chain_seeds( const ma_or_index* x, const ma_or_params* P, const uint64_t* read_lens,
+                                       const uint64_t* seed_off, const ma_or_seed* seeds, uint64_t n )
+{
+    ma_or_chain_result* res = new ma_or_chain_result( );
+    Ctx c{ *x, *P };
+    res->seedOff.push_back( 0 );
+    res->socOff.push_back( 0 );
+    res->hsetOff.push_back( 0 );
+    res->hseedOff.push_back( 0 );
+    for( u64 i = 0; i < n; i++ )
+    {
+        std::vector<Seed> work;
+        for( u64 k = seed_off[ i ]; k < seed_off[ i + 1 ]; k++ )
+        {
+            Seed s;
+            s.q = (u64)seeds[ k ].q_start;
+            s.len = (u64)seeds[ k ].len;
+            s.r = (u64)seeds[ k ].r_start;
+            s.delta = (u64)seeds[ k ].delta;
+            s.amb = seeds[ k ].ambiguity;
+            s.fwd = seeds[ k ].on_forward != 0;
+            work.push_back( s );
+        }
+        SoCQueue Q;
+        socSweep( c, work, read_lens[ i ], Q ); // std::sort by delta, the windows, make_heap, std::sort by reference position
+        for( const Seed& s : work )
+            res->sorted.push_back( toSeedRec( s ) );
+        res->seedOff.push_back( res->sorted.size( ) );
+        for( const SoCEntry& e : Q.vMaxima )
+            res->heap.push_back( toSocRec( e ) );
+        {
+            std::vector<SoCEntry> h = Q.vMaxima; // pop order (SoCPriorityQueue::pop, soc.h:240-284) on a copy of the array
+            while( !h.empty( ) )
+            {
+                res->pops.push_back( toSocRec( h.front( ) ) );
+                std::pop_heap( h.begin( ), h.end( ), SoCQueue::heapOrder );
+                h.pop_back( );
+            }
+        }
+        res->socOff.push_back( res->heap.size( ) );
+        std::vector<SeedSet> harm;
+        harmonize( c, Q, read_lens[ i ], harm );
+        for( const SeedSet& h : harm )
+        {
+            for( const Seed& s : h.v )
+                res->hseeds.push_back( toSeedRec( s ) );
+            res->hseedOff.push_back( res->hseeds.size( ) );
+            res->hsetSoc.push_back( h.socIndex );
+        }
+        res->hsetOff.push_back( res->hsetSoc.size( ) );
+    }
+    return res;
+}
+void ma_or_chain_result_free( ma_or_chain_result* r )
+{
+    delete r;
+}
+const void* ma_or_chain_res_array( const ma_or_chain_result* r, int32_t which, uint64_t* count )
+{
+#define MA_OR_ARR( v )                                                                                                 \
+    {                                                                                                                  \
+        *count = r->v.size( );                                                                                         \
+        return r->v.data( );                                                                                           \
+    }
+    switch( which )
+    {
+        case MA_OR_CHAIN_SEED_OFF: MA_OR_ARR( seedOff )
+        case MA_OR_CHAIN_SORTED_SEEDS: MA_OR_ARR( sorted )
+        case MA_OR_CHAIN_SOC_OFF: MA_OR_ARR( socOff )
+        case MA_OR_CHAIN_SOC_HEAP: MA_OR_ARR( heap )
+        case MA_OR_CHAIN_SOC_POPS: MA_OR_ARR( pops )
+        case MA_OR_CHAIN_HSET_OFF: MA_OR_ARR( hsetOff )
+        case MA_OR_CHAIN_HSEED_OFF: MA_OR_ARR( hseedOff )
+        case MA_OR_CHAIN_HSET_SOC: MA_OR_ARR( hsetSoc )
+        case MA_OR_CHAIN_HSEEDS: MA_OR_ARR( hseeds )
+    }
+#undef MA_OR_ARR
+    *count = 0;
+    return nullptr;
+}
+
 int ma_or_dump_pipe( const ma_or_index* x, const ma_or_params* P, const uint8_t* reads, const uint64_t* off,
                      uint64_t n, const char* out_path )
 {

@@ -7,6 +7,7 @@
 #include "../../ma_amd/csrc/seeding.h"
 #include "../../oracle/dump_format.h"
 #include "../../oracle/ma_oracle.h"
+#include "sort_adversary.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -134,6 +135,26 @@ int main( int argc, char** argv )
                     return 1;
                 }
         }
+        // McIlroy's adversary against std::sort (sort_adversary.h): introsort runs out of its depth budget from n = 130 on and
+        // heap-sorts nearly the whole list; with every key halved / cut in three the heap sort works on equal keys
+        for( int d = 1; d <= 3; d++ )
+            for( int n : { 17, 64, 129, 130, 160, 199, 200, 257, 500, 1025, 2000, 4096, 8192, 65535, 65536 } )
+            {
+                const std::vector<long> keys = sort_adversary_keys( n, d );
+                std::vector<E> a( n );
+                for( int i = 0; i < n; i++ )
+                    a[ i ] = E{ (int)keys[ i ], i };
+                std::vector<E> b = a;
+                auto cmp = []( const E& x, const E& y ) { return x.k < y.k; };
+                std::sort( a.begin( ), a.end( ), cmp );
+                ss::sort( b.data( ), (i64)n, cmp );
+                for( int i = 0; i < n; i++ )
+                    if( a[ i ].tag != b[ i ].tag )
+                    {
+                        fprintf( stderr, "adversary sort mismatch n=%d d=%d\n", n, d );
+                        return 1;
+                    }
+            }
         printf( "sortcheck ok\n" );
         return 0;
     }
@@ -291,6 +312,32 @@ int main( int argc, char** argv )
     NP.max_supplementary = OP.max_supplementary;
     NP.max_overlap_supplementary = OP.max_overlap_supplementary;
 
+    // MA_EMUL_SEEDS=<file>: u64 n_reads, u64 seed_off[n_reads + 1], ma_seed seeds[]: every read's seeds replace the extracted ones
+    std::vector<u64> givenOff;
+    std::vector<ma_seed> givenSeeds;
+    if( const char* e = getenv( "MA_EMUL_SEEDS" ) )
+    {
+        FILE* g = fopen( e, "rb" );
+        u64 nr = 0;
+        if( !g || fread( &nr, 8, 1, g ) != 1 || nr != cs.reads.size( ) )
+        {
+            fprintf( stderr, "MA_EMUL_SEEDS: cannot read %s for %zu reads\n", e, cs.reads.size( ) );
+            return 1;
+        }
+        givenOff.resize( nr + 1 );
+        bool ok = fread( givenOff.data( ), 8, nr + 1, g ) == nr + 1;
+        if( ok )
+        {
+            givenSeeds.resize( givenOff[ nr ] );
+            ok = fread( givenSeeds.data( ), sizeof( ma_seed ), givenOff[ nr ], g ) == givenOff[ nr ];
+        }
+        fclose( g );
+        if( !ok )
+        {
+            fprintf( stderr, "MA_EMUL_SEEDS: %s is short\n", e );
+            return 1;
+        }
+    }
     FILE* f = fopen( argv[ 4 ], "w" );
     for( size_t ri = 0; ri < cs.reads.size( ); ri++ )
     {
@@ -386,6 +433,8 @@ int main( int argc, char** argv )
                 seeds.push_back( sd );
             }
         }
+        if( !givenOff.empty( ) ) // MA_EMUL_SEEDS: the chain stage from given seeds, in the given order (Batch.set_seeds)
+            seeds.assign( givenSeeds.begin( ) + givenOff[ ri ], givenSeeds.begin( ) + givenOff[ ri + 1 ] );
         fprintf( f, "SEED %zu\n", seeds.size( ) );
         for( auto& s : seeds )
             dumpSeed( f, "d", s );

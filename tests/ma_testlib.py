@@ -377,6 +377,7 @@ OR_SEED_DT = np.dtype([("q_start", "<i8"), ("len", "<i8"), ("r_start", "<i8"), (
                        ("on_forward", "<u4")])
 OR_EZ_DT = np.dtype([(k, "<i4") for k in ("max", "zdropped", "max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "score",
                                           "reach_end", "n_cigar")])
+OR_SOC_DT = np.dtype([("acc_len", "<u8"), ("ambiguity", "<u4"), ("n_seeds", "<u4"), ("begin", "<u4"), ("end", "<u4")])
 OR_ALN_DT = np.dtype([("begin_ref", "<i8"), ("end_ref", "<i8"), ("begin_q", "<i8"), ("end_q", "<i8"), ("score", "<i8"),
                       ("soc_index", "<u4"), ("n_ops", "<u4"), ("ops_off", "<u8"), ("secondary", "<u4"),
                       ("supplementary", "<u4"), ("mapq", "<f8")])
@@ -400,6 +401,8 @@ def orlib():
                    "ma_or_res_mq_off", "ma_or_res_mq"):
             getattr(L, fn).restype = C.c_void_p
         L.ma_or_bwt_sa.restype = C.c_int64
+        L.ma_or_chain_seeds.restype = C.c_void_p
+        L.ma_or_chain_res_array.restype = C.c_void_p
         _orlib = L
     return _orlib
 
@@ -514,6 +517,29 @@ class OrIndex:
         res["counters"] = ctr
         res["n_aligned"] = int(L.ma_or_res_n_aligned(r))
         L.ma_or_result_free(r)
+        return res
+
+    def chain_seeds(self, read_lens, seed_off, seeds, params):
+        """StripOfConsiderationSeeds::execute + Harmonization::execute on GIVEN seeds (CSR per read, OR_SEED_DT, in the order the
+        sweep's first std::sort is to see them), with the real std::sort.  Returns the layouts of the product's
+        Batch.socs(heap=True) / socs(heap=False) / hsets(): seed_off, sorted_seeds (re-sorted by reference position), soc_off,
+        soc_heap (the queue's array), soc_pops (pop order), hset_off, hseed_off, hset_soc, hseeds."""
+        read_lens = np.ascontiguousarray(read_lens, dtype=np.uint64)
+        seed_off = np.ascontiguousarray(seed_off, dtype=np.uint64)
+        assert len(seed_off) == len(read_lens) + 1 and int(seed_off[-1]) == len(seeds)
+        seeds = np.ascontiguousarray(np.concatenate([np.asarray(seeds, dtype=OR_SEED_DT), np.zeros(1, dtype=OR_SEED_DT)]))
+        L = orlib()
+        r = C.c_void_p(L.ma_or_chain_seeds(self.h, C.byref(params), read_lens.ctypes.data_as(C.c_void_p),
+                                           seed_off.ctypes.data_as(C.c_void_p), seeds.ctypes.data_as(C.c_void_p),
+                                           C.c_uint64(len(read_lens))))
+        res = {}
+        for which, (name, dt) in enumerate((("seed_off", np.uint64), ("sorted_seeds", OR_SEED_DT), ("soc_off", np.uint64),
+                                            ("soc_heap", OR_SOC_DT), ("soc_pops", OR_SOC_DT), ("hset_off", np.uint64),
+                                            ("hseed_off", np.uint64), ("hset_soc", np.uint32), ("hseeds", OR_SEED_DT))):
+            cnt = C.c_uint64()
+            ptr = L.ma_or_chain_res_array(r, C.c_int32(which), C.byref(cnt))
+            res[name] = _np_from(ptr, int(cnt.value), dt)
+        L.ma_or_chain_result_free(r)
         return res
 
 

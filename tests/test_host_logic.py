@@ -16,7 +16,7 @@ G = os.path.join(ROOT, "tests", "golden")
 def emul():
     build_oracle()
     src = os.path.join(ROOT, "tests", "emul", "host_emul.cpp")
-    deps = [src] + [os.path.join(ROOT, "ma_amd", "csrc", f) for f in os.listdir(os.path.join(ROOT, "ma_amd", "csrc"))
+    deps = [src, os.path.join(ROOT, "tests", "emul", "sort_adversary.h")] + [os.path.join(ROOT, "ma_amd", "csrc", f) for f in os.listdir(os.path.join(ROOT, "ma_amd", "csrc"))
                     if f.endswith(".h")]
     if not os.path.exists(EMUL) or any(os.path.getmtime(d) > os.path.getmtime(EMUL) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-w", "-I" + os.path.join(ROOT, "include"),
