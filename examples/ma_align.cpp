@@ -2,7 +2,11 @@
 // `maCMD -x <genome> -i <reads> [-m <mates>] -o <out.sam> -p <preset>` needs from the hot path.  Not a re-implementation
 // of cmdMa.cpp: no option parsing beyond the four arguments, no thread pool (the batches are the parallelism).
 //
-//   ma_align <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam|stdout> [preset] [mates.fa|fq[.gz]]
+//   ma_align [--host-sam] <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam|stdout> [preset] [mates.fa|fq[.gz]]
+//
+// Single-end input is printed on the device (BatchAligner::executeFlatSam: the SAM text is what comes down) whenever the
+// options are ones the device serves; with "Detect Small Inversions", with the NGMLR tag emulation and with --host-sam the
+// records come down and FileWriter prints them.  The bytes are the same.
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_align.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
@@ -13,9 +17,18 @@ typedef libMS::ContainerVector<std::shared_ptr<NucSeq>> ReadVec;
 
 int main( int argc, char** argv )
 {
+    bool bHostSam = false;
+    for( int i = 1; i < argc; i++ )
+        if( std::string( argv[ i ] ) == "--host-sam" )
+        {
+            bHostSam = true;
+            for( int j = i; j + 1 < argc; j++ )
+                argv[ j ] = argv[ j + 1 ];
+            argc--, i--;
+        }
     if( argc < 4 )
     {
-        fprintf( stderr, "usage: ma_align <genome.fa | index prefix> <reads> <out.sam|stdout> [preset] [mates]\n" );
+        fprintf( stderr, "usage: ma_align [--host-sam] <genome.fa | index prefix> <reads> <out.sam|stdout> [preset] [mates]\n" );
         return 2;
     }
     try
@@ -37,7 +50,28 @@ int main( int argc, char** argv )
         FileReader xReader( xParams );
         auto pIn = fileStreamFromPath( argv[ 2 ] );
         const size_t uiBatch = 1000000; // reads per device batch
-        if( !bPaired )
+        if( !bPaired && xAligner.servesSam( ) && !bHostSam )
+        {
+            // the device path: records formatted by ma_sam_batch, one write per device batch behind FileWriter's header
+            BatchFileWriter xWriter( xParams, std::make_shared<FileWriter>( xParams, std::string( argv[ 3 ] ), pPack ), pPack );
+            while( true )
+            {
+                auto pReads = std::make_shared<ReadVec>( );
+                while( pReads->size( ) < uiBatch )
+                {
+                    auto pQ = xReader.execute( pIn );
+                    if( pQ == nullptr )
+                        break;
+                    pReads->push_back( pQ );
+                }
+                if( pReads->empty( ) )
+                    break;
+                auto pFlat = xAligner.executeFlatSam( pFM, pReads, pPack );
+                for( auto& pBatch : *pFlat )
+                    xWriter.write( *pBatch, pPack );
+            }
+        }
+        else if( !bPaired )
         {
             FileWriter xWriter( xParams, std::string( argv[ 3 ] ), pPack );
             while( true )

@@ -236,7 +236,7 @@ int main( int argc, char** argv )
 {
     if( argc < 6 )
     {
-        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats]]\n" );
+        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | sam [repeats]]\n" );
         return 2;
     }
     try
@@ -247,7 +247,7 @@ int main( int argc, char** argv )
         maCheck( ma_set_device( atoi( argv[ 5 ] ) ) );
         maCheck( ma_host_bind_thread( atoi( argv[ 5 ] ), 0, nullptr ) ); // this thread and all it starts: the CPUs next to the GPU
         const unsigned uiHw = std::max( 1u, std::thread::hardware_concurrency( ) );
-        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
+        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "sam" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         double t0 = now( );
@@ -381,6 +381,79 @@ int main( int argc, char** argv )
             pReads->push_back( pQ );
         }
         std::vector<uint8_t>( ).swap( vPac );
+        if( argc >= 7 && !strcmp( argv[ 6 ], "sam" ) )
+        {
+            // ---- the SAM leg: n single-end reads host to host INCLUDING SAM text through (a) BatchAligner::executeFlat +
+            // BatchFileWriter -- records downloaded, formatted by up to 16 host threads -- and (b) executeFlatSam -- formatted on
+            // the device, the text is what comes down; alternating, <repeats> times each after one warm-up of each.  The phase
+            // sums of the last repeat of each (AlignerTiming; d2h of (b) holds ma_sam_batch and the text download) are the
+            // step timeline.
+            const int iRepeats = argc >= 8 ? std::max( 1, atoi( argv[ 7 ] ) ) : 5;
+            BatchAligner xAligner( xParams );
+            xAligner.uiBatchReads = std::min<size_t>( pReads->size( ), 1u << 18 );
+            xAligner.uiInflight = 3;
+            xAligner.warmUp( pFM, pReads );
+            uint64_t uiBytesHost = 0, uiBytesDevice = 0, uiRecordBytes = 0;
+            double fWriterHost = 0, fWriterDevice = 0;
+            AlignerTiming xHost, xDevice;
+            auto host = [ & ]( ) {
+                auto pSink = std::make_shared<CountingSink>( );
+                BatchFileWriter xWriter( xParams, std::static_pointer_cast<OutStream>( pSink ), pPack );
+                xWriter.uiFormatThreads = std::min( 16u, uiHw );
+                const double t = now( );
+                auto pFlat = xAligner.executeFlat( pFM, pReads );
+                const double tW = now( );
+                uiRecordBytes = 0;
+                for( auto& pB : *pFlat )
+                {
+                    xWriter.write( *pB, pPack );
+                    uiRecordBytes += ( pB->size( ) + 1 ) * 8 + pB->pResult->uiMqAlignments * sizeof( ma_alignment ) + pB->pResult->uiMqOps * 16;
+                }
+                const double f = now( ) - t;
+                fWriterHost = now( ) - tW;
+                xHost = xAligner.xLast;
+                uiBytesHost = pSink->uiBytes.load( );
+                return f;
+            };
+            auto device = [ & ]( ) {
+                auto pSink = std::make_shared<CountingSink>( );
+                BatchFileWriter xWriter( xParams, std::static_pointer_cast<OutStream>( pSink ), pPack );
+                const double t = now( );
+                auto pFlat = xAligner.executeFlatSam( pFM, pReads, pPack );
+                const double tW = now( );
+                for( auto& pB : *pFlat )
+                    xWriter.write( *pB, pPack );
+                const double f = now( ) - t;
+                fWriterDevice = now( ) - tW;
+                xDevice = xAligner.xLast;
+                uiBytesDevice = pSink->uiBytes.load( );
+                return f;
+            };
+            host( ), device( ); // warm-up of both
+            std::vector<double> vH, vD;
+            for( int r = 0; r < iRepeats; r++ )
+                vH.push_back( n / host( ) ), vD.push_back( n / device( ) );
+            auto list = []( std::vector<double> v ) {
+                std::sort( v.begin( ), v.end( ) );
+                return "{\"median\": " + std::to_string( v[ v.size( ) / 2 ] ) + ", \"min\": " + std::to_string( v.front( ) ) +
+                       ", \"max\": " + std::to_string( v.back( ) ) + "}";
+            };
+            auto phases = []( const AlignerTiming& rT, double fWriter ) {
+                char buf[ 256 ];
+                snprintf( buf, sizeof( buf ), "{\"wall_s\": %.4f, \"batches\": %llu, \"pack_s\": %.4f, \"h2d_s\": %.4f, \"stages_s\": %.4f, "
+                          "\"d2h_s\": %.4f, \"writer_s\": %.4f}", rT.fWall, (unsigned long long)rT.uiBatches, rT.fPack, rT.fH2D, rT.fKernels,
+                          rT.fD2H, fWriter );
+                return std::string( buf );
+            };
+            printf( "{\"sam\": {\"reads\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_reads\": %zu, \"in_flight\": 3, "
+                    "\"format_threads\": %u, \"execute_flat_plus_writer_reads_per_s\": %s, \"execute_flat_sam_reads_per_s\": %s, "
+                    "\"sam_bytes_host\": %llu, \"sam_bytes_device\": %llu, \"record_bytes\": %llu, \"phases_host\": %s, "
+                    "\"phases_device\": %s}}\n",
+                    n, uiLen, iRepeats, xAligner.uiBatchReads, std::min( 16u, uiHw ), list( vH ).c_str( ), list( vD ).c_str( ),
+                    (unsigned long long)uiBytesHost, (unsigned long long)uiBytesDevice, (unsigned long long)uiRecordBytes,
+                    phases( xHost, fWriterHost ).c_str( ), phases( xDevice, fWriterDevice ).c_str( ) );
+            return uiBytesHost == uiBytesDevice ? 0 : 1;
+        }
         if( getenv( "MA_BOUNDARY_ONLY_GRAPH" ) ) // diagnostics: the per-read graph with the prefetching reader alone
         {
             defaultBatcherOptions( ).bStages = false;

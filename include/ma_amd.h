@@ -293,6 +293,40 @@ int ma_batch_get_pairs( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, ma_alignmen
                         int32_t* other );
 int ma_batch_start_pair_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, ma_alignment* alns, uint64_t* ops, int32_t* mate,
                                   int32_t* other );
+/* ---- SAM text: FileWriter::execute (fileWriter.cpp:11-158) on the device ----
+ * The single-end records of a batch as the bytes the reference's FileWriter prints for them (and ma_amd/host/ma_flat_sam.h
+ * makes of the downloaded MappingQuality records), formatted by two kernels and downloaded as ONE text instead of records and
+ * ops: per alignment of a read's MappingQuality list one record with Alignment::getSamFlag / getSamPosition / cigarString /
+ * getQuerySequence (alignment.h:367-467, 576-623), the CG:B:I tag of cigars from 0x10000 ops on (TagGenerator, fileWriter.h:
+ * 327-357), the unmapped record (fileWriter.cpp:126-140) for a read without a printed alignment.  The paired writer and the
+ * NGMLR tag emulation stay on the host.
+ *   ma_index_set_contig_names    the RNAME strings (Pack::nameOfSequenceWithId, pack.h:1040-1046): contig i's name is
+ *                                names[name_off[i] .. name_off[i+1]) (no terminators)
+ *   ma_batch_set_read_text       QNAME (NucSeq::sName) and QUAL (NucSeq::pxQualityValues / fastaq quality, nucSeq.h:697-709) of
+ *                                the batch's reads, after the reads were set: read r's name is names[name_off[r] ..
+ *                                name_off[r+1]), qual is NULL (QUAL "*") or holds one character per base in the reads' CSR.
+ *                                Setting reads again drops the text; without it ma_sam_batch fails with a message.
+ *   ma_sam_batch                 after ma_dp_batch / ma_align_batch / ma_batch_set_alignments on the batch's stream; options =
+ *                                MA_SAM_* (the members of FileWriter's settings it serves).  Waits for the stream with the one
+ *                                read-back that sizes the download.  A record that ends beyond its read (possible only through
+ *                                ma_batch_set_alignments) fails the call with the reference's text, "Query length is off by
+ *                                <n>." or "Index out of range (compCharAt)"; nothing beyond a read is ever touched.
+ *   ma_batch_sam_counts          bytes of the text
+ *   ma_batch_get_sam             read r's records are text[rec_off[r] .. rec_off[r+1]) (either pointer may be NULL)
+ *   ma_batch_start_sam_download  the same without the wait, completed by ma_batch_finish_download (cf.
+ *                                ma_batch_start_mapq_download; one download can be pending per object)
+ * The MappingQuality records stay as they are (ma_batch_get_mapq_alignments still serves them). */
+#define MA_SAM_SOFT_CLIP 1u /* xSoftClip: S clips and the whole read as SEQ instead of H clips */
+#define MA_SAM_EQX_CIGAR 2u /* xOutputMCigar off: = and X instead of M */
+#define MA_SAM_NO_SECONDARY 4u /* xNoSecondary */
+#define MA_SAM_NO_SUPPLEMENTARY 8u /* xNoSupplementary */
+#define MA_SAM_NO_CG_TAG 16u /* xCGTag off: cigars of 0x10000 ops and more are printed in the CIGAR column */
+int ma_index_set_contig_names( ma_index*, const char* names, const uint64_t* name_off /*n_contigs+1*/ );
+int ma_batch_set_read_text( ma_batch*, const char* names, const uint64_t* name_off /*n+1*/, const uint8_t* qual );
+int ma_sam_batch( ma_batch*, uint32_t options );
+int ma_batch_sam_counts( ma_batch*, uint64_t* n_bytes );
+int ma_batch_get_sam( ma_batch*, uint64_t* rec_off /*n+1*/, char* text );
+int ma_batch_start_sam_download( ma_batch*, uint64_t* rec_off /*n+1*/, char* text );
 /* work counters for the roofline model (same meaning as the oracle's): [0] extend_backward steps,
  * [1] distinct occ blocks touched, [2] bwt_sa LF steps, [3] SA rows, [4] DP band cells, [5] ksw jobs */
 int ma_batch_counters( ma_batch*, uint64_t out[ 8 ] );

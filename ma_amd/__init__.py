@@ -5,7 +5,9 @@ ma_amd/csrc by __graft_entry__.build()).  There is no CPU fallback: every comput
 device and raises MaError otherwise.
 """
 from .api import (MaError, Params, Index, Batch, HostArray, lib, lib_path, device_count, set_device, bind_host_thread,
-                  ksw_batch, SEGMENT_DT, SEED_DT, EZ_DT, ALIGNMENT_DT, KSW_JOB_DT)
+                  ksw_batch, SEGMENT_DT, SEED_DT, EZ_DT, ALIGNMENT_DT, KSW_JOB_DT, SAM_SOFT_CLIP, SAM_EQX_CIGAR, SAM_NO_SECONDARY,
+                  SAM_NO_SUPPLEMENTARY, SAM_NO_CG_TAG)
 
 __all__ = ["MaError", "Params", "Index", "Batch", "HostArray", "lib", "lib_path", "device_count", "set_device", "bind_host_thread",
-           "ksw_batch", "SEGMENT_DT", "SEED_DT", "EZ_DT", "ALIGNMENT_DT", "KSW_JOB_DT"]
+           "ksw_batch", "SEGMENT_DT", "SEED_DT", "EZ_DT", "ALIGNMENT_DT", "KSW_JOB_DT", "SAM_SOFT_CLIP", "SAM_EQX_CIGAR",
+           "SAM_NO_SECONDARY", "SAM_NO_SUPPLEMENTARY", "SAM_NO_CG_TAG"]

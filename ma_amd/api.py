@@ -87,6 +87,18 @@ def _ptr(a, t=C.c_void_p):
     return a.ctypes.data_as(t)
 
 
+SAM_SOFT_CLIP, SAM_EQX_CIGAR, SAM_NO_SECONDARY, SAM_NO_SUPPLEMENTARY, SAM_NO_CG_TAG = 1, 2, 4, 8, 16  # MA_SAM_*
+
+
+def _csr_text(strings):
+    """strings (str or bytes) back to back + their offsets (n + 1 u64)"""
+    bs = [x.encode() if isinstance(x, str) else bytes(x) for x in strings]
+    off = np.zeros(len(bs) + 1, dtype=np.uint64)
+    if bs:
+        off[1:] = np.cumsum([len(x) for x in bs])
+    return np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8).copy(), off
+
+
 def device_count():
     n = C.c_int(0)
     _chk(lib().ma_device_count(C.byref(n)))
@@ -244,6 +256,11 @@ class Index:
         _chk(lib().ma_bwt_sa_batch(self.h, _ptr(rows), C.c_uint64(len(rows)), _ptr(pos)))
         return pos
 
+    def set_contig_names(self, names):
+        """The RNAME strings of the SAM text (ma_index_set_contig_names): one str / bytes per contig."""
+        cat, off = _csr_text(names)
+        _chk(lib().ma_index_set_contig_names(self.h, _ptr(cat), _ptr(off)))
+
     def close(self):
         if self.h:
             lib().ma_index_destroy(self.h)
@@ -287,6 +304,7 @@ class Batch:
         _chk(lib().ma_batch_create(index.h, C.byref(params), C.c_uint64(max_reads), C.c_uint64(max_bases),
                                    C.byref(self.h)))
         self.n = 0
+        self.read_off, self.n_bases = np.zeros(1, dtype=np.uint64), 0  # CSR offsets of the reads that are set (set_read_text)
 
     def set_stream(self, stream_ptr):
         _chk(lib().ma_batch_set_stream(self.h, C.c_void_p(int(stream_ptr))))
@@ -309,16 +327,20 @@ class Batch:
             cat = np.zeros(1, dtype=np.uint8)
         _chk(lib().ma_batch_set_reads(self.h, _ptr(cat), _ptr(off), C.c_uint64(len(reads))))
         self.n = len(reads)
+        self.read_off, self.n_bases = off, int(off[-1])
 
     def set_reads_flat(self, codes_ptr, offsets_ptr, n_reads):
         """reads that already are one host array of codes + CSR offsets (n + 1 u64, starting at 0), e.g. in page-locked memory"""
         _chk(lib().ma_batch_set_reads(self.h, C.c_void_p(int(codes_ptr)), C.c_void_p(int(offsets_ptr)), C.c_uint64(n_reads)))
         self.n = n_reads
+        self.read_off = np.ctypeslib.as_array((C.c_uint64 * (n_reads + 1)).from_address(int(offsets_ptr))).copy()
+        self.n_bases = int(self.read_off[-1])
 
     def set_reads_device(self, d_codes_ptr, d_offsets_ptr, n_reads, n_bases):
         _chk(lib().ma_batch_set_reads_device(self.h, C.c_void_p(int(d_codes_ptr)), C.c_void_p(int(d_offsets_ptr)),
                                              C.c_uint64(n_reads), C.c_uint64(n_bases)))
         self.n = n_reads
+        self.read_off, self.n_bases = None, int(n_bases)  # (the offsets live on the device)
 
     def seed(self):
         _chk(lib().ma_seed_batch(self.h))
@@ -448,10 +470,12 @@ class Batch:
     def stage_reads_flat(self, codes_ptr, offsets_ptr, n_reads):
         _chk(lib().ma_batch_stage_reads(self.h, C.c_void_p(int(codes_ptr)), C.c_void_p(int(offsets_ptr)), C.c_uint64(n_reads)))
         self._staged_n = n_reads
+        self._staged_off = np.ctypeslib.as_array((C.c_uint64 * (n_reads + 1)).from_address(int(offsets_ptr))).copy()
 
     def use_staged_reads(self):
         _chk(lib().ma_batch_use_staged_reads(self.h))
         self.n = self._staged_n
+        self.read_off, self.n_bases = self._staged_off, int(self._staged_off[-1])
 
     def start_mapq_download(self, off, alns, ops):
         """mapq_alignments_into without the wait: returns None when the arrays are too small, else the counts; the arrays are
@@ -498,6 +522,54 @@ class Batch:
         _chk(lib().ma_batch_start_pair_download(self.h, C.c_void_p(off.ptr), C.c_void_p(alns.ptr), C.c_void_p(ops.ptr),
                                                 C.c_void_p(mate.ptr), C.c_void_p(other.ptr)))
         return c
+
+    # ---- SAM text (ma_sam_batch): the single-end records of the batch formatted on the device
+    def set_read_text(self, names, quals=None):
+        """QNAME and QUAL of the reads that were set (ma_batch_set_read_text): one str / bytes per read; quals None (QUAL "*")
+        or one quality string per read, as long as the read."""
+        if len(names) != self.n:
+            raise MaError("set_read_text: %d names for %d reads" % (len(names), self.n))
+        cat, off = _csr_text(names)
+        q = None
+        if quals is not None:
+            if len(quals) != self.n:
+                raise MaError("set_read_text: %d quality strings for %d reads" % (len(quals), self.n))
+            q, qoff = _csr_text(quals)
+            # the library copies one character per base: every quality string has to be as long as its read
+            if self.read_off is None and int(qoff[-1]) != self.n_bases:
+                raise MaError("set_read_text: %d quality characters for %d bases" % (int(qoff[-1]), self.n_bases))
+            if self.read_off is not None and not np.array_equal(qoff, self.read_off):
+                bad = int(np.flatnonzero(np.diff(qoff.astype(np.int64)) != np.diff(self.read_off.astype(np.int64)))[0])
+                raise MaError("set_read_text: quality string %d has %d characters, its read %d bases" % (
+                    bad, int(qoff[bad + 1] - qoff[bad]), int(self.read_off[bad + 1] - self.read_off[bad])))
+        _chk(lib().ma_batch_set_read_text(self.h, _ptr(cat), _ptr(off), _ptr(q)))
+
+    def sam(self, options=0):
+        """FileWriter::execute for every read on the device, after align() / dp() / set_alignments(); options = SAM_* bits.
+        Returns the bytes of the text."""
+        _chk(lib().ma_sam_batch(self.h, C.c_uint32(options)))
+        return self.sam_bytes()
+
+    def sam_bytes(self):
+        n = C.c_uint64()
+        _chk(lib().ma_batch_sam_counts(self.h, C.byref(n)))
+        return n.value
+
+    def sam_text(self):
+        """(rec_off, text): read r's records are text[rec_off[r]:rec_off[r + 1]] (bytes)."""
+        off = np.zeros(self.n + 1, dtype=np.uint64)
+        text = np.zeros(self.sam_bytes() + 1, dtype=np.uint8)
+        _chk(lib().ma_batch_get_sam(self.h, _ptr(off), _ptr(text)))
+        return off, text[:-1].tobytes()
+
+    def start_sam_download(self, off, text):
+        """sam_text() into caller-owned HostArrays (u64[n + 1], u8[bytes]) without the wait: None when they are too small, else
+        the bytes of the text; complete after finish_download()."""
+        nb = self.sam_bytes()
+        if off.n < self.n + 1 or text.n < nb:
+            return None
+        _chk(lib().ma_batch_start_sam_download(self.h, C.c_void_p(off.ptr), C.c_void_p(text.ptr)))
+        return nb
 
     def close(self):
         if self.h:

@@ -99,6 +99,8 @@ struct ma_index
 {
     ma::IndexView v; // device pointers
     ma::DevBuf bwt, sa, saDense, kmerTab, pac, cstart, clen;
+    ma::DevBuf cnames, cnameOff; // RNAME strings (ma_index_set_contig_names), CSR
+    bool namesSet = false;
     uint64_t n_words = 0, n_sa = 0;
     std::vector<uint64_t> h_cstart, h_clen;
     int device = 0;

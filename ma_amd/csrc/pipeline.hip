@@ -81,6 +81,9 @@ static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0
 #include "../host/ma_pair_flat.h"
 #include "stage_pair.h"
 
+#include "../host/ma_sam_dev.h"
+#include "stage_sam.h"
+
 // ------------------------------------------------------------------------------------------------
 // batch object
 // ------------------------------------------------------------------------------------------------
@@ -118,6 +121,11 @@ struct ma_batch
     // pairing (ma_pair_batch): per pair its pick and sizes, the pairs left to the host and their round trip, the packed columns
     DevBuf pairPick, pairCnt, pairOps, pairOver, pairHostOff, pairHostLists, pairHostPick, pairMate, pairOther;
     u64 pairRecs = 0, pairNOps = 0, pairOnHost = 0;
+    // SAM text (ma_sam_batch): the reads' names and qualities (ma_batch_set_read_text; dropped when reads are set), per read the
+    // bytes of its records and their scan, where SEQ of every record goes, the text, the statistics of the one read-back
+    DevBuf txtNames, txtNameOff, txtQual, samCnt, samOff, samSeqPos, samText, samStat;
+    bool txtSet = false, txtHasQual = false, samDone = false;
+    u64 samBytes = 0;
     u64 cigPoolCap = 0, cigPoolMin = 0, nOpsCap = 0, nJobSlots = 0;
     KswSide kswSide; // created on first use
     // double-buffered I/O (ma_batch_stage_reads / ma_batch_start_mapq_download): the next reads are uploaded into reads2 / roff2
@@ -361,6 +369,7 @@ int ma_batch_use_staged_reads( ma_batch* b )
     b->d_roff = b->roff.as<u64>( );
     b->reads_external = false;
     b->stage_done = 0;
+    b->txtSet = b->samDone = false;
     b->stagedPending = false;
     return 0;
 }
@@ -387,6 +396,7 @@ int ma_batch_set_reads( ma_batch* b, const uint8_t* codes, const uint64_t* offse
     b->d_roff = b->roff.as<u64>( );
     b->reads_external = false;
     b->stage_done = 0;
+    b->txtSet = b->samDone = false;
     return 0;
 }
 
@@ -422,6 +432,7 @@ int ma_batch_set_reads_device( ma_batch* b, const void* d_codes, const void* d_o
         return 1;
     b->max_qlen = (u32)b->hctr[ 0 ];
     b->stage_done = 0;
+    b->txtSet = b->samDone = false;
     return 0;
 }
 
@@ -1125,3 +1136,5 @@ int ma_debug_seed_prof( unsigned long long* out )
 } // extern "C"
 
 #include "launch_pair.h"
+
+#include "launch_sam.h"

@@ -187,7 +187,11 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
     std::atomic<uint64_t> uiBytes{ 0 }, uiReads{ 0 };
 
     BatchFileWriter( const ParameterSetManager& rParameters, std::shared_ptr<OutStream> pOut, std::shared_ptr<Pack> pPack )
-        : pPerRead( std::make_shared<FileWriter>( rParameters, pOut, pPack ) )
+        : BatchFileWriter( rParameters, std::make_shared<FileWriter>( rParameters, pOut, pPack ), pPack )
+    {}
+    // on the stream (and behind the header) of a FileWriter that exists already
+    BatchFileWriter( const ParameterSetManager& rParameters, std::shared_ptr<FileWriter> pWriter, std::shared_ptr<Pack> pPack )
+        : pPerRead( pWriter )
     {
         const SamOptions& rO = rParameters.xSam;
         xFormat.bNoSecondary = rO.bNoSecondary, xFormat.bNoSupplementary = rO.bNoSupplementary;
@@ -201,6 +205,11 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
         const size_t n = pReads->size( );
         if( pAligned->size( ) != n )
             throw std::runtime_error( "BatchFileWriter: the batch of alignments does not belong to these reads" );
+        if( pAligned->hasSamText( ) ) // formatted on the device (BatchAligner::executeFlatSam): the batch's text as it is
+        {
+            write( *pAligned );
+            return std::make_shared<libMS::Container>( );
+        }
         if( pPerRead->xOptions.bEmulateNgmlrTags ) // needs Alignment objects and reference bases: the per-read writer
         {
             for( size_t i = 0; i < n; i++ )
@@ -254,6 +263,29 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
         }
         uiBytes += uiTotal, uiReads += n;
         return std::make_shared<libMS::Container>( );
+    }
+    // A batch of BatchAligner::executeFlat / executeFlatSam outside of a graph: device text goes out with ONE write, records
+    // are formatted as in execute( ).
+    void write( const AlignedBatch& rBatch, std::shared_ptr<Pack> pPack = nullptr )
+    {
+        if( !rBatch.hasSamText( ) )
+        {
+            if( pPack == nullptr && pPerRead->xOptions.bEmulateNgmlrTags )
+                throw std::runtime_error( "BatchFileWriter::write: the NGMLR tags need the pack" );
+            auto pReads = std::make_shared<ReadVector>( rBatch.pReads->begin( ) + rBatch.uiFirst,
+                                                        rBatch.pReads->begin( ) + rBatch.uiFirst + rBatch.size( ) );
+            auto pView = std::make_shared<AlignedBatch>( );
+            pView->pReads = pReads, pView->uiFirst = 0, pView->pResult = rBatch.pResult;
+            execute( pReads, pView, pPack );
+            return;
+        }
+        if( pPerRead->xOptions.bEmulateNgmlrTags )
+            throw std::runtime_error( "BatchFileWriter: device text carries no NGMLR tags" );
+        {
+            std::lock_guard<std::mutex> xGuard( *pPerRead->pLock );
+            pPerRead->pOut->write( rBatch.samText( ), rBatch.samBytes( ) );
+        }
+        uiBytes += rBatch.samBytes( ), uiReads += rBatch.size( );
     }
     virtual bool requiresLock( ) const
     {

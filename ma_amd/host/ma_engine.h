@@ -50,6 +50,20 @@ struct ReadRef
     {}
 };
 
+// QNAME and QUAL of a read for the SAM mode of Engine::run (pQuality: nullptr or one character per base)
+struct ReadText
+{
+    const char* pName = nullptr;
+    size_t uiNameLen = 0;
+    const uint8_t* pQuality = nullptr;
+};
+// SAM mode of Engine::run: the text of the batch's reads (one entry per read) and the MA_SAM_* bits of ma_sam_batch
+struct SamMode
+{
+    const std::vector<ReadText>* pText = nullptr;
+    uint32_t uiOptions = 0;
+};
+
 inline void engineCheck( int rc )
 {
     if( rc != 0 )
@@ -196,6 +210,14 @@ struct BatchResult
     HostBuf<uint64_t> vPairOps;
     HostBuf<int32_t> vPairMate, vPairOther;
     uint64_t uiPairRecords = 0, uiPairOps = 0, uiPairsOnHost = 0; // (uiPairsOnHost: pairs the library finished on the host)
+    // SAM batches (Engine::run with a SamMode): INSTEAD of the MappingQuality records the SAM text the device formatted from
+    // them (ma_sam_batch / ma_batch_get_sam): read r's records are vSam[ vSamOff[r] .. vSamOff[r+1] ), what FileWriter::execute
+    // prints for it.  A batch the device does not serve (some reads with qualities, some without) keeps bSam false and
+    // carries the records as usual.
+    bool bSam = false;
+    HostBuf<uint64_t> vSamOff; // uiReads + 1
+    HostBuf<char> vSam;
+    uint64_t uiSamBytes = 0;
     double fPack = 0, fH2D = 0, fKernels = 0, fD2H = 0; // seconds: gathering the reads, upload, all stages, download
     float aStageMs[ 8 ] = { 0, 0, 0, 0, 0, 0, 0, 0 }; // host wall time of seed / extract / chain / dp (ma_batch_host_ms)
 };
@@ -209,6 +231,9 @@ class Engine
     uint64_t uiCapReads = 0, uiCapBases = 0;
     HostBuf<uint8_t> vCodes; // page-locked staging of the reads
     HostBuf<uint64_t> vOff;
+    HostBuf<char> vNames; // SAM mode: QNAMEs, their CSR offsets and the qualities of the batch
+    HostBuf<uint64_t> vNameOff;
+    HostBuf<uint8_t> vQual;
     const bool bBlocking; // waits sleep instead of spinning (hosts that run far more threads than cores)
     // results are handed out as shared_ptr; one that nobody holds any more is reused (its page-locked arrays are kept)
     std::vector<std::shared_ptr<BatchResult>> vPool;
@@ -292,7 +317,8 @@ class Engine
             vRefs.emplace_back( *pRead );
         return run( vRefs, bStages );
     }
-    std::shared_ptr<BatchResult> run( const std::vector<ReadRef>& vReads, bool bStages, bool bPairs = false )
+    // pSam: SAM mode -- the result carries the SAM text of the reads instead of their MappingQuality records
+    std::shared_ptr<BatchResult> run( const std::vector<ReadRef>& vReads, bool bStages, bool bPairs = false, const SamMode* pSam = nullptr )
     {
         const size_t n = vReads.size( );
         auto tPack = std::chrono::steady_clock::now( );
@@ -319,14 +345,57 @@ class Engine
             for( auto& rT : vT )
                 rT.join( );
         }
+        // SAM mode: names and qualities next to the codes.  The device takes qualities for all reads of a batch or for none
+        // (ma_batch_set_read_text); a batch that mixes the two is not served and comes back as records.
+        SamText xText;
+        if( pSam != nullptr )
+        {
+            if( bPairs || pSam->pText == nullptr || pSam->pText->size( ) != n )
+                throw std::runtime_error( "Engine::run: the SAM mode needs one ReadText per read and no pairs" );
+            const std::vector<ReadText>& rT = *pSam->pText;
+            size_t uiWithQual = 0;
+            uint64_t* pNameOff = vNameOff.need( n + 1 );
+            pNameOff[ 0 ] = 0;
+            for( size_t i = 0; i < n; i++ )
+            {
+                pNameOff[ i + 1 ] = pNameOff[ i ] + rT[ i ].uiNameLen;
+                uiWithQual += rT[ i ].pQuality != nullptr;
+            }
+            if( uiWithQual == 0 || uiWithQual == n )
+            {
+                char* pNames = vNames.need( pNameOff[ n ] + 1 );
+                uint8_t* pQual = uiWithQual ? vQual.need( pOff[ n ] + 1 ) : nullptr;
+                for( size_t i = 0; i < n; i++ )
+                {
+                    if( rT[ i ].uiNameLen != 0 )
+                        memcpy( pNames + pNameOff[ i ], rT[ i ].pName, rT[ i ].uiNameLen );
+                    if( pQual != nullptr && vReads[ i ].uiLength != 0 )
+                        memcpy( pQual + pOff[ i ], rT[ i ].pQuality, vReads[ i ].uiLength );
+                }
+                xText.pNames = pNames, xText.pNameOff = pNameOff, xText.pQual = pQual, xText.uiOptions = pSam->uiOptions;
+                xText.bOn = true;
+            }
+        }
         const double fPack = secondsSince( tPack );
-        auto pRes = runFlat( pCodes, pOff, n, bStages, bPairs );
+        auto pRes = runFlat( pCodes, pOff, n, bStages, bPairs, xText.bOn ? &xText : nullptr );
         pRes->fPack = fPack;
         return pRes;
     }
+    // SAM mode of runFlat: the reads' names (CSR, n + 1 offsets), their qualities (nullptr, or one character per base in the
+    // reads' CSR) and the MA_SAM_* bits
+    struct SamText
+    {
+        const char* pNames = nullptr;
+        const uint64_t* pNameOff = nullptr;
+        const uint8_t* pQual = nullptr;
+        uint32_t uiOptions = 0;
+        bool bOn = false;
+    };
     // reads that already are one array of codes + CSR offsets (n + 1), e.g. in page-locked memory the caller filled
     // bPairs: the reads are mate pairs (2k, 2k + 1); the result carries the pair records instead of the MappingQuality ones
-    std::shared_ptr<BatchResult> runFlat( const uint8_t* pCodes, const uint64_t* pOff, size_t n, bool bStages, bool bPairs = false )
+    // pSam: the result carries the SAM text (BatchResult::vSamOff / vSam) instead of the MappingQuality records
+    std::shared_ptr<BatchResult> runFlat( const uint8_t* pCodes, const uint64_t* pOff, size_t n, bool bStages, bool bPairs = false,
+                                          const SamText* pSam = nullptr )
     {
         auto pRes = freshResult( );
         BatchResult& R = *pRes;
@@ -334,10 +403,14 @@ class Engine
         R.bStages = bStages;
         R.bSocQueues = false;
         R.bPairs = bPairs;
+        R.bSam = pSam != nullptr;
+        R.uiSamBytes = 0;
         R.fPack = 0;
         fit( n, pOff[ n ] );
         auto t0 = std::chrono::steady_clock::now( );
         engineCheck( ma_batch_set_reads( pBatch, pCodes, pOff, n ) );
+        if( pSam != nullptr )
+            engineCheck( ma_batch_set_read_text( pBatch, pSam->pNames, pSam->pNameOff, pSam->pQual ) );
         R.fH2D = secondsSince( t0 );
         t0 = std::chrono::steady_clock::now( );
         engineCheck( ma_align_batch( pBatch ) );
@@ -387,6 +460,14 @@ class Engine
                                              R.vPairOps.need( 2 * R.uiPairOps + 2 ), R.vPairMate.need( R.uiPairRecords + 1 ),
                                              R.vPairOther.need( R.uiPairRecords + 1 ) ) );
             memset( pMqOff, 0, ( n + 1 ) * sizeof( uint64_t ) ); // no per-read records in a paired result
+        }
+        else if( pSam != nullptr )
+        {
+            // the text replaces the record download: ma_sam_batch waits once for the size, then one copy of offsets + bytes
+            engineCheck( ma_sam_batch( pBatch, pSam->uiOptions ) );
+            engineCheck( ma_batch_sam_counts( pBatch, &R.uiSamBytes ) );
+            engineCheck( ma_batch_get_sam( pBatch, R.vSamOff.need( n + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
+            memset( pMqOff, 0, ( n + 1 ) * sizeof( uint64_t ) ); // no records in a SAM result
         }
         else
             engineCheck( ma_batch_get_mapq_alignments( pBatch, pMqOff, R.vMq.need( nAln + 1 ), R.vMqOps.need( 2 * nOps + 2 ) ) );

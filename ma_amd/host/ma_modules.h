@@ -1443,6 +1443,24 @@ class AlignedBatch : public libMS::Container
     {
         return pResult->vPairOther.data( );
     }
+    // A SAM batch (BatchAligner::executeFlatSam): instead of records it holds the SAM text the device formatted, read i's
+    // records are samText()[ samOffsets()[i] .. samOffsets()[i+1] ) -- the bytes FileWriter::execute prints for it
+    bool hasSamText( ) const
+    {
+        return pResult != nullptr && pResult->bSam;
+    }
+    const uint64_t* samOffsets( ) const
+    {
+        return pResult->vSamOff.data( );
+    }
+    const char* samText( ) const
+    {
+        return pResult->vSam.data( );
+    }
+    uint64_t samBytes( ) const
+    {
+        return pResult->uiSamBytes;
+    }
     std::shared_ptr<AlignmentVector> alignmentsOf( size_t uiRead ) const
     {
         auto pV = std::make_shared<AlignmentVector>( );
@@ -1528,7 +1546,7 @@ class BatchAligner
     void alignRangeOn( const std::vector<const ma_index*>& vIndices, const libMS::ContainerVector<std::shared_ptr<NucSeq>>& rQueries,
                        size_t uiFrom, size_t uiTo, TP_RESULT* pOut, AlignerTiming& rT, TP_FLAT* pFlat = nullptr,
                        std::shared_ptr<ReadVector> pReadsOfFlat = nullptr, std::vector<AlignerTiming>* pPerIndex = nullptr,
-                       bool bPairs = false ) const
+                       bool bPairs = false, const uint32_t* pSamOptions = nullptr ) const
     {
         if( vIndices.empty( ) )
             throw std::runtime_error( "BatchAligner: no index" );
@@ -1549,7 +1567,25 @@ class BatchAligner
             vReads.reserve( hi - lo );
             for( size_t i = lo; i < hi; i++ )
                 vReads.emplace_back( rQueries[ i ]->xCodes );
-            auto pRes = xEngine.run( vReads, false, bPairs );
+            // pSamOptions: the batch comes back as SAM text (Engine::run's SAM mode) instead of records
+            std::vector<detail::ReadText> vText;
+            detail::SamMode xSam;
+            if( pSamOptions != nullptr )
+            {
+                vText.resize( hi - lo );
+                for( size_t i = lo; i < hi; i++ )
+                {
+                    const NucSeq& rQ = *rQueries[ i ];
+                    vText[ i - lo ].pName = rQ.sName.data( ), vText[ i - lo ].uiNameLen = rQ.sName.size( );
+                    vText[ i - lo ].pQuality = rQ.xQuality.empty( ) ? nullptr : rQ.xQuality.data( );
+                    if( !rQ.xQuality.empty( ) && rQ.xQuality.size( ) != rQ.xCodes.size( ) )
+                        throw std::runtime_error( "BatchAligner::executeFlatSam: read '" + rQ.sName + "' has " +
+                                                  std::to_string( rQ.xQuality.size( ) ) + " quality values for " +
+                                                  std::to_string( rQ.xCodes.size( ) ) + " bases" );
+                }
+                xSam.pText = &vText, xSam.uiOptions = *pSamOptions;
+            }
+            auto pRes = xEngine.run( vReads, false, bPairs, pSamOptions != nullptr ? &xSam : nullptr );
             const auto t0 = std::chrono::steady_clock::now( );
             if( pFlat )
             {
@@ -1727,6 +1763,66 @@ class BatchAligner
         const auto t0 = std::chrono::steady_clock::now( );
         if( !pQueries->empty( ) )
             alignRangeOn( pFM_index->pDev->all( ), *pQueries, 0, pQueries->size( ), nullptr, xLast, pRet.get( ), pQueries, &vLastPerIndex );
+        xLast.fWall = detail::secondsSince( t0 );
+        return pRet;
+    }
+
+    // The MA_SAM_* bits of ma_sam_batch for the writer's options.  The NGMLR tag emulation needs reference bases and Alignment
+    // objects and is not served by the device: servesSam( ) is false for it (and for "Detect Small Inversions", which needs
+    // containers before the records are final).
+    static uint32_t samOptionBits( const SamOptions& rO )
+    {
+        return ( rO.bSoftClip ? MA_SAM_SOFT_CLIP : 0u ) | ( rO.bOutputMCigar ? 0u : MA_SAM_EQX_CIGAR ) |
+               ( rO.bNoSecondary ? MA_SAM_NO_SECONDARY : 0u ) | ( rO.bNoSupplementary ? MA_SAM_NO_SUPPLEMENTARY : 0u ) |
+               ( rO.bCGTag ? 0u : MA_SAM_NO_CG_TAG );
+    }
+    bool servesSam( ) const
+    {
+        return !xP.search_inversions && !xParams.xSam.bEmulateNgmlrTags;
+    }
+    // RNAME strings of pPack on an index and its replicas (ma_index_set_contig_names)
+    static void nameContigs( const DeviceIndex& rDev, const Pack& rPack )
+    {
+        std::string sNames;
+        std::vector<uint64_t> vOff( 1, 0 );
+        for( const std::string& rName : rPack.vNames )
+        {
+            sNames += rName;
+            vOff.push_back( sNames.size( ) );
+        }
+        int32_t nContigs = 0;
+        maCheck( ma_index_sizes( rDev.p, nullptr, nullptr, nullptr, &nContigs ) );
+        if( (size_t)nContigs != rPack.vNames.size( ) )
+            throw std::runtime_error( "BatchAligner::executeFlatSam: the pack names " + std::to_string( rPack.vNames.size( ) ) +
+                                      " contigs, the index holds " + std::to_string( nContigs ) );
+        maCheck( ma_index_set_contig_names( rDev.p, sNames.data( ), vOff.data( ) ) );
+        for( const auto& pR : rDev.vReplicas )
+            maCheck( ma_index_set_contig_names( pR->p, sNames.data( ), vOff.data( ) ) );
+    }
+
+    // executeFlat with the SAM records formatted on the DEVICE (ma_sam_batch): one AlignedBatch per device batch, in input
+    // order, holding the text of its reads (AlignedBatch::hasSamText) instead of records -- the bytes FileWriter::execute
+    // prints under this aligner's SAM options; no record download and no host formatting.  BatchFileWriter writes such a batch
+    // with one call.  A batch whose reads only partly have qualities comes back with records as from executeFlat.
+    std::shared_ptr<TP_FLAT> executeFlatSam( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<ReadVector> pQueries,
+                                             std::shared_ptr<Pack> pPack )
+    {
+        nameContigs( *pFM_index->pDev, *pPack );
+        return executeFlatSamOn( pFM_index->pDev->all( ), pQueries, &vLastPerIndex );
+    }
+    // (the contigs of vIndices are named already)
+    std::shared_ptr<TP_FLAT> executeFlatSamOn( const std::vector<const ma_index*>& vIndices, std::shared_ptr<ReadVector> pQueries,
+                                               std::vector<AlignerTiming>* pPerIndex )
+    {
+        if( !servesSam( ) )
+            throw std::runtime_error( "BatchAligner::executeFlatSam: not with 'Detect Small Inversions' or the NGMLR tag emulation "
+                                      "(use executeFlat and BatchFileWriter)" );
+        const uint32_t uiOptions = samOptionBits( xParams.xSam );
+        auto pRet = std::make_shared<TP_FLAT>( );
+        xLast = AlignerTiming( );
+        const auto t0 = std::chrono::steady_clock::now( );
+        if( !pQueries->empty( ) )
+            alignRangeOn( vIndices, *pQueries, 0, pQueries->size( ), nullptr, xLast, pRet.get( ), pQueries, pPerIndex, false, &uiOptions );
         xLast.fWall = detail::secondsSince( t0 );
         return pRet;
     }
@@ -1949,6 +2045,20 @@ class MultiDeviceAligner
         if( !pQueries->empty( ) )
             xAligner.alignRangeOn( vIndices, *pQueries, 0, pQueries->size( ), nullptr, xLast, pRet.get( ), pQueries, &vLast );
         xLast.fWall = detail::secondsSince( t0 );
+        for( auto& rT : vLast )
+            rT.fWall = xLast.fWall;
+        return pRet;
+    }
+
+    // BatchAligner::executeFlatSam over all replicas: every device batch comes back as the SAM text its device formatted.
+    std::shared_ptr<BatchAligner::TP_FLAT> executeFlatSam( std::shared_ptr<ReadVector> pQueries, std::shared_ptr<Pack> pPack )
+    {
+        configure( );
+        for( const auto& pFM : vReplicas )
+            BatchAligner::nameContigs( *pFM->pDev, *pPack );
+        vLast.assign( vIndices.size( ), AlignerTiming( ) );
+        auto pRet = xAligner.executeFlatSamOn( vIndices, pQueries, &vLast );
+        xLast = xAligner.xLast;
         for( auto& rT : vLast )
             rT.fWall = xLast.fWall;
         return pRet;

@@ -1,0 +1,417 @@
+// ma_sam_dev.h -- the single-end SAM record formatter of ma_flat_sam.h (flat::formatRead / putRecord / putUnmapped: the bytes of
+// the reference's FileWriter::execute, libs/ma/src/module/fileWriter.cpp:11-158) restated ONCE over a templated sink, for
+// three users:
+//   - the device stage (ma_amd/csrc/stage_sam.h) runs formatRead( ) inside its two kernels: with the counting sink to size
+//     every read's text, with a writing sink to store it;
+//   - the CPU tests (tests/emul/sam_dev_test.cpp) run the same function on the host and pin it, byte for byte, to
+//     flat::formatRead and to the SAM goldens the compiled reference wrote;
+//   - libma_amd.so words the error of a bad record with errorText( ).
+// No reference headers, no containers, no strings: include/ma_amd.h only.  ma_flat_sam.h stays the yardstick and documents
+// where each oddity comes from; they are kept as they are:
+//   position one further on the reverse strand; MAPQ = (int)ceil( mapq * 254 ), 255 for NaN; the cigar walked backwards on the
+//   reverse strand; seed / match / mismatch merged into M (or printed as = / X); H or S clips with the left-over clip taken
+//   against the read length; SEQ reverse-complemented on the reverse strand, QUAL the aligned part and never reversed, "*"
+//   without qualities; "<len>S" + the CG:B:I tag from 0x10000 ops on; alignments of op length 0 skipped; secondary /
+//   supplementary records dropped on request; the unmapped record with MAPQ text 255 for an empty list and 0 when every
+//   alignment was skipped.
+//
+// A sink is anything with
+//   put( c ), bytes( p, n ), number( x ), size( )          plain columns
+//   seq( read, from, to, reverse, k )                       SEQ of record k of the list (k = UNMAPPED: of the unmapped record)
+//   qual( read, from, to, k )                               QUAL (only called when the read has qualities)
+//   error( kind, value, k )                                 record k cannot be printed (see ERR_*)
+// The kernels' writing sink leaves SEQ and QUAL out (it only notes where they go): the wavefront copies them together.
+#pragma once
+#if !defined( MA_AMD_H ) // (libma_amd.so includes it by its own path)
+#include "ma_amd.h"
+#endif
+
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#if defined( __HIPCC__ )
+#define MA_SAM_HD __host__ __device__ __forceinline__
+#else
+#define MA_SAM_HD inline
+#endif
+
+namespace ma_sam
+{
+enum : uint32_t // == MA_SAM_* of include/ma_amd.h
+{
+    SOFT_CLIP = 1u, // S instead of H clips, SEQ = the whole read
+    EQX_CIGAR = 2u, // = and X instead of M
+    NO_SECONDARY = 4u,
+    NO_SUPPLEMENTARY = 8u,
+    NO_CG_TAG = 16u, // over-long cigars are printed as they are
+    ALL_OPTIONS = 31u
+};
+enum : uint32_t
+{
+    ERR_QUERY_LENGTH = 1u, // "Query length is off by <value>." (forward strand, end_q beyond the read; fileWriter.cpp:106)
+    ERR_COMP_CHAR_AT = 2u // "Index out of range (compCharAt)" (reverse strand, the same)
+};
+enum : uint32_t
+{
+    UNMAPPED = 0xffffffffu
+};
+
+// contig table of the pack (forward strand); names[ name_off[ i ] .. name_off[ i + 1 ] ) is contig i's RNAME
+struct Contigs
+{
+    const char* names;
+    const uint64_t* name_off;
+    const uint64_t* starts;
+    const uint64_t* lengths;
+    uint32_t n; // >= 1
+    MA_SAM_HD uint64_t forwardSize( ) const
+    {
+        return starts[ n - 1 ] + lengths[ n - 1 ];
+    }
+    // Pack::uiSequenceIdForPosition (pack.h:933-990) of a position on the forward strand
+    MA_SAM_HD uint32_t idOfForward( uint64_t uiPos ) const
+    {
+        uint32_t lo = 0, hi = n;
+        while( hi - lo > 1 )
+        {
+            const uint32_t mid = lo + ( hi - lo ) / 2;
+            if( uiPos >= starts[ mid ] )
+                lo = mid;
+            else
+                hi = mid;
+        }
+        return lo;
+    }
+};
+struct Read
+{
+    const char* name;
+    uint64_t name_len;
+    const uint8_t* codes; // A0 C1 G2 T3, else N
+    const uint8_t* qual; // FASTQ quality characters or null
+    uint64_t length;
+};
+// what a record reads of an alignment
+struct Rec
+{
+    uint64_t begin_ref, end_ref, begin_q, end_q;
+    uint32_t n_ops, secondary, supplementary;
+    double mapq;
+};
+// A list is anything with size( ), rec( k ), opType( k, j ), opLen( k, j ).  This one is over the arrays of
+// ma_batch_get_mapq_alignments (ops_off counts (type, length) pairs).
+struct FlatList
+{
+    const ma_alignment* alns;
+    uint32_t n;
+    const uint64_t* ops;
+    MA_SAM_HD uint32_t size( ) const
+    {
+        return n;
+    }
+    MA_SAM_HD Rec rec( uint32_t k ) const
+    {
+        const ma_alignment& a = alns[ k ];
+        return Rec{ (uint64_t)a.begin_ref, (uint64_t)a.end_ref, (uint64_t)a.begin_q, (uint64_t)a.end_q, a.n_ops, a.secondary, a.supplementary, a.mapq };
+    }
+    MA_SAM_HD uint64_t opType( uint32_t k, uint32_t j ) const
+    {
+        return ops[ 2 * ( alns[ k ].ops_off + j ) ];
+    }
+    MA_SAM_HD uint64_t opLen( uint32_t k, uint32_t j ) const
+    {
+        return ops[ 2 * ( alns[ k ].ops_off + j ) + 1 ];
+    }
+};
+
+// ---- characters ----------------------------------------------------------------------------------------------------------
+MA_SAM_HD char baseChar( uint8_t c ) // "ACGTN"[ c < 4 ? c : 4 ] without a table
+{
+    return (char)( ( 0x4E54474341ull >> ( 8 * ( c < 4 ? c : 4 ) ) ) & 0xff );
+}
+MA_SAM_HD char complementChar( uint8_t c )
+{
+    return baseChar( c < 4 ? (uint8_t)( 3 - c ) : (uint8_t)4 );
+}
+MA_SAM_HD uint32_t digits( uint64_t x ) // decimal digits of x
+{
+    uint32_t d = 1;
+    uint64_t p = 10;
+    while( d < 20 && x >= p )
+    {
+        d++;
+        p *= 10; // (wraps only after d reached 20)
+    }
+    return d;
+}
+
+// ---- the two sinks -------------------------------------------------------------------------------------------------------
+struct CountSink
+{
+    uint64_t n = 0;
+    uint32_t nErrors = 0, firstKind = 0, firstRecord = 0;
+    int64_t firstValue = 0;
+    MA_SAM_HD uint64_t size( ) const
+    {
+        return n;
+    }
+    MA_SAM_HD void put( char )
+    {
+        n++;
+    }
+    MA_SAM_HD void bytes( const char*, uint64_t k )
+    {
+        n += k;
+    }
+    MA_SAM_HD void number( uint64_t x )
+    {
+        n += digits( x );
+    }
+    MA_SAM_HD void seq( const Read&, uint64_t uiFrom, uint64_t uiTo, bool, uint32_t )
+    {
+        n += uiTo - uiFrom;
+    }
+    MA_SAM_HD void qual( const Read&, uint64_t uiFrom, uint64_t uiTo, uint32_t )
+    {
+        n += uiTo - uiFrom;
+    }
+    MA_SAM_HD void error( uint32_t uiKind, int64_t iValue, uint32_t k )
+    {
+        if( nErrors++ == 0 )
+            firstKind = uiKind, firstValue = iValue, firstRecord = k;
+    }
+};
+struct WriteSink
+{
+    char* p;
+    uint64_t n = 0;
+    MA_SAM_HD uint64_t size( ) const
+    {
+        return n;
+    }
+    MA_SAM_HD void put( char c )
+    {
+        p[ n++ ] = c;
+    }
+    MA_SAM_HD void bytes( const char* s, uint64_t k )
+    {
+        for( uint64_t i = 0; i < k; i++ )
+            p[ n + i ] = s[ i ];
+        n += k;
+    }
+    MA_SAM_HD void number( uint64_t x ) // by digit count: the last digit first, each where it belongs
+    {
+        const uint32_t d = digits( x );
+        for( uint32_t i = d; i > 0; i-- )
+        {
+            p[ n + i - 1 ] = (char)( '0' + x % 10 );
+            x /= 10;
+        }
+        n += d;
+    }
+    MA_SAM_HD void seq( const Read& rQ, uint64_t uiFrom, uint64_t uiTo, bool bRev, uint32_t )
+    {
+        for( uint64_t i = 0; i < uiTo - uiFrom; i++ )
+            p[ n + i ] = bRev ? complementChar( rQ.codes[ uiTo - 1 - i ] ) : baseChar( rQ.codes[ uiFrom + i ] );
+        n += uiTo - uiFrom;
+    }
+    MA_SAM_HD void qual( const Read& rQ, uint64_t uiFrom, uint64_t uiTo, uint32_t )
+    {
+        bytes( (const char*)rQ.qual + uiFrom, uiTo - uiFrom );
+    }
+    MA_SAM_HD void error( uint32_t, int64_t, uint32_t )
+    {}
+};
+
+namespace detail
+{
+template <class Sink, size_t N> MA_SAM_HD void lit( Sink& rOut, const char ( &s )[ N ] )
+{
+    for( size_t i = 0; i + 1 < N; i++ )
+        rOut.put( s[ i ] );
+}
+template <class Sink> MA_SAM_HD void numberAnd( Sink& rOut, uint64_t x, char c )
+{
+    rOut.number( x );
+    rOut.put( c );
+}
+// QUAL of [uiFrom, uiTo): clamped to the read (nucSeq.h:697-709), never reversed
+template <class Sink> MA_SAM_HD void putQuality( Sink& rOut, const Read& rQ, uint64_t uiFrom, uint64_t uiTo, uint32_t k )
+{
+    if( rQ.qual == nullptr )
+    {
+        rOut.put( '*' );
+        return;
+    }
+    if( uiTo > rQ.length )
+        uiTo = rQ.length;
+    if( uiFrom < uiTo )
+        rOut.qual( rQ, uiFrom, uiTo, k );
+}
+template <class Sink> MA_SAM_HD void putUnmapped( Sink& rOut, const Read& rQ, bool bEmptyList ) // fileWriter.cpp:126-140
+{
+    rOut.bytes( rQ.name, rQ.name_len );
+    lit( rOut, "\t4\t*\t0\t" );
+    if( bEmptyList )
+        lit( rOut, "255" );
+    else
+        rOut.put( '0' );
+    lit( rOut, "\t*\t*\t0\t0\t" );
+    if( rQ.length > 0 )
+        rOut.seq( rQ, 0, rQ.length, false, UNMAPPED );
+    rOut.put( '\t' );
+    putQuality( rOut, rQ, 0, rQ.length, UNMAPPED );
+    rOut.put( '\n' );
+}
+// One record of an aligned read: the eleven columns and the CG tag
+template <class Sink, class List>
+MA_SAM_HD void putRecord( Sink& rOut, uint32_t uiOptions, const Contigs& rContigs, const Read& rQ, const Rec& rA, const List& rList, uint32_t k )
+{
+    const bool bSoftClip = ( uiOptions & SOFT_CLIP ) != 0, bMCigar = ( uiOptions & EQX_CIGAR ) == 0;
+    const uint64_t uiFwd = rContigs.forwardSize( );
+    const uint64_t uiBeginRef = rA.begin_ref, uiEndRef = rA.end_ref, uiBeginQ = rA.begin_q, uiEndQ = rA.end_q;
+    const bool bRev = uiBeginRef >= uiFwd;
+    const bool bLong = ( uiOptions & NO_CG_TAG ) == 0 && rA.n_ops >= 0x10000;
+    // QNAME FLAG RNAME POS MAPQ
+    rOut.bytes( rQ.name, rQ.name_len );
+    rOut.put( '\t' );
+    numberAnd( rOut, ( bRev ? 0x10u : 0u ) | ( rA.secondary ? 0x100u : 0u ) | ( rA.supplementary ? 0x800u : 0u ), '\t' );
+    // contig of the begin (pack.h:1063-1067); position of the alignment's forward-strand start, 1-based, (sic) one further for
+    // reverse-strand alignments (alignment.h:596-603)
+    const uint32_t uiContig = rContigs.idOfForward( bRev ? 2 * uiFwd - ( uiBeginRef + 1 ) : uiBeginRef );
+    rOut.bytes( rContigs.names + rContigs.name_off[ uiContig ], rContigs.name_off[ uiContig + 1 ] - rContigs.name_off[ uiContig ] );
+    rOut.put( '\t' );
+    const uint64_t uiAbs = uiEndRef >= uiFwd ? 2 * uiFwd - ( uiEndRef + 1 ) : uiBeginRef;
+    numberAnd( rOut, uiAbs - rContigs.starts[ rContigs.idOfForward( uiAbs ) ] + ( bRev ? 1 : 0 ) + 1, '\t' );
+    if( rA.mapq != rA.mapq ) // NaN
+        lit( rOut, "255" );
+    else
+    {
+        const int iMapQ = (int)ceil( rA.mapq * 254 );
+        if( iMapQ < 0 )
+        {
+            rOut.put( '-' );
+            rOut.number( (uint64_t)( -(int64_t)iMapQ ) );
+        }
+        else
+            rOut.number( (uint64_t)iMapQ );
+    }
+    rOut.put( '\t' );
+    // CIGAR (alignment.h:367-467): clip, the sections in forward-strand direction, clip
+    if( bLong )
+        numberAnd( rOut, uiEndQ - uiBeginQ, 'S' );
+    else
+    {
+        const uint64_t uiLeftOver = uiEndQ < rQ.length ? rQ.length - uiEndQ : 0;
+        const uint64_t uiHead = bRev ? uiLeftOver : uiBeginQ, uiTail = bRev ? uiBeginQ : uiLeftOver;
+        const char cClip = bSoftClip ? 'S' : 'H';
+        if( uiHead > 0 )
+            numberAnd( rOut, uiHead, cClip );
+        uint64_t uiRunM = 0;
+        for( uint32_t j = 0; j < rA.n_ops; j++ )
+        {
+            const uint32_t jj = bRev ? rA.n_ops - 1 - j : j;
+            const uint64_t uiType = rList.opType( k, jj ), uiLen = rList.opLen( k, jj );
+            if( uiType <= 2 ) // seed, match, missmatch
+            {
+                if( bMCigar )
+                    uiRunM += uiLen;
+                else
+                    numberAnd( rOut, uiLen, uiType == 2 ? 'X' : '=' );
+            }
+            else
+            {
+                if( bMCigar && uiRunM > 0 )
+                {
+                    numberAnd( rOut, uiRunM, 'M' );
+                    uiRunM = 0;
+                }
+                numberAnd( rOut, uiLen, uiType == 3 ? 'I' : 'D' );
+            }
+        }
+        if( bMCigar && uiRunM > 0 )
+            numberAnd( rOut, uiRunM, 'M' );
+        if( uiTail > 0 )
+            numberAnd( rOut, uiTail, cClip );
+    }
+    lit( rOut, "\t*\t0\t0\t" );
+    // SEQ: the whole read when soft clipping, else the aligned part; reverse-complemented on the reverse strand.  A record that
+    // ends beyond the read is an error (the host formatter throws); nothing beyond the read is ever touched.
+    const uint64_t uiFrom = bSoftClip ? 0 : uiBeginQ;
+    uint64_t uiTo = bSoftClip ? rQ.length : uiEndQ;
+    if( uiTo > rQ.length )
+    {
+        if( bRev )
+            rOut.error( ERR_COMP_CHAR_AT, 0, k );
+        else
+            rOut.error( ERR_QUERY_LENGTH, (int64_t)rQ.length - (int64_t)uiTo, k );
+        uiTo = rQ.length;
+    }
+    if( uiFrom < uiTo )
+        rOut.seq( rQ, uiFrom, uiTo, bRev, k );
+    rOut.put( '\t' );
+    putQuality( rOut, rQ, uiBeginQ, uiEndQ, k ); // (sic) the aligned part, not reversed (alignment.h:611-614)
+    if( bLong ) // TagGenerator::computeTag (fileWriter.h:327-357): the real cigar as CG:B:I
+    {
+        lit( rOut, "\tCG:B:I" );
+        for( uint32_t j = 0; j < rA.n_ops; j++ )
+        {
+            const uint64_t uiType = rList.opType( k, j );
+            rOut.put( ',' );
+            // op codes 7 7 8 1 2 of seed, match, missmatch, insertion, deletion
+            rOut.number( (uint32_t)( rList.opLen( k, j ) << 4 ) | (uint32_t)( ( 0x21877u >> ( 4 * ( uiType < 5 ? uiType : 0 ) ) ) & 0xf ) );
+        }
+    }
+    rOut.put( '\n' );
+}
+} // namespace detail
+
+// The SAM records of ONE read: the alignments of rList in MappingQuality order.
+template <class Sink, class List>
+MA_SAM_HD void formatRead( Sink& rOut, uint32_t uiOptions, const Contigs& rContigs, const Read& rQ, const List& rList )
+{
+    const uint32_t uiAlns = rList.size( );
+    bool bAny = false;
+    for( uint32_t k = 0; k < uiAlns; k++ )
+    {
+        const Rec xA = rList.rec( k );
+        bool bNonZero = false; // Alignment::length( ) != 0
+        for( uint32_t j = 0; j < xA.n_ops && !bNonZero; j++ )
+            bNonZero = rList.opLen( k, j ) != 0;
+        if( !bNonZero )
+            continue;
+        if( ( ( uiOptions & NO_SECONDARY ) && xA.secondary ) || ( ( uiOptions & NO_SUPPLEMENTARY ) && xA.supplementary ) )
+            continue;
+        detail::putRecord( rOut, uiOptions, rContigs, rQ, xA, rList, k );
+        bAny = true;
+    }
+    if( uiAlns == 0 )
+        detail::putUnmapped( rOut, rQ, true );
+    else if( !bAny )
+        detail::putUnmapped( rOut, rQ, false );
+}
+
+// The text of the host formatter's exception for an error a sink was told of; returns its length (buf holds >= 64 bytes, the
+// text is 0-terminated).
+inline size_t errorText( char* buf, uint32_t uiKind, int64_t iValue )
+{
+    WriteSink xOut{ buf };
+    if( uiKind == ERR_QUERY_LENGTH )
+    {
+        detail::lit( xOut, "Query length is off by " );
+        if( iValue < 0 )
+        {
+            xOut.put( '-' );
+            xOut.number( (uint64_t)( -iValue ) );
+        }
+        else
+            xOut.number( (uint64_t)iValue );
+        xOut.put( '.' );
+    }
+    else
+        detail::lit( xOut, "Index out of range (compCharAt)" );
+    xOut.put( '\0' );
+    return (size_t)xOut.size( ) - 1;
+}
+} // namespace ma_sam
