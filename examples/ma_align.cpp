@@ -6,7 +6,9 @@
 //
 // Single-end input is printed on the device (BatchAligner::executeFlatSam: the SAM text is what comes down) whenever the
 // options are ones the device serves; with "Detect Small Inversions", with the NGMLR tag emulation and with --host-sam the
-// records come down and FileWriter prints them.  The bytes are the same.
+// records come down and FileWriter prints them.  Paired input likewise: mates are paired and their records printed on the
+// device (BatchAligner::executePairedFlatSam), or the pair records come down and BatchPairedFileWriter formats them.  The
+// bytes are the same.
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_align.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
@@ -95,8 +97,10 @@ int main( int argc, char** argv )
         {
             PairedFileReader xPairedReader( xParams );
             auto pStreams = std::make_shared<PairedFileStream>( pIn, fileStreamFromPath( argv[ 5 ] ) );
-            // the flat paired path: mates paired on the device, SAM text straight from the pair records (with "Detect Small
+            // the flat paired path: mates paired on the device, and -- where the device serves the options -- printed there
+            // (ma_pair_sam_batch), one write per device batch; else SAM text straight from the pair records (with "Detect Small
             // Inversions" executePairedFlat itself goes through containers); the bytes are PairedFileWriter's
+            const bool bDeviceSam = xAligner.servesSam( ) && !bHostSam;
             BatchPairedFileWriter xWriter( xParams, std::make_shared<PairedFileWriter>( xParams, std::string( argv[ 3 ] ), pPack ), pPack );
             while( true )
             {
@@ -111,7 +115,7 @@ int main( int argc, char** argv )
                 }
                 if( pMates->empty( ) )
                     break;
-                auto pFlat = xAligner.executePairedFlat( pFM, pMates );
+                auto pFlat = bDeviceSam ? xAligner.executePairedFlatSam( pFM, pMates, pPack ) : xAligner.executePairedFlat( pFM, pMates );
                 for( auto& pBatch : *pFlat )
                     xWriter.execute( *pBatch );
             }

@@ -270,7 +270,8 @@ int main( int argc, char** argv )
             // ---- the paired leg: n mates (n / 2 pairs, outer distance 340 .. 460, every second pair seen from the other strand)
             // host to host INCLUDING SAM text through (a) BatchAligner::executePaired + PairedFileWriter -- Alignment
             // containers, PairedReads on one host thread -- and (b) executePairedFlat + BatchPairedFileWriter -- paired on the
-            // device, text from the flat pair records; alternating, <repeats> times each after one warm-up of each
+            // device, text from the flat pair records -- and (c) executePairedFlatSam + BatchPairedFileWriter -- paired AND
+            // printed on the device, the text is what comes down; alternating, <repeats> times each after one warm-up of each
             const int iRepeats = argc >= 8 ? std::max( 1, atoi( argv[ 7 ] ) ) : 5;
             auto pMates = std::make_shared<ReadVec>( );
             auto window = [ & ]( uint64_t uiPos, bool bRev, size_t uiName ) {
@@ -341,22 +342,41 @@ int main( int argc, char** argv )
                 uiBytesFlat = pSink->uiBytes.load( );
                 return f;
             };
-            container( ), flat( ); // warm-up of both
-            std::vector<double> vC, vF;
+            uint64_t uiBytesDevice = 0, uiTextBatches = 0;
+            auto device = [ & ]( ) {
+                auto pSink = std::make_shared<CountingSink>( );
+                BatchPairedFileWriter xWriter( xParams, std::static_pointer_cast<OutStream>( pSink ), pPack );
+                const double t = now( );
+                uiTextBatches = 0;
+                auto pFlat = xAligner.executePairedFlatSam( pFM, pMates, pPack );
+                for( auto& pB : *pFlat )
+                {
+                    xWriter.execute( *pB );
+                    uiTextBatches += pB->hasSamText( );
+                }
+                const double f = now( ) - t;
+                uiBytesDevice = pSink->uiBytes.load( );
+                return f;
+            };
+            container( ), flat( ), device( ); // warm-up of all three
+            std::vector<double> vC, vF, vD;
             for( int r = 0; r < iRepeats; r++ )
-                vC.push_back( pMates->size( ) / container( ) ), vF.push_back( pMates->size( ) / flat( ) );
+                vC.push_back( pMates->size( ) / container( ) ), vF.push_back( pMates->size( ) / flat( ) ), vD.push_back( pMates->size( ) / device( ) );
             auto list = []( std::vector<double> v ) {
                 std::sort( v.begin( ), v.end( ) );
                 std::string s = "{\"median\": " + std::to_string( v[ v.size( ) / 2 ] ) + ", \"min\": " + std::to_string( v.front( ) ) +
                                 ", \"max\": " + std::to_string( v.back( ) ) + "}";
                 return s;
             };
+            printf( "{\"paired_device_sam\": {\"mates\": %zu, \"repeats\": %d, \"execute_paired_flat_sam_reads_per_s\": %s, \"sam_bytes_device\": %llu, "
+                    "\"text_batches\": %llu}}\n",
+                    pMates->size( ), iRepeats, list( vD ).c_str( ), (unsigned long long)uiBytesDevice, (unsigned long long)uiTextBatches );
             printf( "{\"paired\": {\"mates\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_reads\": %zu, \"in_flight\": 3, "
                     "\"execute_paired_reads_per_s\": %s, \"execute_paired_flat_reads_per_s\": %s, \"sam_bytes_container\": %llu, "
                     "\"sam_bytes_flat\": %llu, \"pairs_finished_on_host\": %llu}}\n",
                     pMates->size( ), uiLen, iRepeats, xAligner.uiBatchReads, list( vC ).c_str( ), list( vF ).c_str( ),
                     (unsigned long long)uiBytesContainer, (unsigned long long)uiBytesFlat, (unsigned long long)uiHostPairs );
-            return uiBytesContainer == uiBytesFlat ? 0 : 1;
+            return uiBytesContainer == uiBytesFlat && uiBytesFlat == uiBytesDevice ? 0 : 1;
         }
         for( size_t i = 0; i < n; i++ )
         {

@@ -298,8 +298,8 @@ int ma_batch_start_pair_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, m
  * makes of the downloaded MappingQuality records), formatted by two kernels and downloaded as ONE text instead of records and
  * ops: per alignment of a read's MappingQuality list one record with Alignment::getSamFlag / getSamPosition / cigarString /
  * getQuerySequence (alignment.h:367-467, 576-623), the CG:B:I tag of cigars from 0x10000 ops on (TagGenerator, fileWriter.h:
- * 327-357), the unmapped record (fileWriter.cpp:126-140) for a read without a printed alignment.  The paired writer and the
- * NGMLR tag emulation stay on the host.
+ * 327-357), the unmapped record (fileWriter.cpp:126-140) for a read without a printed alignment.  The paired writer is the
+ * block below; the NGMLR tag emulation stays on the host.
  *   ma_index_set_contig_names    the RNAME strings (Pack::nameOfSequenceWithId, pack.h:1040-1046): contig i's name is
  *                                names[name_off[i] .. name_off[i+1]) (no terminators)
  *   ma_batch_set_read_text       QNAME (NucSeq::sName) and QUAL (NucSeq::pxQualityValues / fastaq quality, nucSeq.h:697-709) of
@@ -327,6 +327,28 @@ int ma_sam_batch( ma_batch*, uint32_t options );
 int ma_batch_sam_counts( ma_batch*, uint64_t* n_bytes );
 int ma_batch_get_sam( ma_batch*, uint64_t* rec_off /*n+1*/, char* text );
 int ma_batch_start_sam_download( ma_batch*, uint64_t* rec_off /*n+1*/, char* text );
+/* ---- paired-end SAM text: PairedFileWriter::execute (fileWriter.cpp:158-383) on the device ----
+ * The records of a batch's mate pairs (ma_pair_batch) as the bytes the reference's PairedFileWriter prints for them (and
+ * ma_amd/host/ma_flat_sam.h formatPair makes of the arrays of ma_batch_get_pairs), formatted by two kernels from what is in
+ * device memory after ma_pair_batch -- nothing is uploaded, nothing packed -- and downloaded as ONE text: per printed record of
+ * a pair FLAG with 0x1 | 0x2 | 0x40 / 0x80 (| 0x20: partner on the reverse strand), RNEXT / PNEXT of the partner ("=" on a
+ * contig of the same NAME), TLEN 0, MAPQ capped at 255, the cigar's left-over clip taken against the FIRST mate's length (sic);
+ * two records for a pair without any printed record (FLAG 0x4 | 0x1 | 0x40 / 0x80 | 0x8, QUAL printed); for one mate without a
+ * printed record one record at record 0 of the pair's list (RNEXT "=", QUAL "*").  Contig names and read text as above.
+ *   ma_pair_sam_batch                 after ma_pair_batch on the batch's stream; options = MA_SAM_*.  Waits for a pending
+ *                                     download, then for the stream with the one read-back that sizes the download.  A record
+ *                                     that ends beyond its own mate (possible only through ma_batch_set_alignments) fails the
+ *                                     call with the reference's text as ma_sam_batch does; the object stays usable.
+ *   ma_batch_pair_sam_counts          pairs (n / 2) and bytes of the text
+ *   ma_batch_get_pair_sam             pair k's records are text[pair_off[k] .. pair_off[k+1]) (either pointer may be NULL)
+ *   ma_batch_start_pair_sam_download  the same without the wait, completed by ma_batch_finish_download (one download can be
+ *                                     pending per object)
+ * The text is kept apart from the single-end one: ma_batch_get_sam never returns pair text, and ma_batch_get_pairs /
+ * ma_batch_get_mapq_alignments serve their records as before. */
+int ma_pair_sam_batch( ma_batch*, uint32_t options );
+int ma_batch_pair_sam_counts( ma_batch*, uint64_t* n_pairs, uint64_t* n_bytes );
+int ma_batch_get_pair_sam( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, char* text );
+int ma_batch_start_pair_sam_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, char* text );
 /* work counters for the roofline model (same meaning as the oracle's): [0] extend_backward steps,
  * [1] distinct occ blocks touched, [2] bwt_sa LF steps, [3] SA rows, [4] DP band cells, [5] ksw jobs */
 int ma_batch_counters( ma_batch*, uint64_t out[ 8 ] );

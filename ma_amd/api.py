@@ -571,6 +571,34 @@ class Batch:
         _chk(lib().ma_batch_start_sam_download(self.h, C.c_void_p(off.ptr), C.c_void_p(text.ptr)))
         return nb
 
+    # ---- paired-end SAM text (ma_pair_sam_batch): the records of the batch's mate pairs formatted on the device
+    def pair_sam(self, options=0):
+        """PairedFileWriter::execute for every pair on the device, after pair() (names / qualities: set_read_text); options =
+        SAM_* bits.  Returns the bytes of the text."""
+        _chk(lib().ma_pair_sam_batch(self.h, C.c_uint32(options)))
+        return self.pair_sam_bytes()
+
+    def pair_sam_bytes(self):
+        np_, nb = C.c_uint64(), C.c_uint64()
+        _chk(lib().ma_batch_pair_sam_counts(self.h, C.byref(np_), C.byref(nb)))
+        return nb.value
+
+    def pair_sam_text(self):
+        """(pair_off, text): pair k's records are text[pair_off[k]:pair_off[k + 1]] (bytes)."""
+        off = np.zeros(self.n // 2 + 1, dtype=np.uint64)
+        text = np.zeros(self.pair_sam_bytes() + 1, dtype=np.uint8)
+        _chk(lib().ma_batch_get_pair_sam(self.h, _ptr(off), _ptr(text)))
+        return off, text[:-1].tobytes()
+
+    def start_pair_sam_download(self, off, text):
+        """pair_sam_text() into caller-owned HostArrays (u64[pairs + 1], u8[bytes]) without the wait: None when they are too
+        small, else the bytes of the text; complete after finish_download()."""
+        nb = self.pair_sam_bytes()
+        if off.n < self.n // 2 + 1 or text.n < nb:
+            return None
+        _chk(lib().ma_batch_start_pair_sam_download(self.h, C.c_void_p(off.ptr), C.c_void_p(text.ptr)))
+        return nb
+
     def close(self):
         if self.h:
             lib().ma_batch_destroy(self.h)

@@ -108,6 +108,7 @@ int ma_pair_batch( ma_batch* b )
     const u64 np = b->n_reads / 2;
     b->pairOnHost = 0;
     b->pairRecs = b->pairNOps = 0;
+    b->pairSamDone = false; // (a text printed before is of other picks)
     b->stage_done = 4;
     if( np && b->nHsets )
     {

@@ -90,7 +90,7 @@ int ma_batch_set_read_text( ma_batch* b, const char* names, const uint64_t* name
         if( name_off[ i + 1 ] < name_off[ i ] )
             return fail( "ma_batch_set_read_text: offsets decrease" );
     MA_BIND_DEVICE( b->device );
-    b->txtSet = b->samDone = false;
+    b->txtSet = b->samDone = b->pairSamDone = false;
     if( b->txtNames.reserve( name_off[ n ] + 1 ) || b->txtNameOff.reserve( ( n + 1 ) * 8 ) || ( qual && b->txtQual.reserve( b->n_bases + 1 ) ) )
         return 1;
     if( name_off[ n ] )

@@ -83,6 +83,7 @@ static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0
 
 #include "../host/ma_sam_dev.h"
 #include "stage_sam.h"
+#include "stage_pair_sam.h"
 
 // ------------------------------------------------------------------------------------------------
 // batch object
@@ -126,6 +127,10 @@ struct ma_batch
     DevBuf txtNames, txtNameOff, txtQual, samCnt, samOff, samSeqPos, samText, samStat;
     bool txtSet = false, txtHasQual = false, samDone = false;
     u64 samBytes = 0;
+    // paired-end SAM text (ma_pair_sam_batch): the same per pair, all of its own -- the single-end text stays what it was
+    DevBuf pairSamCnt, pairSamOff, pairSamSeqPos, pairSamText, pairSamStat;
+    bool pairSamDone = false;
+    u64 pairSamBytes = 0;
     u64 cigPoolCap = 0, cigPoolMin = 0, nOpsCap = 0, nJobSlots = 0;
     KswSide kswSide; // created on first use
     // double-buffered I/O (ma_batch_stage_reads / ma_batch_start_mapq_download): the next reads are uploaded into reads2 / roff2
@@ -369,7 +374,7 @@ int ma_batch_use_staged_reads( ma_batch* b )
     b->d_roff = b->roff.as<u64>( );
     b->reads_external = false;
     b->stage_done = 0;
-    b->txtSet = b->samDone = false;
+    b->txtSet = b->samDone = b->pairSamDone = false;
     b->stagedPending = false;
     return 0;
 }
@@ -396,7 +401,7 @@ int ma_batch_set_reads( ma_batch* b, const uint8_t* codes, const uint64_t* offse
     b->d_roff = b->roff.as<u64>( );
     b->reads_external = false;
     b->stage_done = 0;
-    b->txtSet = b->samDone = false;
+    b->txtSet = b->samDone = b->pairSamDone = false;
     return 0;
 }
 
@@ -432,7 +437,7 @@ int ma_batch_set_reads_device( ma_batch* b, const void* d_codes, const void* d_o
         return 1;
     b->max_qlen = (u32)b->hctr[ 0 ];
     b->stage_done = 0;
-    b->txtSet = b->samDone = false;
+    b->txtSet = b->samDone = b->pairSamDone = false;
     return 0;
 }
 
@@ -1138,3 +1143,4 @@ int ma_debug_seed_prof( unsigned long long* out )
 #include "launch_pair.h"
 
 #include "launch_sam.h"
+#include "launch_pair_sam.h"

@@ -295,7 +295,8 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
 
 // SAM records of a whole PAIRED batch (BatchAligner::executePairedFlat): PairedFileWriter::execute (fileWriter.cpp:158-383)
 // per pair, formatted from the flat pair records (ma_flat_sam.h formatPair) by uiFormatThreads threads into one arena each and
-// written in input order under one acquisition of the writer's lock.  The NGMLR tags are refused like PairedFileWriter does.
+// written in input order under one acquisition of the writer's lock.  A batch that carries the text the device formatted
+// (BatchAligner::executePairedFlatSam) goes out as it is, with one write.  The NGMLR tags are refused like PairedFileWriter does.
 class BatchPairedFileWriter
 {
     std::shared_ptr<PairedFileWriter> pPerPair; // owns stream + lock, writes the header
@@ -324,6 +325,15 @@ class BatchPairedFileWriter
         if( !rBatch.paired( ) )
             throw std::runtime_error( "BatchPairedFileWriter: not a paired batch" );
         const size_t n = rBatch.pairs( );
+        if( rBatch.hasSamText( ) ) // formatted on the device (BatchAligner::executePairedFlatSam): the batch's text as it is
+        {
+            {
+                std::lock_guard<std::mutex> xGuard( *pPerPair->pLock );
+                pPerPair->pOut->write( rBatch.samText( ), rBatch.samBytes( ) );
+            }
+            uiBytes += rBatch.samBytes( ), uiReads += 2 * n;
+            return;
+        }
         const size_t uiThreads = std::max<size_t>( 1, std::min<size_t>( uiFormatThreads, n / 1024 + 1 ) );
         std::vector<ma_amd::flat::Arena> vArenas( uiThreads );
         std::string sFailure;

@@ -213,9 +213,11 @@ struct BatchResult
     // SAM batches (Engine::run with a SamMode): INSTEAD of the MappingQuality records the SAM text the device formatted from
     // them (ma_sam_batch / ma_batch_get_sam): read r's records are vSam[ vSamOff[r] .. vSamOff[r+1] ), what FileWriter::execute
     // prints for it.  A batch the device does not serve (some reads with qualities, some without) keeps bSam false and
-    // carries the records as usual.
+    // carries the records as usual.  With bPairs as well (ma_pair_sam_batch / ma_batch_get_pair_sam) the text is that of the
+    // PAIRS, what PairedFileWriter::execute prints: pair k's records are vSam[ vSamOff[k] .. vSamOff[k+1] ), and there are no pair
+    // records.
     bool bSam = false;
-    HostBuf<uint64_t> vSamOff; // uiReads + 1
+    HostBuf<uint64_t> vSamOff; // uiReads + 1 (pairs: uiReads / 2 + 1)
     HostBuf<char> vSam;
     uint64_t uiSamBytes = 0;
     double fPack = 0, fH2D = 0, fKernels = 0, fD2H = 0; // seconds: gathering the reads, upload, all stages, download
@@ -317,7 +319,8 @@ class Engine
             vRefs.emplace_back( *pRead );
         return run( vRefs, bStages );
     }
-    // pSam: SAM mode -- the result carries the SAM text of the reads instead of their MappingQuality records
+    // pSam: SAM mode -- the result carries the SAM text of the reads instead of their MappingQuality records; with bPairs the
+    // text of the PAIRS (PairedFileWriter's records, one vSamOff entry per pair) instead of the pair records
     std::shared_ptr<BatchResult> run( const std::vector<ReadRef>& vReads, bool bStages, bool bPairs = false, const SamMode* pSam = nullptr )
     {
         const size_t n = vReads.size( );
@@ -350,8 +353,8 @@ class Engine
         SamText xText;
         if( pSam != nullptr )
         {
-            if( bPairs || pSam->pText == nullptr || pSam->pText->size( ) != n )
-                throw std::runtime_error( "Engine::run: the SAM mode needs one ReadText per read and no pairs" );
+            if( pSam->pText == nullptr || pSam->pText->size( ) != n )
+                throw std::runtime_error( "Engine::run: the SAM mode needs one ReadText per read" );
             const std::vector<ReadText>& rT = *pSam->pText;
             size_t uiWithQual = 0;
             uint64_t* pNameOff = vNameOff.need( n + 1 );
@@ -394,6 +397,7 @@ class Engine
     // reads that already are one array of codes + CSR offsets (n + 1), e.g. in page-locked memory the caller filled
     // bPairs: the reads are mate pairs (2k, 2k + 1); the result carries the pair records instead of the MappingQuality ones
     // pSam: the result carries the SAM text (BatchResult::vSamOff / vSam) instead of the MappingQuality records
+    // both: the pairs' SAM text (ma_pair_sam_batch), vSamOff per PAIR, instead of the pair records; bPairs and bSam are both set
     std::shared_ptr<BatchResult> runFlat( const uint8_t* pCodes, const uint64_t* pOff, size_t n, bool bStages, bool bPairs = false,
                                           const SamText* pSam = nullptr )
     {
@@ -451,7 +455,20 @@ class Engine
             engineCheck( ma_batch_get_alignments( pBatch, R.vAlnOff.data( ), R.vAlns.data( ), R.vAlnOps.data( ) ) );
         }
         uint64_t* pMqOff = R.vMqOff.need( n + 1 );
-        if( bPairs )
+        if( bPairs && pSam != nullptr )
+        {
+            // pairing and formatting behind the alignment: the text replaces the download of records, ops, mate and other
+            uint64_t nPairs = 0;
+            R.uiPairRecords = R.uiPairOps = 0;
+            engineCheck( ma_pair_batch( pBatch ) );
+            engineCheck( ma_batch_pair_counts( pBatch, &nPairs, nullptr, nullptr, &R.uiPairsOnHost ) );
+            engineCheck( ma_pair_sam_batch( pBatch, pSam->uiOptions ) );
+            engineCheck( ma_batch_pair_sam_counts( pBatch, &nPairs, &R.uiSamBytes ) );
+            engineCheck( ma_batch_get_pair_sam( pBatch, R.vSamOff.need( nPairs + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
+            memset( R.vPairOff.need( nPairs + 1 ), 0, ( nPairs + 1 ) * sizeof( uint64_t ) ); // no pair records either (a recycled result)
+            memset( pMqOff, 0, ( n + 1 ) * sizeof( uint64_t ) ); // no records in a SAM result
+        }
+        else if( bPairs )
         {
             uint64_t nPairs = 0;
             engineCheck( ma_pair_batch( pBatch ) );

@@ -1444,7 +1444,9 @@ class AlignedBatch : public libMS::Container
         return pResult->vPairOther.data( );
     }
     // A SAM batch (BatchAligner::executeFlatSam): instead of records it holds the SAM text the device formatted, read i's
-    // records are samText()[ samOffsets()[i] .. samOffsets()[i+1] ) -- the bytes FileWriter::execute prints for it
+    // records are samText()[ samOffsets()[i] .. samOffsets()[i+1] ) -- the bytes FileWriter::execute prints for it.  A batch of
+    // BatchAligner::executePairedFlatSam is paired( ) as well: then the offsets are per PAIR and the bytes PairedFileWriter's.
+    // Such a batch has no pair records: pairOffsets( ) are all 0, the other pair accessors are not valid on it.
     bool hasSamText( ) const
     {
         return pResult != nullptr && pResult->bSam;
@@ -1877,6 +1879,43 @@ class BatchAligner
         xLast.fWall = detail::secondsSince( t0 );
         return pRet;
     }
+    // executePairedFlat with the pairs' SAM records formatted on the DEVICE (ma_pair_batch + ma_pair_sam_batch): one
+    // AlignedBatch per device batch of whole pairs, in input order, that is paired( ) AND hasSamText( ) -- pair k's records are
+    // samText( )[ samOffsets( )[k] .. samOffsets( )[k+1] ), the bytes PairedFileWriter::execute prints under this aligner's SAM
+    // options; no download of records, ops, mate and other, no host formatting.  BatchPairedFileWriter writes such a batch with
+    // one call.  A batch whose reads only partly have qualities comes back with pair records as from executePairedFlat, and so
+    // does everything with "Detect Small Inversions" (the container path).  Not with the NGMLR tag emulation.
+    std::shared_ptr<TP_FLAT> executePairedFlatSam( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<ReadVector> vMates,
+                                                   std::shared_ptr<Pack> pPack )
+    {
+        if( vMates->size( ) % 2 )
+            throw std::runtime_error( "BatchAligner::executePairedFlatSam: odd number of reads" );
+        if( xParams.xSam.bEmulateNgmlrTags )
+            throw std::runtime_error( "BatchAligner::executePairedFlatSam: not with the NGMLR tag emulation (use executePaired and "
+                                      "PairedFileWriter)" );
+        if( xP.search_inversions )
+            return flattenPairs( executePaired( pFM_index, vMates ), vMates );
+        nameContigs( *pFM_index->pDev, *pPack );
+        return executePairedFlatSamOn( pFM_index->pDev->all( ), vMates, &vLastPerIndex );
+    }
+    // (the contigs of vIndices are named already)
+    std::shared_ptr<TP_FLAT> executePairedFlatSamOn( const std::vector<const ma_index*>& vIndices, std::shared_ptr<ReadVector> vMates,
+                                                     std::vector<AlignerTiming>* pPerIndex )
+    {
+        if( vMates->size( ) % 2 )
+            throw std::runtime_error( "BatchAligner::executePairedFlatSam: odd number of reads" );
+        if( !servesSam( ) )
+            throw std::runtime_error( "BatchAligner::executePairedFlatSam: not with 'Detect Small Inversions' or the NGMLR tag emulation "
+                                      "(use executePairedFlat and BatchPairedFileWriter)" );
+        const uint32_t uiOptions = samOptionBits( xParams.xSam );
+        auto pRet = std::make_shared<TP_FLAT>( );
+        xLast = AlignerTiming( );
+        const auto t0 = std::chrono::steady_clock::now( );
+        if( !vMates->empty( ) )
+            alignRangeOn( vIndices, *vMates, 0, vMates->size( ), nullptr, xLast, pRet.get( ), vMates, pPerIndex, true, &uiOptions );
+        xLast.fWall = detail::secondsSince( t0 );
+        return pRet;
+    }
     // the pairs of executePaired as ONE paired AlignedBatch (host memory; the records keep PairedReads' changes)
     static std::shared_ptr<TP_FLAT> flattenPairs( std::shared_ptr<TP_RESULT> pPairs, std::shared_ptr<ReadVector> vMates )
     {
@@ -2073,6 +2112,23 @@ class MultiDeviceAligner
         configure( );
         vLast.assign( vIndices.size( ), AlignerTiming( ) );
         auto pRet = xAligner.executePairedFlatOn( vIndices, vMates, &vLast );
+        xLast = xAligner.xLast;
+        for( auto& rT : vLast )
+            rT.fWall = xLast.fWall;
+        return pRet;
+    }
+
+    // BatchAligner::executePairedFlatSam over all replicas: every device batch of whole pairs comes back as the SAM text its
+    // device formatted.  (search_inversions: use BatchAligner::executePairedFlatSam, which takes the container path.)
+    std::shared_ptr<BatchAligner::TP_FLAT> executePairedFlatSam( std::shared_ptr<ReadVector> vMates, std::shared_ptr<Pack> pPack )
+    {
+        if( xParams.getSelected( )->search_inversions )
+            throw std::runtime_error( "MultiDeviceAligner::executePairedFlatSam: not with 'Detect Small Inversions' (SmallInversions needs containers)" );
+        configure( );
+        for( const auto& pFM : vReplicas )
+            BatchAligner::nameContigs( *pFM->pDev, *pPack );
+        vLast.assign( vIndices.size( ), AlignerTiming( ) );
+        auto pRet = xAligner.executePairedFlatSamOn( vIndices, vMates, &vLast );
         xLast = xAligner.xLast;
         for( auto& rT : vLast )
             rT.fWall = xLast.fWall;

@@ -1,10 +1,10 @@
-// ma_sam_dev.h -- the single-end SAM record formatter of ma_flat_sam.h (flat::formatRead / putRecord / putUnmapped: the bytes of
-// the reference's FileWriter::execute, libs/ma/src/module/fileWriter.cpp:11-158) restated ONCE over a templated sink, for
-// three users:
-//   - the device stage (ma_amd/csrc/stage_sam.h) runs formatRead( ) inside its two kernels: with the counting sink to size
-//     every read's text, with a writing sink to store it;
-//   - the CPU tests (tests/emul/sam_dev_test.cpp) run the same function on the host and pin it, byte for byte, to
-//     flat::formatRead and to the SAM goldens the compiled reference wrote;
+// ma_sam_dev.h -- the SAM record formatters of ma_flat_sam.h (flat::formatRead / putRecord / putUnmapped: the bytes of the
+// reference's FileWriter::execute, libs/ma/src/module/fileWriter.cpp:11-158; flat::formatPair: those of
+// PairedFileWriter::execute, :158-383) restated ONCE over a templated sink, for three users:
+//   - the device stages (ma_amd/csrc/stage_sam.h, stage_pair_sam.h) run formatRead( ) / formatPair( ) inside their two kernels:
+//     with the counting sink to size every read's (pair's) text, with a writing sink to store it;
+//   - the CPU tests (tests/emul/sam_dev_test.cpp, sam_pair_dev_test.cpp) run the same functions on the host and pin them, byte
+//     for byte, to flat::formatRead / flat::formatPair and to the SAM goldens the compiled reference wrote;
 //   - libma_amd.so words the error of a bad record with errorText( ).
 // No reference headers, no containers, no strings: include/ma_amd.h only.  ma_flat_sam.h stays the yardstick and documents
 // where each oddity comes from; they are kept as they are:
@@ -17,7 +17,8 @@
 //
 // A sink is anything with
 //   put( c ), bytes( p, n ), number( x ), size( )          plain columns
-//   seq( read, from, to, reverse, k )                       SEQ of record k of the list (k = UNMAPPED: of the unmapped record)
+//   seq( read, from, to, reverse, k )                       SEQ of record k of the list (k = UNMAPPED: of the unmapped record;
+//                                                           UNMAPPED_FIRST / UNMAPPED_SECOND: of a pair's unaligned mate)
 //   qual( read, from, to, k )                               QUAL (only called when the read has qualities)
 //   error( kind, value, k )                                 record k cannot be printed (see ERR_*)
 // The kernels' writing sink leaves SEQ and QUAL out (it only notes where they go): the wavefront copies them together.
@@ -54,7 +55,9 @@ enum : uint32_t
 };
 enum : uint32_t
 {
-    UNMAPPED = 0xffffffffu
+    UNMAPPED = 0xffffffffu, // the one unmapped record of a read (formatRead)
+    UNMAPPED_FIRST = 0xfffffffeu, // the record of an unaligned first / second mate (formatPair): a pair can have both
+    UNMAPPED_SECOND = 0xfffffffdu
 };
 
 // contig table of the pack (forward strand); names[ name_off[ i ] .. name_off[ i + 1 ] ) is contig i's RNAME
@@ -99,6 +102,15 @@ struct Rec
     uint32_t n_ops, secondary, supplementary;
     double mapq;
 };
+// what a record of a pair has beyond a single read's (flat::detail::RecordExtras); the defaults are a single read's
+struct RecordExtras
+{
+    uint32_t extra_flags = 0;
+    bool cap_mapq = false; // the paired writer caps MAPQ at 255 (fileWriter.cpp:262)
+    bool has_partner = false; // RNEXT / PNEXT of partner, else "*" and 0
+    uint64_t clip_length = 0; // query length the cigar is clipped against
+    uint64_t partner_begin_ref = 0, partner_end_ref = 0;
+};
 // A list is anything with size( ), rec( k ), opType( k, j ), opLen( k, j ).  This one is over the arrays of
 // ma_batch_get_mapq_alignments (ops_off counts (type, length) pairs).
 struct FlatList
@@ -122,6 +134,22 @@ struct FlatList
     MA_SAM_HD uint64_t opLen( uint32_t k, uint32_t j ) const
     {
         return ops[ 2 * ( alns[ k ].ops_off + j ) + 1 ];
+    }
+};
+// A pair list is a list that yields the records of ONE pair in the order of ma_batch_get_pairs and also has mate( k ) (!= 0:
+// record of the first mate) and other( k ) (index of the partner's record in the pair or -1).  This one is over the arrays
+// of ma_batch_get_pairs.
+struct FlatPairList : FlatList
+{
+    const int32_t* mates;
+    const int32_t* others;
+    MA_SAM_HD int32_t mate( uint32_t k ) const
+    {
+        return mates[ k ];
+    }
+    MA_SAM_HD int32_t other( uint32_t k ) const
+    {
+        return others[ k ];
     }
 };
 
@@ -264,9 +292,34 @@ template <class Sink> MA_SAM_HD void putUnmapped( Sink& rOut, const Read& rQ, bo
     putQuality( rOut, rQ, 0, rQ.length, UNMAPPED );
     rOut.put( '\n' );
 }
-// One record of an aligned read: the eleven columns and the CG tag
+// contig of the begin (pack.h:1063-1067)
+MA_SAM_HD uint32_t contigOf( const Contigs& rContigs, uint64_t uiBeginRef )
+{
+    const uint64_t uiFwd = rContigs.forwardSize( );
+    return rContigs.idOfForward( uiBeginRef >= uiFwd ? 2 * uiFwd - ( uiBeginRef + 1 ) : uiBeginRef );
+}
+// Alignment::getSamPosition (alignment.h:596-603), see putRecord
+MA_SAM_HD uint64_t samPosition( const Contigs& rContigs, uint64_t uiBeginRef, uint64_t uiEndRef )
+{
+    const uint64_t uiFwd = rContigs.forwardSize( );
+    const uint64_t uiAbs = uiEndRef >= uiFwd ? 2 * uiFwd - ( uiEndRef + 1 ) : uiBeginRef;
+    return uiAbs - rContigs.starts[ rContigs.idOfForward( uiAbs ) ] + ( uiBeginRef >= uiFwd ? 1 : 0 ) + 1;
+}
+MA_SAM_HD bool sameName( const Contigs& rContigs, uint32_t a, uint32_t b ) // by bytes: two contigs may share a name
+{
+    const uint64_t oa = rContigs.name_off[ a ], ob = rContigs.name_off[ b ], n = rContigs.name_off[ a + 1 ] - oa;
+    if( rContigs.name_off[ b + 1 ] - ob != n )
+        return false;
+    for( uint64_t i = 0; i < n; i++ )
+        if( rContigs.names[ oa + i ] != rContigs.names[ ob + i ] )
+            return false;
+    return true;
+}
+// One record of an aligned read: the eleven columns and the CG tag.  rX: what a mate's record has beyond a single read's
+// (its clip_length is the read's length for a single read).
 template <class Sink, class List>
-MA_SAM_HD void putRecord( Sink& rOut, uint32_t uiOptions, const Contigs& rContigs, const Read& rQ, const Rec& rA, const List& rList, uint32_t k )
+MA_SAM_HD void putRecord( Sink& rOut, uint32_t uiOptions, const Contigs& rContigs, const Read& rQ, const Rec& rA, const List& rList, uint32_t k,
+                          const RecordExtras& rX )
 {
     const bool bSoftClip = ( uiOptions & SOFT_CLIP ) != 0, bMCigar = ( uiOptions & EQX_CIGAR ) == 0;
     const uint64_t uiFwd = rContigs.forwardSize( );
@@ -276,7 +329,7 @@ MA_SAM_HD void putRecord( Sink& rOut, uint32_t uiOptions, const Contigs& rContig
     // QNAME FLAG RNAME POS MAPQ
     rOut.bytes( rQ.name, rQ.name_len );
     rOut.put( '\t' );
-    numberAnd( rOut, ( bRev ? 0x10u : 0u ) | ( rA.secondary ? 0x100u : 0u ) | ( rA.supplementary ? 0x800u : 0u ), '\t' );
+    numberAnd( rOut, ( bRev ? 0x10u : 0u ) | ( rA.secondary ? 0x100u : 0u ) | ( rA.supplementary ? 0x800u : 0u ) | rX.extra_flags, '\t' );
     // contig of the begin (pack.h:1063-1067); position of the alignment's forward-strand start, 1-based, (sic) one further for
     // reverse-strand alignments (alignment.h:596-603)
     const uint32_t uiContig = rContigs.idOfForward( bRev ? 2 * uiFwd - ( uiBeginRef + 1 ) : uiBeginRef );
@@ -295,7 +348,7 @@ MA_SAM_HD void putRecord( Sink& rOut, uint32_t uiOptions, const Contigs& rContig
             rOut.number( (uint64_t)( -(int64_t)iMapQ ) );
         }
         else
-            rOut.number( (uint64_t)iMapQ );
+            rOut.number( (uint64_t)( rX.cap_mapq && iMapQ > 255 ? 255 : iMapQ ) );
     }
     rOut.put( '\t' );
     // CIGAR (alignment.h:367-467): clip, the sections in forward-strand direction, clip
@@ -303,7 +356,7 @@ MA_SAM_HD void putRecord( Sink& rOut, uint32_t uiOptions, const Contigs& rContig
         numberAnd( rOut, uiEndQ - uiBeginQ, 'S' );
     else
     {
-        const uint64_t uiLeftOver = uiEndQ < rQ.length ? rQ.length - uiEndQ : 0;
+        const uint64_t uiLeftOver = uiEndQ < rX.clip_length ? rX.clip_length - uiEndQ : 0;
         const uint64_t uiHead = bRev ? uiLeftOver : uiBeginQ, uiTail = bRev ? uiBeginQ : uiLeftOver;
         const char cClip = bSoftClip ? 'S' : 'H';
         if( uiHead > 0 )
@@ -335,7 +388,20 @@ MA_SAM_HD void putRecord( Sink& rOut, uint32_t uiOptions, const Contigs& rContig
         if( uiTail > 0 )
             numberAnd( rOut, uiTail, cClip );
     }
-    lit( rOut, "\t*\t0\t0\t" );
+    if( !rX.has_partner )
+        lit( rOut, "\t*\t0\t0\t" );
+    else // RNEXT ("=" on a contig of the same name) PNEXT, TLEN is not output by the reference (fileWriter.cpp:317)
+    {
+        const uint32_t uiNext = contigOf( rContigs, rX.partner_begin_ref );
+        rOut.put( '\t' );
+        if( sameName( rContigs, uiNext, uiContig ) )
+            rOut.put( '=' );
+        else
+            rOut.bytes( rContigs.names + rContigs.name_off[ uiNext ], rContigs.name_off[ uiNext + 1 ] - rContigs.name_off[ uiNext ] );
+        rOut.put( '\t' );
+        rOut.number( samPosition( rContigs, rX.partner_begin_ref, rX.partner_end_ref ) );
+        lit( rOut, "\t0\t" );
+    }
     // SEQ: the whole read when soft clipping, else the aligned part; reverse-complemented on the reverse strand.  A record that
     // ends beyond the read is an error (the host formatter throws); nothing beyond the read is ever touched.
     const uint64_t uiFrom = bSoftClip ? 0 : uiBeginQ;
@@ -383,13 +449,107 @@ MA_SAM_HD void formatRead( Sink& rOut, uint32_t uiOptions, const Contigs& rConti
             continue;
         if( ( ( uiOptions & NO_SECONDARY ) && xA.secondary ) || ( ( uiOptions & NO_SUPPLEMENTARY ) && xA.supplementary ) )
             continue;
-        detail::putRecord( rOut, uiOptions, rContigs, rQ, xA, rList, k );
+        RecordExtras xExtras;
+        xExtras.clip_length = rQ.length;
+        detail::putRecord( rOut, uiOptions, rContigs, rQ, xA, rList, k, xExtras );
         bAny = true;
     }
     if( uiAlns == 0 )
         detail::putUnmapped( rOut, rQ, true );
     else if( !bAny )
         detail::putUnmapped( rOut, rQ, false );
+}
+
+namespace detail
+{
+// The record of an unaligned mate (fileWriter.cpp:320-366): without an anchor the pair has no record at all (QUAL printed), with
+// one the mate is placed at the anchor's position (RNEXT "=", QUAL "*")
+template <class Sink>
+MA_SAM_HD void putUnalignedMate( Sink& rOut, const Contigs& rContigs, const Read& rQ, bool bFirst, uint32_t uiExtraFlags, bool bAnchor,
+                                 uint64_t uiAnchorBeginRef, uint64_t uiAnchorEndRef )
+{
+    const uint32_t k = bFirst ? UNMAPPED_FIRST : UNMAPPED_SECOND;
+    rOut.bytes( rQ.name, rQ.name_len );
+    rOut.put( '\t' );
+    numberAnd( rOut, 0x4u | 0x1u | ( bFirst ? 0x40u : 0x80u ) | uiExtraFlags, '\t' );
+    if( !bAnchor )
+        lit( rOut, "*\t0\t0\t*\t*\t0\t0\t" );
+    else
+    {
+        const uint32_t uiContig = contigOf( rContigs, uiAnchorBeginRef );
+        const uint64_t uiPos = samPosition( rContigs, uiAnchorBeginRef, uiAnchorEndRef );
+        rOut.bytes( rContigs.names + rContigs.name_off[ uiContig ], rContigs.name_off[ uiContig + 1 ] - rContigs.name_off[ uiContig ] );
+        rOut.put( '\t' );
+        rOut.number( uiPos );
+        lit( rOut, "\t0\t*\t=\t" );
+        rOut.number( uiPos );
+        lit( rOut, "\t0\t" );
+    }
+    if( rQ.length > 0 )
+        rOut.seq( rQ, 0, rQ.length, false, k );
+    rOut.put( '\t' );
+    if( !bAnchor )
+        putQuality( rOut, rQ, 0, rQ.length, k );
+    else
+        rOut.put( '*' );
+    rOut.put( '\n' );
+}
+} // namespace detail
+
+// The SAM records of ONE mate pair: flat::formatPair of ma_flat_sam.h (PairedFileWriter::execute, fileWriter.cpp:158-383) over
+// a pair list, in its three record shapes, oddities included:
+//   aligned mate          FLAG = strand | secondary | supplementary | 0x1 | 0x2 (always) | 0x40 / 0x80 | 0x20 (partner on the
+//                         reverse strand), RNEXT / PNEXT = the partner ("=" on a contig of the same name), TLEN 0, MAPQ capped
+//                         at 255, CIGAR clipped against the length of the FIRST mate (sic, :191-193)
+//   pair without any      FLAG = 0x4 | 0x1 | 0x40 / 0x80 | 0x8, everything else empty, QUAL printed
+//   one mate unaligned    placed at record 0 of the list, printed or not (:348-366), RNEXT "=", QUAL "*"
+// error( kind, value, k ) names record k of the pair list.
+template <class Sink, class PairList>
+MA_SAM_HD void formatPair( Sink& rOut, uint32_t uiOptions, const Contigs& rContigs, const Read& rQ1, const Read& rQ2, const PairList& rList )
+{
+    const uint32_t uiAlns = rList.size( );
+    const uint64_t uiFwd = rContigs.forwardSize( );
+    bool bHasFirst = false, bHasSecond = false;
+    for( uint32_t k = 0; k < uiAlns; k++ )
+    {
+        const Rec xA = rList.rec( k );
+        bool bNonZero = false; // Alignment::length( ) != 0
+        for( uint32_t j = 0; j < xA.n_ops && !bNonZero; j++ )
+            bNonZero = rList.opLen( k, j ) != 0;
+        if( !bNonZero || ( ( uiOptions & NO_SECONDARY ) && xA.secondary ) || ( ( uiOptions & NO_SUPPLEMENTARY ) && xA.supplementary ) )
+            continue;
+        const bool bFirst = rList.mate( k ) != 0;
+        if( bFirst )
+            bHasFirst = true;
+        else
+            bHasSecond = true;
+        RecordExtras xExtras;
+        xExtras.extra_flags = 0x1u | 0x2u | ( bFirst ? 0x40u : 0x80u );
+        xExtras.cap_mapq = true;
+        xExtras.clip_length = rQ1.length;
+        const int32_t iOther = rList.other( k );
+        if( iOther >= 0 )
+        {
+            xExtras.has_partner = true;
+            const Rec xOther = rList.rec( (uint32_t)iOther );
+            xExtras.partner_begin_ref = xOther.begin_ref, xExtras.partner_end_ref = xOther.end_ref;
+            if( xOther.begin_ref >= uiFwd )
+                xExtras.extra_flags |= 0x20u;
+        }
+        const Read xQ = bFirst ? rQ1 : rQ2; // (a copy: a reference would pin both reads in memory on the device)
+        detail::putRecord( rOut, uiOptions, rContigs, xQ, xA, rList, k, xExtras );
+    }
+    if( !bHasFirst && !bHasSecond )
+    {
+        detail::putUnalignedMate( rOut, rContigs, rQ1, true, 0x8u, false, 0, 0 );
+        detail::putUnalignedMate( rOut, rContigs, rQ2, false, 0x8u, false, 0, 0 );
+    }
+    else if( bHasFirst != bHasSecond )
+    {
+        const Read xQ = bHasFirst ? rQ2 : rQ1;
+        const Rec xAnchor = rList.rec( 0 );
+        detail::putUnalignedMate( rOut, rContigs, xQ, !bHasFirst, 0, true, xAnchor.begin_ref, xAnchor.end_ref );
+    }
 }
 
 // The text of the host formatter's exception for an error a sink was told of; returns its length (buf holds >= 64 bytes, the
