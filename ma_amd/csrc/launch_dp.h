@@ -51,7 +51,7 @@ int ma_dp_batch( ma_batch* b )
         return fail( "ma_dp_batch: run ma_chain_batch first" );
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads, nh = b->nHsets, nhs = b->nHseeds;
-    b->samDone = b->pairSamDone = false; // (a text printed before is of other records)
+    b->sam.done = b->pairSam.done = false; // (a text printed before is of other records)
     if( b->mqCnt.reserve( ( n + 1 ) * 4 ) )
         return 1;
     MA_HIP( hipMemsetAsync( b->mqCnt.p, 0, ( n + 1 ) * 4, b->stream ) );
@@ -329,7 +329,7 @@ int ma_batch_set_alignments( ma_batch* b, const uint64_t* aln_off, const ma_alig
     if( na && !alns )
         return fail( "ma_batch_set_alignments: null argument" );
     MA_BIND_DEVICE( b->device );
-    b->samDone = b->pairSamDone = false;
+    b->sam.done = b->pairSam.done = false;
     u64 no = 0;
     for( u64 i = 0; i < na; i++ )
         no += alns[ i ].n_ops;

@@ -108,7 +108,7 @@ int ma_pair_batch( ma_batch* b )
     const u64 np = b->n_reads / 2;
     b->pairOnHost = 0;
     b->pairRecs = b->pairNOps = 0;
-    b->pairSamDone = false; // (a text printed before is of other picks)
+    b->pairSam.done = false; // (a text printed before is of other picks)
     b->stage_done = 4;
     if( np && b->nHsets )
     {
@@ -155,14 +155,7 @@ static int get_pairs( ma_batch* b, uint64_t* pair_off, ma_alignment* alns, uint6
     if( !b || b->stage_done < 5 )
         return fail( "ma_batch_get_pairs: run ma_pair_batch first" );
     MA_BIND_DEVICE( b->device );
-    if( b->downPending )
-    {
-        if( async )
-            return fail( "ma_batch_start_pair_download: the download started before was not finished (ma_batch_finish_download)" );
-        MA_HIP( hipEventSynchronize( b->evDown ) );
-        b->downPending = false;
-    }
-    if( async && io_init( b ) )
+    if( download_begin( b, async, "ma_batch_start_pair_download" ) )
         return 1;
     const u64 np = b->n_reads / 2, totalA = b->pairRecs, totalO = b->pairNOps;
     if( totalA == 0 )
@@ -184,13 +177,9 @@ static int get_pairs( ma_batch* b, uint64_t* pair_off, ma_alignment* alns, uint6
                         b->outAlnOff.as<u64>( ), b->outOpsOff.as<u64>( ), b->outAlns.as<ma_alignment>( ), b->outOpsPairs.as<u64>( ),
                         b->pairMate.as<i32>( ), b->pairOther.as<i32>( ) );
     MA_HIP( hipGetLastError( ) );
-    hipStream_t cs = b->stream;
-    if( async )
-    {
-        cs = b->ioStream;
-        MA_HIP( hipEventRecord( b->evPacked, b->stream ) );
-        MA_HIP( hipStreamWaitEvent( cs, b->evPacked, 0 ) );
-    }
+    hipStream_t cs;
+    if( download_stream( b, async, &cs ) )
+        return 1;
     if( pair_off )
         MA_HIP( hipMemcpyAsync( pair_off, b->outAlnOff.p, ( np + 1 ) * 8, hipMemcpyDeviceToHost, cs ) );
     if( alns )
@@ -201,13 +190,7 @@ static int get_pairs( ma_batch* b, uint64_t* pair_off, ma_alignment* alns, uint6
         MA_HIP( hipMemcpyAsync( mate, b->pairMate.p, totalA * 4, hipMemcpyDeviceToHost, cs ) );
     if( other )
         MA_HIP( hipMemcpyAsync( other, b->pairOther.p, totalA * 4, hipMemcpyDeviceToHost, cs ) );
-    if( async )
-    {
-        MA_HIP( hipEventRecord( b->evDown, cs ) );
-        b->downPending = true;
-        return 0;
-    }
-    return batch_wait( b );
+    return download_end( b, async, cs );
 }
 
 extern "C" {

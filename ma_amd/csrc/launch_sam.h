@@ -1,11 +1,15 @@
-// launch_sam.h -- ma_batch_set_read_text, ma_sam_batch and the download of its text.  Textually part of pipeline.hip.
+// launch_sam.h -- ma_batch_set_read_text, ma_sam_batch, ma_pair_sam_batch and the downloads of their texts.  Textually part of
+// pipeline.hip.
 //
-// ma_sam_batch runs k_sam_size behind the MappingQuality stage on the batch's stream, scans the per-read byte counts into
-// offsets and waits with the ONE read-back of the batch's SAM statistics: the bytes of the text (the size of the download) and
-// the records that end beyond their read -- the host formatter's exception, which the call then fails with, launching nothing
-// more.  k_sam_write follows on the stream; ma_batch_get_sam / ma_batch_start_sam_download are two plain copies.
+// Both calls are one sequence (sam_text_launch) over a SamTextState of their own: the size kernel behind the stage before on the
+// batch's stream, a scan of the per-item byte counts into offsets, and the wait with the ONE read-back of the text's
+// statistics: its bytes (the size of the download) and the records that end beyond their read -- the host formatter's
+// exception, which the call then fails with, launching nothing more.  The write kernel follows on the stream with nobody
+// waiting; the gets and downloads (get_sam_text) are two plain copies.  The calls differ in their items (reads / pairs), their
+// kernels and arguments (stage_sam.h / stage_pair_sam.h) and in how the first bad record is found again.
 namespace
 {
+// (cnt, off, seq_pos, text and stat are the launcher's to fill)
 SamKernelArgs sam_args( ma_batch* b, u32 options )
 {
     const ma_index* x = b->idx;
@@ -23,11 +27,6 @@ SamKernelArgs sam_args( ma_batch* b, u32 options )
     A.names = b->txtNames.as<char>( );
     A.name_off = b->txtNameOff.as<u64>( );
     A.qual = b->txtHasQual ? b->txtQual.as<uint8_t>( ) : nullptr;
-    A.cnt = b->samCnt.as<u64>( );
-    A.off = b->samOff.as<u64>( );
-    A.seq_pos = b->samSeqPos.as<u64>( );
-    A.text = b->samText.as<char>( );
-    A.stat = b->samStat.as<unsigned long long>( );
     return A;
 }
 
@@ -53,6 +52,103 @@ int sam_fail( ma_batch* b, u64 slot )
     ma_sam::errorText( text, rev ? ma_sam::ERR_COMP_CHAR_AT : ma_sam::ERR_QUERY_LENGTH,
                        (i64)( roff[ r + 1 ] - roff[ r ] ) - (i64)h.end_q );
     return fail( text );
+}
+
+PairSamKernelArgs pair_sam_args( ma_batch* b, u32 options )
+{
+    const ma_index* x = b->idx;
+    PairSamKernelArgs A;
+    A.contigs = ma_sam::Contigs{ x->cnames.as<char>( ), x->cnameOff.as<u64>( ), x->v.cstart, x->v.clen, (u32)x->v.n_contigs };
+    A.options = options;
+    A.n_pairs = (u32)( b->n_reads / 2 );
+    A.picks_valid = b->nHsets ? 1u : 0u; // (ma_pair_batch launches nothing without harmonized sets)
+    A.hset_off = b->hsetOff.as<u64>( );
+    A.roff = b->d_roff;
+    A.reads = b->d_reads;
+    A.hdr = b->hdr.as<AlnHeader>( );
+    A.pool = b->ops.as<u64>( );
+    A.mq_order = b->mqOrder.as<u32>( );
+    A.mq_cnt = b->mqCnt.as<u32>( );
+    A.pick = b->pairPick.as<ma_pair::Pick>( );
+    A.names = b->txtNames.as<char>( );
+    A.name_off = b->txtNameOff.as<u64>( );
+    A.qual = b->txtHasQual ? b->txtQual.as<uint8_t>( ) : nullptr;
+    return A;
+}
+
+// the host formatter's text for the first bad record (error path only): key = pair << 32 | index in the pair's records
+int pair_sam_fail( ma_batch* b, u64 key )
+{
+    const u64 p = key >> 32;
+    const u32 k = (u32)key;
+    ma_pair::Pick pick;
+    u64 hoff[ 2 ], roff[ 3 ];
+    MA_HIP( hipMemcpyAsync( &pick, b->pairPick.as<ma_pair::Pick>( ) + p, sizeof( pick ), hipMemcpyDeviceToHost, b->stream ) );
+    MA_HIP( hipMemcpyAsync( hoff, b->hsetOff.as<u64>( ) + 2 * p, 16, hipMemcpyDeviceToHost, b->stream ) );
+    MA_HIP( hipMemcpyAsync( roff, b->d_roff + 2 * p, 24, hipMemcpyDeviceToHost, b->stream ) );
+    if( batch_wait( b ) )
+        return 1;
+    // the record's mate and its place in that mate's MappingQuality order
+    const bool first = pick.kind == ma_pair::PICKED ? k == 0 : pick.kind == ma_pair::FIRST_LIST;
+    const u64 idx = pick.kind == ma_pair::PICKED ? ( k == 0 ? pick.i : pick.j ) : k;
+    const u64 base = hoff[ first ? 0 : 1 ];
+    u32 ord = 0;
+    AlnHeader h;
+    MA_HIP( hipMemcpyAsync( &ord, b->mqOrder.as<u32>( ) + base + idx, 4, hipMemcpyDeviceToHost, b->stream ) );
+    if( batch_wait( b ) )
+        return 1;
+    MA_HIP( hipMemcpyAsync( &h, b->hdr.as<AlnHeader>( ) + base + ord, sizeof( h ), hipMemcpyDeviceToHost, b->stream ) );
+    if( batch_wait( b ) )
+        return 1;
+    char text[ 64 ];
+    const bool rev = h.begin_ref >= b->idx->v.F;
+    const u64 len = first ? roff[ 1 ] - roff[ 0 ] : roff[ 2 ] - roff[ 1 ];
+    ma_sam::errorText( text, rev ? ma_sam::ERR_COMP_CHAR_AT : ma_sam::ERR_QUERY_LENGTH, (i64)len - (i64)h.end_q );
+    return fail( text );
+}
+
+// The text of n items into s.  A: the stage's arguments but for the state's arrays.
+template <typename Args, void ( *SizeKernel )( Args ), void ( *WriteKernel )( Args ), int ( *Fail )( ma_batch*, u64 )>
+int sam_text_launch( ma_batch* b, SamTextState& s, u64 n, Args A )
+{
+    if( download_wait( b ) ) // the text of the last call may still be on its way down
+        return 1;
+    s.done = false;
+    s.bytes = 0;
+    if( n )
+    {
+        if( s.cnt.reserve( ( n + 2 ) * 8 ) || s.off.reserve( ( n + 2 ) * 8 ) || s.stat.reserve( SAM_STAT_COUNT * 8 ) ||
+            s.seqPos.reserve( ( b->nHsets + 1 ) * 8 ) )
+            return 1;
+        const unsigned long long init[ SAM_STAT_COUNT ] = { 0, 0, ~0ull, 0 };
+        MA_HIP( hipMemcpyAsync( s.stat.p, init, sizeof( init ), hipMemcpyHostToDevice, b->stream ) );
+        MA_HIP( hipMemsetAsync( (char*)s.cnt.p + n * 8, 0, 8, b->stream ) );
+        A.cnt = s.cnt.as<u64>( );
+        A.off = s.off.as<u64>( );
+        A.seq_pos = s.seqPos.as<u64>( );
+        A.text = s.text.as<char>( );
+        A.stat = s.stat.as<unsigned long long>( );
+        const dim3 grid( (unsigned)( ( n + 255 ) / 256 ) ), block( 256 );
+        hipLaunchKernelGGL( SizeKernel, grid, block, 0, b->stream, A );
+        MA_HIP( hipGetLastError( ) );
+        if( scan_exclusive<u64>( b, s.cnt.as<u64>( ), s.off.as<u64>( ), n + 1 ) )
+            return 1;
+        MA_HIP( hipMemcpyAsync( A.stat + SAM_STAT_BYTES, s.off.as<u64>( ) + n, 8, hipMemcpyDeviceToDevice, b->stream ) );
+        unsigned long long stat[ SAM_STAT_COUNT ];
+        MA_HIP( hipMemcpyAsync( stat, s.stat.p, sizeof( stat ), hipMemcpyDeviceToHost, b->stream ) );
+        if( batch_wait( b ) ) // (init goes out of scope as well)
+            return 1;
+        if( stat[ SAM_STAT_ERRORS ] )
+            return Fail( b, stat[ SAM_STAT_FIRST ] );
+        if( s.text.reserve( stat[ SAM_STAT_BYTES ] + 64 ) )
+            return 1;
+        A.text = s.text.as<char>( );
+        hipLaunchKernelGGL( WriteKernel, grid, block, 0, b->stream, A );
+        MA_HIP( hipGetLastError( ) );
+        s.bytes = stat[ SAM_STAT_BYTES ];
+    }
+    s.done = true;
+    return 0;
 }
 } // namespace
 
@@ -90,7 +186,7 @@ int ma_batch_set_read_text( ma_batch* b, const char* names, const uint64_t* name
         if( name_off[ i + 1 ] < name_off[ i ] )
             return fail( "ma_batch_set_read_text: offsets decrease" );
     MA_BIND_DEVICE( b->device );
-    b->txtSet = b->samDone = b->pairSamDone = false;
+    b->txtSet = b->sam.done = b->pairSam.done = false;
     if( b->txtNames.reserve( name_off[ n ] + 1 ) || b->txtNameOff.reserve( ( n + 1 ) * 8 ) || ( qual && b->txtQual.reserve( b->n_bases + 1 ) ) )
         return 1;
     if( name_off[ n ] )
@@ -118,96 +214,80 @@ int ma_sam_batch( ma_batch* b, uint32_t options )
     if( !b->txtSet )
         return fail( "ma_sam_batch: the reads have no names (ma_batch_set_read_text after the reads were set)" );
     MA_BIND_DEVICE( b->device );
-    if( b->downPending ) // the text of the last call may still be on its way down
-    {
-        MA_HIP( hipEventSynchronize( b->evDown ) );
-        b->downPending = false;
-    }
-    const u64 n = b->n_reads;
-    b->samDone = false;
-    b->samBytes = 0;
-    if( n )
-    {
-        if( b->samCnt.reserve( ( n + 2 ) * 8 ) || b->samOff.reserve( ( n + 2 ) * 8 ) || b->samStat.reserve( SAM_STAT_COUNT * 8 ) ||
-            b->samSeqPos.reserve( ( b->nHsets + 1 ) * 8 ) )
-            return 1;
-        const unsigned long long init[ SAM_STAT_COUNT ] = { 0, 0, ~0ull, 0 };
-        MA_HIP( hipMemcpyAsync( b->samStat.p, init, sizeof( init ), hipMemcpyHostToDevice, b->stream ) );
-        MA_HIP( hipMemsetAsync( (char*)b->samCnt.p + n * 8, 0, 8, b->stream ) );
-        SamKernelArgs A = sam_args( b, options );
-        const dim3 grid( (unsigned)( ( n + 255 ) / 256 ) ), block( 256 );
-        hipLaunchKernelGGL( k_sam_size, grid, block, 0, b->stream, A );
-        MA_HIP( hipGetLastError( ) );
-        if( scan_exclusive<u64>( b, b->samCnt.as<u64>( ), b->samOff.as<u64>( ), n + 1 ) )
-            return 1;
-        MA_HIP( hipMemcpyAsync( b->samStat.as<unsigned long long>( ) + SAM_STAT_BYTES, b->samOff.as<u64>( ) + n, 8, hipMemcpyDeviceToDevice, b->stream ) );
-        unsigned long long stat[ SAM_STAT_COUNT ];
-        MA_HIP( hipMemcpyAsync( stat, b->samStat.p, sizeof( stat ), hipMemcpyDeviceToHost, b->stream ) );
-        if( batch_wait( b ) ) // (init goes out of scope as well)
-            return 1;
-        if( stat[ SAM_STAT_ERRORS ] )
-            return sam_fail( b, stat[ SAM_STAT_FIRST ] );
-        if( b->samText.reserve( stat[ SAM_STAT_BYTES ] + 64 ) )
-            return 1;
-        A.text = b->samText.as<char>( );
-        hipLaunchKernelGGL( k_sam_write, grid, block, 0, b->stream, A );
-        MA_HIP( hipGetLastError( ) );
-        b->samBytes = stat[ SAM_STAT_BYTES ];
-    }
-    b->samDone = true;
-    return 0;
+    return sam_text_launch<SamKernelArgs, k_sam_size, k_sam_write, sam_fail>( b, b->sam, b->n_reads, sam_args( b, options ) );
+}
+
+int ma_pair_sam_batch( ma_batch* b, uint32_t options )
+{
+    if( !b )
+        return fail( "ma_pair_sam_batch: null batch" );
+    if( b->stage_done < 5 )
+        return fail( "ma_pair_sam_batch: no pairs to print (run ma_pair_batch first)" );
+    if( options & ~(uint32_t)ma_sam::ALL_OPTIONS )
+        return fail( "ma_pair_sam_batch: unknown option bits " + std::to_string( options & ~(uint32_t)ma_sam::ALL_OPTIONS ) );
+    if( !b->idx->namesSet )
+        return fail( "ma_pair_sam_batch: the index has no contig names (ma_index_set_contig_names)" );
+    if( !b->txtSet )
+        return fail( "ma_pair_sam_batch: the reads have no names (ma_batch_set_read_text after the reads were set)" );
+    MA_BIND_DEVICE( b->device );
+    return sam_text_launch<PairSamKernelArgs, k_pair_sam_size, k_pair_sam_write, pair_sam_fail>( b, b->pairSam, b->n_reads / 2,
+                                                                                                 pair_sam_args( b, options ) );
 }
 
 int ma_batch_sam_counts( ma_batch* b, uint64_t* n_bytes )
 {
-    if( !b || !b->samDone )
+    if( !b || !b->sam.done )
         return fail( "ma_batch_sam_counts: run ma_sam_batch first" );
     if( n_bytes )
-        *n_bytes = b->samBytes;
+        *n_bytes = b->sam.bytes;
+    return 0;
+}
+
+int ma_batch_pair_sam_counts( ma_batch* b, uint64_t* n_pairs, uint64_t* n_bytes )
+{
+    if( !b || !b->pairSam.done )
+        return fail( "ma_batch_pair_sam_counts: run ma_pair_sam_batch first" );
+    if( n_pairs )
+        *n_pairs = b->n_reads / 2;
+    if( n_bytes )
+        *n_bytes = b->pairSam.bytes;
     return 0;
 }
 } // extern "C"
 
-// async: see get_alns
-static int get_sam( ma_batch* b, uint64_t* rec_off, char* text, bool async )
+// The download of one text of n items and of its offsets; async and start: see get_alns, download_begin
+static int get_sam_text( ma_batch* b, const SamTextState& s, u64 n, const char* start, uint64_t* off, char* text, bool async )
 {
-    if( !b || !b->samDone )
-        return fail( "ma_batch_get_sam: run ma_sam_batch first" );
     MA_BIND_DEVICE( b->device );
-    if( b->downPending )
-    {
-        if( async )
-            return fail( "ma_batch_start_sam_download: the download started before was not finished (ma_batch_finish_download)" );
-        MA_HIP( hipEventSynchronize( b->evDown ) );
-        b->downPending = false;
-    }
-    if( async && io_init( b ) )
+    if( download_begin( b, async, start ) )
         return 1;
-    const u64 n = b->n_reads;
     if( n == 0 )
     {
-        if( rec_off )
-            rec_off[ 0 ] = 0;
+        if( off )
+            off[ 0 ] = 0;
         return 0;
     }
-    hipStream_t cs = b->stream;
-    if( async )
-    {
-        cs = b->ioStream;
-        MA_HIP( hipEventRecord( b->evPacked, b->stream ) );
-        MA_HIP( hipStreamWaitEvent( cs, b->evPacked, 0 ) );
-    }
-    if( rec_off )
-        MA_HIP( hipMemcpyAsync( rec_off, b->samOff.p, ( n + 1 ) * 8, hipMemcpyDeviceToHost, cs ) );
-    if( text && b->samBytes )
-        MA_HIP( hipMemcpyAsync( text, b->samText.p, b->samBytes, hipMemcpyDeviceToHost, cs ) );
-    if( async )
-    {
-        MA_HIP( hipEventRecord( b->evDown, cs ) );
-        b->downPending = true;
-        return 0;
-    }
-    return batch_wait( b );
+    hipStream_t cs;
+    if( download_stream( b, async, &cs ) )
+        return 1;
+    if( off )
+        MA_HIP( hipMemcpyAsync( off, s.off.p, ( n + 1 ) * 8, hipMemcpyDeviceToHost, cs ) );
+    if( text && s.bytes )
+        MA_HIP( hipMemcpyAsync( text, s.text.p, s.bytes, hipMemcpyDeviceToHost, cs ) );
+    return download_end( b, async, cs );
+}
+
+static int get_sam( ma_batch* b, uint64_t* rec_off, char* text, bool async )
+{
+    if( !b || !b->sam.done )
+        return fail( "ma_batch_get_sam: run ma_sam_batch first" );
+    return get_sam_text( b, b->sam, b->n_reads, "ma_batch_start_sam_download", rec_off, text, async );
+}
+static int get_pair_sam( ma_batch* b, uint64_t* pair_off, char* text, bool async )
+{
+    if( !b || !b->pairSam.done )
+        return fail( "ma_batch_get_pair_sam: run ma_pair_sam_batch first" );
+    return get_sam_text( b, b->pairSam, b->n_reads / 2, "ma_batch_start_pair_sam_download", pair_off, text, async );
 }
 
 extern "C" {
@@ -218,5 +298,13 @@ int ma_batch_get_sam( ma_batch* b, uint64_t* rec_off, char* text )
 int ma_batch_start_sam_download( ma_batch* b, uint64_t* rec_off, char* text )
 {
     return get_sam( b, rec_off, text, true );
+}
+int ma_batch_get_pair_sam( ma_batch* b, uint64_t* pair_off, char* text )
+{
+    return get_pair_sam( b, pair_off, text, false );
+}
+int ma_batch_start_pair_sam_download( ma_batch* b, uint64_t* pair_off, char* text )
+{
+    return get_pair_sam( b, pair_off, text, true );
 }
 } // extern "C"

@@ -88,6 +88,15 @@ static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0
 // ------------------------------------------------------------------------------------------------
 // batch object
 // ------------------------------------------------------------------------------------------------
+// One SAM text of a batch (launch_sam.h): per item -- a read, or a pair -- the bytes of its records and their scan, where SEQ
+// of every record goes, the text, the statistics of the one read-back (SAM_STAT_*)
+struct SamTextState
+{
+    DevBuf cnt, off, seqPos, text, stat;
+    bool done = false;
+    u64 bytes = 0;
+};
+
 struct ma_batch
 {
     const ma_index* idx = nullptr;
@@ -122,15 +131,11 @@ struct ma_batch
     // pairing (ma_pair_batch): per pair its pick and sizes, the pairs left to the host and their round trip, the packed columns
     DevBuf pairPick, pairCnt, pairOps, pairOver, pairHostOff, pairHostLists, pairHostPick, pairMate, pairOther;
     u64 pairRecs = 0, pairNOps = 0, pairOnHost = 0;
-    // SAM text (ma_sam_batch): the reads' names and qualities (ma_batch_set_read_text; dropped when reads are set), per read the
-    // bytes of its records and their scan, where SEQ of every record goes, the text, the statistics of the one read-back
-    DevBuf txtNames, txtNameOff, txtQual, samCnt, samOff, samSeqPos, samText, samStat;
-    bool txtSet = false, txtHasQual = false, samDone = false;
-    u64 samBytes = 0;
-    // paired-end SAM text (ma_pair_sam_batch): the same per pair, all of its own -- the single-end text stays what it was
-    DevBuf pairSamCnt, pairSamOff, pairSamSeqPos, pairSamText, pairSamStat;
-    bool pairSamDone = false;
-    u64 pairSamBytes = 0;
+    // SAM text: the reads' names and qualities (ma_batch_set_read_text; dropped when reads are set), the single-end text per
+    // read (ma_sam_batch) and the paired-end text per pair (ma_pair_sam_batch), each all of its own: one never touches the other
+    DevBuf txtNames, txtNameOff, txtQual;
+    bool txtSet = false, txtHasQual = false;
+    SamTextState sam, pairSam;
     u64 cigPoolCap = 0, cigPoolMin = 0, nOpsCap = 0, nJobSlots = 0;
     KswSide kswSide; // created on first use
     // double-buffered I/O (ma_batch_stage_reads / ma_batch_start_mapq_download): the next reads are uploaded into reads2 / roff2
@@ -329,6 +334,53 @@ static int io_init( ma_batch* b )
     return 0;
 }
 
+// The download slot.  A batch has ONE I/O stream and ONE pending download (downPending, evDown), whatever was started:
+// MappingQuality records, pair records, either SAM text.  Every download, and everything that overwrites what a download
+// reads, goes through these:
+//   download_wait    waits for the pending download, if any
+//   download_begin   async (ma_batch_start_*_download, named by `start`): refused while one is pending, else the I/O stream is
+//                    made; the synchronous form waits for the pending one
+//   download_stream  the stream of the copies: the batch's own, or the I/O stream behind what the batch's stream holds so far
+//   download_end     async: the download is pending from here on; else waits for the copies
+// An early return between begin and end (nothing to copy) leaves nothing pending.
+static int download_wait( ma_batch* b )
+{
+    if( b->downPending )
+    {
+        MA_HIP( hipEventSynchronize( b->evDown ) );
+        b->downPending = false;
+    }
+    return 0;
+}
+
+static int download_begin( ma_batch* b, bool async, const char* start )
+{
+    if( async && b->downPending )
+        return fail( std::string( start ) + ": the download started before was not finished (ma_batch_finish_download)" );
+    return download_wait( b ) || ( async && io_init( b ) );
+}
+
+static int download_stream( ma_batch* b, bool async, hipStream_t* cs )
+{
+    *cs = b->stream;
+    if( async )
+    {
+        *cs = b->ioStream;
+        MA_HIP( hipEventRecord( b->evPacked, b->stream ) );
+        MA_HIP( hipStreamWaitEvent( *cs, b->evPacked, 0 ) );
+    }
+    return 0;
+}
+
+static int download_end( ma_batch* b, bool async, hipStream_t cs )
+{
+    if( !async )
+        return batch_wait( b );
+    MA_HIP( hipEventRecord( b->evDown, cs ) );
+    b->downPending = true;
+    return 0;
+}
+
 int ma_batch_stage_reads( ma_batch* b, const uint8_t* codes, const uint64_t* offsets, uint64_t n )
 {
     if( !b || !offsets || ( n && !codes ) )
@@ -374,7 +426,7 @@ int ma_batch_use_staged_reads( ma_batch* b )
     b->d_roff = b->roff.as<u64>( );
     b->reads_external = false;
     b->stage_done = 0;
-    b->txtSet = b->samDone = b->pairSamDone = false;
+    b->txtSet = b->sam.done = b->pairSam.done = false;
     b->stagedPending = false;
     return 0;
 }
@@ -401,7 +453,7 @@ int ma_batch_set_reads( ma_batch* b, const uint8_t* codes, const uint64_t* offse
     b->d_roff = b->roff.as<u64>( );
     b->reads_external = false;
     b->stage_done = 0;
-    b->txtSet = b->samDone = b->pairSamDone = false;
+    b->txtSet = b->sam.done = b->pairSam.done = false;
     return 0;
 }
 
@@ -437,7 +489,7 @@ int ma_batch_set_reads_device( ma_batch* b, const void* d_codes, const void* d_o
         return 1;
     b->max_qlen = (u32)b->hctr[ 0 ];
     b->stage_done = 0;
-    b->txtSet = b->samDone = b->pairSamDone = false;
+    b->txtSet = b->sam.done = b->pairSam.done = false;
     return 0;
 }
 
@@ -932,15 +984,7 @@ static int get_alns( ma_batch* b, bool mq, uint64_t* aln_off, ma_alignment* alns
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )
         return 1;
-    if( b->downPending )
-    {
-        // the packed arrays are still being downloaded: nothing may overwrite them before that
-        if( async )
-            return fail( "ma_batch_start_mapq_download: the download started before was not finished (ma_batch_finish_download)" );
-        MA_HIP( hipEventSynchronize( b->evDown ) );
-        b->downPending = false;
-    }
-    if( async && io_init( b ) )
+    if( download_begin( b, async, "ma_batch_start_mapq_download" ) ) // (the packed arrays may be overwritten only behind it)
         return 1;
     const u64 n = b->n_reads, nh = b->nHsets;
     if( aln_off )
@@ -971,28 +1015,16 @@ static int get_alns( ma_batch* b, bool mq, uint64_t* aln_off, ma_alignment* alns
                         b->ops.as<u64>( ), mq ? 1 : 0, b->outAlnOff.as<u64>( ), b->outOpsOff.as<u64>( ), b->outAlns.as<ma_alignment>( ),
                         b->outOpsPairs.as<u64>( ) );
     MA_HIP( hipGetLastError( ) );
-    hipStream_t cs = b->stream;
-    if( async )
-    {
-        cs = b->ioStream;
-        MA_HIP( hipEventRecord( b->evPacked, b->stream ) );
-        MA_HIP( hipStreamWaitEvent( cs, b->evPacked, 0 ) );
-    }
+    hipStream_t cs;
+    if( download_stream( b, async, &cs ) )
+        return 1;
     if( aln_off )
         MA_HIP( hipMemcpyAsync( aln_off, b->outAlnOff.p, ( n + 1 ) * 8, hipMemcpyDeviceToHost, cs ) );
     if( alns && totalA )
         MA_HIP( hipMemcpyAsync( alns, b->outAlns.p, totalA * sizeof( ma_alignment ), hipMemcpyDeviceToHost, cs ) );
     if( ops && totalO )
         MA_HIP( hipMemcpyAsync( ops, b->outOpsPairs.p, totalO * 16, hipMemcpyDeviceToHost, cs ) );
-    if( async )
-    {
-        MA_HIP( hipEventRecord( b->evDown, cs ) );
-        b->downPending = true;
-        return 0;
-    }
-    if( batch_wait( b ) )
-        return 1;
-    return 0;
+    return download_end( b, async, cs );
 }
 
 int ma_batch_start_mapq_download( ma_batch* b, uint64_t* aln_off, ma_alignment* alns, uint64_t* ops )
@@ -1007,9 +1039,7 @@ int ma_batch_finish_download( ma_batch* b )
     if( !b->downPending )
         return 0;
     MA_BIND_DEVICE( b->device );
-    MA_HIP( hipEventSynchronize( b->evDown ) );
-    b->downPending = false;
-    return 0;
+    return download_wait( b );
 }
 
 int ma_batch_get_alignments( ma_batch* b, uint64_t* aln_off, ma_alignment* alns, uint64_t* ops )
@@ -1143,4 +1173,3 @@ int ma_debug_seed_prof( unsigned long long* out )
 #include "launch_pair.h"
 
 #include "launch_sam.h"
-#include "launch_pair_sam.h"

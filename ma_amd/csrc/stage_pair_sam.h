@@ -65,14 +65,6 @@ struct PairSamDevList
     }
 };
 
-enum : int
-{
-    PSAM_STAT_BYTES = 0, // bytes of the batch's text (the launcher copies the scan's last offset here)
-    PSAM_STAT_ERRORS = 1, // records that end beyond their mate
-    PSAM_STAT_FIRST = 2, // the first of them in pair order: pair << 32 | index in the pair's records
-    PSAM_STAT_COUNT = 4
-};
-
 struct PairSamKernelArgs
 {
     ma_sam::Contigs contigs;
@@ -141,15 +133,16 @@ __device__ __forceinline__ ma_sam::Read pair_sam_read( const PairSamKernelArgs& 
     return ma_sam::Read{ A.names + no, A.name_off[ r + 1 ] - no, A.reads + o, A.qual && len ? A.qual + o : nullptr, len };
 }
 
-// the counting sink, with the errors going to the batch's statistics
+// the counting sink, with the errors going to the batch's statistics (SAM_STAT_* of stage_sam.h): the records that end beyond
+// their mate, and as SAM_STAT_FIRST the first of them in pair order, pair << 32 | index in the pair's records
 struct PairSamCountSink : ma_sam::CountSink
 {
     unsigned long long* stat;
     u64 pair;
     __device__ __forceinline__ void error( u32, i64, u32 k )
     {
-        atomicAdd( &stat[ PSAM_STAT_ERRORS ], 1ull );
-        atomicMin( &stat[ PSAM_STAT_FIRST ], (unsigned long long)( ( pair << 32 ) | k ) );
+        atomicAdd( &stat[ SAM_STAT_ERRORS ], 1ull );
+        atomicMin( &stat[ SAM_STAT_FIRST ], (unsigned long long)( ( pair << 32 ) | k ) );
     }
 };
 

@@ -36,11 +36,11 @@ struct SamDevList
     }
 };
 
-enum : int
+enum : int // the statistics of a SAM text, of this stage and of stage_pair_sam.h
 {
     SAM_STAT_BYTES = 0, // bytes of the batch's text (the launcher copies the scan's last offset here)
-    SAM_STAT_ERRORS = 1, // records that end beyond their read
-    SAM_STAT_FIRST = 2, // the first of them in read order: hset_off[ read ] + index in the read's list
+    SAM_STAT_ERRORS = 1, // records that end beyond their read (paired: their mate)
+    SAM_STAT_FIRST = 2, // the first of them in the batch's order, as the stage's count sink writes it
     SAM_STAT_COUNT = 4
 };
 
@@ -78,7 +78,8 @@ __device__ __forceinline__ ma_sam::Read sam_read( const SamKernelArgs& A, u32 r 
     return ma_sam::Read{ A.names + no, A.name_off[ r + 1 ] - no, A.reads + o, A.qual ? A.qual + o : nullptr, A.roff[ r + 1 ] - o };
 }
 
-// the counting sink, with the errors going to the batch's statistics
+// the counting sink, with the errors going to the batch's statistics: the records that end beyond their read, and as
+// SAM_STAT_FIRST the first of them in read order, the slot hset_off[ read ] + index in the read's list
 struct SamCountSink : ma_sam::CountSink
 {
     unsigned long long* stat;

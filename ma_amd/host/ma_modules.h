@@ -1760,13 +1760,13 @@ class BatchAligner
     // container is built; SmallInversions needs containers and is not applied here).
     std::shared_ptr<TP_FLAT> executeFlat( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<ReadVector> pQueries )
     {
-        auto pRet = std::make_shared<TP_FLAT>( );
-        xLast = AlignerTiming( );
-        const auto t0 = std::chrono::steady_clock::now( );
-        if( !pQueries->empty( ) )
-            alignRangeOn( pFM_index->pDev->all( ), *pQueries, 0, pQueries->size( ), nullptr, xLast, pRet.get( ), pQueries, &vLastPerIndex );
-        xLast.fWall = detail::secondsSince( t0 );
-        return pRet;
+        return executeFlatOn( pFM_index->pDev->all( ), pQueries, &vLastPerIndex );
+    }
+    // (on the replicas given, as the other ...On functions: what MultiDeviceAligner calls)
+    std::shared_ptr<TP_FLAT> executeFlatOn( const std::vector<const ma_index*>& vIndices, std::shared_ptr<ReadVector> pQueries,
+                                            std::vector<AlignerTiming>* pPerIndex )
+    {
+        return runFlatOn( vIndices, pQueries, pPerIndex, false, nullptr );
     }
 
     // The MA_SAM_* bits of ma_sam_batch for the writer's options.  The NGMLR tag emulation needs reference bases and Alignment
@@ -1820,13 +1820,7 @@ class BatchAligner
             throw std::runtime_error( "BatchAligner::executeFlatSam: not with 'Detect Small Inversions' or the NGMLR tag emulation "
                                       "(use executeFlat and BatchFileWriter)" );
         const uint32_t uiOptions = samOptionBits( xParams.xSam );
-        auto pRet = std::make_shared<TP_FLAT>( );
-        xLast = AlignerTiming( );
-        const auto t0 = std::chrono::steady_clock::now( );
-        if( !pQueries->empty( ) )
-            alignRangeOn( vIndices, *pQueries, 0, pQueries->size( ), nullptr, xLast, pRet.get( ), pQueries, pPerIndex, false, &uiOptions );
-        xLast.fWall = detail::secondsSince( t0 );
-        return pRet;
+        return runFlatOn( vIndices, pQueries, pPerIndex, false, &uiOptions );
     }
 
     // Paired mode (setUpCompGraphPaired, export.cpp:130-202) for a batch: vMates holds the mates of pair k at 2k and
@@ -1871,13 +1865,7 @@ class BatchAligner
     {
         if( vMates->size( ) % 2 )
             throw std::runtime_error( "BatchAligner::executePairedFlat: odd number of reads" );
-        auto pRet = std::make_shared<TP_FLAT>( );
-        xLast = AlignerTiming( );
-        const auto t0 = std::chrono::steady_clock::now( );
-        if( !vMates->empty( ) )
-            alignRangeOn( vIndices, *vMates, 0, vMates->size( ), nullptr, xLast, pRet.get( ), vMates, pPerIndex, true );
-        xLast.fWall = detail::secondsSince( t0 );
-        return pRet;
+        return runFlatOn( vIndices, vMates, pPerIndex, true, nullptr );
     }
     // executePairedFlat with the pairs' SAM records formatted on the DEVICE (ma_pair_batch + ma_pair_sam_batch): one
     // AlignedBatch per device batch of whole pairs, in input order, that is paired( ) AND hasSamText( ) -- pair k's records are
@@ -1908,13 +1896,7 @@ class BatchAligner
             throw std::runtime_error( "BatchAligner::executePairedFlatSam: not with 'Detect Small Inversions' or the NGMLR tag emulation "
                                       "(use executePairedFlat and BatchPairedFileWriter)" );
         const uint32_t uiOptions = samOptionBits( xParams.xSam );
-        auto pRet = std::make_shared<TP_FLAT>( );
-        xLast = AlignerTiming( );
-        const auto t0 = std::chrono::steady_clock::now( );
-        if( !vMates->empty( ) )
-            alignRangeOn( vIndices, *vMates, 0, vMates->size( ), nullptr, xLast, pRet.get( ), vMates, pPerIndex, true, &uiOptions );
-        xLast.fWall = detail::secondsSince( t0 );
-        return pRet;
+        return runFlatOn( vIndices, vMates, pPerIndex, true, &uiOptions );
     }
     // the pairs of executePaired as ONE paired AlignedBatch (host memory; the records keep PairedReads' changes)
     static std::shared_ptr<TP_FLAT> flattenPairs( std::shared_ptr<TP_RESULT> pPairs, std::shared_ptr<ReadVector> vMates )
@@ -1965,6 +1947,21 @@ class BatchAligner
         pRet->push_back( pB );
         return pRet;
     }
+
+  private:
+    // One flat run, the body of executeFlat and the ...On functions: pReads in device batches on vIndices, one AlignedBatch per
+    // batch in input order; bPairs: batches of whole pairs, paired on the device; pSamOptions: SAM text instead of records
+    std::shared_ptr<TP_FLAT> runFlatOn( const std::vector<const ma_index*>& vIndices, std::shared_ptr<ReadVector> pReads,
+                                        std::vector<AlignerTiming>* pPerIndex, bool bPairs, const uint32_t* pSamOptions )
+    {
+        auto pRet = std::make_shared<TP_FLAT>( );
+        xLast = AlignerTiming( );
+        const auto t0 = std::chrono::steady_clock::now( );
+        if( !pReads->empty( ) )
+            alignRangeOn( vIndices, *pReads, 0, pReads->size( ), nullptr, xLast, pRet.get( ), pReads, pPerIndex, bPairs, pSamOptions );
+        xLast.fWall = detail::secondsSince( t0 );
+        return pRet;
+    }
 };
 
 // Throughput API, several GPUs of one node: reads are independent, the index is replicated, the device batches
@@ -1984,6 +1981,26 @@ class MultiDeviceAligner
     {
         xAligner.uiBatchReads = uiBatchReads;
         xAligner.uiInflight = uiInflight;
+    }
+
+    // RNAME strings of rPack on every replica (before a run that prints on the device)
+    void nameContigs( const Pack& rPack )
+    {
+        for( const auto& pFM : vReplicas )
+            BatchAligner::nameContigs( *pFM->pDev, rPack );
+    }
+    // One flat run of the aligner over all replicas; its times into xLast and vLast
+    typedef std::shared_ptr<BatchAligner::TP_FLAT> ( BatchAligner::*TP_FLAT_ON )( const std::vector<const ma_index*>&,
+                                                                                    std::shared_ptr<ReadVector>, std::vector<AlignerTiming>* );
+    std::shared_ptr<BatchAligner::TP_FLAT> runFlat( TP_FLAT_ON pRunOn, std::shared_ptr<ReadVector> pReads )
+    {
+        configure( );
+        vLast.assign( vIndices.size( ), AlignerTiming( ) );
+        auto pRet = ( xAligner.*pRunOn )( vIndices, pReads, &vLast );
+        xLast = xAligner.xLast;
+        for( auto& rT : vLast )
+            rT.fWall = xLast.fWall;
+        return pRet;
     }
 
   public:
@@ -2076,31 +2093,14 @@ class MultiDeviceAligner
     // The same run with the results left FLAT: one AlignedBatch per device batch, in input order, whichever replica ran it.
     std::shared_ptr<BatchAligner::TP_FLAT> executeFlat( std::shared_ptr<ReadVector> pQueries )
     {
-        configure( );
-        auto pRet = std::make_shared<BatchAligner::TP_FLAT>( );
-        xLast = AlignerTiming( );
-        vLast.assign( vIndices.size( ), AlignerTiming( ) );
-        const auto t0 = std::chrono::steady_clock::now( );
-        if( !pQueries->empty( ) )
-            xAligner.alignRangeOn( vIndices, *pQueries, 0, pQueries->size( ), nullptr, xLast, pRet.get( ), pQueries, &vLast );
-        xLast.fWall = detail::secondsSince( t0 );
-        for( auto& rT : vLast )
-            rT.fWall = xLast.fWall;
-        return pRet;
+        return runFlat( &BatchAligner::executeFlatOn, pQueries );
     }
 
     // BatchAligner::executeFlatSam over all replicas: every device batch comes back as the SAM text its device formatted.
     std::shared_ptr<BatchAligner::TP_FLAT> executeFlatSam( std::shared_ptr<ReadVector> pQueries, std::shared_ptr<Pack> pPack )
     {
-        configure( );
-        for( const auto& pFM : vReplicas )
-            BatchAligner::nameContigs( *pFM->pDev, *pPack );
-        vLast.assign( vIndices.size( ), AlignerTiming( ) );
-        auto pRet = xAligner.executeFlatSamOn( vIndices, pQueries, &vLast );
-        xLast = xAligner.xLast;
-        for( auto& rT : vLast )
-            rT.fWall = xLast.fWall;
-        return pRet;
+        nameContigs( *pPack );
+        return runFlat( &BatchAligner::executeFlatSamOn, pQueries );
     }
 
     // BatchAligner::executePairedFlat over all replicas: batches of whole pairs rotate over them, paired on the device that
@@ -2109,13 +2109,7 @@ class MultiDeviceAligner
     {
         if( xParams.getSelected( )->search_inversions )
             throw std::runtime_error( "MultiDeviceAligner::executePairedFlat: not with 'Detect Small Inversions' (SmallInversions needs containers)" );
-        configure( );
-        vLast.assign( vIndices.size( ), AlignerTiming( ) );
-        auto pRet = xAligner.executePairedFlatOn( vIndices, vMates, &vLast );
-        xLast = xAligner.xLast;
-        for( auto& rT : vLast )
-            rT.fWall = xLast.fWall;
-        return pRet;
+        return runFlat( &BatchAligner::executePairedFlatOn, vMates );
     }
 
     // BatchAligner::executePairedFlatSam over all replicas: every device batch of whole pairs comes back as the SAM text its
@@ -2124,15 +2118,8 @@ class MultiDeviceAligner
     {
         if( xParams.getSelected( )->search_inversions )
             throw std::runtime_error( "MultiDeviceAligner::executePairedFlatSam: not with 'Detect Small Inversions' (SmallInversions needs containers)" );
-        configure( );
-        for( const auto& pFM : vReplicas )
-            BatchAligner::nameContigs( *pFM->pDev, *pPack );
-        vLast.assign( vIndices.size( ), AlignerTiming( ) );
-        auto pRet = xAligner.executePairedFlatSamOn( vIndices, vMates, &vLast );
-        xLast = xAligner.xLast;
-        for( auto& rT : vLast )
-            rT.fWall = xLast.fWall;
-        return pRet;
+        nameContigs( *pPack );
+        return runFlat( &BatchAligner::executePairedFlatSamOn, vMates );
     }
 };
 } // namespace libMA
