@@ -2,13 +2,13 @@
 // `maCMD -x <genome> -i <reads> [-m <mates>] -o <out.sam> -p <preset>` needs from the hot path.  Not a re-implementation
 // of cmdMa.cpp: no option parsing beyond the four arguments, no thread pool (the batches are the parallelism).
 //
-//   ma_align [--host-sam] <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam|stdout> [preset] [mates.fa|fq[.gz]]
+//   ma_align [--host-sam] [--ngmlr-tags] <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam|stdout> [preset] [mates.fa|fq[.gz]]
 //
 // Single-end input is printed on the device (BatchAligner::executeFlatSam: the SAM text is what comes down) whenever the
-// options are ones the device serves; with "Detect Small Inversions", with the NGMLR tag emulation and with --host-sam the
-// records come down and FileWriter prints them.  Paired input likewise: mates are paired and their records printed on the
-// device (BatchAligner::executePairedFlatSam), or the pair records come down and BatchPairedFileWriter formats them.  The
-// bytes are the same.
+// options are ones the device serves -- with --ngmlr-tags ("Emulate NGMLR's tag output") too; with "Detect Small Inversions"
+// and with --host-sam the records come down and FileWriter prints them.  Paired input likewise: mates are paired and their
+// records printed on the device (BatchAligner::executePairedFlatSam), or the pair records come down and
+// BatchPairedFileWriter formats them (the paired writers refuse the tag emulation).  The bytes are the same.
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_align.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
@@ -19,24 +19,25 @@ typedef libMS::ContainerVector<std::shared_ptr<NucSeq>> ReadVec;
 
 int main( int argc, char** argv )
 {
-    bool bHostSam = false;
+    bool bHostSam = false, bNgmlrTags = false;
     for( int i = 1; i < argc; i++ )
-        if( std::string( argv[ i ] ) == "--host-sam" )
+        if( std::string( argv[ i ] ) == "--host-sam" || std::string( argv[ i ] ) == "--ngmlr-tags" )
         {
-            bHostSam = true;
+            ( std::string( argv[ i ] ) == "--host-sam" ? bHostSam : bNgmlrTags ) = true;
             for( int j = i; j + 1 < argc; j++ )
                 argv[ j ] = argv[ j + 1 ];
             argc--, i--;
         }
     if( argc < 4 )
     {
-        fprintf( stderr, "usage: ma_align [--host-sam] <genome.fa | index prefix> <reads> <out.sam|stdout> [preset] [mates]\n" );
+        fprintf( stderr, "usage: ma_align [--host-sam] [--ngmlr-tags] <genome.fa | index prefix> <reads> <out.sam|stdout> [preset] [mates]\n" );
         return 2;
     }
     try
     {
         ParameterSetManager xParams;
         xParams.setSelected( argc >= 5 ? argv[ 4 ] : ( argc >= 6 ? "illuminapaired" : "default" ) );
+        xParams.xSam.bEmulateNgmlrTags = bNgmlrTags;
         const bool bPaired = argc >= 6;
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
@@ -100,7 +101,7 @@ int main( int argc, char** argv )
             // the flat paired path: mates paired on the device, and -- where the device serves the options -- printed there
             // (ma_pair_sam_batch), one write per device batch; else SAM text straight from the pair records (with "Detect Small
             // Inversions" executePairedFlat itself goes through containers); the bytes are PairedFileWriter's
-            const bool bDeviceSam = xAligner.servesSam( ) && !bHostSam;
+            const bool bDeviceSam = xAligner.servesPairSam( ) && !bHostSam;
             BatchPairedFileWriter xWriter( xParams, std::make_shared<PairedFileWriter>( xParams, std::string( argv[ 3 ] ), pPack ), pPack );
             while( true )
             {

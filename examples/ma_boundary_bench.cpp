@@ -236,7 +236,7 @@ int main( int argc, char** argv )
 {
     if( argc < 6 )
     {
-        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | sam [repeats]]\n" );
+        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | sam [repeats] | sam-tags [repeats]]\n" );
         return 2;
     }
     try
@@ -247,7 +247,7 @@ int main( int argc, char** argv )
         maCheck( ma_set_device( atoi( argv[ 5 ] ) ) );
         maCheck( ma_host_bind_thread( atoi( argv[ 5 ] ), 0, nullptr ) ); // this thread and all it starts: the CPUs next to the GPU
         const unsigned uiHw = std::max( 1u, std::thread::hardware_concurrency( ) );
-        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "sam" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
+        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         double t0 = now( );
@@ -400,14 +400,22 @@ int main( int argc, char** argv )
             }
             pReads->push_back( pQ );
         }
+        const bool bSamTags = argc >= 7 && !strcmp( argv[ 6 ], "sam-tags" );
+        if( bSamTags ) // "Emulate NGMLR's tag output": the host writer reads the reference's bases from a host copy of the pack
+        {
+            xParams.xSam.bEmulateNgmlrTags = true;
+            pPack->vPacHost.assign( vPac.begin( ), vPac.end( ) );
+        }
         std::vector<uint8_t>( ).swap( vPac );
-        if( argc >= 7 && !strcmp( argv[ 6 ], "sam" ) )
+        if( argc >= 7 && ( !strcmp( argv[ 6 ], "sam" ) || bSamTags ) )
         {
             // ---- the SAM leg: n single-end reads host to host INCLUDING SAM text through (a) BatchAligner::executeFlat +
             // BatchFileWriter -- records downloaded, formatted by up to 16 host threads -- and (b) executeFlatSam -- formatted on
             // the device, the text is what comes down; alternating, <repeats> times each after one warm-up of each.  The phase
             // sums of the last repeat of each (AlignerTiming; d2h of (b) holds ma_sam_batch and the text download) are the
-            // step timeline.
+            // step timeline.  sam-tags: the same reads and repeats with the NGMLR tag emulation -- (a) is then the per-read
+            // FileWriter on Alignment containers (BatchFileWriter's path for the option), (b) ma_sam_batch with
+            // MA_SAM_NGMLR_TAGS.
             const int iRepeats = argc >= 8 ? std::max( 1, atoi( argv[ 7 ] ) ) : 5;
             BatchAligner xAligner( xParams );
             xAligner.uiBatchReads = std::min<size_t>( pReads->size( ), 1u << 18 );
@@ -465,11 +473,11 @@ int main( int argc, char** argv )
                           rT.fD2H, fWriter );
                 return std::string( buf );
             };
-            printf( "{\"sam\": {\"reads\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_reads\": %zu, \"in_flight\": 3, "
+            printf( "{\"%s\": {\"reads\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_reads\": %zu, \"in_flight\": 3, "
                     "\"format_threads\": %u, \"execute_flat_plus_writer_reads_per_s\": %s, \"execute_flat_sam_reads_per_s\": %s, "
                     "\"sam_bytes_host\": %llu, \"sam_bytes_device\": %llu, \"record_bytes\": %llu, \"phases_host\": %s, "
                     "\"phases_device\": %s}}\n",
-                    n, uiLen, iRepeats, xAligner.uiBatchReads, std::min( 16u, uiHw ), list( vH ).c_str( ), list( vD ).c_str( ),
+                    bSamTags ? "sam_tags" : "sam", n, uiLen, iRepeats, xAligner.uiBatchReads, std::min( 16u, uiHw ), list( vH ).c_str( ), list( vD ).c_str( ),
                     (unsigned long long)uiBytesHost, (unsigned long long)uiBytesDevice, (unsigned long long)uiRecordBytes,
                     phases( xHost, fWriterHost ).c_str( ), phases( xDevice, fWriterDevice ).c_str( ) );
             return uiBytesHost == uiBytesDevice ? 0 : 1;

@@ -298,10 +298,17 @@ int ma_batch_start_pair_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, m
  * makes of the downloaded MappingQuality records), formatted by two kernels and downloaded as ONE text instead of records and
  * ops: per alignment of a read's MappingQuality list one record with Alignment::getSamFlag / getSamPosition / cigarString /
  * getQuerySequence (alignment.h:367-467, 576-623), the CG:B:I tag of cigars from 0x10000 ops on (TagGenerator, fileWriter.h:
- * 327-357), the unmapped record (fileWriter.cpp:126-140) for a read without a printed alignment.  The paired writer is the
- * block below; the NGMLR tag emulation stays on the host.
+ * 327-357), the unmapped record (fileWriter.cpp:126-140) for a read without a printed alignment.  With MA_SAM_NGMLR_TAGS every
+ * record also carries the tags of "Emulate NGMLR's tag output" (TagGenerator::computeTag, fileWriter.h:120-326): MD SV AS NM
+ * XI XE XR CV SA QS QE, with the CIGAR column M-style and the insertion / deletion pairs of reverse-strand records swapped as
+ * the reference's writer leaves them (fileWriter.cpp:27-31); the bases come from the index's packed text, the runs of N from
+ * ma_index_set_holes.  The paired writer is the block below; for paired text the tag emulation stays on the host.
  *   ma_index_set_contig_names    the RNAME strings (Pack::nameOfSequenceWithId, pack.h:1040-1046): contig i's name is
  *                                names[name_off[i] .. name_off[i+1]) (no terminators)
+ *   ma_index_set_holes           the runs of N of the input that random bases replaced (Pack::vAppendSequence, pack.h:630-666;
+ *                                the .amb file): (start, length) on the forward strand, sorted, not overlapping, inside it;
+ *                                read by the NM and SV tags.  Setting again replaces the list; an index without the call has
+ *                                no holes.  Like the names it is set while no batch of the index runs.
  *   ma_batch_set_read_text       QNAME (NucSeq::sName) and QUAL (NucSeq::pxQualityValues / fastaq quality, nucSeq.h:697-709) of
  *                                the batch's reads, after the reads were set: read r's name is names[name_off[r] ..
  *                                name_off[r+1]), qual is NULL (QUAL "*") or holds one character per base in the reads' CSR.
@@ -310,7 +317,11 @@ int ma_batch_start_pair_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, m
  *                                MA_SAM_* (the members of FileWriter's settings it serves).  Waits for the stream with the one
  *                                read-back that sizes the download.  A record that ends beyond its read (possible only through
  *                                ma_batch_set_alignments) fails the call with the reference's text, "Query length is off by
- *                                <n>." or "Index out of range (compCharAt)"; nothing beyond a read is ever touched.
+ *                                <n>." or "Index out of range (compCharAt)"; nothing beyond a read is ever touched.  With
+ *                                MA_SAM_NGMLR_TAGS two more: a record across the two strands or beyond the doubled text fails
+ *                                with the reference's "(vExtractSubsection) Try to extract bridging sequence. This is
+ *                                impossible.", one whose ops do not cover exactly [begin_ref, end_ref) and [begin_q, end_q)
+ *                                with a message that names it; nothing outside [begin_ref, end_ref) of the text is read.
  *   ma_batch_sam_counts          bytes of the text
  *   ma_batch_get_sam             read r's records are text[rec_off[r] .. rec_off[r+1]) (either pointer may be NULL)
  *   ma_batch_start_sam_download  the same without the wait, completed by ma_batch_finish_download (cf.
@@ -321,7 +332,9 @@ int ma_batch_start_pair_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, m
 #define MA_SAM_NO_SECONDARY 4u /* xNoSecondary */
 #define MA_SAM_NO_SUPPLEMENTARY 8u /* xNoSupplementary */
 #define MA_SAM_NO_CG_TAG 16u /* xCGTag off: cigars of 0x10000 ops and more are printed in the CIGAR column */
+#define MA_SAM_NGMLR_TAGS 32u /* xEmulateNgmlrTags (ma_sam_batch only): the tags MD SV AS NM XI XE XR CV SA QS QE */
 int ma_index_set_contig_names( ma_index*, const char* names, const uint64_t* name_off /*n_contigs+1*/ );
+int ma_index_set_holes( ma_index*, const uint64_t* start, const uint64_t* length, uint64_t n );
 int ma_batch_set_read_text( ma_batch*, const char* names, const uint64_t* name_off /*n+1*/, const uint8_t* qual );
 int ma_sam_batch( ma_batch*, uint32_t options );
 int ma_batch_sam_counts( ma_batch*, uint64_t* n_bytes );
@@ -376,6 +389,10 @@ int ma_debug_dp_family_stats( unsigned long long out[ 16 ] );
 /* diagnostics: the device libm the chaining stage decides with (harmonization.h:82-89, ransac.cpp:112,131-135 use
  * glibc's): op 0 tan, 1 sin, 2 atan, 3 log over n doubles (host arrays); tests compare the bits with glibc's */
 int ma_debug_libm( int op, const double* in, uint64_t n, double* out );
+/* diagnostics: the single-precision arithmetic and the "%f" formatter of the XI:f (kind 0: num / den) and CV:f (kind 1:
+ * 100 * num / den) tags of MA_SAM_NGMLR_TAGS as the kernels run them, over n pairs (host arrays); pair i's text goes to
+ * out[16 i ..), padded with NUL (empty where it would not fit); tests compare with printf of the same arithmetic in float */
+int ma_debug_ngmlr_floats( int kind, const uint64_t* num, const uint64_t* den, uint64_t n, char* out /*16 n*/ );
 
 /* ---- synthetic workloads (BASELINE.json configs; deterministic counter-based generators) ---- */
 /* genome: d_codes[total] (device, 1 byte/base). reads sampled from it: device CSR. */

@@ -88,6 +88,7 @@ def _ptr(a, t=C.c_void_p):
 
 
 SAM_SOFT_CLIP, SAM_EQX_CIGAR, SAM_NO_SECONDARY, SAM_NO_SUPPLEMENTARY, SAM_NO_CG_TAG = 1, 2, 4, 8, 16  # MA_SAM_*
+SAM_NGMLR_TAGS = 32  # (Batch.sam only)
 
 
 def _csr_text(strings):
@@ -97,6 +98,18 @@ def _csr_text(strings):
     if bs:
         off[1:] = np.cumsum([len(x) for x in bs])
     return np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8).copy(), off
+
+
+def debug_ngmlr_floats(kind, num, den):
+    """diagnostics (ma_debug_ngmlr_floats): the texts of the XI:f (kind 0: num / den) or CV:f (kind 1: 100 * num / den) tags as
+    the device computes and prints them, a list of bytes"""
+    num = np.ascontiguousarray(num, dtype=np.uint64)
+    den = np.ascontiguousarray(den, dtype=np.uint64)
+    if len(num) != len(den):
+        raise MaError("debug_ngmlr_floats: %d numerators for %d denominators" % (len(num), len(den)))
+    out = np.zeros((len(num), 16), dtype=np.uint8)
+    _chk(lib().ma_debug_ngmlr_floats(C.c_int(kind), _ptr(num), _ptr(den), C.c_uint64(len(num)), _ptr(out)))
+    return out.view("S16").ravel()
 
 
 def device_count():
@@ -260,6 +273,15 @@ class Index:
         """The RNAME strings of the SAM text (ma_index_set_contig_names): one str / bytes per contig."""
         cat, off = _csr_text(names)
         _chk(lib().ma_index_set_contig_names(self.h, _ptr(cat), _ptr(off)))
+
+    def set_holes(self, starts, lens):
+        """The runs of N of the forward strand that random bases replaced (ma_index_set_holes), read by the NM and SV tags of
+        Batch.sam(SAM_NGMLR_TAGS | ...): sorted, not overlapping; setting again replaces the list."""
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        ln = np.ascontiguousarray(lens, dtype=np.uint64)
+        if len(st) != len(ln):
+            raise MaError("set_holes: %d starts for %d lengths" % (len(st), len(ln)))
+        _chk(lib().ma_index_set_holes(self.h, _ptr(st), _ptr(ln), C.c_uint64(len(st))))
 
     def close(self):
         if self.h:
@@ -545,8 +567,9 @@ class Batch:
         _chk(lib().ma_batch_set_read_text(self.h, _ptr(cat), _ptr(off), _ptr(q)))
 
     def sam(self, options=0):
-        """FileWriter::execute for every read on the device, after align() / dp() / set_alignments(); options = SAM_* bits.
-        Returns the bytes of the text."""
+        """FileWriter::execute for every read on the device, after align() / dp() / set_alignments(); options = SAM_* bits,
+        SAM_NGMLR_TAGS (the NGMLR tag emulation; the runs of N come from Index.set_holes) among them.  Returns the bytes of
+        the text."""
         _chk(lib().ma_sam_batch(self.h, C.c_uint32(options)))
         return self.sam_bytes()
 

@@ -101,6 +101,8 @@ struct ma_index
     ma::DevBuf bwt, sa, saDense, kmerTab, pac, cstart, clen;
     ma::DevBuf cnames, cnameOff; // RNAME strings (ma_index_set_contig_names), CSR
     bool namesSet = false;
+    ma::DevBuf holeStart, holeLen; // runs of N of the forward strand (ma_index_set_holes), sorted; none without the call
+    uint64_t nHoles = 0;
     uint64_t n_words = 0, n_sa = 0;
     std::vector<uint64_t> h_cstart, h_clen;
     int device = 0;

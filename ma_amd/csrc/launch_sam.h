@@ -27,6 +27,7 @@ SamKernelArgs sam_args( ma_batch* b, u32 options )
     A.names = b->txtNames.as<char>( );
     A.name_off = b->txtNameOff.as<u64>( );
     A.qual = b->txtHasQual ? b->txtQual.as<uint8_t>( ) : nullptr;
+    A.ref = ma_sam::Ref{ x->v.pac, x->holeStart.as<u64>( ), x->holeLen.as<u64>( ), x->nHoles, x->v.F };
     return A;
 }
 
@@ -52,6 +53,28 @@ int sam_fail( ma_batch* b, u64 slot )
     ma_sam::errorText( text, rev ? ma_sam::ERR_COMP_CHAR_AT : ma_sam::ERR_QUERY_LENGTH,
                        (i64)( roff[ r + 1 ] - roff[ r ] ) - (i64)h.end_q );
     return fail( text );
+}
+
+// the same for a text with tags: key = slot * 4 + kind - 1 (SamTagCountSink).  The two kinds of the tags: the reference's text for
+// a record across the strands, the library's own -- naming the record -- for ops that do not cover the record's intervals
+int sam_tag_fail( ma_batch* b, u64 key )
+{
+    const u64 slot = key >> 2;
+    const u32 kind = (u32)( key & 3 ) + 1;
+    if( kind == ma_sam::ERR_QUERY_LENGTH || kind == ma_sam::ERR_COMP_CHAR_AT )
+        return sam_fail( b, slot );
+    char text[ 96 ];
+    ma_sam::errorText( text, kind, 0 );
+    if( kind == ma_sam::ERR_BRIDGING )
+        return fail( text );
+    const u64 n = b->n_reads;
+    std::vector<u64> hoff( n + 1 );
+    MA_HIP( hipMemcpyAsync( hoff.data( ), b->hsetOff.p, ( n + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
+    if( batch_wait( b ) )
+        return 1;
+    const u64 r = (u64)( std::upper_bound( hoff.begin( ), hoff.end( ), slot ) - hoff.begin( ) ) - 1;
+    return fail( "ma_sam_batch: record " + std::to_string( slot - hoff[ r ] ) + " of read " + std::to_string( r ) + ": " + text +
+                 " (MA_SAM_NGMLR_TAGS reads the reference along them)" );
 }
 
 PairSamKernelArgs pair_sam_args( ma_batch* b, u32 options )
@@ -175,6 +198,48 @@ int ma_index_set_contig_names( ma_index* x, const char* names, const uint64_t* n
     return 0;
 }
 
+int ma_index_set_holes( ma_index* x, const uint64_t* start, const uint64_t* length, uint64_t n )
+{
+    if( !x || ( n && ( !start || !length ) ) )
+        return fail( "ma_index_set_holes: null argument" );
+    for( u64 i = 0; i < n; i++ )
+    {
+        if( length[ i ] == 0 || start[ i ] >= x->v.F || length[ i ] > x->v.F - start[ i ] )
+            return fail( "ma_index_set_holes: hole " + std::to_string( i ) + " is empty or not inside the forward strand" );
+        if( i && start[ i ] < start[ i - 1 ] + length[ i - 1 ] )
+            return fail( "ma_index_set_holes: hole " + std::to_string( i ) + " starts before the one before it ends (sorted, not overlapping)" );
+    }
+    MA_BIND_DEVICE( x->device );
+    x->nHoles = 0;
+    if( n )
+    {
+        if( x->holeStart.reserve( n * 8 ) || x->holeLen.reserve( n * 8 ) )
+            return 1;
+        MA_HIP( hipMemcpy( x->holeStart.p, start, n * 8, hipMemcpyHostToDevice ) );
+        MA_HIP( hipMemcpy( x->holeLen.p, length, n * 8, hipMemcpyHostToDevice ) );
+    }
+    x->nHoles = n;
+    return 0;
+}
+
+int ma_debug_ngmlr_floats( int kind, const uint64_t* num, const uint64_t* den, uint64_t n, char* out )
+{
+    if( !num || !den || !out || kind < 0 || kind > 1 )
+        return fail( "ma_debug_ngmlr_floats: bad argument" );
+    if( n == 0 )
+        return 0;
+    DevBuf dn, dd, dout;
+    if( dn.reserve( n * 8 ) || dd.reserve( n * 8 ) || dout.reserve( n * 16 ) )
+        return 1;
+    MA_HIP( hipMemcpy( dn.p, num, n * 8, hipMemcpyHostToDevice ) );
+    MA_HIP( hipMemcpy( dd.p, den, n * 8, hipMemcpyHostToDevice ) );
+    hipLaunchKernelGGL( k_ngmlr_float_probe, dim3( (unsigned)( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, 0, kind, dn.as<u64>( ), dd.as<u64>( ), n,
+                        dout.as<char>( ) );
+    MA_HIP( hipGetLastError( ) );
+    MA_HIP( hipMemcpy( out, dout.p, n * 16, hipMemcpyDeviceToHost ) );
+    return 0;
+}
+
 int ma_batch_set_read_text( ma_batch* b, const char* names, const uint64_t* name_off, const uint8_t* qual )
 {
     if( !b || !b->d_roff || !name_off )
@@ -214,7 +279,9 @@ int ma_sam_batch( ma_batch* b, uint32_t options )
     if( !b->txtSet )
         return fail( "ma_sam_batch: the reads have no names (ma_batch_set_read_text after the reads were set)" );
     MA_BIND_DEVICE( b->device );
-    return sam_text_launch<SamKernelArgs, k_sam_size, k_sam_write, sam_fail>( b, b->sam, b->n_reads, sam_args( b, options ) );
+    if( options & ma_sam::NGMLR_TAGS )
+        return sam_text_launch<SamKernelArgs, k_sam_size<true>, k_sam_write<true>, sam_tag_fail>( b, b->sam, b->n_reads, sam_args( b, options ) );
+    return sam_text_launch<SamKernelArgs, k_sam_size<false>, k_sam_write<false>, sam_fail>( b, b->sam, b->n_reads, sam_args( b, options ) );
 }
 
 int ma_pair_sam_batch( ma_batch* b, uint32_t options )
@@ -223,8 +290,8 @@ int ma_pair_sam_batch( ma_batch* b, uint32_t options )
         return fail( "ma_pair_sam_batch: null batch" );
     if( b->stage_done < 5 )
         return fail( "ma_pair_sam_batch: no pairs to print (run ma_pair_batch first)" );
-    if( options & ~(uint32_t)ma_sam::ALL_OPTIONS )
-        return fail( "ma_pair_sam_batch: unknown option bits " + std::to_string( options & ~(uint32_t)ma_sam::ALL_OPTIONS ) );
+    if( options & ~(uint32_t)ma_sam::PAIR_OPTIONS ) // (the tag emulation is the single-end writer's)
+        return fail( "ma_pair_sam_batch: unknown option bits " + std::to_string( options & ~(uint32_t)ma_sam::PAIR_OPTIONS ) );
     if( !b->idx->namesSet )
         return fail( "ma_pair_sam_batch: the index has no contig names (ma_index_set_contig_names)" );
     if( !b->txtSet )

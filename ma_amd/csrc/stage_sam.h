@@ -8,6 +8,10 @@
 //                the tabs, a CG tag -- and notes where SEQ goes; (2) all 64 lanes walk the records of the 64 reads together and
 //                copy SEQ (code -> letter, reverse-complemented on the reverse strand) and QUAL with lanes striding over
 //                bytes: coalesced stores for the ~80 % of a short read's record that these two columns are.
+// Both kernels are templates over Tags: with MA_SAM_NGMLR_TAGS the read's lane also writes the tags (ma_sam::putNgmlrTags: MD SV
+// AS NM XI XE XR CV SA QS QE) in phase (1), behind the place it leaves for QUAL, reading the reference's bases from the index's
+// pac and the runs of N from the index's holes (ma_index_set_holes); phase (2) is the same.  The instantiations without tags
+// hold the code they held before there were tags.
 // No arrays indexed at run time, decimal numbers by digit count (ma_sam::WriteSink::number).
 
 // the MappingQuality list of one read as a list of ma_sam_dev.h
@@ -24,7 +28,7 @@ struct SamDevList
     __device__ __forceinline__ ma_sam::Rec rec( u32 k ) const
     {
         const AlnHeader& h = hdr[ order[ k ] ];
-        return ma_sam::Rec{ h.begin_ref, h.end_ref, h.begin_q, h.end_q, h.n_ops, h.secondary, h.supplementary, h.mapq };
+        return ma_sam::Rec{ h.begin_ref, h.end_ref, h.begin_q, h.end_q, h.n_ops, h.secondary, h.supplementary, h.mapq, h.score };
     }
     __device__ __forceinline__ u64 opType( u32 k, u32 j ) const
     {
@@ -40,7 +44,8 @@ enum : int // the statistics of a SAM text, of this stage and of stage_pair_sam.
 {
     SAM_STAT_BYTES = 0, // bytes of the batch's text (the launcher copies the scan's last offset here)
     SAM_STAT_ERRORS = 1, // records that end beyond their read (paired: their mate)
-    SAM_STAT_FIRST = 2, // the first of them in the batch's order, as the stage's count sink writes it
+    SAM_STAT_FIRST = 2, // the first of them in the batch's order, as the stage's count sink writes it (with tags: the slot times
+                        // 4 plus the error's kind less one, so that the first kind of the first record is kept)
     SAM_STAT_COUNT = 4
 };
 
@@ -64,6 +69,7 @@ struct SamKernelArgs
     u64* seq_pos; // per slot hset_off[ r ] + k: where SEQ of record k starts in the text, ~0 for a record that is not printed
     char* text;
     unsigned long long* stat;
+    ma_sam::Ref ref; // the tags' reference bases and holes: the index's pac, its holes, the forward strand's size
 };
 
 __device__ __forceinline__ SamDevList sam_list( const SamKernelArgs& A, u32 r )
@@ -91,17 +97,40 @@ struct SamCountSink : ma_sam::CountSink
     }
 };
 
-__global__ void __launch_bounds__( 256 ) k_sam_size( SamKernelArgs A )
+// the same for records with tags, which can fail in four ways: slot and kind go into SAM_STAT_FIRST together
+struct SamTagCountSink : ma_sam::CountSink
+{
+    unsigned long long* stat;
+    u64 slot0;
+    __device__ __forceinline__ void error( u32 kind, i64, u32 k )
+    {
+        atomicAdd( &stat[ SAM_STAT_ERRORS ], 1ull );
+        atomicMin( &stat[ SAM_STAT_FIRST ], (unsigned long long)( ( ( slot0 + k ) << 2 ) | ( kind - 1 ) ) );
+    }
+};
+
+template <bool Tags> __global__ void __launch_bounds__( 256 ) k_sam_size( SamKernelArgs A )
 {
     const u32 r = blockIdx.x * 256 + threadIdx.x;
     if( r >= A.n_reads )
         return;
     const SamDevList l = sam_list( A, r );
-    SamCountSink s;
-    s.stat = A.stat;
-    s.slot0 = l.n ? A.hset_off[ r ] : 0;
-    ma_sam::formatRead( s, A.options, A.contigs, sam_read( A, r ), l );
-    A.cnt[ r ] = s.n;
+    if constexpr( Tags )
+    {
+        SamTagCountSink s;
+        s.stat = A.stat;
+        s.slot0 = l.n ? A.hset_off[ r ] : 0;
+        ma_sam::formatRead( s, A.options, A.contigs, sam_read( A, r ), l, A.ref );
+        A.cnt[ r ] = s.n;
+    }
+    else
+    {
+        SamCountSink s;
+        s.stat = A.stat;
+        s.slot0 = l.n ? A.hset_off[ r ] : 0;
+        ma_sam::formatRead( s, A.options, A.contigs, sam_read( A, r ), l );
+        A.cnt[ r ] = s.n;
+    }
 }
 
 // the short columns: everything but the bytes of SEQ and QUAL, whose places are noted for the wavefront
@@ -145,7 +174,7 @@ __device__ __forceinline__ u64 sam_bcast( u64 v, u32 src )
     return ( (u64)(u32)__shfl( (int)( v >> 32 ), (int)src, 64 ) << 32 ) | (u32)__shfl( (int)(u32)v, (int)src, 64 );
 }
 
-__global__ void __launch_bounds__( 256 ) k_sam_write( SamKernelArgs A )
+template <bool Tags> __global__ void __launch_bounds__( 256 ) k_sam_write( SamKernelArgs A )
 {
     const u32 lane = threadIdx.x & 63;
     const u32 r0 = blockIdx.x * 256 + ( threadIdx.x & ~63u ); // first read of this wavefront
@@ -165,7 +194,10 @@ __global__ void __launch_bounds__( 256 ) k_sam_write( SamKernelArgs A )
         s.unmapped_seq = ~0ull;
         for( u32 k = 0; k < c; k++ )
             s.seq_pos[ k ] = ~0ull;
-        ma_sam::formatRead( s, A.options, A.contigs, sam_read( A, r ), l );
+        if constexpr( Tags )
+            ma_sam::formatRead( s, A.options, A.contigs, sam_read( A, r ), l, A.ref );
+        else
+            ma_sam::formatRead( s, A.options, A.contigs, sam_read( A, r ), l );
         unm = s.unmapped_seq;
     }
     // seq_pos was written by other lanes of this wavefront.  The fence orders the stores before the loads below; that the
@@ -202,4 +234,21 @@ __global__ void __launch_bounds__( 256 ) k_sam_write( SamKernelArgs A )
             sam_copy_record( A.text + outT, pos, codes, qual, from, to, h.begin_ref >= F, h.begin_q, qto, lane );
         }
     }
+}
+
+// ---- diagnostics: the tags' XI (kind 0: num / den) or CV (kind 1: 100 * num / den) arithmetic and "%f" formatter as the
+// kernels run them (ma_sam::putRatio), one pair per lane into a 0-padded slot of 16 bytes.  A text that would not fit its slot
+// (a quotient of 10^8 and more) leaves the slot empty.
+__global__ void __launch_bounds__( 256 ) k_ngmlr_float_probe( int kind, const u64* num, const u64* den, u64 n, char* out )
+{
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if( i >= n )
+        return;
+    ma_sam::CountSink c;
+    ma_sam::detail::putRatio( c, kind != 0, num[ i ], den[ i ] );
+    ma_sam::WriteSink w{ out + 16 * i };
+    if( c.n <= 15 )
+        ma_sam::detail::putRatio( w, kind != 0, num[ i ], den[ i ] );
+    for( u64 j = w.n; j < 16; j++ )
+        out[ 16 * i + j ] = 0;
 }

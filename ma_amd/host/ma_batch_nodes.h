@@ -279,8 +279,10 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
             execute( pReads, pView, pPack );
             return;
         }
-        if( pPerRead->xOptions.bEmulateNgmlrTags )
+        if( pPerRead->xOptions.bEmulateNgmlrTags && !( rBatch.samOptions( ) & MA_SAM_NGMLR_TAGS ) )
             throw std::runtime_error( "BatchFileWriter: device text carries no NGMLR tags" );
+        if( !pPerRead->xOptions.bEmulateNgmlrTags && ( rBatch.samOptions( ) & MA_SAM_NGMLR_TAGS ) )
+            throw std::runtime_error( "BatchFileWriter: device text carries NGMLR tags the writer's options do not ask for" );
         {
             std::lock_guard<std::mutex> xGuard( *pPerRead->pLock );
             pPerRead->pOut->write( rBatch.samText( ), rBatch.samBytes( ) );

@@ -217,6 +217,7 @@ struct BatchResult
     // PAIRS, what PairedFileWriter::execute prints: pair k's records are vSam[ vSamOff[k] .. vSamOff[k+1] ), and there are no pair
     // records.
     bool bSam = false;
+    uint32_t uiSamOptions = 0; // the MA_SAM_* bits the text was made with (bSam)
     HostBuf<uint64_t> vSamOff; // uiReads + 1 (pairs: uiReads / 2 + 1)
     HostBuf<char> vSam;
     uint64_t uiSamBytes = 0;
@@ -408,6 +409,7 @@ class Engine
         R.bSocQueues = false;
         R.bPairs = bPairs;
         R.bSam = pSam != nullptr;
+        R.uiSamOptions = pSam != nullptr ? pSam->uiOptions : 0;
         R.uiSamBytes = 0;
         R.fPack = 0;
         fit( n, pOff[ n ] );

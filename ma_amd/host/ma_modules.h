@@ -1463,6 +1463,10 @@ class AlignedBatch : public libMS::Container
     {
         return pResult->uiSamBytes;
     }
+    uint32_t samOptions( ) const // the MA_SAM_* bits the text was made with
+    {
+        return pResult->uiSamOptions;
+    }
     std::shared_ptr<AlignmentVector> alignmentsOf( size_t uiRead ) const
     {
         auto pV = std::make_shared<AlignmentVector>( );
@@ -1769,20 +1773,26 @@ class BatchAligner
         return runFlatOn( vIndices, pQueries, pPerIndex, false, nullptr );
     }
 
-    // The MA_SAM_* bits of ma_sam_batch for the writer's options.  The NGMLR tag emulation needs reference bases and Alignment
-    // objects and is not served by the device: servesSam( ) is false for it (and for "Detect Small Inversions", which needs
-    // containers before the records are final).
+    // The MA_SAM_* bits of ma_sam_batch for the writer's options.  The device serves the single-end text with every option, the
+    // NGMLR tag emulation included (MA_SAM_NGMLR_TAGS: the bases come from the index, the holes from the pack), but not with
+    // "Detect Small Inversions", which needs containers before the records are final: servesSam( ).  The paired text is not
+    // served with the tag emulation either (PairedFileWriter refuses it): servesPairSam( ).
     static uint32_t samOptionBits( const SamOptions& rO )
     {
         return ( rO.bSoftClip ? MA_SAM_SOFT_CLIP : 0u ) | ( rO.bOutputMCigar ? 0u : MA_SAM_EQX_CIGAR ) |
                ( rO.bNoSecondary ? MA_SAM_NO_SECONDARY : 0u ) | ( rO.bNoSupplementary ? MA_SAM_NO_SUPPLEMENTARY : 0u ) |
-               ( rO.bCGTag ? 0u : MA_SAM_NO_CG_TAG );
+               ( rO.bCGTag ? 0u : MA_SAM_NO_CG_TAG ) | ( rO.bEmulateNgmlrTags ? MA_SAM_NGMLR_TAGS : 0u );
     }
     bool servesSam( ) const
     {
+        return !xP.search_inversions;
+    }
+    bool servesPairSam( ) const
+    {
         return !xP.search_inversions && !xParams.xSam.bEmulateNgmlrTags;
     }
-    // RNAME strings of pPack on an index and its replicas (ma_index_set_contig_names)
+    // RNAME strings and holes (Pack::vHoles, read by the NGMLR tags) of pPack on an index and its replicas
+    // (ma_index_set_contig_names, ma_index_set_holes)
     static void nameContigs( const DeviceIndex& rDev, const Pack& rPack )
     {
         std::string sNames;
@@ -1797,9 +1807,19 @@ class BatchAligner
         if( (size_t)nContigs != rPack.vNames.size( ) )
             throw std::runtime_error( "BatchAligner::executeFlatSam: the pack names " + std::to_string( rPack.vNames.size( ) ) +
                                       " contigs, the index holds " + std::to_string( nContigs ) );
+        std::vector<uint64_t> vHoleStart, vHoleLength;
+        for( const auto& rHole : rPack.vHoles )
+        {
+            vHoleStart.push_back( rHole.first );
+            vHoleLength.push_back( rHole.second );
+        }
         maCheck( ma_index_set_contig_names( rDev.p, sNames.data( ), vOff.data( ) ) );
+        maCheck( ma_index_set_holes( rDev.p, vHoleStart.data( ), vHoleLength.data( ), vHoleStart.size( ) ) );
         for( const auto& pR : rDev.vReplicas )
+        {
             maCheck( ma_index_set_contig_names( pR->p, sNames.data( ), vOff.data( ) ) );
+            maCheck( ma_index_set_holes( pR->p, vHoleStart.data( ), vHoleLength.data( ), vHoleStart.size( ) ) );
+        }
     }
 
     // executeFlat with the SAM records formatted on the DEVICE (ma_sam_batch): one AlignedBatch per device batch, in input
@@ -1817,8 +1837,7 @@ class BatchAligner
                                                std::vector<AlignerTiming>* pPerIndex )
     {
         if( !servesSam( ) )
-            throw std::runtime_error( "BatchAligner::executeFlatSam: not with 'Detect Small Inversions' or the NGMLR tag emulation "
-                                      "(use executeFlat and BatchFileWriter)" );
+            throw std::runtime_error( "BatchAligner::executeFlatSam: not with 'Detect Small Inversions' (use executeFlat and BatchFileWriter)" );
         const uint32_t uiOptions = samOptionBits( xParams.xSam );
         return runFlatOn( vIndices, pQueries, pPerIndex, false, &uiOptions );
     }
@@ -1892,7 +1911,7 @@ class BatchAligner
     {
         if( vMates->size( ) % 2 )
             throw std::runtime_error( "BatchAligner::executePairedFlatSam: odd number of reads" );
-        if( !servesSam( ) )
+        if( !servesPairSam( ) )
             throw std::runtime_error( "BatchAligner::executePairedFlatSam: not with 'Detect Small Inversions' or the NGMLR tag emulation "
                                       "(use executePairedFlat and BatchPairedFileWriter)" );
         const uint32_t uiOptions = samOptionBits( xParams.xSam );

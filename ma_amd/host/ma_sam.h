@@ -2,9 +2,10 @@
 // FileReader with the reference's name,
 // Module signature, constructors, options and output bytes (libs/ma/inc/ma/module/fileWriter.h:21-78,364-440,
 // libs/ma/src/module/fileWriter.cpp:11-158), plus the Alignment / Pack / NucSeq string helpers it calls
-// (alignment.h:367-467,576-623; pack.h:900-997,1063-1067; nucSeq.h:558-713).  Pure host code: SAM text is
-// formatting of what the device path produced, there is nothing here to put on the GPU.
-// Not implemented: the NGMLR tag emulation ("Emulate NGMLR's tag output", off by default) -- requesting it throws.
+// (alignment.h:367-467,576-623; pack.h:900-997,1063-1067; nucSeq.h:558-713).  Pure host code, on Alignment containers; the
+// same bytes formatted on the device are ma_sam_batch's (ma_sam_dev.h), for which this file is the yardstick.
+// The NGMLR tag emulation ("Emulate NGMLR's tag output", off by default) is implemented for FileWriter (sam::ngmlrTags);
+// PairedFileWriter refuses it.
 #pragma once
 #include "ma_modules.h"
 

@@ -6,6 +6,10 @@
 //   - the CPU tests (tests/emul/sam_dev_test.cpp, sam_pair_dev_test.cpp) run the same functions on the host and pin them, byte
 //     for byte, to flat::formatRead / flat::formatPair and to the SAM goldens the compiled reference wrote;
 //   - libma_amd.so words the error of a bad record with errorText( ).
+// With NGMLR_TAGS (single-end only) a record also carries the tags of the reference's "Emulate NGMLR's tag output"
+// (TagGenerator::computeTag, fileWriter.h:120-326): MD SV AS NM XI XE XR CV SA QS QE, byte for byte what ma_amd::FileWriter
+// (ma_sam.h: sam::ngmlrTags, FileWriter::execute) prints, which is the yardstick of tests/emul/sam_tags_dev_test.cpp.  They
+// need the reference's bases and its runs of N: a Ref (below), handed to formatRead( sink, options, contigs, read, list, ref ).
 // No reference headers, no containers, no strings: include/ma_amd.h only.  ma_flat_sam.h stays the yardstick and documents
 // where each oddity comes from; they are kept as they are:
 //   position one further on the reverse strand; MAPQ = (int)ceil( mapq * 254 ), 255 for NaN; the cigar walked backwards on the
@@ -46,12 +50,18 @@ enum : uint32_t // == MA_SAM_* of include/ma_amd.h
     NO_SECONDARY = 4u,
     NO_SUPPLEMENTARY = 8u,
     NO_CG_TAG = 16u, // over-long cigars are printed as they are
-    ALL_OPTIONS = 31u
+    NGMLR_TAGS = 32u, // the NGMLR tag emulation (single-end records only); the CIGAR column is M-style then
+    PAIR_OPTIONS = 31u, // what formatPair serves
+    ALL_OPTIONS = 63u
 };
 enum : uint32_t
 {
     ERR_QUERY_LENGTH = 1u, // "Query length is off by <value>." (forward strand, end_q beyond the read; fileWriter.cpp:106)
-    ERR_COMP_CHAR_AT = 2u // "Index out of range (compCharAt)" (reverse strand, the same)
+    ERR_COMP_CHAR_AT = 2u, // "Index out of range (compCharAt)" (reverse strand, the same)
+    // with NGMLR_TAGS only:
+    ERR_BRIDGING = 3u, // [begin_ref, end_ref) lies on both strands or ends beyond the doubled text (pack.h:1238-1330)
+    ERR_OPS_COVERAGE = 4u // the ops do not cover exactly [begin_ref, end_ref) and [begin_q, end_q): the host formatter would read
+                          // outside its buffer, the library refuses the record
 };
 enum : uint32_t
 {
@@ -101,7 +111,56 @@ struct Rec
     uint64_t begin_ref, end_ref, begin_q, end_q;
     uint32_t n_ops, secondary, supplementary;
     double mapq;
+    int64_t score = 0; // (read by the tags only)
 };
+// Reference bases and runs of N for the tags.  pac: the forward strand, 2 bits per base, first base in the top bits (Pack's
+// packed text, the index's pac); holes: Pack::vHoles, (start, length) on the forward strand, sorted and not overlapping.
+struct Ref
+{
+    const uint8_t* pac;
+    const uint64_t* hole_start;
+    const uint64_t* hole_len;
+    uint64_t n_holes;
+    uint64_t forward; // size of the forward strand
+    // base of position p of the doubled text (referenceCodes of ma_sam.h without hole marking: the random base that replaced an N)
+    MA_SAM_HD uint8_t code( uint64_t p ) const
+    {
+        const bool bRev = p >= forward;
+        const uint64_t a = bRev ? 2 * forward - 1 - p : p;
+        const uint8_t b = (uint8_t)( ( pac[ a >> 2 ] >> ( ( ~a & 3 ) << 1 ) ) & 3 );
+        return bRev ? (uint8_t)( 3 - b ) : b;
+    }
+    // bases of the raw interval [a, b) that lie inside holes: a binary search for the first hole that ends behind a, then
+    // the holes that start before b (0 for a > b)
+    MA_SAM_HD uint64_t holeBases( uint64_t a, uint64_t b ) const
+    {
+        if( a >= b )
+            return 0;
+        uint64_t lo = 0, hi = n_holes;
+        while( lo < hi )
+        {
+            const uint64_t mid = lo + ( hi - lo ) / 2;
+            if( hole_start[ mid ] + hole_len[ mid ] > a )
+                hi = mid;
+            else
+                lo = mid + 1;
+        }
+        uint64_t uiSum = 0;
+        for( ; lo < n_holes && hole_start[ lo ] < b; lo++ )
+        {
+            const uint64_t s = hole_start[ lo ] > a ? hole_start[ lo ] : a, e = hole_start[ lo ] + hole_len[ lo ];
+            uiSum += ( e < b ? e : b ) - s;
+        }
+        return uiSum;
+    }
+    // the same for [p, p + n) of the doubled text, which lies on one strand
+    MA_SAM_HD uint64_t holeBasesDoubled( uint64_t p, uint64_t n ) const
+    {
+        return p >= forward ? holeBases( 2 * forward - ( p + n ), 2 * forward - p ) : holeBases( p, p + n );
+    }
+};
+struct NoRef
+{};
 // what a record of a pair has beyond a single read's (flat::detail::RecordExtras); the defaults are a single read's
 struct RecordExtras
 {
@@ -125,7 +184,8 @@ struct FlatList
     MA_SAM_HD Rec rec( uint32_t k ) const
     {
         const ma_alignment& a = alns[ k ];
-        return Rec{ (uint64_t)a.begin_ref, (uint64_t)a.end_ref, (uint64_t)a.begin_q, (uint64_t)a.end_q, a.n_ops, a.secondary, a.supplementary, a.mapq };
+        return Rec{ (uint64_t)a.begin_ref, (uint64_t)a.end_ref, (uint64_t)a.begin_q, (uint64_t)a.end_q, a.n_ops, a.secondary, a.supplementary, a.mapq,
+                    a.score };
     }
     MA_SAM_HD uint64_t opType( uint32_t k, uint32_t j ) const
     {
@@ -315,11 +375,375 @@ MA_SAM_HD bool sameName( const Contigs& rContigs, uint32_t a, uint32_t b ) // by
             return false;
     return true;
 }
-// One record of an aligned read: the eleven columns and the CG tag.  rX: what a mate's record has beyond a single read's
-// (its clip_length is the read's length for a single read).
+// ---- the NGMLR tag emulation -----------------------------------------------------------------------------------------------
+// The ops of record k as FileWriter::execute leaves them behind Alignment::invertSuccessiveInserionAndDeletion
+// (alignment.h:328-345; ma_sam.h): an insertion directly followed by a deletion, or the other way round, swap places, greedily
+// from the left and without overlap (I D I -> D I I, I D I D -> D I D I).  The host mutates the alignment; this is a view, the
+// pool stays as it is.  forward( j ) / backward( j ) give the index of the op that stands at place j, for j running up from 0 /
+// down from n - 1 in steps of one; both are O( n ) over a whole walk (a run of alternating insertions and deletions is
+// measured once, when the backward walk enters it at its end).
+template <class List> struct SwappedOps
+{
+    const List& l;
+    uint32_t k, n;
+    bool swap;
+    bool second = false; // forward: the place at hand is the second of a swapped pair (it shows the pair's first op)
+    bool odd = false; // backward: place j is at an odd distance from its run's start
+    MA_SAM_HD bool pairable( uint32_t i ) const // ops i - 1 and i: an insertion and a deletion, in either order
+    {
+        const uint64_t a = l.opType( k, i - 1 ), b = l.opType( k, i );
+        return ( a == 3 && b == 4 ) || ( a == 4 && b == 3 );
+    }
+    MA_SAM_HD uint32_t forward( uint32_t j )
+    {
+        if( !swap )
+            return j;
+        if( second )
+        {
+            second = false;
+            return j - 1;
+        }
+        if( j + 1 < n && pairable( j + 1 ) )
+        {
+            second = true;
+            return j + 1;
+        }
+        return j;
+    }
+    MA_SAM_HD uint32_t backward( uint32_t j )
+    {
+        if( !swap )
+            return j;
+        const bool bNext = j + 1 < n && pairable( j + 1 ); // place j + 1 belongs to the same run
+        if( bNext )
+            odd = !odd;
+        else
+        {
+            uint32_t r0 = j;
+            while( r0 > 0 && pairable( r0 ) )
+                r0--;
+            odd = ( ( j - r0 ) & 1 ) != 0;
+        }
+        return odd ? j - 1 : bNext ? j + 1 : j;
+    }
+};
+// Alignment::cigarString (alignment.h:367-467) with M for seed / match / missmatch, of record k as the tags print it: the
+// CIGAR column of a record with tags and the cigars of the SA tag; bSwap: the record's ops were swapped before
 template <class Sink, class List>
+MA_SAM_HD void putCigarM( Sink& rOut, const List& rList, uint32_t k, const Rec& rA, bool bRev, bool bSwap, bool bSoftClip, uint64_t uiClipLength )
+{
+    const uint64_t uiLeftOver = rA.end_q < uiClipLength ? uiClipLength - rA.end_q : 0;
+    const uint64_t uiHead = bRev ? uiLeftOver : rA.begin_q, uiTail = bRev ? rA.begin_q : uiLeftOver;
+    const char cClip = bSoftClip ? 'S' : 'H';
+    if( uiHead > 0 )
+        numberAnd( rOut, uiHead, cClip );
+    SwappedOps<List> xOps{ rList, k, rA.n_ops, bSwap && bRev };
+    uint64_t uiRunM = 0;
+    for( uint32_t j = 0; j < rA.n_ops; j++ )
+    {
+        const uint32_t jj = bRev ? xOps.backward( rA.n_ops - 1 - j ) : j;
+        const uint64_t uiType = rList.opType( k, jj ), uiLen = rList.opLen( k, jj );
+        if( uiType <= 2 )
+            uiRunM += uiLen;
+        else
+        {
+            if( uiRunM > 0 )
+                numberAnd( rOut, uiRunM, 'M' );
+            uiRunM = 0;
+            numberAnd( rOut, uiLen, uiType == 3 ? 'I' : 'D' );
+        }
+    }
+    if( uiRunM > 0 )
+        numberAnd( rOut, uiRunM, 'M' );
+    if( uiTail > 0 )
+        numberAnd( rOut, uiTail, cClip );
+}
+template <class Sink> MA_SAM_HD void putSigned( Sink& rOut, int64_t x )
+{
+    if( x < 0 )
+    {
+        rOut.put( '-' );
+        rOut.number( (uint64_t)0 - (uint64_t)x );
+    }
+    else
+        rOut.number( (uint64_t)x );
+}
+// ---- XI:f and CV:f: std::to_string( float ), i.e. "%f" of the float promoted to double, without printf -----------------------
+// single-precision operations, each rounded to nearest even whatever the flags of the translation unit
+MA_SAM_HD float floatOf( uint64_t x )
+{
+#if defined( __HIP_DEVICE_COMPILE__ )
+    return __ull2float_rn( x );
+#else
+    return (float)x;
+#endif
+}
+MA_SAM_HD float floatDiv( float a, float b )
+{
+#if defined( __HIP_DEVICE_COMPILE__ )
+    return __fdiv_rn( a, b );
+#else
+    return a / b;
+#endif
+}
+MA_SAM_HD float floatMul( float a, float b )
+{
+#if defined( __HIP_DEVICE_COMPILE__ )
+    return __fmul_rn( a, b );
+#else
+    return a * b;
+#endif
+}
+template <class Sink> MA_SAM_HD void putPadded18( Sink& rOut, uint64_t x ) // 18 digits
+{
+    for( uint32_t d = digits( x ); d < 18; d++ )
+        rOut.put( '0' );
+    rOut.number( x );
+}
+// "%f" of a float: it is m * 2^e with m < 2^24.  The integer part is exact; the six fraction digits are
+// m_frac * 10^6 / 2^k (k = -e) rounded half to even on the exact value, as glibc does.  m_frac * 10^6 < 2^44: u64 suffices;
+// for k >= 64 the digits are 0.
+template <class Sink> MA_SAM_HD void putFloat( Sink& rOut, float f )
+{
+    uint32_t uiBits;
+    __builtin_memcpy( &uiBits, &f, 4 );
+    const uint32_t uiExp = ( uiBits >> 23 ) & 0xff, uiMant = uiBits & 0x7fffff;
+    if( uiBits >> 31 )
+        rOut.put( '-' );
+    if( uiExp == 0xff )
+    {
+        if( uiMant )
+            lit( rOut, "nan" );
+        else
+            lit( rOut, "inf" );
+        return;
+    }
+    const uint64_t m = uiExp ? ( uiMant | 0x800000u ) : uiMant;
+    const int e = uiExp ? (int)uiExp - 150 : -149;
+    if( e >= 0 )
+    {
+        if( e <= 40 )
+            rOut.number( m << e );
+        else // up to 2^128: three limbs of 18 decimal digits, doubled e times
+        {
+            const uint64_t P = 1000000000000000000ull;
+            uint64_t a = 0, b = 0, c = m;
+            for( int i = 0; i < e; i++ )
+            {
+                c *= 2; // (c < 10^18: no wrap)
+                const uint64_t cc = c >= P ? 1 : 0;
+                c -= cc ? P : 0;
+                b = 2 * b + cc;
+                const uint64_t cb = b >= P ? 1 : 0;
+                b -= cb ? P : 0;
+                a = 2 * a + cb;
+            }
+            if( a )
+            {
+                rOut.number( a );
+                putPadded18( rOut, b );
+            }
+            else
+                rOut.number( b );
+            putPadded18( rOut, c );
+        }
+        lit( rOut, ".000000" );
+        return;
+    }
+    const uint32_t k = (uint32_t)-e; // 1 .. 149
+    uint64_t uiInt = k < 64 ? m >> k : 0, uiFrac = 0;
+    if( k < 64 )
+    {
+        const uint64_t uiProduct = ( m & ( ( 1ull << k ) - 1 ) ) * 1000000u, uiHalf = 1ull << ( k - 1 );
+        const uint64_t uiRest = uiProduct & ( ( 1ull << k ) - 1 );
+        uiFrac = uiProduct >> k;
+        if( uiRest > uiHalf || ( uiRest == uiHalf && ( uiFrac & 1 ) ) )
+            uiFrac++;
+        if( uiFrac == 1000000u )
+            uiFrac = 0, uiInt++;
+    }
+    numberAnd( rOut, uiInt, '.' );
+    for( uint32_t d = digits( uiFrac ); d < 6; d++ )
+        rOut.put( '0' );
+    rOut.number( uiFrac );
+}
+// num / den as the host computes and prints XI ( (float)matches / (float)min( spans ) ) and CV ( 100.0f * (float)span /
+// (float)length ).  A denominator of 0 is taken here, on the integers: 0 / 0 is the NaN the host's division makes, which its
+// printf shows as "-nan"; x / 0 is "inf".
+template <class Sink> MA_SAM_HD void putRatio( Sink& rOut, bool bTimes100, uint64_t uiNum, uint64_t uiDen )
+{
+    if( uiDen == 0 )
+    {
+        if( uiNum == 0 )
+            lit( rOut, "-nan" );
+        else
+            lit( rOut, "inf" );
+        return;
+    }
+    const float fNum = bTimes100 ? floatMul( 100.0f, floatOf( uiNum ) ) : floatOf( uiNum );
+    putFloat( rOut, floatDiv( fNum, floatOf( uiDen ) ) );
+}
+// Alignment::length( ) != 0 and not dropped by the options: the record is printed
+template <class List> MA_SAM_HD bool isPrinted( uint32_t uiOptions, const List& rList, uint32_t k, const Rec& rA )
+{
+    if( ( ( uiOptions & NO_SECONDARY ) && rA.secondary ) || ( ( uiOptions & NO_SUPPLEMENTARY ) && rA.supplementary ) )
+        return false;
+    for( uint32_t j = 0; j < rA.n_ops; j++ )
+        if( rList.opLen( k, j ) != 0 )
+            return true;
+    return false;
+}
+// The tags of record k (sam::ngmlrTags of ma_sam.h), in NGMLR's order.  The host code is the contract, oddities included:
+//   MD   over the swapped ops; no "0" for an empty count, but one before every mismatching base after the first of its section
+//        and before the first directly behind a deletion; bases without hole marking
+//   SV   +1: more than 0.8 of the 100 positions before begin_ref or behind end_ref lie in holes -- on RAW positions of the
+//        doubled text, begin_ref - 100 wrapping around below 100 (sic, pack.h:551-566); +2: the record spans 95 % of the read,
+//        or soft clipping
+//   AS = XE = the score; NM = mismatches + inserted + deleted bases + hole bases under seeds and matches; XR = QE - QS
+//   SA   every other alignment of the list that is not secondary, printed or not, with the NM of THIS record (sic); a sister
+//        that stands before this record, is on the reverse strand and was printed shows its swapped ops (the host swapped them
+//        when it printed her)
+// A record that cannot be printed reports ERR_BRIDGING or ERR_OPS_COVERAGE and has no tags; nothing outside
+// [begin_ref, end_ref) of pac is ever read.
+template <class Sink, class List, class RefT>
+MA_SAM_HD void putNgmlrTags( Sink& rOut, uint32_t uiOptions, const Contigs& rContigs, const Read& rQ, const Rec& rA, const List& rList, uint32_t k,
+                             const RefT& rRef )
+{
+    const uint64_t uiFwd = rContigs.forwardSize( );
+    const bool bSoftClip = ( uiOptions & SOFT_CLIP ) != 0, bRev = rA.begin_ref >= uiFwd;
+    if( rA.end_ref > rA.begin_ref && ( rA.end_ref > 2 * uiFwd || bRev != ( rA.end_ref - 1 >= uiFwd ) ) )
+    {
+        rOut.error( ERR_BRIDGING, 0, k );
+        return;
+    }
+    const uint64_t uiSpanR = rA.end_ref - rA.begin_ref, uiSpanQ = rA.end_q - rA.begin_q;
+    uint64_t uiMatches = 0, uiNm = 0;
+    {
+        uint64_t uiLeftR = uiSpanR, uiLeftQ = uiSpanQ; // (counted down: no sum can wrap)
+        bool bBad = rA.end_ref < rA.begin_ref || rA.end_q < rA.begin_q;
+        for( uint32_t j = 0; j < rA.n_ops && !bBad; j++ )
+        {
+            const uint64_t uiType = rList.opType( k, j ), uiLen = rList.opLen( k, j );
+            if( uiType > 4 || ( uiType != 3 && uiLen > uiLeftR ) || ( uiType != 4 && uiLen > uiLeftQ ) )
+                bBad = true;
+            else
+            {
+                uiLeftR -= uiType != 3 ? uiLen : 0;
+                uiLeftQ -= uiType != 4 ? uiLen : 0;
+                if( uiType <= 1 )
+                    uiMatches += uiLen;
+                else
+                    uiNm += uiLen;
+            }
+        }
+        if( bBad || uiLeftR != 0 || uiLeftQ != 0 )
+        {
+            rOut.error( ERR_OPS_COVERAGE, 0, k );
+            return;
+        }
+    }
+    lit( rOut, "\tMD:Z:" );
+    {
+        SwappedOps<List> xOps{ rList, k, rA.n_ops, bRev };
+        uint64_t uiAt = rA.begin_ref, uiPending = 0;
+        bool bAfterDeletion = false;
+        for( uint32_t j = 0; j < rA.n_ops; j++ )
+        {
+            const uint32_t jj = xOps.forward( j );
+            const uint64_t uiType = rList.opType( k, jj ), uiLen = rList.opLen( k, jj );
+            if( uiType == 3 )
+            {
+                bAfterDeletion = false;
+                continue;
+            }
+            if( uiType <= 1 )
+            {
+                uiPending += uiLen;
+                uiNm += rRef.holeBasesDoubled( uiAt, uiLen );
+            }
+            else
+            {
+                if( uiPending > 0 )
+                    rOut.number( uiPending );
+                uiPending = 0;
+                if( uiType == 4 )
+                    rOut.put( '^' );
+                for( uint64_t i = 0; i < uiLen; i++ )
+                {
+                    if( uiType == 2 && ( i > 0 || bAfterDeletion ) )
+                        rOut.put( '0' );
+                    rOut.put( baseChar( rRef.code( uiAt + i ) ) );
+                }
+            }
+            uiAt += uiLen;
+            bAfterDeletion = uiType == 4;
+        }
+        if( uiPending > 0 )
+            rOut.number( uiPending );
+    }
+    {
+        // covered / 100.0 > .8 of the host: 80 / 100.0 is the double 0.8 itself, so it is "more than 80 positions"
+        uint32_t uiSv = 0;
+        if( rRef.holeBases( rA.begin_ref - 100, rA.begin_ref ) > 80 || rRef.holeBases( rA.end_ref, rA.end_ref + 100 ) > 80 )
+            uiSv += 1;
+        if( (double)uiSpanQ >= (double)rQ.length * 0.95 || bSoftClip )
+            uiSv += 2;
+        lit( rOut, "\tSV:i:" );
+        rOut.number( uiSv );
+    }
+    lit( rOut, "\tAS:i:" );
+    putSigned( rOut, rA.score );
+    lit( rOut, "\tNM:i:" );
+    rOut.number( uiNm );
+    lit( rOut, "\tXI:f:" );
+    putRatio( rOut, false, uiMatches, uiSpanQ < uiSpanR ? uiSpanQ : uiSpanR );
+    lit( rOut, "\tXE:i:" ); // (sic) NGMLR puts the score here
+    putSigned( rOut, rA.score );
+    lit( rOut, "\tXR:i:" );
+    rOut.number( uiSpanQ );
+    lit( rOut, "\tCV:f:" );
+    putRatio( rOut, true, uiSpanQ, rQ.length );
+    const uint32_t uiAlns = rList.size( );
+    bool bTagOpen = false;
+    for( uint32_t s = 0; s < uiAlns && uiAlns > 1; s++ )
+    {
+        if( s == k )
+            continue;
+        const Rec xS = rList.rec( s );
+        if( xS.secondary )
+            continue;
+        if( !bTagOpen )
+            lit( rOut, "\tSA:Z:" );
+        bTagOpen = true;
+        const bool bSisterRev = xS.begin_ref >= uiFwd;
+        const uint32_t uiContig = contigOf( rContigs, xS.begin_ref );
+        rOut.bytes( rContigs.names + rContigs.name_off[ uiContig ], rContigs.name_off[ uiContig + 1 ] - rContigs.name_off[ uiContig ] );
+        rOut.put( ',' );
+        rOut.number( samPosition( rContigs, xS.begin_ref, xS.end_ref ) );
+        rOut.put( ',' );
+        rOut.put( bSisterRev ? '-' : '+' );
+        rOut.put( ',' );
+        putCigarM( rOut, rList, s, xS, bSisterRev, s < k && bSisterRev && isPrinted( uiOptions, rList, s, xS ), bSoftClip, rQ.length );
+        rOut.put( ',' );
+        if( xS.mapq != xS.mapq )
+            lit( rOut, "255" );
+        else
+            putSigned( rOut, (int64_t)(int)ceil( xS.mapq * 254 ) );
+        rOut.put( ',' );
+        numberAnd( rOut, uiNm, ';' );
+    }
+    lit( rOut, "\tQS:i:" );
+    rOut.number( rA.begin_q );
+    lit( rOut, "\tQE:i:" );
+    rOut.number( rA.end_q );
+}
+// One record of an aligned read: the eleven columns and the CG tag.  rX: what a mate's record has beyond a single read's
+// (its clip_length is the read's length for a single read).  Tags: with the NGMLR tags of a single read's record (rRef: a
+// Ref) -- the ops of a reverse-strand record are swapped before anything of it is printed, the CIGAR column is M-style
+// whatever EQX_CIGAR says (ma_sam.h: FileWriter::execute), the tags stand behind QUAL and before the CG tag.
+template <bool Tags = false, class RefT = NoRef, class Sink, class List>
 MA_SAM_HD void putRecord( Sink& rOut, uint32_t uiOptions, const Contigs& rContigs, const Read& rQ, const Rec& rA, const List& rList, uint32_t k,
-                          const RecordExtras& rX )
+                          const RecordExtras& rX, const RefT& rRef = RefT( ) )
 {
     const bool bSoftClip = ( uiOptions & SOFT_CLIP ) != 0, bMCigar = ( uiOptions & EQX_CIGAR ) == 0;
     const uint64_t uiFwd = rContigs.forwardSize( );
@@ -354,6 +778,8 @@ MA_SAM_HD void putRecord( Sink& rOut, uint32_t uiOptions, const Contigs& rContig
     // CIGAR (alignment.h:367-467): clip, the sections in forward-strand direction, clip
     if( bLong )
         numberAnd( rOut, uiEndQ - uiBeginQ, 'S' );
+    else if constexpr( Tags )
+        putCigarM( rOut, rList, k, rA, bRev, true, bSoftClip, rX.clip_length );
     else
     {
         const uint64_t uiLeftOver = uiEndQ < rX.clip_length ? rX.clip_length - uiEndQ : 0;
@@ -418,16 +844,30 @@ MA_SAM_HD void putRecord( Sink& rOut, uint32_t uiOptions, const Contigs& rContig
         rOut.seq( rQ, uiFrom, uiTo, bRev, k );
     rOut.put( '\t' );
     putQuality( rOut, rQ, uiBeginQ, uiEndQ, k ); // (sic) the aligned part, not reversed (alignment.h:611-614)
+    if constexpr( Tags )
+        putNgmlrTags( rOut, uiOptions, rContigs, rQ, rA, rList, k, rRef );
     if( bLong ) // TagGenerator::computeTag (fileWriter.h:327-357): the real cigar as CG:B:I
     {
         lit( rOut, "\tCG:B:I" );
-        for( uint32_t j = 0; j < rA.n_ops; j++ )
+        if constexpr( Tags )
         {
-            const uint64_t uiType = rList.opType( k, j );
-            rOut.put( ',' );
-            // op codes 7 7 8 1 2 of seed, match, missmatch, insertion, deletion
-            rOut.number( (uint32_t)( rList.opLen( k, j ) << 4 ) | (uint32_t)( ( 0x21877u >> ( 4 * ( uiType < 5 ? uiType : 0 ) ) ) & 0xf ) );
+            SwappedOps<List> xOps{ rList, k, rA.n_ops, bRev };
+            for( uint32_t j = 0; j < rA.n_ops; j++ )
+            {
+                const uint32_t jj = xOps.forward( j );
+                const uint64_t uiType = rList.opType( k, jj );
+                rOut.put( ',' );
+                rOut.number( (uint32_t)( rList.opLen( k, jj ) << 4 ) | (uint32_t)( ( 0x21877u >> ( 4 * ( uiType < 5 ? uiType : 0 ) ) ) & 0xf ) );
+            }
         }
+        else
+            for( uint32_t j = 0; j < rA.n_ops; j++ )
+            {
+                const uint64_t uiType = rList.opType( k, j );
+                rOut.put( ',' );
+                // op codes 7 7 8 1 2 of seed, match, missmatch, insertion, deletion
+                rOut.number( (uint32_t)( rList.opLen( k, j ) << 4 ) | (uint32_t)( ( 0x21877u >> ( 4 * ( uiType < 5 ? uiType : 0 ) ) ) & 0xf ) );
+            }
     }
     rOut.put( '\n' );
 }
@@ -452,6 +892,33 @@ MA_SAM_HD void formatRead( Sink& rOut, uint32_t uiOptions, const Contigs& rConti
         RecordExtras xExtras;
         xExtras.clip_length = rQ.length;
         detail::putRecord( rOut, uiOptions, rContigs, rQ, xA, rList, k, xExtras );
+        bAny = true;
+    }
+    if( uiAlns == 0 )
+        detail::putUnmapped( rOut, rQ, true );
+    else if( !bAny )
+        detail::putUnmapped( rOut, rQ, false );
+}
+// The same with reference bases and holes at hand: with NGMLR_TAGS among the options every record carries the tags, without
+// the bit this is formatRead above.
+template <class Sink, class List, class RefT>
+MA_SAM_HD void formatRead( Sink& rOut, uint32_t uiOptions, const Contigs& rContigs, const Read& rQ, const List& rList, const RefT& rRef )
+{
+    if( ( uiOptions & NGMLR_TAGS ) == 0 )
+    {
+        formatRead( rOut, uiOptions, rContigs, rQ, rList );
+        return;
+    }
+    const uint32_t uiAlns = rList.size( );
+    bool bAny = false;
+    for( uint32_t k = 0; k < uiAlns; k++ )
+    {
+        const Rec xA = rList.rec( k );
+        if( !detail::isPrinted( uiOptions, rList, k, xA ) )
+            continue;
+        RecordExtras xExtras;
+        xExtras.clip_length = rQ.length;
+        detail::putRecord<true>( rOut, uiOptions, rContigs, rQ, xA, rList, k, xExtras, rRef );
         bAny = true;
     }
     if( uiAlns == 0 )
@@ -552,8 +1019,8 @@ MA_SAM_HD void formatPair( Sink& rOut, uint32_t uiOptions, const Contigs& rConti
     }
 }
 
-// The text of the host formatter's exception for an error a sink was told of; returns its length (buf holds >= 64 bytes, the
-// text is 0-terminated).
+// The text of the host formatter's exception for an error a sink was told of; returns its length (the text is
+// 0-terminated; 64 bytes hold the two kinds of a record beyond its read, 96 bytes every kind).
 inline size_t errorText( char* buf, uint32_t uiKind, int64_t iValue )
 {
     WriteSink xOut{ buf };
@@ -569,6 +1036,10 @@ inline size_t errorText( char* buf, uint32_t uiKind, int64_t iValue )
             xOut.number( (uint64_t)iValue );
         xOut.put( '.' );
     }
+    else if( uiKind == ERR_BRIDGING )
+        detail::lit( xOut, "(vExtractSubsection) Try to extract bridging sequence. This is impossible." );
+    else if( uiKind == ERR_OPS_COVERAGE ) // (the library's own: the caller names the record)
+        detail::lit( xOut, "the ops do not cover the record's reference and query intervals" );
     else
         detail::lit( xOut, "Index out of range (compCharAt)" );
     xOut.put( '\0' );
