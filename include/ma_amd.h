@@ -294,8 +294,8 @@ int ma_batch_get_pairs( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, ma_alignmen
 int ma_batch_start_pair_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, ma_alignment* alns, uint64_t* ops, int32_t* mate,
                                   int32_t* other );
 /* ---- SAM text: FileWriter::execute (fileWriter.cpp:11-158) on the device ----
- * The single-end records of a batch as the bytes the reference's FileWriter prints for them (and ma_amd/host/ma_flat_sam.h
- * makes of the downloaded MappingQuality records), formatted by two kernels and downloaded as ONE text instead of records and
+ * The single-end records of a batch as the bytes the reference's FileWriter prints for them (and ma_amd/host/ma_sam.h, the
+ * yardstick, makes of the MappingQuality records), formatted by two kernels and downloaded as ONE text instead of records and
  * ops: per alignment of a read's MappingQuality list one record with Alignment::getSamFlag / getSamPosition / cigarString /
  * getQuerySequence (alignment.h:367-467, 576-623), the CG:B:I tag of cigars from 0x10000 ops on (TagGenerator, fileWriter.h:
  * 327-357), the unmapped record (fileWriter.cpp:126-140) for a read without a printed alignment.  With MA_SAM_NGMLR_TAGS every
@@ -342,7 +342,7 @@ int ma_batch_get_sam( ma_batch*, uint64_t* rec_off /*n+1*/, char* text );
 int ma_batch_start_sam_download( ma_batch*, uint64_t* rec_off /*n+1*/, char* text );
 /* ---- paired-end SAM text: PairedFileWriter::execute (fileWriter.cpp:158-383) on the device ----
  * The records of a batch's mate pairs (ma_pair_batch) as the bytes the reference's PairedFileWriter prints for them (and
- * ma_amd/host/ma_flat_sam.h formatPair makes of the arrays of ma_batch_get_pairs), formatted by two kernels from what is in
+ * ma_amd/host/ma_sam.h, the yardstick, makes of the records of ma_batch_get_pairs), formatted by two kernels from what is in
  * device memory after ma_pair_batch -- nothing is uploaded, nothing packed -- and downloaded as ONE text: per printed record of
  * a pair FLAG with 0x1 | 0x2 | 0x40 / 0x80 (| 0x20: partner on the reverse strand), RNEXT / PNEXT of the partner ("=" on a
  * contig of the same NAME), TLEN 0, MAPQ capped at 255, the cigar's left-over clip taken against the FIRST mate's length (sic);

@@ -1,6 +1,6 @@
-// stage_pair_sam.h -- the paired-end SAM records of a batch as text, formatted on the device: the bytes flat::formatPair
-// (ma_amd/host/ma_flat_sam.h) makes of the downloaded pair records, i.e. those of the reference's PairedFileWriter::execute
-// (fileWriter.cpp:158-383).  The record layout is ma_sam::formatPair of ma_amd/host/ma_sam_dev.h, the code the CPU tests pin to
+// stage_pair_sam.h -- the paired-end SAM records of a batch as text, formatted on the device: the bytes PairedFileWriter::execute
+// (ma_amd/host/ma_sam.h, the yardstick) makes of the downloaded pair records, i.e. those of the reference's
+// PairedFileWriter::execute (fileWriter.cpp:158-383).  The record layout is ma_sam::formatPair of ma_amd/host/ma_sam_dev.h, the code the CPU tests pin to
 // the goldens; the kernels only supply its pair list and its sinks.  Nothing is packed: the records are read where k_finish
 // left them, through the picks of k_pair_pick, with the overrides k_pair_pack would apply.  Textually part of pipeline.hip.
 //   k_pair_sam_size   one lane per pair: formatPair over the counting sink -> the pair's byte count (scanned into offsets by

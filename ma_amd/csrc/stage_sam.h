@@ -1,5 +1,5 @@
-// stage_sam.h -- the single-end SAM records of a batch as text, formatted on the device: the bytes flat::formatRead
-// (ma_amd/host/ma_flat_sam.h) makes of the downloaded MappingQuality records, i.e. those of the reference's
+// stage_sam.h -- the single-end SAM records of a batch as text, formatted on the device: the bytes FileWriter::execute
+// (ma_amd/host/ma_sam.h, the yardstick) makes of the downloaded MappingQuality records, i.e. those of the reference's
 // FileWriter::execute (fileWriter.cpp:11-158).  The record layout is ma_sam::formatRead of ma_amd/host/ma_sam_dev.h, the code
 // the CPU tests pin to the goldens; the kernels only supply its sinks.  Textually part of pipeline.hip.
 //   k_sam_size   one lane per read: formatRead over the counting sink -> the read's byte count (scanned into offsets by the

@@ -180,7 +180,7 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
 {
     std::shared_ptr<FileWriter> pPerRead; // owns stream + lock (and serves the options the flat formatter does not)
     ma_amd::flat::SamFormat xFormat;
-    ma_amd::flat::Contigs xContigs;
+    ma_amd::flat::ContigTable xContigs;
 
   public:
     size_t uiFormatThreads = 8;
@@ -196,7 +196,7 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
         const SamOptions& rO = rParameters.xSam;
         xFormat.bNoSecondary = rO.bNoSecondary, xFormat.bNoSupplementary = rO.bNoSupplementary;
         xFormat.bOutputMCigar = rO.bOutputMCigar, xFormat.bCGTag = rO.bCGTag, xFormat.bSoftClip = rO.bSoftClip;
-        xContigs.vNames = pPack->vNames, xContigs.vStarts = pPack->vStarts, xContigs.vLengths = pPack->vLengths;
+        xContigs.set( pPack->vNames, pPack->vStarts, pPack->vLengths );
     }
 
     virtual std::shared_ptr<libMS::Container> execute( std::shared_ptr<ReadVector> pReads, std::shared_ptr<AlignedBatch> pAligned,
@@ -303,7 +303,7 @@ class BatchPairedFileWriter
 {
     std::shared_ptr<PairedFileWriter> pPerPair; // owns stream + lock, writes the header
     ma_amd::flat::SamFormat xFormat;
-    ma_amd::flat::Contigs xContigs;
+    ma_amd::flat::ContigTable xContigs;
 
   public:
     size_t uiFormatThreads = 8;
@@ -319,7 +319,7 @@ class BatchPairedFileWriter
         const SamOptions& rO = rParameters.xSam;
         xFormat.bNoSecondary = rO.bNoSecondary, xFormat.bNoSupplementary = rO.bNoSupplementary;
         xFormat.bOutputMCigar = rO.bOutputMCigar, xFormat.bCGTag = rO.bCGTag, xFormat.bSoftClip = rO.bSoftClip;
-        xContigs.vNames = pPack->vNames, xContigs.vStarts = pPack->vStarts, xContigs.vLengths = pPack->vLengths;
+        xContigs.set( pPack->vNames, pPack->vStarts, pPack->vLengths );
     }
 
     void execute( const AlignedBatch& rBatch )

@@ -2,8 +2,9 @@
 // FileReader with the reference's name,
 // Module signature, constructors, options and output bytes (libs/ma/inc/ma/module/fileWriter.h:21-78,364-440,
 // libs/ma/src/module/fileWriter.cpp:11-158), plus the Alignment / Pack / NucSeq string helpers it calls
-// (alignment.h:367-467,576-623; pack.h:900-997,1063-1067; nucSeq.h:558-713).  Pure host code, on Alignment containers; the
-// same bytes formatted on the device are ma_sam_batch's (ma_sam_dev.h), for which this file is the yardstick.
+// (alignment.h:367-467,576-623; pack.h:900-997,1063-1067; nucSeq.h:558-713).  Pure host code, on Alignment containers, and
+// the yardstick of the formatter over flat records (ma_sam_dev.h): of ma_sam_batch / ma_pair_sam_batch on the device and of
+// the host's flat writers (ma_flat_sam.h), which all run that one formatter and share no code with this file.
 // The NGMLR tag emulation ("Emulate NGMLR's tag output", off by default) is implemented for FileWriter (sam::ngmlrTags);
 // PairedFileWriter refuses it.
 #pragma once

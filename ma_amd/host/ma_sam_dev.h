@@ -1,23 +1,32 @@
-// ma_sam_dev.h -- the SAM record formatters of ma_flat_sam.h (flat::formatRead / putRecord / putUnmapped: the bytes of the
-// reference's FileWriter::execute, libs/ma/src/module/fileWriter.cpp:11-158; flat::formatPair: those of
-// PairedFileWriter::execute, :158-383) restated ONCE over a templated sink, for three users:
+// ma_sam_dev.h -- the SAM record formatter over FLAT records (the arrays of ma_batch_get_mapq_alignments / ma_batch_get_pairs),
+// written ONCE over a templated sink: formatRead prints the bytes of the reference's FileWriter::execute
+// (libs/ma/src/module/fileWriter.cpp:11-158), formatPair those of PairedFileWriter::execute (:158-383), both with
+// Alignment::cigarString / getSamFlag / getSamPosition / getQuerySequence (libs/ma/inc/ma/container/alignment.h:367-467, 576-623)
+// and Pack's position arithmetic (pack.h:900-997, 1063-1067).  Its users:
 //   - the device stages (ma_amd/csrc/stage_sam.h, stage_pair_sam.h) run formatRead( ) / formatPair( ) inside their two kernels:
 //     with the counting sink to size every read's (pair's) text, with a writing sink to store it;
-//   - the CPU tests (tests/emul/sam_dev_test.cpp, sam_pair_dev_test.cpp) run the same functions on the host and pin them, byte
-//     for byte, to flat::formatRead / flat::formatPair and to the SAM goldens the compiled reference wrote;
+//   - the host's flat writers (ma_flat_sam.h: flat::formatRead / flat::formatPair, an adapter that runs the same functions over
+//     a sink on its byte arena) for BatchFileWriter / BatchPairedFileWriter of ma_batch_nodes.h;
 //   - libma_amd.so words the error of a bad record with errorText( ).
+// The yardstick is the independent implementation on Alignment containers, FileWriter / PairedFileWriter of ma_sam.h, which
+// tests/test_sam_writer.py and tests/test_pairs_host.py pin to the SAM goldens the compiled reference wrote: the CPU tests
+// (tests/emul/sam_dev_test.cpp, sam_pair_dev_test.cpp, sam_tags_dev_test.cpp) run the functions of this file on the host and
+// compare them with it byte for byte, and the GPU tests compare the kernels' text with it.
 // With NGMLR_TAGS (single-end only) a record also carries the tags of the reference's "Emulate NGMLR's tag output"
 // (TagGenerator::computeTag, fileWriter.h:120-326): MD SV AS NM XI XE XR CV SA QS QE, byte for byte what ma_amd::FileWriter
-// (ma_sam.h: sam::ngmlrTags, FileWriter::execute) prints, which is the yardstick of tests/emul/sam_tags_dev_test.cpp.  They
-// need the reference's bases and its runs of N: a Ref (below), handed to formatRead( sink, options, contigs, read, list, ref ).
-// No reference headers, no containers, no strings: include/ma_amd.h only.  ma_flat_sam.h stays the yardstick and documents
-// where each oddity comes from; they are kept as they are:
-//   position one further on the reverse strand; MAPQ = (int)ceil( mapq * 254 ), 255 for NaN; the cigar walked backwards on the
-//   reverse strand; seed / match / mismatch merged into M (or printed as = / X); H or S clips with the left-over clip taken
-//   against the read length; SEQ reverse-complemented on the reverse strand, QUAL the aligned part and never reversed, "*"
-//   without qualities; "<len>S" + the CG:B:I tag from 0x10000 ops on; alignments of op length 0 skipped; secondary /
-//   supplementary records dropped on request; the unmapped record with MAPQ text 255 for an empty list and 0 when every
-//   alignment was skipped.
+// (ma_sam.h: sam::ngmlrTags, FileWriter::execute) prints.  They need the reference's bases and its runs of N: a Ref (below),
+// handed to formatRead( sink, options, contigs, read, list, ref ).
+// No reference headers, no containers, no strings: include/ma_amd.h only.  The reference's oddities are listed HERE and nowhere
+// else; they are kept as they are:
+//   position one further on the reverse strand (alignment.h:596-603), the contig that of the begin (pack.h:1063-1067);
+//   MAPQ = (int)ceil( mapq * 254 ), 255 for NaN, capped at 255 by the paired writer only (fileWriter.cpp:262); the cigar walked
+//   backwards on the reverse strand, seed / match / mismatch merged into M (or printed as = / X), H or S clips with the
+//   left-over clip taken against the read length -- of the FIRST mate in a pair (alignment.h:367-467, fileWriter.cpp:191-193);
+//   SEQ reverse-complemented on the reverse strand, QUAL the aligned part and never reversed (alignment.h:611-614,
+//   nucSeq.h:697-709), "*" without qualities; "<len>S" + the CG:B:I tag from 0x10000 ops on (fileWriter.h:327-357); alignments of
+//   op length 0 skipped; secondary / supplementary records dropped on request; the unmapped record with MAPQ text 255 for an
+//   empty list and 0 when every alignment was skipped (fileWriter.cpp:126-140); a pair's TLEN is never output (:317), RNEXT is
+//   "=" on a contig of the same NAME, an unaligned mate stands at record 0 of the list, printed or not (:348-366).
 //
 // A sink is anything with
 //   put( c ), bytes( p, n ), number( x ), size( )          plain columns
@@ -161,7 +170,7 @@ struct Ref
 };
 struct NoRef
 {};
-// what a record of a pair has beyond a single read's (flat::detail::RecordExtras); the defaults are a single read's
+// what a record of a pair has beyond a single read's; the defaults are a single read's
 struct RecordExtras
 {
     uint32_t extra_flags = 0;
@@ -963,8 +972,8 @@ MA_SAM_HD void putUnalignedMate( Sink& rOut, const Contigs& rContigs, const Read
 }
 } // namespace detail
 
-// The SAM records of ONE mate pair: flat::formatPair of ma_flat_sam.h (PairedFileWriter::execute, fileWriter.cpp:158-383) over
-// a pair list, in its three record shapes, oddities included:
+// The SAM records of ONE mate pair: the bytes of PairedFileWriter::execute (fileWriter.cpp:158-383; ma_sam.h) from a pair
+// list, in its three record shapes, oddities included:
 //   aligned mate          FLAG = strand | secondary | supplementary | 0x1 | 0x2 (always) | 0x40 / 0x80 | 0x20 (partner on the
 //                         reverse strand), RNEXT / PNEXT = the partner ("=" on a contig of the same name), TLEN 0, MAPQ capped
 //                         at 255, CIGAR clipped against the length of the FIRST mate (sic, :191-193)

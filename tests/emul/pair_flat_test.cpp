@@ -46,15 +46,15 @@ static int golden( int argc, char** argv )
     for( auto& x : c.contigs )
         uiN += 2 * x.size( );
     const int iOptions = atoi( argv[ 6 ] );
-    ma_amd::flat::Contigs xContigs;
+    ma_amd::flat::ContigTable xContigs;
     auto pPack = std::make_shared<Pack>( );
     for( size_t i = 0; i < c.contigs.size( ); i++ )
     {
-        xContigs.vNames.push_back( c.names[ i ] );
-        xContigs.vStarts.push_back( uiN / 2 - [ & ] { uint64_t r = 0; for( size_t k = i; k < c.contigs.size( ); k++ ) r += c.contigs[ k ].size( ); return r; }( ) );
-        xContigs.vLengths.push_back( c.contigs[ i ].size( ) );
+        pPack->vNames.push_back( c.names[ i ] );
+        pPack->vStarts.push_back( uiN / 2 - [ & ] { uint64_t r = 0; for( size_t k = i; k < c.contigs.size( ); k++ ) r += c.contigs[ k ].size( ); return r; }( ) );
+        pPack->vLengths.push_back( c.contigs[ i ].size( ) );
     }
-    pPack->vNames = xContigs.vNames, pPack->vStarts = xContigs.vStarts, pPack->vLengths = xContigs.vLengths;
+    xContigs.set( pPack->vNames, pPack->vStarts, pPack->vLengths );
     ma_amd::flat::SamFormat xFormat;
     xFormat.bSoftClip = ( iOptions & 1 ) != 0;
     xFormat.bOutputMCigar = ( iOptions & 2 ) == 0;

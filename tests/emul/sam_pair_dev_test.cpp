@@ -1,48 +1,26 @@
 // CPU-only checks of the paired-end record formatter the device stage runs (ma_amd/host/ma_sam_dev.h: ma_sam::formatPair over
-// its counting and its writing sink) against the yardstick, flat::formatPair of ma_amd/host/ma_flat_sam.h, and the paired SAM
+// its counting and its writing sink) and of the host's flat writer on top of it (flat::formatPair of ma_amd/host/ma_flat_sam.h)
+// against the yardstick, PairedFileWriter::execute of ma_amd/host/ma_sam.h on fresh Alignment containers, and the paired SAM
 // golden.
 //   sam_pair_dev_test golden <case> <f4 dump> <golden.sam> <options>   the "P" / "p" records of an f4 dump of the compiled
-//                                                                       reference: both formatters and the record lines of
-//                                                                       the golden must agree byte for byte
+//                                                                       reference: the formatter under both sinks, the flat
+//                                                                       writer, the yardstick and the record lines of the
+//                                                                       golden must agree byte for byte
 //   sam_pair_dev_test random <seed> <pairs>                            seeded random pairs under every option combination
 //   sam_pair_dev_test special                                          cigars of 65 535 / 65 536 ops inside a pair (CG tag),
 //                                                                       the two error texts for either mate
 //   sam_pair_dev_test dump <dump> <out> <options>                      the yardstick of tests/test_gpu_pair_sam.py: writes
-//                                                                       flat::formatPair's text of a dump (the arrays of
+//                                                                       PairedFileWriter's text of a dump (the arrays of
 //                                                                       ma_batch_get_pairs) to <out> and the per-pair offsets
 //                                                                       (u64) to <out>.off; a formatter exception is printed
 //                                                                       as "ERROR: <text>" (exit code 3)
 // options: the MA_SAM_* bits of include/ma_amd.h.  Every count of the counting sink is checked against the bytes written; the
 // writing sink gets a buffer of exactly that size and the reads hold exactly their bases, so that an AddressSanitizer build of
 // this program sees any byte touched outside of them.
-#include "../../oracle/dump_format.h"
-#include "ma_flat_sam.h"
-#include "ma_sam_dev.h"
+#include "sam_dev_common.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <limits>
-#include <memory>
-#include <random>
-#include <sstream>
-
-using namespace ma_amd;
-
-struct ReadData
+struct PairInput : Input // vReads: 2 per pair, vOff: pairs + 1
 {
-    std::string sName;
-    std::vector<uint8_t> vCodes, vQual;
-    bool bQual = false;
-};
-struct Input
-{
-    flat::Contigs xContigs;
-    std::vector<ReadData> vReads; // 2 per pair
-    std::vector<uint64_t> vOff; // pairs + 1
-    std::vector<ma_alignment> vAlns;
-    std::vector<uint64_t> vOps; // (type, length) pairs
     std::vector<int32_t> vMate, vOther;
     size_t pairs( ) const
     {
@@ -50,131 +28,51 @@ struct Input
     }
 };
 
-static flat::SamFormat formatOf( uint32_t uiOptions )
+// the yardstick: PairedFileWriter::execute over all pairs, the containers' xStats set from mate and other (throws what it
+// throws).  formatPair does not know the tag bit, which the paired writer refuses: the yardstick runs without it.
+static std::string yardstick( const PairInput& rIn, uint32_t uiOptions, std::vector<uint64_t>* pOff = nullptr )
 {
-    flat::SamFormat f;
-    f.bSoftClip = ( uiOptions & MA_SAM_SOFT_CLIP ) != 0;
-    f.bOutputMCigar = ( uiOptions & MA_SAM_EQX_CIGAR ) == 0;
-    f.bNoSecondary = ( uiOptions & MA_SAM_NO_SECONDARY ) != 0;
-    f.bNoSupplementary = ( uiOptions & MA_SAM_NO_SUPPLEMENTARY ) != 0;
-    f.bCGTag = ( uiOptions & MA_SAM_NO_CG_TAG ) == 0;
-    return f;
+    return writerText<PairedFileWriter>( rIn, uiOptions & ma_sam::PAIR_OPTIONS, rIn.pairs( ), pOff,
+                                         [ & ]( PairedFileWriter& rWriter, std::shared_ptr<Pack> pPack, size_t p ) {
+                                             auto pV = rIn.containers( p );
+                                             for( size_t k = 0; k < pV->size( ); k++ )
+                                             {
+                                                 const uint64_t o = rIn.vOff[ p ] + k;
+                                                 ( *pV )[ k ]->xStats.bFirst = rIn.vMate[ o ] != 0;
+                                                 if( rIn.vOther[ o ] >= 0 )
+                                                     ( *pV )[ k ]->xStats.pOther = ( *pV )[ (size_t)rIn.vOther[ o ] ];
+                                             }
+                                             rWriter.execute( rIn.vReads[ 2 * p ].container( ), rIn.vReads[ 2 * p + 1 ].container( ), pV, pPack );
+                                         } );
 }
-
-// the contig table as ma_sam_dev.h reads it
-struct DevContigs
+// the host's flat writer: flat::formatPair, the adapter of ma_flat_sam.h, over all pairs (throws what it throws)
+static std::string adapter( const PairInput& rIn, uint32_t uiOptions )
 {
-    std::vector<char> vNames;
-    std::vector<uint64_t> vNameOff;
-    ma_sam::Contigs view( const flat::Contigs& r )
-    {
-        vNames.clear( );
-        vNameOff.assign( 1, 0 );
-        for( auto& s : r.vNames )
-        {
-            vNames.insert( vNames.end( ), s.begin( ), s.end( ) );
-            vNameOff.push_back( vNames.size( ) );
-        }
-        return ma_sam::Contigs{ vNames.data( ), vNameOff.data( ), r.vStarts.data( ), r.vLengths.data( ), (uint32_t)r.vStarts.size( ) };
-    }
-};
-
-// the yardstick: flat::formatPair over all pairs (throws what it throws).  An empty mate has no quality string, as in the host
-// layer (NucSeq::xQuality empty -> no qualities): its QUAL is "*".
-static std::string yardstick( const Input& rIn, uint32_t uiOptions, std::vector<uint64_t>* pOff = nullptr )
-{
-    flat::Arena xOut;
-    const flat::SamFormat xF = formatOf( uiOptions );
-    if( pOff )
-        pOff->assign( 1, 0 );
+    ma_amd::flat::Arena xOut;
+    const ma_amd::flat::ContigTable xContigs = rIn.flatContigs( );
     for( size_t p = 0; p < rIn.pairs( ); p++ )
     {
-        flat::ReadView v[ 2 ];
-        for( int m = 0; m < 2; m++ )
-        {
-            const ReadData& q = rIn.vReads[ 2 * p + m ];
-            v[ m ].sName = q.sName.data( ), v[ m ].uiNameLen = q.sName.size( );
-            v[ m ].pCodes = q.vCodes.data( ), v[ m ].pQuality = q.bQual && !q.vQual.empty( ) ? q.vQual.data( ) : nullptr, v[ m ].uiLength = q.vCodes.size( );
-        }
         const uint64_t o = rIn.vOff[ p ];
-        flat::formatPair( xOut, xF, rIn.xContigs, v[ 0 ], v[ 1 ], rIn.vAlns.data( ) + o, (size_t)( rIn.vOff[ p + 1 ] - o ), rIn.vOps.data( ),
-                          rIn.vMate.data( ) + o, rIn.vOther.data( ) + o );
-        if( pOff )
-            pOff->push_back( xOut.size( ) );
+        ma_amd::flat::formatPair( xOut, formatOf( uiOptions ), xContigs, rIn.vReads[ 2 * p ].flatView( ), rIn.vReads[ 2 * p + 1 ].flatView( ),
+                                  rIn.vAlns.data( ) + o, (size_t)( rIn.vOff[ p + 1 ] - o ), rIn.vOps.data( ), rIn.vMate.data( ) + o, rIn.vOther.data( ) + o );
     }
     return std::string( xOut.data( ), xOut.size( ) );
 }
-
-struct DevResult
-{
-    std::string sText;
-    uint32_t uiErrors = 0, uiKind = 0, uiRecord = 0;
-    size_t uiPair = 0;
-    int64_t iValue = 0;
-};
 // the shared formatter: counting sink, then the writing sink into exactly that many bytes
-static DevResult shared( const Input& rIn, uint32_t uiOptions )
+static DevResult shared( const PairInput& rIn, uint32_t uiOptions )
 {
-    DevContigs xNames;
-    const ma_sam::Contigs xC = xNames.view( rIn.xContigs );
-    DevResult xRes;
-    for( size_t p = 0; p < rIn.pairs( ); p++ )
-    {
-        const ReadData &q1 = rIn.vReads[ 2 * p ], &q2 = rIn.vReads[ 2 * p + 1 ];
-        const ma_sam::Read xQ1{ q1.sName.data( ), q1.sName.size( ), q1.vCodes.data( ), q1.bQual && !q1.vQual.empty( ) ? q1.vQual.data( ) : nullptr, q1.vCodes.size( ) };
-        const ma_sam::Read xQ2{ q2.sName.data( ), q2.sName.size( ), q2.vCodes.data( ), q2.bQual && !q2.vQual.empty( ) ? q2.vQual.data( ) : nullptr, q2.vCodes.size( ) };
-        const uint64_t o = rIn.vOff[ p ];
-        const ma_sam::FlatPairList xL{ { rIn.vAlns.data( ) + o, (uint32_t)( rIn.vOff[ p + 1 ] - o ), rIn.vOps.data( ) },
-                                       rIn.vMate.data( ) + o,
-                                       rIn.vOther.data( ) + o };
-        ma_sam::CountSink xCount;
-        ma_sam::formatPair( xCount, uiOptions, xC, xQ1, xQ2, xL );
-        if( xCount.nErrors && !xRes.uiErrors )
-            xRes.uiKind = xCount.firstKind, xRes.iValue = xCount.firstValue, xRes.uiRecord = xCount.firstRecord, xRes.uiPair = p;
-        xRes.uiErrors += xCount.nErrors;
-        std::unique_ptr<char[]> pBuf( new char[ xCount.n ] ); // (exactly: the sanitizer build sees a byte too many)
-        ma_sam::WriteSink xWrite{ pBuf.get( ) };
-        ma_sam::formatPair( xWrite, uiOptions, xC, xQ1, xQ2, xL );
-        if( xWrite.n != xCount.n )
-            throw std::runtime_error( "pair " + std::to_string( p ) + ": the counting sink says " + std::to_string( xCount.n ) + " bytes, " +
-                                      std::to_string( xWrite.n ) + " were written" );
-        xRes.sText.append( pBuf.get( ), xWrite.n );
-    }
-    return xRes;
-}
-
-static void compare( const std::string& sGot, const std::string& sWant, const std::string& sWhat )
-{
-    if( sGot == sWant )
-        return;
-    size_t i = 0;
-    while( i < sGot.size( ) && i < sWant.size( ) && sGot[ i ] == sWant[ i ] )
-        i++;
-    const size_t b = sWant.rfind( '\n', i ) == std::string::npos ? 0 : sWant.rfind( '\n', i ) + 1;
-    throw std::runtime_error( sWhat + ": texts differ at byte " + std::to_string( i ) + "\n want: " + sWant.substr( b, 300 ) + "\n got:  " +
-                              sGot.substr( b < sGot.size( ) ? b : 0, 300 ) );
+    const DevContigs xC( rIn );
+    return countThenWrite( rIn.pairs( ), [ & ]( auto& rSink, size_t p ) {
+        const ma_sam::FlatPairList xL{ rIn.list( p ), rIn.vMate.data( ) + rIn.vOff[ p ], rIn.vOther.data( ) + rIn.vOff[ p ] };
+        ma_sam::formatPair( rSink, uiOptions, xC.xView, rIn.vReads[ 2 * p ].view( ), rIn.vReads[ 2 * p + 1 ].view( ), xL );
+    } );
 }
 
 // ---- golden pass ---------------------------------------------------------------------------------------------------------
-static Input fromF4Dump( const char* sCase, const char* sDump )
+static PairInput fromF4Dump( const char* sCase, const char* sDump )
 {
-    CaseFile c = readCase( sCase );
-    Input in;
-    uint64_t off = 0;
-    for( size_t i = 0; i < c.contigs.size( ); i++ )
-    {
-        in.xContigs.vNames.push_back( c.names[ i ] );
-        in.xContigs.vStarts.push_back( off );
-        in.xContigs.vLengths.push_back( c.contigs[ i ].size( ) );
-        off += c.contigs[ i ].size( );
-    }
-    for( size_t r = 0; r < c.reads.size( ); r++ )
-    {
-        ReadData q;
-        q.sName = "r" + std::to_string( r );
-        q.vCodes = c.reads[ r ];
-        in.vReads.push_back( q );
-    }
+    PairInput in;
+    static_cast<Input&>( in ) = fromCase( sCase );
     if( in.vReads.size( ) % 2 )
         in.vReads.pop_back( );
     std::ifstream f( sDump );
@@ -206,14 +104,7 @@ static Input fromF4Dump( const char* sCase, const char* sDump )
             a.mapq = sMq == "nan" ? NAN : strtod( sMq.c_str( ), nullptr );
             a.n_ops = (uint32_t)nops;
             a.ops_off = in.vOps.size( ) / 2;
-            for( size_t k = 0; k < nops; k++ )
-            {
-                std::string op;
-                ss >> op;
-                const size_t colon = op.find( ':' );
-                in.vOps.push_back( (uint64_t)atoi( op.substr( 0, colon ).c_str( ) ) );
-                in.vOps.push_back( strtoull( op.c_str( ) + colon + 1, nullptr, 10 ) );
-            }
+            readOps( ss, nops, in.vOps );
             in.vAlns.push_back( a );
             in.vMate.push_back( first );
             in.vOther.push_back( other );
@@ -231,41 +122,21 @@ static int golden( int argc, char** argv )
 {
     if( argc < 6 )
         return 2;
-    const Input in = fromF4Dump( argv[ 2 ], argv[ 3 ] );
+    const PairInput in = fromF4Dump( argv[ 2 ], argv[ 3 ] );
     const uint32_t uiOptions = (uint32_t)atoi( argv[ 5 ] );
-    std::ifstream f( argv[ 4 ] );
-    std::string line, sGolden;
-    while( std::getline( f, line ) )
-        if( line.empty( ) || line[ 0 ] != '@' )
-            sGolden += line + "\n";
+    const std::string sGolden = goldenRecords( argv[ 4 ] );
     const std::string sYard = yardstick( in, uiOptions );
     const DevResult xDev = shared( in, uiOptions );
     if( xDev.uiErrors )
         throw std::runtime_error( "the shared formatter reports errors on the golden records" );
-    compare( xDev.sText, sYard, "shared formatter against flat::formatPair" );
+    compare( xDev.sText, sYard, "shared formatter against PairedFileWriter" );
     compare( xDev.sText, sGolden, "shared formatter against the golden" );
+    compare( adapter( in, uiOptions ), sYard, "flat::formatPair against PairedFileWriter" );
     printf( "golden ok: %zu pairs, %zu records, %zu bytes\n", in.pairs( ), in.vAlns.size( ), sYard.size( ) );
     return 0;
 }
 
 // ---- random pass ---------------------------------------------------------------------------------------------------------
-typedef std::mt19937_64 Rng;
-static uint64_t below( Rng& g, uint64_t n ) // [0, n)
-{
-    return n ? g( ) % n : 0;
-}
-// a number next to a decimal boundary (9/10, 99/100, ... 10^9), or any
-static uint64_t nearBoundary( Rng& g, uint64_t uiMax )
-{
-    if( below( g, 4 ) == 0 )
-        return below( g, uiMax + 1 );
-    uint64_t p = 10;
-    for( uint64_t e = below( g, 9 ); e > 0; e-- )
-        p *= 10;
-    const uint64_t v = p - 2 + below( g, 4 ); // p-2 .. p+1
-    return v > uiMax ? uiMax : v;
-}
-
 struct Census
 {
     size_t picked[ 4 ] = { 0, 0, 0, 0 }, lists = 0, emptied = 0, firstFiltered = 0, zeroLength = 0, otherContig = 0, sameName = 0, capped = 0,
@@ -273,12 +144,12 @@ struct Census
 };
 
 // one record of a mate of uiLen bases (the record lies inside the mate); iStrand 0 / 1 forward / reverse, else either
-static ma_alignment randomRecord( Rng& g, Input& in, uint64_t uiLen, int iStrand, size_t uiContig, bool bZero, Census& rC )
+static ma_alignment randomRecord( Rng& g, PairInput& in, uint64_t uiLen, int iStrand, size_t uiContig, bool bZero, Census& rC )
 {
-    const uint64_t F = in.xContigs.forwardSize( );
+    const uint64_t F = in.forward( );
     ma_alignment a{ };
     const bool bRev = iStrand < 0 ? below( g, 2 ) != 0 : iStrand != 0;
-    const uint64_t cs = in.xContigs.vStarts[ uiContig ], cl = in.xContigs.vLengths[ uiContig ];
+    const uint64_t cs = in.vStarts[ uiContig ], cl = in.vLengths[ uiContig ];
     const uint64_t span = 1 + below( g, 300 );
     const uint64_t fs = cs + nearBoundary( g, cl - span ), fe = fs + span; // forward interval [fs, fe) inside the contig
     a.begin_ref = (int64_t)( bRev ? 2 * F - fe : fs );
@@ -301,20 +172,17 @@ static ma_alignment randomRecord( Rng& g, Input& in, uint64_t uiLen, int iStrand
     return a;
 }
 
-static Input randomInput( Rng& g, size_t uiPairs, Census& rC )
+static PairInput randomInput( Rng& g, size_t uiPairs, Census& rC )
 {
     static const uint64_t aLens[] = { 0, 1, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257 }; // (0: an empty mate)
     const size_t nLens = sizeof( aLens ) / sizeof( aLens[ 0 ] );
-    Input in;
+    PairInput in;
     const size_t nC = 1 + below( g, 3 );
-    uint64_t off = 0;
     for( size_t i = 0; i < nC; i++ )
     {
         // two contigs share a name
-        in.xContigs.vNames.push_back( i == 2 ? in.xContigs.vNames[ 0 ] : std::string( 1 + below( g, 12 ), (char)( 'a' + below( g, 26 ) ) ) );
-        in.xContigs.vStarts.push_back( off );
-        in.xContigs.vLengths.push_back( 300 + nearBoundary( g, 2000000000ull ) );
-        off += in.xContigs.vLengths.back( );
+        const std::string sName = i == 2 ? in.vNames[ 0 ] : std::string( 1 + below( g, 12 ), (char)( 'a' + below( g, 26 ) ) );
+        in.addContig( sName, 300 + nearBoundary( g, 2000000000ull ) );
     }
     const bool bQual = below( g, 2 ) != 0; // (a run has qualities or has none)
     in.vOff.assign( 1, 0 );
@@ -347,7 +215,7 @@ static Input randomInput( Rng& g, size_t uiPairs, Census& rC )
             const size_t c1 = below( g, nC ), c2 = below( g, 3 ) == 0 ? below( g, nC ) : c1;
             rC.picked[ kind - 1 ]++;
             rC.otherContig += c1 != c2;
-            rC.sameName += c1 != c2 && in.xContigs.vNames[ c1 ] == in.xContigs.vNames[ c2 ];
+            rC.sameName += c1 != c2 && in.vNames[ c1 ] == in.vNames[ c2 ];
             const bool bZero = below( g, 12 ) == 0; // (a picked record of length 0 is skipped as any other)
             in.vAlns.push_back( randomRecord( g, in, aLen[ 0 ], ( kind - 1 ) & 1, c1, bZero, rC ) );
             in.vAlns.push_back( randomRecord( g, in, aLen[ 1 ], ( ( kind - 1 ) >> 1 ) & 1, c2, false, rC ) );
@@ -397,7 +265,7 @@ static int randomPass( int argc, char** argv )
     Census xC;
     for( size_t done = 0; done < uiPairs; done += 200, uiRounds++ )
     {
-        const Input in = randomInput( g, 200, xC ); // (a new contig table every 200 pairs)
+        const PairInput in = randomInput( g, 200, xC ); // (a new contig table every 200 pairs)
         uiWithQual += in.vReads[ 0 ].bQual;
         for( uint32_t uiOptions = 0; uiOptions <= ma_sam::ALL_OPTIONS; uiOptions++ )
         {
@@ -406,6 +274,7 @@ static int randomPass( int argc, char** argv )
             if( xDev.uiErrors )
                 throw std::runtime_error( "errors on records that lie inside their reads" );
             compare( xDev.sText, sYard, "options " + std::to_string( uiOptions ) );
+            compare( adapter( in, uiOptions ), sYard, "flat::formatPair, options " + std::to_string( uiOptions ) );
             uiBytes += sYard.size( );
         }
     }
@@ -428,12 +297,10 @@ static int randomPass( int argc, char** argv )
 
 // ---- special pass --------------------------------------------------------------------------------------------------------
 // a picked pair: the first mate a 70 kb read with uiOps single-base ops, the second a plain 150 bp record
-static Input longCigarPair( uint32_t uiOps, bool bRev, bool bLongIsFirst )
+static PairInput longCigarPair( uint32_t uiOps, bool bRev, bool bLongIsFirst )
 {
-    Input in;
-    in.xContigs.vNames = { "chrL", "chrM" };
-    in.xContigs.vStarts = { 0, 200000 };
-    in.xContigs.vLengths = { 200000, 1000 };
+    PairInput in;
+    in.addContig( "chrL", 200000 ), in.addContig( "chrM", 1000 );
     const uint64_t F = 201000;
     ReadData q, s;
     q.sName = "long", s.sName = "short";
@@ -472,33 +339,27 @@ static int special( )
             for( int iFirst = 0; iFirst < 2; iFirst++ )
                 for( uint32_t uiOptions : { 0u, (uint32_t)MA_SAM_NO_CG_TAG, (uint32_t)MA_SAM_EQX_CIGAR, (uint32_t)( MA_SAM_NO_CG_TAG | MA_SAM_EQX_CIGAR | MA_SAM_SOFT_CLIP ) } )
                 {
-                    const Input in = longCigarPair( uiOps, iRev != 0, iFirst != 0 );
+                    const PairInput in = longCigarPair( uiOps, iRev != 0, iFirst != 0 );
                     const std::string sYard = yardstick( in, uiOptions );
                     compare( shared( in, uiOptions ).sText, sYard, "long cigar" );
+                    compare( adapter( in, uiOptions ), sYard, "long cigar through flat::formatPair" );
                     const bool bTag = sYard.find( "\tCG:B:I," ) != std::string::npos;
                     if( bTag != ( uiOps >= 0x10000 && !( uiOptions & MA_SAM_NO_CG_TAG ) ) )
                         throw std::runtime_error( "CG tag present / absent against expectation" );
                 }
     // a record that ends beyond its OWN mate -- the other mate is longer, so that only the own length tells -- in the first
     // and in the second mate: the yardstick throws, the shared formatter reports the same text for that record, touches
-    // nothing beyond the read and writes what it counted
+    // nothing beyond the read and writes what it counted; the flat writer throws the same text
     for( int iBadMate = 0; iBadMate < 2; iBadMate++ )
         for( int iRev = 0; iRev < 2; iRev++ )
             for( uint32_t uiOptions : { 0u, (uint32_t)MA_SAM_EQX_CIGAR } )
             {
-                Input in = longCigarPair( 10, iRev != 0, iBadMate == 0 ); // the 70 kb mate is the bad one, cut to 150 bases
+                PairInput in = longCigarPair( 10, iRev != 0, iBadMate == 0 ); // the 70 kb mate is the bad one, cut to 150 bases
                 in.vReads[ iBadMate ].vCodes.resize( 150 ), in.vReads[ iBadMate ].vQual.resize( 150 );
                 in.vReads[ 1 - iBadMate ].vCodes.resize( 400, 2 ), in.vReads[ 1 - iBadMate ].vQual.resize( 400, (uint8_t)'I' );
                 in.vAlns[ iBadMate ].begin_q = 120, in.vAlns[ iBadMate ].end_q = 153;
-                std::string sWant;
-                try
-                {
-                    yardstick( in, uiOptions );
-                }
-                catch( const std::exception& e )
-                {
-                    sWant = e.what( );
-                }
+                const std::string sWant = errorOf( [ & ] { yardstick( in, uiOptions ); } );
+                const std::string sAdapter = errorOf( [ & ] { adapter( in, uiOptions ); } );
                 const DevResult xDev = shared( in, uiOptions );
                 char aText[ 64 ];
                 ma_sam::errorText( aText, xDev.uiKind, xDev.iValue );
@@ -507,12 +368,22 @@ static int special( )
                                               std::to_string( xDev.uiRecord ) );
                 if( sWant != ( iRev ? "Index out of range (compCharAt)" : "Query length is off by -3." ) )
                     throw std::runtime_error( "unexpected text of the yardstick: " + sWant );
+                if( sAdapter != sWant )
+                    throw std::runtime_error( "error text of flat::formatPair: want '" + sWant + "', got '" + sAdapter + "'" );
                 // soft clipping prints the whole read: no error even then (the yardstick does not throw either)
                 const DevResult xSoft = shared( in, uiOptions | MA_SAM_SOFT_CLIP );
                 if( xSoft.uiErrors )
                     throw std::runtime_error( "error reported under soft clipping" );
                 compare( xSoft.sText, yardstick( in, uiOptions | MA_SAM_SOFT_CLIP ), "soft clipping beyond the read" );
+                compare( adapter( in, uiOptions | MA_SAM_SOFT_CLIP ), xSoft.sText, "soft clipping beyond the read through flat::formatPair" );
             }
+    // a pack without contigs can only yield unmapped records: the flat writer prints them without looking at its table
+    {
+        PairInput in = longCigarPair( 10, false, true );
+        in.vNames.clear( ), in.vStarts.clear( ), in.vLengths.clear( ), in.vAlns.clear( );
+        in.vOff = { 0, 0 };
+        compare( adapter( in, 0 ), yardstick( in, 0 ), "pair without records, no contigs" );
+    }
     printf( "special ok\n" );
     return 0;
 }
@@ -522,84 +393,16 @@ static int dump( int argc, char** argv )
 {
     if( argc < 5 )
         return 2;
-    FILE* f = fopen( argv[ 2 ], "rb" );
-    if( !f )
-        throw std::runtime_error( std::string( "cannot open " ) + argv[ 2 ] );
-    auto rd = [ & ]( void* p, size_t n ) {
-        if( n && fread( p, 1, n, f ) != n )
-            throw std::runtime_error( "dump too short" );
-    };
-    auto u32 = [ & ]( ) {
-        uint32_t v;
-        rd( &v, 4 );
-        return v;
-    };
-    auto u64 = [ & ]( ) {
-        uint64_t v;
-        rd( &v, 8 );
-        return v;
-    };
-    char magic[ 8 ];
-    rd( magic, 8 );
-    if( memcmp( magic, "MASAMP01", 8 ) )
-        throw std::runtime_error( "bad dump magic" );
-    Input in;
-    for( uint32_t i = 0, n = u32( ); i < n; i++ )
+    PairInput in;
     {
-        std::string s( u32( ), ' ' );
-        rd( &s[ 0 ], s.size( ) );
-        in.xContigs.vNames.push_back( s );
-        in.xContigs.vStarts.push_back( u64( ) );
-        in.xContigs.vLengths.push_back( u64( ) );
+        DumpFile f( argv[ 2 ] );
+        readDump( f, in, "MASAMP01", false, 2 );
+        const size_t nA = in.vAlns.size( );
+        in.vMate.resize( nA + 1 ), in.vOther.resize( nA + 1 );
+        f.rd( in.vMate.data( ), nA * 4 );
+        f.rd( in.vOther.data( ), nA * 4 );
     }
-    const uint32_t nR = u32( ), bQual = u32( );
-    if( nR % 2 )
-        throw std::runtime_error( "odd number of reads" );
-    for( uint32_t r = 0; r < nR; r++ )
-    {
-        ReadData q;
-        q.sName.assign( u32( ), ' ' );
-        rd( &q.sName[ 0 ], q.sName.size( ) );
-        q.vCodes.resize( u32( ) );
-        rd( q.vCodes.data( ), q.vCodes.size( ) );
-        q.bQual = bQual != 0;
-        if( q.bQual )
-        {
-            q.vQual.resize( q.vCodes.size( ) );
-            rd( q.vQual.data( ), q.vQual.size( ) );
-        }
-        in.vReads.push_back( q );
-    }
-    const size_t nP = nR / 2;
-    in.vOff.resize( nP + 1 );
-    rd( in.vOff.data( ), ( nP + 1 ) * 8 );
-    const size_t nA = in.vOff[ nP ];
-    in.vAlns.resize( nA );
-    rd( in.vAlns.data( ), nA * sizeof( ma_alignment ) );
-    in.vOps.resize( 2 * u64( ) + 2 );
-    rd( in.vOps.data( ), ( in.vOps.size( ) - 2 ) * 8 );
-    in.vMate.resize( nA + 1 ), in.vOther.resize( nA + 1 );
-    rd( in.vMate.data( ), nA * 4 );
-    rd( in.vOther.data( ), nA * 4 );
-    fclose( f );
-    std::vector<uint64_t> vOff;
-    std::string sText;
-    try
-    {
-        sText = yardstick( in, (uint32_t)atoi( argv[ 4 ] ), &vOff );
-    }
-    catch( const std::exception& e )
-    {
-        printf( "ERROR: %s\n", e.what( ) );
-        return 3;
-    }
-    FILE* o = fopen( argv[ 3 ], "wb" );
-    fwrite( sText.data( ), 1, sText.size( ), o );
-    fclose( o );
-    o = fopen( ( std::string( argv[ 3 ] ) + ".off" ).c_str( ), "wb" );
-    fwrite( vOff.data( ), 8, vOff.size( ), o );
-    fclose( o );
-    return 0;
+    return writeYardstick( argv[ 3 ], [ & ]( std::vector<uint64_t>* pOff ) { return yardstick( in, (uint32_t)atoi( argv[ 4 ] ), pOff ); } );
 }
 
 int main( int argc, char** argv )

@@ -17,265 +17,34 @@
 // options: the MA_SAM_* bits of include/ma_amd.h.  Every count of the counting sink is checked against the bytes written; the
 // writing sink gets a buffer of exactly that size, the reads hold exactly their bases and pac exactly the forward strand, so
 // that an AddressSanitizer build of this program sees any byte touched outside of them.
-#include "../../oracle/dump_format.h"
-#include "ma_sam.h"
-#include "ma_sam_dev.h"
+#include "sam_dev_common.h"
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <limits>
 #include <map>
-#include <memory>
-#include <random>
-#include <sstream>
-
-using namespace libMA;
-
-struct ReadData
-{
-    std::string sName;
-    std::vector<uint8_t> vCodes, vQual;
-    bool bQual = false;
-};
-struct Input
-{
-    std::vector<std::string> vNames;
-    std::vector<uint64_t> vStarts, vLengths;
-    std::vector<uint8_t> vGenome; // forward strand, one code per base
-    std::vector<uint64_t> vHoleStart, vHoleLen;
-    std::vector<ReadData> vReads;
-    std::vector<uint64_t> vOff; // n + 1
-    std::vector<ma_alignment> vAlns;
-    std::vector<uint64_t> vOps; // (type, length) pairs
-    uint64_t forward( ) const
-    {
-        return vStarts.back( ) + vLengths.back( );
-    }
-    std::vector<uint8_t> pac( ) const // exactly the bytes of the forward strand
-    {
-        std::vector<uint8_t> v( ( vGenome.size( ) + 3 ) / 4, 0 );
-        for( uint64_t p = 0; p < vGenome.size( ); p++ )
-            v[ p >> 2 ] |= (uint8_t)( ( vGenome[ p ] & 3 ) << ( ( ~p & 3 ) << 1 ) );
-        return v;
-    }
-};
-
-static SamOptions optionsOf( uint32_t uiOptions )
-{
-    SamOptions o;
-    o.bSoftClip = ( uiOptions & MA_SAM_SOFT_CLIP ) != 0;
-    o.bOutputMCigar = ( uiOptions & MA_SAM_EQX_CIGAR ) == 0;
-    o.bNoSecondary = ( uiOptions & MA_SAM_NO_SECONDARY ) != 0;
-    o.bNoSupplementary = ( uiOptions & MA_SAM_NO_SUPPLEMENTARY ) != 0;
-    o.bCGTag = ( uiOptions & MA_SAM_NO_CG_TAG ) == 0;
-    o.bEmulateNgmlrTags = ( uiOptions & MA_SAM_NGMLR_TAGS ) != 0;
-    return o;
-}
 
 // the yardstick: FileWriter::execute over all reads, on fresh Alignment containers (it swaps their ops); throws what it throws
 static std::string yardstick( const Input& rIn, uint32_t uiOptions, std::vector<uint64_t>* pOff = nullptr )
 {
-    auto pPack = std::make_shared<Pack>( );
-    pPack->vNames = rIn.vNames, pPack->vStarts = rIn.vStarts, pPack->vLengths = rIn.vLengths;
-    pPack->vPacHost = rIn.pac( );
-    for( size_t i = 0; i < rIn.vHoleStart.size( ); i++ )
-        pPack->vHoles.emplace_back( rIn.vHoleStart[ i ], rIn.vHoleLen[ i ] );
-    ParameterSetManager xParams;
-    xParams.xSam = optionsOf( uiOptions );
-    auto pStream = std::make_shared<StringOutStream>( );
-    FileWriter xWriter( xParams, std::static_pointer_cast<OutStream>( pStream ), pPack );
-    const size_t uiHeader = pStream->sText.size( );
-    if( pOff )
-        pOff->assign( 1, 0 );
-    for( size_t r = 0; r < rIn.vReads.size( ); r++ )
-    {
-        auto pQ = std::make_shared<NucSeq>( );
-        pQ->sName = rIn.vReads[ r ].sName, pQ->xCodes = rIn.vReads[ r ].vCodes;
-        if( rIn.vReads[ r ].bQual )
-            pQ->xQuality = rIn.vReads[ r ].vQual;
-        auto pV = std::make_shared<libMS::ContainerVector<std::shared_ptr<Alignment>>>( );
-        for( uint64_t k = rIn.vOff[ r ]; k < rIn.vOff[ r + 1 ]; k++ )
-        {
-            const ma_alignment& a = rIn.vAlns[ k ];
-            auto pA = std::make_shared<Alignment>( );
-            pA->uiBeginOnRef = (uint64_t)a.begin_ref, pA->uiEndOnRef = (uint64_t)a.end_ref;
-            pA->uiBeginOnQuery = (uint64_t)a.begin_q, pA->uiEndOnQuery = (uint64_t)a.end_q;
-            pA->iScore = a.score, pA->fMappingQuality = a.mapq, pA->bSecondary = a.secondary != 0, pA->bSupplementary = a.supplementary != 0;
-            for( uint32_t j = 0; j < a.n_ops; j++ )
-                pA->data.emplace_back( (MatchType)rIn.vOps[ 2 * ( a.ops_off + j ) ], rIn.vOps[ 2 * ( a.ops_off + j ) + 1 ] );
-            pV->push_back( pA );
-        }
-        xWriter.execute( pQ, pV, pPack );
-        if( pOff )
-            pOff->push_back( pStream->sText.size( ) - uiHeader );
-    }
-    xWriter.flush( );
-    return pStream->sText.substr( uiHeader );
+    return fileWriterText( rIn, uiOptions, pOff );
 }
-
-struct DevResult
-{
-    std::string sText;
-    uint32_t uiErrors = 0, uiKind = 0, uiRead = 0, uiRecord = 0;
-    int64_t iValue = 0;
-};
 // the shared formatter: counting sink, then the writing sink into exactly that many bytes
 static DevResult shared( const Input& rIn, uint32_t uiOptions )
 {
-    std::vector<char> vNames;
-    std::vector<uint64_t> vNameOff( 1, 0 );
-    for( auto& s : rIn.vNames )
-    {
-        vNames.insert( vNames.end( ), s.begin( ), s.end( ) );
-        vNameOff.push_back( vNames.size( ) );
-    }
-    const ma_sam::Contigs xC{ vNames.data( ), vNameOff.data( ), rIn.vStarts.data( ), rIn.vLengths.data( ), (uint32_t)rIn.vStarts.size( ) };
+    const DevContigs xC( rIn );
     const std::vector<uint8_t> vPac = rIn.pac( );
     const ma_sam::Ref xRef{ vPac.data( ), rIn.vHoleStart.data( ), rIn.vHoleLen.data( ), rIn.vHoleStart.size( ), rIn.forward( ) };
-    DevResult xRes;
-    for( size_t r = 0; r < rIn.vReads.size( ); r++ )
-    {
-        const ReadData& q = rIn.vReads[ r ];
-        const ma_sam::Read xQ{ q.sName.data( ), q.sName.size( ), q.vCodes.data( ), q.bQual ? q.vQual.data( ) : nullptr, q.vCodes.size( ) };
-        const ma_sam::FlatList xL{ rIn.vAlns.data( ) + rIn.vOff[ r ], (uint32_t)( rIn.vOff[ r + 1 ] - rIn.vOff[ r ] ), rIn.vOps.data( ) };
-        ma_sam::CountSink xCount;
-        ma_sam::formatRead( xCount, uiOptions, xC, xQ, xL, xRef );
-        if( xCount.nErrors && !xRes.uiErrors )
-            xRes.uiKind = xCount.firstKind, xRes.iValue = xCount.firstValue, xRes.uiRead = (uint32_t)r, xRes.uiRecord = xCount.firstRecord;
-        xRes.uiErrors += xCount.nErrors;
-        std::unique_ptr<char[]> pBuf( new char[ xCount.n ] ); // (exactly: the sanitizer build sees a byte too many)
-        ma_sam::WriteSink xWrite{ pBuf.get( ) };
-        ma_sam::formatRead( xWrite, uiOptions, xC, xQ, xL, xRef );
-        if( xWrite.n != xCount.n )
-            throw std::runtime_error( "read " + std::to_string( r ) + ": the counting sink says " + std::to_string( xCount.n ) + " bytes, " +
-                                      std::to_string( xWrite.n ) + " were written" );
-        xRes.sText.append( pBuf.get( ), xWrite.n );
-    }
-    return xRes;
-}
-
-static void compare( const std::string& sGot, const std::string& sWant, const std::string& sWhat )
-{
-    if( sGot == sWant )
-        return;
-    size_t i = 0;
-    while( i < sGot.size( ) && i < sWant.size( ) && sGot[ i ] == sWant[ i ] )
-        i++;
-    const size_t b = sWant.rfind( '\n', i ) == std::string::npos ? 0 : sWant.rfind( '\n', i ) + 1;
-    throw std::runtime_error( sWhat + ": texts differ at byte " + std::to_string( i ) + "\n want: " + sWant.substr( b, 400 ) + "\n got:  " +
-                              sGot.substr( b < sGot.size( ) ? b : 0, 400 ) );
+    return countThenWrite( rIn.vReads.size( ), [ & ]( auto& rSink, size_t r ) {
+        ma_sam::formatRead( rSink, uiOptions, xC.xView, rIn.vReads[ r ].view( ), rIn.list( r ), xRef );
+    } );
 }
 
 // ---- golden pass ---------------------------------------------------------------------------------------------------------
-static Input fromPipeDump( const char* sCase, const char* sPipe )
-{
-    CaseFile c = readCase( sCase );
-    Input in;
-    uint64_t off = 0;
-    for( size_t i = 0; i < c.contigs.size( ); i++ )
-    {
-        in.vNames.push_back( c.names[ i ] );
-        in.vStarts.push_back( off );
-        in.vLengths.push_back( c.contigs[ i ].size( ) );
-        in.vGenome.insert( in.vGenome.end( ), c.contigs[ i ].begin( ), c.contigs[ i ].end( ) );
-        off += c.contigs[ i ].size( );
-    }
-    for( size_t r = 0; r < c.reads.size( ); r++ )
-    {
-        ReadData q;
-        q.sName = "r" + std::to_string( r );
-        q.vCodes = c.reads[ r ];
-        in.vReads.push_back( q );
-    }
-    struct Rec
-    {
-        unsigned long long br, er, bq, eq;
-        long long score;
-        std::vector<uint64_t> ops;
-    };
-    std::vector<Rec> alns;
-    std::vector<std::vector<ma_alignment>> vPerRead( c.reads.size( ) );
-    std::vector<std::vector<std::vector<uint64_t>>> vPerReadOps( c.reads.size( ) );
-    std::ifstream f( sPipe );
-    std::string line;
-    long read = -1;
-    while( std::getline( f, line ) )
-    {
-        std::istringstream is( line );
-        std::string tag;
-        is >> tag;
-        if( tag == "R" )
-        {
-            is >> read;
-            alns.clear( );
-        }
-        else if( tag == "a" )
-        {
-            Rec r;
-            unsigned soc;
-            size_t n;
-            is >> r.br >> r.er >> r.bq >> r.eq >> r.score >> soc >> n;
-            for( size_t k = 0; k < n; k++ )
-            {
-                std::string t;
-                is >> t;
-                const size_t colon = t.find( ':' );
-                r.ops.push_back( (uint64_t)atoi( t.substr( 0, colon ).c_str( ) ) );
-                r.ops.push_back( strtoull( t.substr( colon + 1 ).c_str( ), nullptr, 10 ) );
-            }
-            alns.push_back( r );
-        }
-        else if( tag == "m" )
-        {
-            unsigned long long br, er, bq, eq;
-            long long score;
-            int sec, sup;
-            std::string sQ;
-            is >> br >> er >> bq >> eq >> score >> sec >> sup >> sQ;
-            ma_alignment a{ };
-            a.begin_ref = (int64_t)br, a.end_ref = (int64_t)er, a.begin_q = (int64_t)bq, a.end_q = (int64_t)eq, a.score = score;
-            a.secondary = sec != 0, a.supplementary = sup != 0, a.mapq = strtod( sQ.c_str( ), nullptr );
-            std::vector<uint64_t> ops;
-            for( auto& r : alns ) // the MQ record is one of the NW alignments
-                if( r.br == br && r.er == er && r.bq == bq && r.eq == eq && r.score == score )
-                {
-                    ops = r.ops;
-                    break;
-                }
-            a.n_ops = (uint32_t)( ops.size( ) / 2 );
-            vPerRead[ (size_t)read ].push_back( a );
-            vPerReadOps[ (size_t)read ].push_back( ops );
-        }
-    }
-    in.vOff.assign( 1, 0 );
-    for( size_t r = 0; r < c.reads.size( ); r++ )
-    {
-        for( size_t k = 0; k < vPerRead[ r ].size( ); k++ )
-        {
-            ma_alignment a = vPerRead[ r ][ k ];
-            a.ops_off = in.vOps.size( ) / 2;
-            in.vOps.insert( in.vOps.end( ), vPerReadOps[ r ][ k ].begin( ), vPerReadOps[ r ][ k ].end( ) );
-            in.vAlns.push_back( a );
-        }
-        in.vOff.push_back( in.vAlns.size( ) );
-    }
-    in.vOps.push_back( 0 ), in.vOps.push_back( 0 );
-    return in;
-}
-
 static int golden( int argc, char** argv )
 {
     if( argc < 6 )
         return 2;
     const Input in = fromPipeDump( argv[ 2 ], argv[ 3 ] );
     const uint32_t uiOptions = (uint32_t)atoi( argv[ 5 ] );
-    std::ifstream f( argv[ 4 ] );
-    std::string line, sGolden;
-    while( std::getline( f, line ) )
-        if( line.empty( ) || line[ 0 ] != '@' )
-            sGolden += line + "\n";
+    const std::string sGolden = goldenRecords( argv[ 4 ] );
     const std::string sYard = yardstick( in, uiOptions );
     const DevResult xDev = shared( in, uiOptions );
     if( xDev.uiErrors )
@@ -287,12 +56,6 @@ static int golden( int argc, char** argv )
 }
 
 // ---- generated records ---------------------------------------------------------------------------------------------------
-typedef std::mt19937_64 Rng;
-static uint64_t below( Rng& g, uint64_t n ) // [0, n)
-{
-    return n ? g( ) % n : 0;
-}
-
 // two contigs; holes: 150 bases 40 bases into contig 0, 120 bases further on, 30 bases, one touching the contig border
 static Input genome( Rng& g, uint64_t uiLen0 = 3000, uint64_t uiLen1 = 2500 )
 {
@@ -607,16 +370,8 @@ static void errors( )
             a.end_ref += 1;
         else // the query's
             a.end_q -= 1;
-        std::string sHost;
-        try
-        {
-            if( uiWant == ma_sam::ERR_BRIDGING ) // (the host reads outside its buffer on the others)
-                yardstick( in, MA_SAM_NGMLR_TAGS );
-        }
-        catch( const std::exception& e )
-        {
-            sHost = e.what( );
-        }
+        // (the host reads outside its buffer on the others)
+        const std::string sHost = uiWant == ma_sam::ERR_BRIDGING ? errorOf( [ & ] { yardstick( in, MA_SAM_NGMLR_TAGS ); } ) : "";
         const DevResult xDev = shared( in, MA_SAM_NGMLR_TAGS );
         char aText[ 96 ];
         ma_sam::errorText( aText, xDev.uiKind, xDev.iValue );
@@ -721,71 +476,6 @@ static int floats( int argc, char** argv )
 }
 
 // ---- dumps -----------------------------------------------------------------------------------------------------------------
-static Input readDump( const char* sPath )
-{
-    FILE* f = fopen( sPath, "rb" );
-    if( !f )
-        throw std::runtime_error( std::string( "cannot open " ) + sPath );
-    auto rd = [ & ]( void* p, size_t n ) {
-        if( n && fread( p, 1, n, f ) != n )
-            throw std::runtime_error( "dump too short" );
-    };
-    auto u32 = [ & ]( ) {
-        uint32_t v;
-        rd( &v, 4 );
-        return v;
-    };
-    auto u64 = [ & ]( ) {
-        uint64_t v;
-        rd( &v, 8 );
-        return v;
-    };
-    char magic[ 8 ];
-    rd( magic, 8 );
-    if( memcmp( magic, "MASAMT01", 8 ) )
-        throw std::runtime_error( "bad dump magic" );
-    Input in;
-    for( uint32_t i = 0, n = u32( ); i < n; i++ )
-    {
-        std::string s( u32( ), ' ' );
-        rd( &s[ 0 ], s.size( ) );
-        in.vNames.push_back( s );
-        in.vStarts.push_back( u64( ) );
-        in.vLengths.push_back( u64( ) );
-    }
-    in.vGenome.resize( u64( ) );
-    rd( in.vGenome.data( ), in.vGenome.size( ) );
-    const uint64_t nH = u64( );
-    for( uint64_t i = 0; i < nH; i++ )
-    {
-        in.vHoleStart.push_back( u64( ) );
-        in.vHoleLen.push_back( u64( ) );
-    }
-    const uint32_t nR = u32( ), bQual = u32( );
-    for( uint32_t r = 0; r < nR; r++ )
-    {
-        ReadData q;
-        q.sName.assign( u32( ), ' ' );
-        rd( &q.sName[ 0 ], q.sName.size( ) );
-        q.vCodes.resize( u32( ) );
-        rd( q.vCodes.data( ), q.vCodes.size( ) );
-        q.bQual = bQual != 0;
-        if( q.bQual )
-        {
-            q.vQual.resize( q.vCodes.size( ) );
-            rd( q.vQual.data( ), q.vQual.size( ) );
-        }
-        in.vReads.push_back( q );
-    }
-    in.vOff.resize( nR + 1 );
-    rd( in.vOff.data( ), ( nR + 1 ) * 8 );
-    in.vAlns.resize( in.vOff[ nR ] );
-    rd( in.vAlns.data( ), in.vAlns.size( ) * sizeof( ma_alignment ) );
-    in.vOps.resize( 2 * u64( ) + 2 );
-    rd( in.vOps.data( ), ( in.vOps.size( ) - 2 ) * 8 );
-    fclose( f );
-    return in;
-}
 static void writeDump( const Input& in, const char* sPath ) // (reads of one kind: all with qualities or all without)
 {
     FILE* f = fopen( sPath, "wb" );
@@ -829,25 +519,12 @@ static int dump( int argc, char** argv )
 {
     if( argc < 5 )
         return 2;
-    const Input in = readDump( argv[ 2 ] );
-    std::vector<uint64_t> vOff;
-    std::string sText;
-    try
+    Input in;
     {
-        sText = yardstick( in, (uint32_t)atoi( argv[ 4 ] ), &vOff );
+        DumpFile f( argv[ 2 ] );
+        readDump( f, in, "MASAMT01", true, 1 );
     }
-    catch( const std::exception& e )
-    {
-        printf( "ERROR: %s\n", e.what( ) );
-        return 3;
-    }
-    FILE* o = fopen( argv[ 3 ], "wb" );
-    fwrite( sText.data( ), 1, sText.size( ), o );
-    fclose( o );
-    o = fopen( ( std::string( argv[ 3 ] ) + ".off" ).c_str( ), "wb" );
-    fwrite( vOff.data( ), 8, vOff.size( ), o );
-    fclose( o );
-    return 0;
+    return writeYardstick( argv[ 3 ], [ & ]( std::vector<uint64_t>* pOff ) { return yardstick( in, (uint32_t)atoi( argv[ 4 ] ), pOff ); } );
 }
 
 int main( int argc, char** argv )

@@ -1,6 +1,6 @@
 """ma_pair_sam_batch: the paired-end SAM records of a batch formatted on the device (ma_amd/csrc/stage_pair_sam.h), through the
 C ABI / ma_amd.api.  Every case compares the device's bytes and pair_off with a yardstick: the SAM golden the compiled reference's
-PairedFileWriter wrote, or flat::formatPair (ma_amd/host/ma_flat_sam.h) run by tests/emul/sam_pair_dev_test.cpp (mode `dump`) on
+PairedFileWriter wrote, or ma_amd's PairedFileWriter (ma_amd/host/ma_sam.h) run by tests/emul/sam_pair_dev_test.cpp (mode `dump`) on
 the pair records the device itself reports (pairs())."""
 import ctypes as C
 import gzip
@@ -24,7 +24,7 @@ SEEDS = dict(pairs=77, random_mates=78, quals=79)
 
 
 def yardstick(tmp, ctx, names, reads, quals, res, options):
-    """flat::formatPair's (pair_off, text) for the arrays of pairs(); a formatter exception comes back as its text (str)"""
+    """PairedFileWriter's (pair_off, text) for the arrays of pairs(); a formatter exception comes back as its text (str)"""
     off, alns, ops, mate, other = res
     path = os.path.join(str(tmp), "pair_sam.dump")
     with open(path, "wb") as f:
@@ -158,7 +158,7 @@ def shapes(gpu_device):
 @pytest.mark.parametrize("with_quals", [True, False], ids=["qualities", "no-qualities"])
 def test_every_record_shape_and_option_bit(tmp_path, shapes, index, with_quals):
     """600 sampled pairs (far, same-strand and random mates among them), 8 pairs of two random mates, 16 pairs out of the repeat
-    family under report_n_best 3, names of varying length, under every option bit against flat::formatPair on the device's
+    family under report_n_best 3, names of varying length, under every option bit against PairedFileWriter on the device's
     pair records; the text holds what makes the comparison mean something.  On the index whose two contigs share a name every
     RNEXT is "=" (the names are compared, not the ids)."""
     ctxs, runs = shapes

@@ -168,7 +168,7 @@ def build_driver():
     src = exe + ".cpp"
     deps = [src, os.path.join(ROOT, "include", "ma_amd.h"), os.path.join(ROOT, "ma_amd", "libma_amd.so")] + [
         os.path.join(ROOT, "ma_amd", "host", h) for h in ("ma_sam.h", "ma_modules.h", "ms_graph.h", "ma_pair_flat.h", "ma_flat_sam.h",
-                                                          "ma_batch_nodes.h", "ma_engine.h")]
+                                                          "ma_sam_dev.h", "ma_batch_nodes.h", "ma_engine.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"),
                                "-I" + os.path.join(ROOT, "ma_amd", "host"), src, "-o", exe, "-L" + os.path.join(ROOT, "ma_amd"),

@@ -1,6 +1,6 @@
 """ma_sam_batch: the single-end SAM records of a batch formatted on the device (ma_amd/csrc/stage_sam.h), through the C ABI /
 ma_amd.api.  Every case compares the device's bytes and rec_off with a yardstick: the SAM goldens the compiled reference
-wrote, or flat::formatRead (ma_amd/host/ma_flat_sam.h) run by tests/emul/sam_dev_test.cpp (mode `dump`) on the records the
+wrote, or ma_amd's FileWriter (ma_amd/host/ma_sam.h) run by tests/emul/sam_dev_test.cpp (mode `dump`) on the records the
 device itself reports."""
 import ctypes as C
 import gzip
@@ -27,7 +27,7 @@ def make_quals(reads, seed):
 
 
 def yardstick(tmp, contig_names, starts, lens, names, reads, quals, off, alns, ops, options):
-    """flat::formatRead's (rec_off, text) for the records given; a formatter exception comes back as its text (str)"""
+    """FileWriter's (rec_off, text) for the records given; a formatter exception comes back as its text (str)"""
     path = os.path.join(str(tmp), "sam.dump")
     with open(path, "wb") as f:
         f.write(b"MASAMD01" + struct.pack("<I", len(contig_names)))
@@ -159,7 +159,7 @@ def record_stats(off, alns, F):
 
 def test_random_genome_every_option_bit(tmp_path, mixed):
     """~400 reads -- 150 bp on both strands, some with N, 20 random ones, 12 chimeric 2 kb reads under pacbio, a run with
-    report_n_best 3 -- with and without qualities under every option bit, against flat::formatRead on the device's records; the
+    report_n_best 3 -- with and without qualities under every option bit, against FileWriter on the device's records; the
     records hold what makes the comparison mean something"""
     ctx = mixed
     short = (sample_reads(ctx.g, 300, 150, 42, sub=0.01) + sample_reads(ctx.g, 60, 150, 43, sub=0.04, n_rate=0.02)

@@ -18,6 +18,7 @@ def build_exe():
     deps = [src, os.path.join(ROOT, "ma_amd", "host", "ms_graph.h"), os.path.join(ROOT, "ma_amd", "host", "ma_modules.h"),
             os.path.join(ROOT, "ma_amd", "host", "ma_sam.h"), os.path.join(ROOT, "include", "ma_amd.h"),
             os.path.join(ROOT, "ma_amd", "host", "ma_batch_nodes.h"), os.path.join(ROOT, "ma_amd", "host", "ma_flat_sam.h"),
+            os.path.join(ROOT, "ma_amd", "host", "ma_sam_dev.h"),
             os.path.join(ROOT, "ma_amd", "host", "ma_engine.h")]
     if not os.path.exists(EXE) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"),

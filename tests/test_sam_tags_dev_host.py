@@ -16,9 +16,9 @@ BUILDS = {"plain": ["-O2"], "sanitized": ["-O1", "-g", "-fsanitize=address,undef
 
 def build_exe(kind="plain"):
     exe = os.path.join(ROOT, "tests", "emul", "sam_tags_dev_test" + ("" if kind == "plain" else "_san"))
-    deps = [SRC, os.path.join(ROOT, "include", "ma_amd.h"), os.path.join(ROOT, "oracle", "dump_format.h"),
-            os.path.join(ROOT, "ma_amd", "libma_amd.so")] + [
-        os.path.join(ROOT, "ma_amd", "host", h) for h in ("ma_sam_dev.h", "ma_sam.h", "ma_modules.h", "ms_graph.h")]
+    deps = [SRC, os.path.join(ROOT, "tests", "emul", "sam_dev_common.h"), os.path.join(ROOT, "include", "ma_amd.h"),
+            os.path.join(ROOT, "oracle", "dump_format.h"), os.path.join(ROOT, "ma_amd", "libma_amd.so")] + [
+        os.path.join(ROOT, "ma_amd", "host", h) for h in ("ma_sam_dev.h", "ma_flat_sam.h", "ma_sam.h", "ma_modules.h", "ms_graph.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-Wall"] + BUILDS[kind] + ["-I" + os.path.join(ROOT, "include"),
                                "-I" + os.path.join(ROOT, "ma_amd", "host"), SRC, "-o", exe, "-L" + os.path.join(ROOT, "ma_amd"),
