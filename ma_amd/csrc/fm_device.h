@@ -87,39 +87,45 @@ MA_HD void init_interval( const IndexView& x, u32 c, i64 ik[ 3 ] ) // fMIndex.h:
 // One FMD backward step. Reads the block of row k-1 and of row l-1 (one 64-B line each; the second
 // load is skipped when both rows fall into the same block). nblocks returns 0/1/2 for the
 // algorithmic-bytes counter.
-MA_HD void extend_backward( const IndexView& x, const i64 ik[ 3 ], u32 c, i64 ok[ 3 ], u32& nblocks )
+// The step in two halves, so that a caller can put loads of its own between them and have all of them share one memory round trip
+// (seeding.h: seed_step).  ExtendReq: the one or two blocks of a step, requested.
+struct ExtendReq
+{
+    Block64 bk, bl;
+    i64 kk, ll;
+    bool hasK, hasL;
+};
+MA_HD void extend_request( const IndexView& x, const i64 ik[ 3 ], ExtendReq& R, u32& nblocks )
 {
     nblocks = 0;
-    if( c >= 4 )
-    {
-        ok[ 0 ] = ok[ 1 ] = ok[ 2 ] = 0;
-        return;
-    }
     const i64 start = ik[ 0 ], size = ik[ 2 ], end = start + size;
-    i64 k = start - 1, l = end - 1;
-    u64 cntk[ 4 ] = { 0, 0, 0, 0 }, cntl[ 4 ] = { 0, 0, 0, 0 };
-    const i64 kk = k - ( k >= x.primary ), ll = l - ( l >= x.primary ); // '$' is not stored
-    const bool hasK = k != -1, hasL = l != -1;
-    Block64 bk, bl;
-    if( hasK )
+    const i64 k = start - 1, l = end - 1;
+    R.kk = k - ( k >= x.primary ), R.ll = l - ( l >= x.primary ); // '$' is not stored
+    R.hasK = k != -1, R.hasL = l != -1;
+    if( R.hasK )
     {
-        load_block( x.bwt, (u64)kk >> 7, bk );
+        load_block( x.bwt, (u64)R.kk >> 7, R.bk );
         nblocks++;
     }
-    if( hasL )
+    if( R.hasL )
     {
-        if( hasK && ( (u64)kk >> 7 ) == ( (u64)ll >> 7 ) )
-            bl = bk;
+        if( R.hasK && ( (u64)R.kk >> 7 ) == ( (u64)R.ll >> 7 ) )
+            R.bl = R.bk;
         else
         {
-            load_block( x.bwt, (u64)ll >> 7, bl );
+            load_block( x.bwt, (u64)R.ll >> 7, R.bl );
             nblocks++;
         }
     }
-    if( hasK )
-        occ4_in_block( bk, (u32)( (u64)kk & 127 ), cntk );
-    if( hasL )
-        occ4_in_block( bl, (u32)( (u64)ll & 127 ), cntl );
+}
+MA_HD void extend_result( const IndexView& x, const i64 ik[ 3 ], u32 c, const ExtendReq& R, i64 ok[ 3 ] )
+{
+    const i64 start = ik[ 0 ], end = start + ik[ 2 ];
+    u64 cntk[ 4 ] = { 0, 0, 0, 0 }, cntl[ 4 ] = { 0, 0, 0, 0 };
+    if( R.hasK )
+        occ4_in_block( R.bk, (u32)( (u64)R.kk & 127 ), cntk );
+    if( R.hasL )
+        occ4_in_block( R.bl, (u32)( (u64)R.ll & 127 ), cntl );
     // selects instead of c-indexed arrays: a dynamically indexed local array would live in scratch memory
     const u64 s0 = cntl[ 0 ] - cntk[ 0 ], s1 = cntl[ 1 ] - cntk[ 1 ], s2 = cntl[ 2 ] - cntk[ 2 ], s3 = cntl[ 3 ] - cntk[ 3 ];
     u64 c2 = (u64)ik[ 1 ];
@@ -133,7 +139,45 @@ MA_HD void extend_backward( const IndexView& x, const i64 ik[ 3 ], u32 c, i64 ok
     ok[ 1 ] = (i64)( c == 0 ? a3 : ( c == 1 ? a2 : ( c == 2 ? a1 : a0 ) ) );
     ok[ 2 ] = (i64)( c == 0 ? s0 : ( c == 1 ? s1 : ( c == 2 ? s2 : s3 ) ) );
 }
+MA_HD void extend_backward( const IndexView& x, const i64 ik[ 3 ], u32 c, i64 ok[ 3 ], u32& nblocks )
+{
+    nblocks = 0;
+    if( c >= 4 )
+    {
+        ok[ 0 ] = ok[ 1 ] = ok[ 2 ] = 0;
+        return;
+    }
+    ExtendReq R;
+    extend_request( x, ik, R, nblocks );
+    extend_result( x, ik, c, R, ok );
+}
 
+// The row an LF step (bwt_invPsi) leads to from stored row xx, whose block is b.  SEL: the word of the row by selects instead of
+// an index -- a dynamically indexed member keeps whatever holds the block in scratch memory (seeding.h: seed_step)
+template <bool SEL = false> MA_HD i64 inv_psi_in_block( const IndexView& x, const Block64& b, i64 xx )
+{
+    const u32 within = (u32)( (u64)xx & 127 ), wi = within >> 4;
+    u32 word;
+    if( SEL )
+    {
+        // selects of VALUES: without the empty asm the compiler folds them back into one load through a selected address (seed_qbyte)
+        u32 w0 = b.w[ 0 ], w1 = b.w[ 1 ], w2 = b.w[ 2 ], w3 = b.w[ 3 ], w4 = b.w[ 4 ], w5 = b.w[ 5 ], w6 = b.w[ 6 ], w7 = b.w[ 7 ];
+#if defined( __HIP_DEVICE_COMPILE__ )
+        asm( "" : "+v"( w0 ), "+v"( w1 ), "+v"( w2 ), "+v"( w3 ), "+v"( w4 ), "+v"( w5 ), "+v"( w6 ), "+v"( w7 ) );
+#endif
+        word = wi & 4 ? ( wi & 2 ? ( wi & 1 ? w7 : w6 ) : ( wi & 1 ? w5 : w4 ) ) : ( wi & 2 ? ( wi & 1 ? w3 : w2 ) : ( wi & 1 ? w1 : w0 ) );
+    }
+    else
+        word = b.w[ wi ];
+    const u32 c = ( word >> ( ( ~within & 15 ) << 1 ) ) & 3;
+    // bwt_occ(k, c): k == n handled by the caller contract (rows are < n here); k -= (k >= primary)
+    // equals xx for k != primary
+    u64 cnt[ 4 ];
+    occ4_in_block( b, within, cnt );
+    const u64 l2c = c == 0 ? l2v( x, 0 ) : ( c == 1 ? l2v( x, 1 ) : ( c == 2 ? l2v( x, 2 ) : l2v( x, 3 ) ) );
+    const u64 cc = c == 0 ? cnt[ 0 ] : ( c == 1 ? cnt[ 1 ] : ( c == 2 ? cnt[ 2 ] : cnt[ 3 ] ) );
+    return (i64)( l2c + cc );
+}
 // bwt_invPsi (fMIndex.h:329-343): one 64-B block per LF step (B0 and occ hit the same block)
 MA_HD i64 inv_psi( const IndexView& x, i64 k )
 {
@@ -142,15 +186,7 @@ MA_HD i64 inv_psi( const IndexView& x, i64 k )
     const i64 xx = k - ( k > x.primary );
     Block64 b;
     load_block( x.bwt, (u64)xx >> 7, b );
-    const u32 within = (u32)( (u64)xx & 127 );
-    const u32 c = ( b.w[ within >> 4 ] >> ( ( ~within & 15 ) << 1 ) ) & 3;
-    // bwt_occ(k, c): k == n handled by the caller contract (rows are < n here); k -= (k >= primary)
-    // equals xx for k != primary
-    u64 cnt[ 4 ];
-    occ4_in_block( b, within, cnt );
-    const u64 l2c = c == 0 ? l2v( x, 0 ) : ( c == 1 ? l2v( x, 1 ) : ( c == 2 ? l2v( x, 2 ) : l2v( x, 3 ) ) );
-    const u64 cc = c == 0 ? cnt[ 0 ] : ( c == 1 ? cnt[ 1 ] : ( c == 2 ? cnt[ 2 ] : cnt[ 3 ] ) );
-    return (i64)( l2c + cc );
+    return inv_psi_in_block( x, b, xx );
 }
 
 // SA value of a sampled row (k a multiple of the sampling interval in use)

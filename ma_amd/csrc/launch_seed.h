@@ -222,6 +222,7 @@ int ma_seed_batch( ma_batch* b )
     const u64 n = b->n_reads;
     MA_HIP( hipMemsetAsync( b->ctr.p, 0, CTR_COUNT * 8, b->stream ) );
     b->nSegs = b->nSeeds = b->nHsets = b->nHseeds = 0;
+    b->segMarked = false;
     if( n == 0 )
     {
         b->stage_done = 1;
@@ -322,7 +323,17 @@ int ma_seed_batch( ma_batch* b )
             A.slow_batch = A.P.technique == 0 ? ( A.q_lds ? 4 : 16 ) : 8;
             if( const char* e = getenv( "MA_SEED_SLOW_BATCH" ) ) // tuning hook
                 A.slow_batch = (u32)std::max( 1, atoi( e ) );
-            if( A.q_lds )
+            // maxSpan reads out of LDS: runs whose interval is down to one row compare with the packed text (seeding.h: text mode).
+            // With min_amb >= 1 such a run stops at once, so the plain kernel serves; MA_SEED_TEXT=0: A/B + test hook
+            bool text = !smem && A.q_lds && A.P.min_amb == 0;
+            if( const char* e = getenv( "MA_SEED_TEXT" ) )
+                text = text && atoi( e ) != 0;
+            if( text )
+            {
+                b->segMarked = true;
+                hipLaunchKernelGGL( ( k_seed<false, true> ), dim3( (unsigned)( lanes / 256 ) ), dim3( 256 ), A.q_lds * 256, b->stream, A );
+            }
+            else if( A.q_lds )
                 hipLaunchKernelGGL( smem ? k_seed<true> : k_seed<false>, dim3( (unsigned)( lanes / 256 ) ), dim3( 256 ), A.q_lds * 256, b->stream, A );
             else
             {

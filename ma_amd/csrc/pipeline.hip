@@ -114,6 +114,7 @@ struct ma_batch
     DevBuf stage, smemA, smemB, segPool, segRead, segOff, segCnt, memsCnt, memsOff;
     DevBuf taskA, taskB, taskCnt, taskKey, taskKey2, taskPerm, taskPerm2, taskStage; // (taskStage: per-lane segments of an SMEM task) // area tasks of long reads (seed_tasks)
     u64 segPoolCap = 0, segPoolMin = 0;
+    bool segMarked = false; // the pool may hold segments that carry a position instead of rows (seeding.h: text mode); see seg_materialise
     // extraction
     DevBuf segSeedCnt, segSeedOff, seedOff, seedCnt, seeds, cubTmp;
     u64 nSegs = 0, nSeeds = 0;
@@ -549,6 +550,7 @@ int ma_batch_set_segments( ma_batch* b, const uint64_t* seg_off, const ma_segmen
         return fail( "ma_batch_set_segments: no reads set or null argument" );
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads, ns = seg_off[ n ];
+    b->segMarked = false;
     std::vector<u64> o;
     std::vector<u32> c, rd( ns + 1 );
     csr_parts( seg_off, n, o, c );
@@ -874,6 +876,21 @@ int ma_batch_counts( ma_batch* b, uint64_t* n_segments, uint64_t* n_seeds, uint6
     return 0;
 }
 
+// The public segment record holds rows.  The text mode of k_seed leaves segments that carry their position instead; whoever hands
+// segments out calls this first.  Not part of the aligned path: extraction takes the position as it is.
+static int seg_materialise( ma_batch* b, u64 ns )
+{
+    if( !b->segMarked || ns == 0 )
+        return 0;
+    hipLaunchKernelGGL( k_seg_materialise, dim3( (unsigned)( ( ns + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream, b->idx->v, b->d_reads, b->d_roff,
+                        b->segRead.as<u32>( ), b->segPool.as<ma_segment>( ), ns );
+    MA_HIP( hipGetLastError( ) );
+    if( batch_wait( b ) )
+        return 1;
+    b->segMarked = false;
+    return 0;
+}
+
 // Downloads gather the per-read ranges (pools are in completion order) into read-order CSR arrays.
 int ma_batch_get_segments( ma_batch* b, uint64_t* seg_off, ma_segment* segs )
 {
@@ -883,6 +900,8 @@ int ma_batch_get_segments( ma_batch* b, uint64_t* seg_off, ma_segment* segs )
     if( ma_batch_sync( b ) )
         return 1;
     const u64 n = b->n_reads, ns = b->hctr[ CTR_SEG_USED ];
+    if( seg_materialise( b, ns ) )
+        return 1;
     std::vector<u64> off( n );
     std::vector<u32> cnt( n );
     std::vector<ma_segment> pool( ns );

@@ -1,7 +1,8 @@
 // seeding.h -- BinarySeeding (binarySeeding.h:55-452, binarySeeding.cpp:32-178) as a per-read state
 // machine that performs exactly one FMIndex::extend_backward per step, so that the 64 reads of a
 // wavefront advance in lockstep through one shared "load two occ blocks + popcount" code path
-// regardless of which extension phase each read is in.
+// regardless of which extension phase each read is in.  (Template flag TXT, k_seed on reads in LDS: a maxSpan run whose
+// interval is down to one row goes on by comparing the read with the packed text, 32 bases per step -- "text mode" below.)
 #pragma once
 #include "fm_device.h"
 
@@ -531,6 +532,152 @@ MA_HD bool seed_stop( const SeedParams& P, const i64 ok[ 3 ], const i64 ik[ 3 ] 
     return ok[ 2 ] <= (i64)P.min_amb && ik[ 2 ] <= (i64)P.max_amb;
 }
 
+// ---- text mode of the maxSpan runs (template flag TXT) ---------------------------------------------------------------------
+// Once the interval of a run has shrunk to ONE row, every further extend_backward answers a single question: does the next base
+// of the read equal the next base of the reference at the one locus the row stands for?  For a 6.2 Gnt text that is the case after
+// 17-20 bases, so about 230 of the 270 occ blocks a unique 150 bp read gathers are spent on it, one random 64-byte line per base.
+// The packed text answers it for 32 bases with one line.  A lane whose interval reaches size 1 while its run goes on
+//   1. locates the row: p = bwt_sa( ik[ 0 ] ), one LF step per trip through the block load of the lanes that still extend,
+//      then the SA sample (the walk is not new work: a segment that becomes a seed paid it in k_lf_walk);
+//   2. compares: up to 32 read bases per trip against the pack, XOR of 2-bit codes and a count of the equal prefix.
+// The position stays known over the direction switch (binarySeeding.h:118-120), so the second run of a pass compares too.
+//
+// Why the result is the same.  The BWT is that of the doubled text T2 = T . revcomp( T ) of length n, which text_base( ) defines
+// (index_build.hip sorts the suffixes of exactly that text, TextView::at == text_base; the reference's builder reads the same pack,
+// and a base the FASTA gave as N is a plain nucleotide in the pack and therefore in both).  bwt_sa returns positions in T2 --
+// k_seed_final folds r >= n / 2 -- and T2 is its own reverse complement: pattern P stands at p iff revcomp( P ) stands at n - p - |P|.
+//  * Left step.  ik[ 0 ] = k is the row of the suffix at p = SA[ k ], ik[ 2 ] == 1.  extend_backward by c counts the rows of
+//    [ k, k + 1 ) whose BWT character is c: size 1 iff the character in front of the suffix is c, i.e. iff p > 0 and
+//    text_base( p - 1 ) == c; the new row is that of the suffix at p - 1.  At p == 0 (row `primary`, whose BWT character is '$')
+//    every base fails.
+//  * Right step by read base b.  The machine extends the interval of the reverse complement, which stands at n - p - len, by
+//    comp_base( b ): size 1 iff n - p - len > 0 and text_base( n - p - len - 1 ) == 3 - b, and the mirror of that position is
+//    p + len: iff p + len < n and text_base( p + len ) == b.  The end of the text fails like its start.
+//  * A read base >= 4 gives size 0 in extend_backward and counts as a mismatch here.
+//  * The junction of the strands at F and the borders of contigs are no special case in the BWT, and none here: matches across
+//    them are found by both and dealt with downstream (bridging seeds) as before.
+//  * The stop rule (seed_stop): with min_amb >= 1 an interval of size 1 stops the run at once, so the mode is entered only for
+//    min_amb == 0, where a run stops iff the extension is empty.
+// State: ik[ 2 ] == 1 and ik[ 1 ] < 0 (a row is never negative).  Locating: ik[ 0 ] = the row reached, -1 - ik[ 1 ] = LF steps so far.
+// Comparing: ik[ 1 ] == MA_TM_CMP, ik[ 0 ] = p, the position in T2 of q[ start .. end ].  A lane enters the mode only with an extension
+// of the same run pending, so a run never ends -- and never turns -- while its row is being located.
+// A segment emitted in this state carries sa_start = -1 - p, sa_start_rc = -1, sa_size = 1: extraction takes the position as
+// given (stage_extract.h), and seed_materialise recomputes the rows where someone asks for the record.
+#define MA_TM_CMP ( (i64)( 1ull << 63 ) )
+template <bool TXT> MA_HD void seed_text_enter( SeedLane& L, const SeedParams& P )
+{
+    if( !TXT || P.min_amb != 0 || L.ik[ 2 ] != 1 )
+        return;
+    const bool right = L.phase == PH_P1_RIGHT || L.phase == PH_P2_RIGHT;
+    if( right ? L.i < L.qlen : L.i != 0xffffffffu )
+        L.ik[ 1 ] = -1;
+}
+// rows of a segment that carries a position: the bi-interval is a function of the pattern, found by plain backward search
+MA_HD void seed_materialise( const IndexView& X, const uint8_t* q, ma_segment& s )
+{
+    if( s.sa_start >= 0 )
+        return;
+    i64 ik[ 3 ];
+    init_interval( X, q[ s.q_start + s.q_size ], ik );
+    for( i64 i = s.q_start + s.q_size - 1; i >= s.q_start; i-- )
+    {
+        i64 ok[ 3 ];
+        u32 nb;
+        extend_backward( X, ik, q[ i ], ok, nb );
+        ik[ 0 ] = ok[ 0 ], ik[ 1 ] = ok[ 1 ], ik[ 2 ] = ok[ 2 ];
+    }
+    s.sa_start = ik[ 0 ], s.sa_start_rc = ik[ 1 ], s.sa_size = ik[ 2 ];
+}
+MA_HD u64 rev2_64( u64 v ) // the 32 2-bit groups of v in reverse order
+{
+    v = ( ( v >> 2 ) & 0x3333333333333333ull ) | ( ( v & 0x3333333333333333ull ) << 2 );
+    v = ( ( v >> 4 ) & 0x0f0f0f0f0f0f0f0full ) | ( ( v & 0x0f0f0f0f0f0f0f0full ) << 4 );
+    return __builtin_bswap64( v );
+}
+MA_HD u64 low2m( u32 m ) // the low 2 m bits, m <= 32
+{
+    return m >= 32 ? ~0ull : ( 1ull << ( 2u * m ) ) - 1ull;
+}
+// 2-bit codes of the read's bases [ a, a + m ), m <= 32: base a + j at bits 2j, 2j + 1 of w; bit 2j of bad set where it is no nucleotide.
+// FAST: five 8-byte groups instead of m byte loads; q is 4-byte aligned and readable up to the next multiple of 8 past a + m (the LDS
+// copy of k_seed: its stride covers the read's length rounded up to 8)
+template <bool FAST> MA_HD void text_read_pack( const uint8_t* q, u32 a, u32 m, u64& w, u64& bad )
+{
+    if( FAST )
+    {
+        auto g = []( u64 v ) -> u64 {
+            v = ( v | ( v >> 6 ) ) & 0x000f000f000f000full;
+            v = ( v | ( v >> 12 ) ) & 0x000000ff000000ffull;
+            return ( v | ( v >> 24 ) ) & 0xffffull;
+        };
+        const u32 g0 = a & ~7u;
+        u64 v[ 5 ];
+#pragma unroll
+        for( u32 t = 0; t < 5; t++ )
+        {
+            v[ t ] = 0;
+            if( g0 + 8 * t < a + m )
+            {
+                const u32* p = (const u32*)__builtin_assume_aligned( q + g0 + 8 * t, 4 );
+                v[ t ] = (u64)p[ 0 ] | (u64)p[ 1 ] << 32;
+            }
+        }
+        u64 c[ 5 ], n[ 5 ];
+#pragma unroll
+        for( u32 t = 0; t < 5; t++ )
+        {
+            c[ t ] = g( v[ t ] & 0x0303030303030303ull );
+            const u64 hi = ( v[ t ] >> 2 ) & 0x3f3f3f3f3f3f3f3full; // a byte's bits 2..7: non-zero = no nucleotide
+            n[ t ] = g( ( ( hi + 0x3f3f3f3f3f3f3f3full ) >> 6 ) & 0x0101010101010101ull );
+        }
+        const u64 cl = c[ 0 ] | c[ 1 ] << 16 | c[ 2 ] << 32 | c[ 3 ] << 48, nl = n[ 0 ] | n[ 1 ] << 16 | n[ 2 ] << 32 | n[ 3 ] << 48;
+        const u32 s = 2u * ( a & 7u );
+        w = ( s ? ( cl >> s ) | ( c[ 4 ] << ( 64u - s ) ) : cl ) & low2m( m );
+        bad = ( s ? ( nl >> s ) | ( n[ 4 ] << ( 64u - s ) ) : nl ) & low2m( m );
+        return;
+    }
+    w = bad = 0;
+    for( u32 j = 0; j < m; j++ )
+    {
+        const u32 b = q[ a + j ];
+        w |= (u64)( b & 3u ) << ( 2u * j );
+        bad |= (u64)( b >= 4 ? 1u : 0u ) << ( 2u * j );
+    }
+}
+// The pack's forward bases [ g, g + m ), m <= 32, base g + j at bits 2j, 2j + 1.  FAST: out of the two aligned 8-byte words w0, w1 that
+// text_pac_request loaded (the pack is 8-byte aligned and readable 16 bytes past its last base: ma_index_create pads it)
+MA_HD u64 text_pac_word( u64 g )
+{
+    return ( g >> 2 ) & ~7ull;
+}
+template <bool FAST> MA_HD void text_pac_request( const IndexView& X, u64 g, u64& w0, u64& w1 )
+{
+    w0 = w1 = 0;
+    if( FAST )
+    {
+        const u64* p = (const u64*)__builtin_assume_aligned( X.pac + text_pac_word( g ), 8 );
+        w0 = p[ 0 ], w1 = p[ 1 ];
+    }
+}
+template <bool FAST> MA_HD u64 text_pac_pack( const IndexView& X, u64 g, u32 m, u64 w0, u64 w1 )
+{
+    if( FAST )
+    {
+        // a byte holds its four bases most significant first: reverse the groups of every byte
+        auto r = []( u64 v ) -> u64 {
+            v = ( ( v >> 2 ) & 0x3333333333333333ull ) | ( ( v & 0x3333333333333333ull ) << 2 );
+            return ( ( v >> 4 ) & 0x0f0f0f0f0f0f0f0full ) | ( ( v & 0x0f0f0f0f0f0f0f0full ) << 4 );
+        };
+        w0 = r( w0 ), w1 = r( w1 );
+        const u32 s = 2u * (u32)( g - 4ull * text_pac_word( g ) ); // 0 .. 62
+        return ( s ? ( w0 >> s ) | ( w1 << ( 64u - s ) ) : w0 ) & low2m( m );
+    }
+    u64 w = 0;
+    for( u32 j = 0; j < m; j++ )
+        w |= (u64)fwd_base( X, g + j ) << ( 2u * j );
+    return w;
+}
+
 // Can the lane extend right away, i.e. without any phase transition?  (The kernel batches the transitions of a
 // wavefront: a lane whose transition is due idles for a few steps until enough lanes wait, so that the divergent
 // bookkeeping of seed_prepare is executed once for many lanes instead of on every step for one or two.)
@@ -611,7 +758,8 @@ template <bool WIN> MA_HD void seed_prefetch( SeedLane& L, const SeedParams& P )
 // Runs cheap bookkeeping until the lane either needs an extension (returns true and sets c) or is done.
 // JUMP: use the K-mer table of the index (only the kernel whose register budget has room for it: inlined into the
 // read-per-lane kernel it costs a wave of occupancy, 117 -> 138 VGPRs, which eats the gain)
-template <bool WIN = false, bool JUMP = false, bool SM = true, bool MS = true> MA_HD bool seed_prepare( SeedLane& L, const SeedParams& P, const SeedScratch& S, const IndexView& X, u32& c )
+// TXT: the text mode of the maxSpan runs (above)
+template <bool WIN = false, bool JUMP = false, bool SM = true, bool MS = true, bool TXT = false> MA_HD bool seed_prepare( SeedLane& L, const SeedParams& P, const SeedScratch& S, const IndexView& X, u32& c )
 {
     while( true )
     {
@@ -637,14 +785,15 @@ template <bool WIN = false, bool JUMP = false, bool SM = true, bool MS = true> M
                         seed_after_center( L, S, L.center, 1 );
                         break;
                     }
-                    L.end = L.center;
+                    L.start = L.end = L.center; // (start: what the left run begins with; the text mode reads the match's extent on the way)
                     L.i = L.center + 1;
+                    L.phase = PH_P1_RIGHT;
                     if( JUMP && kmer_decode( P, eRx, eRy, L.ik ) )
                     {
                         L.end = L.center + X.kmer_k - 1;
                         L.i = L.center + X.kmer_k;
+                        seed_text_enter<TXT>( L, P );
                     }
-                    L.phase = PH_P1_RIGHT;
                 }
                 else if( SM )
                 {
@@ -666,8 +815,9 @@ template <bool WIN = false, bool JUMP = false, bool SM = true, bool MS = true> M
                     c = comp_base( seed_qbyte_c<WIN>( L, P, X, L.i ) );
                     return true;
                 }
-                // end of query: switch direction (binarySeeding.h:118-120)
-                mswap( L.ik[ 0 ], L.ik[ 1 ] );
+                // end of query: switch direction (binarySeeding.h:118-120); a lane in text mode keeps its position
+                if( !TXT || L.ik[ 1 ] >= 0 )
+                    mswap( L.ik[ 0 ], L.ik[ 1 ] );
                 L.start = L.center;
                 if( L.center > 0 )
                 {
@@ -687,17 +837,21 @@ template <bool WIN = false, bool JUMP = false, bool SM = true, bool MS = true> M
                     return true;
                 }
                 // record first segment and start the second pass (binarySeeding.h:152-163)
-                seed_emit( L, S, L.start, L.end - L.start, L.ik[ 0 ], L.ik[ 1 ], L.ik[ 2 ] );
+                if( TXT && L.ik[ 1 ] < 0 )
+                    seed_emit( L, S, L.start, L.end - L.start, -1 - L.ik[ 0 ], -1, 1 );
+                else
+                    seed_emit( L, S, L.start, L.end - L.start, L.ik[ 0 ], L.ik[ 1 ], L.ik[ 2 ] );
                 L.s1_start = L.start;
                 L.s1_end = L.end;
                 init_interval( X, seed_qbyte_c<WIN>( L, P, X, L.center ), L.ik );
-                L.start = L.center;
+                L.start = L.end = L.center;
                 L.phase = PH_P2_LEFT;
                 L.i = L.center > 0 ? L.center - 1 : 0xffffffffu;
                 if( JUMP && kmer_decode( P, L.eL0, L.eL1, L.ik ) )
                 {
                     L.start = L.center - ( X.kmer_k - 1 );
                     L.i = L.start > 0 ? L.start - 1 : 0xffffffffu;
+                    seed_text_enter<TXT>( L, P );
                 }
                 break;
             case PH_P2_LEFT:
@@ -708,7 +862,8 @@ template <bool WIN = false, bool JUMP = false, bool SM = true, bool MS = true> M
                     c = seed_qbyte_c<WIN>( L, P, X, L.i );
                     return true;
                 }
-                mswap( L.ik[ 0 ], L.ik[ 1 ] );
+                if( !TXT || L.ik[ 1 ] >= 0 )
+                    mswap( L.ik[ 0 ], L.ik[ 1 ] );
                 L.end = L.center;
                 L.i = L.center + 1;
                 L.phase = PH_P2_RIGHT;
@@ -727,7 +882,10 @@ template <bool WIN = false, bool JUMP = false, bool SM = true, bool MS = true> M
                         seed_after_center( L, S, L.s1_start, L.s1_end - L.s1_start );
                     else
                     {
-                        seed_emit( L, S, L.start, L.end - L.start, L.ik[ 1 ], L.ik[ 0 ], L.ik[ 2 ] );
+                        if( TXT && L.ik[ 1 ] < 0 )
+                            seed_emit( L, S, L.start, L.end - L.start, -1 - L.ik[ 0 ], -1, 1 );
+                        else
+                            seed_emit( L, S, L.start, L.end - L.start, L.ik[ 1 ], L.ik[ 0 ], L.ik[ 2 ] );
                         const u32 s = L.start < L.s1_start ? L.start : L.s1_start;
                         const u32 e = L.end > L.s1_end ? L.end : L.s1_end;
                         seed_after_center( L, S, s, e - s );
@@ -828,7 +986,7 @@ template <bool WIN = false, bool JUMP = false, bool SM = true, bool MS = true> M
 }
 
 // ---- apply the result of the extension requested by seed_prepare --------------------------------
-template <bool SM = true, bool MS = true> MA_HD void seed_apply( SeedLane& L, const SeedParams& P, const SeedScratch& S, const i64 ok[ 3 ] )
+template <bool SM = true, bool MS = true, bool TXT = false> MA_HD void seed_apply( SeedLane& L, const SeedParams& P, const SeedScratch& S, const i64 ok[ 3 ] )
 {
     switch( L.phase )
     {
@@ -843,6 +1001,7 @@ template <bool SM = true, bool MS = true> MA_HD void seed_apply( SeedLane& L, co
                 L.end = L.i;
                 L.ik[ 0 ] = ok[ 0 ], L.ik[ 1 ] = ok[ 1 ], L.ik[ 2 ] = ok[ 2 ];
                 L.i++;
+                seed_text_enter<TXT>( L, P );
             }
             break;
         case PH_P1_LEFT:
@@ -856,6 +1015,7 @@ template <bool SM = true, bool MS = true> MA_HD void seed_apply( SeedLane& L, co
                 L.start = L.i;
                 L.ik[ 0 ] = ok[ 0 ], L.ik[ 1 ] = ok[ 1 ], L.ik[ 2 ] = ok[ 2 ];
                 L.i = L.i == 0 ? 0xffffffffu : L.i - 1;
+                seed_text_enter<TXT>( L, P );
             }
             break;
         case PH_SMEM_FWD:
@@ -1010,18 +1170,137 @@ MA_HD void mems_from( const IndexView& X, const SeedParams& P, const uint8_t* q,
     }
 }
 
-// Whole read on one lane (used by the host emulation and as the loop body of the kernel).
-MA_HD void seed_read_serial( SeedLane& L, const SeedParams& P, const SeedScratch& S, const IndexView& X )
+// One trip of a lane that seed_try / seed_prepare found ready to extend by c: an FM step -- or, TXT, whatever the lane's text mode
+// is at: an LF step of the locate walk, the SA sample at its end, or a compare of up to 32 bases.  All loads are requested before
+// any result is looked at, so the lanes of a wavefront share one memory round trip whichever of the four they do.
+// steps counts the extend_backward calls, blocks every 64-byte line asked for (occ, LF, SA sample and text).
+// FAST: see text_read_pack / text_pac_request
+template <bool TXT, bool SM, bool MS, bool FAST> MA_HD void seed_step( SeedLane& L, const SeedParams& P, const SeedScratch& S, const IndexView& X, u32 c )
 {
-    u32 c;
-    while( seed_prepare( L, P, S, X, c ) )
+    i64 ok[ 3 ];
+    u32 nb;
+    if( !TXT )
     {
-        i64 ok[ 3 ];
-        u32 nb;
         extend_backward( X, L.ik, c, ok, nb );
         L.steps++;
         L.blocks += nb;
-        seed_apply( L, P, S, ok );
+        seed_apply<SM, MS>( L, P, S, ok );
+        return;
     }
+    const bool fm = L.ik[ 1 ] >= 0, cmp = L.ik[ 1 ] == MA_TM_CMP;
+    const bool smp = !fm && !cmp && ( L.ik[ 0 ] & ( ( (i64)1 << X.sa_shift ) - 1 ) ) == 0, lf = !fm && !cmp && !smp;
+    const bool right = L.phase == PH_P1_RIGHT || L.phase == PH_P2_RIGHT;
+    const u32 len = L.end - L.start + 1;
+    // ---- requests
+    ExtendReq R;
+    R.hasK = R.hasL = false;
+    R.kk = R.ll = 0;
+    nb = 0;
+    if( fm && c < 4 )
+        extend_request( X, L.ik, R, nb );
+    else if( lf && L.ik[ 0 ] != X.primary )
+    {
+        R.kk = L.ik[ 0 ] - ( L.ik[ 0 ] > X.primary );
+        R.hasK = true;
+        load_block( X.bwt, (u64)R.kk >> 7, R.bk );
+        nb = 1;
+    }
+    i64 sv = 0;
+    if( smp )
+    {
+        sv = sa_sample( X, L.ik[ 0 ] );
+        nb = 1;
+    }
+    // compare: m bases, the read's from a on, the pack's from g on; rev: the locus lies on the reverse strand (the pack's bases
+    // run against the read's and are complemented); top: the first base compared is the chunk's last
+    u32 m = 0, a = 0;
+    u64 g = 0, w0 = 0, w1 = 0;
+    bool rev = false;
+    if( cmp )
+    {
+        const u64 p = (u64)L.ik[ 0 ];
+        if( right )
+        {
+            const u64 pos = p + len;
+            rev = pos >= X.F;
+            const u64 avail = pos >= X.n ? 0 : ( rev ? X.n - pos : X.F - pos );
+            m = (u32)mmin<u64>( mmin<u64>( 32, L.qlen - L.i ), avail );
+            a = L.i;
+            g = rev ? X.n - pos - m : pos;
+        }
+        else
+        {
+            rev = p > X.F;
+            const u64 avail = rev ? p - X.F : p;
+            m = (u32)mmin<u64>( mmin<u64>( 32, (u64)L.i + 1 ), avail );
+            a = L.i + 1 - m;
+            g = rev ? X.n - p : p - m;
+        }
+        if( m )
+        {
+            text_pac_request<FAST>( X, g, w0, w1 );
+            nb = 1 + ( ( text_pac_word( g ) & 63 ) == 56 ? 1 : 0 );
+        }
+    }
+    L.blocks += nb;
+    // ---- results
+    if( fm )
+    {
+        if( c < 4 )
+            extend_result( X, L.ik, c, R, ok );
+        else
+            ok[ 0 ] = ok[ 1 ] = ok[ 2 ] = 0;
+        L.steps++;
+        seed_apply<SM, MS, TXT>( L, P, S, ok );
+    }
+    else if( lf )
+    {
+        L.ik[ 0 ] = R.hasK ? inv_psi_in_block<true>( X, R.bk, R.kk ) : 0;
+        L.ik[ 1 ]--;
+    }
+    else if( smp )
+    {
+        const i64 r = ( -1 - L.ik[ 1 ] ) + sv; // bwt_sa: where the pattern of ik[ 0 ] stands -- the reverse complement's in a right run
+        L.ik[ 0 ] = right ? (i64)X.n - r - (i64)len : r;
+        L.ik[ 1 ] = MA_TM_CMP;
+    }
+    else
+    {
+        u32 eq = 0;
+        if( m )
+        {
+            u64 w, bad;
+            text_read_pack<FAST>( L.q, a, m, w, bad );
+            u64 t = text_pac_pack<FAST>( X, g, m, w0, w1 );
+            if( rev )
+            {
+                w = rev2_64( w ) >> ( 64u - 2u * m );
+                bad = rev2_64( bad ) >> ( 64u - 2u * m );
+                t ^= low2m( m );
+            }
+            const u64 x = ( w ^ t ) | bad;
+            const bool top = right == rev;
+            eq = x == 0 ? m : top ? m - 1 - (u32)( 63 - __builtin_clzll( x ) ) / 2 : (u32)__builtin_ctzll( x ) / 2;
+        }
+        if( right )
+        {
+            L.end += eq;
+            L.i = eq == m && m ? L.i + eq : L.qlen; // a mismatch, or the text's end: the run is over
+        }
+        else
+        {
+            L.ik[ 0 ] -= eq;
+            L.start -= eq;
+            L.i = eq == m && m ? L.i - eq : 0xffffffffu; // (i + 1 == eq: the read's start, the same value)
+        }
+    }
+}
+
+// Whole read on one lane (used by the host emulation and as the loop body of the kernel).
+template <bool TXT = false, bool FAST = false> MA_HD void seed_read_serial( SeedLane& L, const SeedParams& P, const SeedScratch& S, const IndexView& X )
+{
+    u32 c;
+    while( seed_prepare<false, false, true, true, TXT>( L, P, S, X, c ) )
+        seed_step<TXT, true, true, FAST>( L, P, S, X, c );
 }
 } // namespace ma

@@ -45,7 +45,7 @@ __global__ void k_seed_rows( const ma_segment* pool, const u64* seg_seed_off, u6
     const u64 o = seg_seed_off[ i ], cnt = seg_seed_off[ i + 1 ] - o;
     if( cnt == 0 )
         return;
-    const i64 r0 = pool[ i ].sa_start;
+    const i64 r0 = pool[ i ].sa_start; // negative: -1 - position, the segment's one seed needs no walk (seeding.h: text mode)
     for( u64 t = 0; t < cnt; t++ )
     {
         row[ o + t ] = r0 + (i64)t;
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__( 256 ) k_lf_walk( IndexView X, i64* row /* in:
     u64 qCur = 0, qEnd = 0; // this wave's slice of the seed queue: one device atomic per 256 seeds
     while( true )
     {
-        if( have && ( k & saMask ) == 0 )
+        if( have && ( k < 0 || ( k & saMask ) == 0 ) ) // (k < 0: a position, handed on as it is)
         {
             row[ j ] = k;
             nsteps[ j ] = st; // not bounded by the sampling interval: the walk ends when it HITS a sampled row
@@ -103,7 +103,7 @@ __global__ void __launch_bounds__( 256 ) k_lf_walk( IndexView X, i64* row /* in:
         }
         if( __ballot( alive ) == 0 )
             break;
-        if( have && ( k & saMask ) )
+        if( have && k >= 0 && ( k & saMask ) )
         {
             k = inv_psi( X, k );
             st++;
@@ -122,7 +122,8 @@ __global__ void k_seed_final( IndexView X, const ma_segment* pool, const u32* po
         const u64 i = seg_of[ j ];
         const ma_segment s = pool[ i ];
         steps = nsteps[ j ];
-        u64 r = (u64)( (i64)steps + sa_sample( X, row[ j ] ) ); // bwt_sa (fMIndex.h:788-814)
+        const i64 k = row[ j ];
+        u64 r = k < 0 ? (u64)( -1 - k ) : (u64)( (i64)steps + sa_sample( X, k ) ); // bwt_sa (fMIndex.h:788-814), or the position the segment carries
         const bool fwd = r < X.n / 2;
         if( !fwd )
             r = X.n - r - 1;

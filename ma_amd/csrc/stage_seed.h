@@ -33,7 +33,8 @@ static __device__ unsigned long long g_seed_prof[ 8 ];
 // One read per lane at a time; lanes refill from a global queue, so a wavefront keeps stepping 64
 // reads in lockstep through extend_backward until the batch is exhausted.
 // LONG: the reads stay in HBM (longer than 240 bases) and are read through the register window of seed_qbyte.
-template <bool LONG, bool SM, bool MS = !SM> __device__ __forceinline__ void seed_kernel_body( const SeedKernelArgs& A )
+// TXT: maxSpan runs whose interval has shrunk to one row go on by comparing the read with the packed text (seeding.h: seed_step)
+template <bool LONG, bool SM, bool TXT = false, bool MS = !SM> __device__ __forceinline__ void seed_kernel_body( const SeedKernelArgs& A )
 {
     const u32 lane = blockIdx.x * blockDim.x + threadIdx.x;
     SeedScratch S;
@@ -161,7 +162,7 @@ template <bool LONG, bool SM, bool MS = !SM> __device__ __forceinline__ void see
 #endif
             if( sm && ( (u32)__popcll( sm ) >= A.slow_batch || __ballot( ext ) == 0 ) )
                 if( act && !ext )
-                    ext = seed_prepare<LONG, true, SM, MS>( L, A.P, S, A.X, c );
+                    ext = seed_prepare<LONG, true, SM, MS, TXT>( L, A.P, S, A.X, c );
 #if defined( MA_KSW_PROF )
             if( sm && ( (u32)__popcll( sm ) >= A.slow_batch || __ballot( ext ) == 0 ) )
                 pf[ 0 ] += clock64( );
@@ -173,14 +174,9 @@ template <bool LONG, bool SM, bool MS = !SM> __device__ __forceinline__ void see
 #endif
         if( ext )
         {
-            i64 ok[ 3 ];
-            u32 nb;
             if( LONG )
                 seed_prefetch<LONG>( L, A.P );
-            extend_backward( A.X, L.ik, c, ok, nb );
-            L.steps++;
-            L.blocks += nb;
-            seed_apply<SM, MS>( L, A.P, S, ok );
+            seed_step<TXT, SM, MS, !LONG>( L, A.P, S, A.X, c );
         }
 #if defined( MA_KSW_PROF )
         const unsigned long long tD = clock64( );
@@ -201,13 +197,26 @@ template <bool LONG, bool SM, bool MS = !SM> __device__ __forceinline__ void see
 }
 // Two register budgets: short reads (staged in LDS) run best without spills at 3 waves per SIMD (137 VGPRs: 8.4 vs 9.2 ms
 // per 1 M x 150 bp reads), long reads want the fourth wave more than the 16 spilled dwords hurt (200 k x 10 kb: 155 vs 180 ms).
-template <bool SM> __global__ void __launch_bounds__( 256 ) k_seed( SeedKernelArgs A )
+template <bool SM, bool TXT = false> __global__ void __launch_bounds__( 256 ) k_seed( SeedKernelArgs A )
 {
-    seed_kernel_body<false, SM>( A );
+    seed_kernel_body<false, SM, TXT>( A );
 }
 template <bool SM> __global__ void __launch_bounds__( 256 ) __attribute__( ( amdgpu_waves_per_eu( 4 ) ) ) k_seed_long( SeedKernelArgs A )
 {
     seed_kernel_body<true, SM>( A );
+}
+
+// rows of the pooled segments that carry a position (seeding.h: seed_materialise), for the getters
+__global__ void k_seg_materialise( IndexView X, const uint8_t* reads, const u64* roff, const u32* pool_read, ma_segment* pool, u64 n )
+{
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if( i >= n )
+        return;
+    ma_segment s = pool[ i ];
+    if( s.sa_start >= 0 )
+        return;
+    seed_materialise( X, reads + roff[ pool_read[ i ] ], s );
+    pool[ i ] = s;
 }
 
 __device__ __forceinline__ u64 wave_sum_u64( u64 v );
