@@ -5,8 +5,8 @@
 //   ma_align [--host-sam] [--ngmlr-tags] <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam|stdout> [preset] [mates.fa|fq[.gz]]
 //
 // Single-end input is printed on the device (BatchAligner::executeFlatSam: the SAM text is what comes down) whenever the
-// options are ones the device serves -- with --ngmlr-tags ("Emulate NGMLR's tag output") too; with "Detect Small Inversions"
-// and with --host-sam the records come down and FileWriter prints them.  Paired input likewise: mates are paired and their
+// options are ones the device serves -- with --ngmlr-tags ("Emulate NGMLR's tag output") and with "Detect Small Inversions"
+// (found on the device, ma_inversions_batch) too; with --host-sam the records come down and FileWriter prints them.  Paired input likewise: mates are paired and their
 // records printed on the device (BatchAligner::executePairedFlatSam), or the pair records come down and
 // BatchPairedFileWriter formats them (the paired writers refuse the tag emulation).  The bytes are the same.
 //

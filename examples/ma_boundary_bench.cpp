@@ -236,7 +236,7 @@ int main( int argc, char** argv )
 {
     if( argc < 6 )
     {
-        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | sam [repeats] | sam-tags [repeats]]\n" );
+        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | sam [repeats] | sam-tags [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
         return 2;
     }
     try
@@ -247,7 +247,7 @@ int main( int argc, char** argv )
         maCheck( ma_set_device( atoi( argv[ 5 ] ) ) );
         maCheck( ma_host_bind_thread( atoi( argv[ 5 ] ), 0, nullptr ) ); // this thread and all it starts: the CPUs next to the GPU
         const unsigned uiHw = std::max( 1u, std::thread::hardware_concurrency( ) );
-        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
+        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         double t0 = now( );
@@ -407,6 +407,89 @@ int main( int argc, char** argv )
             pPack->vPacHost.assign( vPac.begin( ), vPac.end( ) );
         }
         std::vector<uint8_t>( ).swap( vPac );
+        if( argc >= 7 && !strcmp( argv[ 6 ], "inversions" ) )
+        {
+            // ---- the inversions leg: n single-end reads, <share> per mille of them with their middle third (40 .. 300 bases)
+            // reverse-complemented in place, host to host INCLUDING SAM text with "Detect Small Inversions" through (a)
+            // BatchAligner::execute + FileWriter -- Alignment containers, the host module SmallInversions -- and (b) executeFlatSam
+            // -- ma_inversions_batch and ma_sam_batch on the device, the text is what comes down -- and (c) executeFlatSam with
+            // the option OFF: against (b) at share 0 the price of the stage when it finds nothing.  (a) <repeats> times after one
+            // warm-up, then (c) and (b) alternating, 2 x <repeats> times each after one warm-up of each.
+            const int iRepeats = argc >= 8 ? std::max( 1, atoi( argv[ 7 ] ) ) : 3;
+            const uint64_t uiShare = argc >= 9 ? (uint64_t)atoll( argv[ 8 ] ) : 50;
+            const size_t uiInv = std::min<size_t>( 300, std::max<size_t>( 40, uiLen / 3 ) );
+            size_t uiInverted = 0;
+            for( auto& pQ : *pReads )
+                if( uiLen >= 3 * uiInv && rnd( ) % 1000 < uiShare )
+                {
+                    auto b = pQ->xCodes.begin( ) + ( uiLen - uiInv ) / 2;
+                    std::reverse( b, b + uiInv );
+                    for( auto it = b; it != b + uiInv; ++it )
+                        *it = 3 - *it;
+                    uiInverted++;
+                }
+            ParameterSetManager xOn = xParams, xOff = xParams;
+            xOn.getSelected( )->search_inversions = 1;
+            xOff.getSelected( )->search_inversions = 0;
+            BatchAligner xAlignerOn( xOn ), xAlignerOff( xOff );
+            for( BatchAligner* pA : { &xAlignerOn, &xAlignerOff } )
+            {
+                pA->uiBatchReads = std::min<size_t>( pReads->size( ), 1u << 18 );
+                pA->uiInflight = 3;
+                pA->warmUp( pFM, pReads );
+            }
+            uint64_t uiBytesContainer = 0, uiBytesOn = 0, uiBytesOff = 0;
+            AlignerTiming xTimeOn, xTimeOff;
+            auto container = [ & ]( ) {
+                auto pSink = std::make_shared<CountingSink>( );
+                FileWriter xWriter( xOn, std::static_pointer_cast<OutStream>( pSink ), pPack );
+                const double t = now( );
+                auto pRes = xAlignerOn.execute( pFM, pReads );
+                for( size_t r = 0; r < pRes->size( ); r++ )
+                    xWriter.execute( ( *pReads )[ r ], ( *pRes )[ r ], pPack );
+                xWriter.flush( );
+                const double f = now( ) - t;
+                uiBytesContainer = pSink->uiBytes.load( );
+                return f;
+            };
+            auto device = [ & ]( BatchAligner& rAligner, const ParameterSetManager& rP, uint64_t& rBytes, AlignerTiming& rTime ) {
+                auto pSink = std::make_shared<CountingSink>( );
+                BatchFileWriter xWriter( rP, std::static_pointer_cast<OutStream>( pSink ), pPack );
+                const double t = now( );
+                auto pFlat = rAligner.executeFlatSam( pFM, pReads, pPack );
+                for( auto& pB : *pFlat )
+                    xWriter.write( *pB, pPack );
+                const double f = now( ) - t;
+                rTime = rAligner.xLast;
+                rBytes = pSink->uiBytes.load( );
+                return f;
+            };
+            // (the container runs first and apart: the millions of containers a run frees leave the allocator busy under whatever
+            // runs next, which is not what (b) against (c) is to show)
+            std::vector<double> vC, vOn, vOff;
+            container( );
+            for( int r = 0; r < iRepeats; r++ )
+                vC.push_back( n / container( ) );
+            device( xAlignerOn, xOn, uiBytesOn, xTimeOn ), device( xAlignerOff, xOff, uiBytesOff, xTimeOff ); // warm-up of both
+            for( int r = 0; r < 2 * iRepeats; r++ )
+            {
+                vOff.push_back( n / device( xAlignerOff, xOff, uiBytesOff, xTimeOff ) );
+                vOn.push_back( n / device( xAlignerOn, xOn, uiBytesOn, xTimeOn ) );
+            }
+            auto list = []( std::vector<double> v ) {
+                std::sort( v.begin( ), v.end( ) );
+                return "{\"median\": " + std::to_string( v[ v.size( ) / 2 ] ) + ", \"min\": " + std::to_string( v.front( ) ) +
+                       ", \"max\": " + std::to_string( v.back( ) ) + "}";
+            };
+            printf( "{\"inversions\": {\"reads\": %zu, \"read_len\": %zu, \"inverted_reads\": %zu, \"inverted_bases\": %zu, \"repeats\": %d, "
+                    "\"batch_reads\": %zu, \"in_flight\": 3, \"execute_plus_file_writer_reads_per_s\": %s, \"execute_flat_sam_reads_per_s\": %s, "
+                    "\"execute_flat_sam_option_off_reads_per_s\": %s, \"sam_bytes_container\": %llu, \"sam_bytes_device\": %llu, "
+                    "\"sam_bytes_option_off\": %llu, \"stages_s_option_on\": %.4f, \"stages_s_option_off\": %.4f, \"batches\": %llu}}\n",
+                    n, uiLen, uiInverted, uiInv, iRepeats, xAlignerOn.uiBatchReads, list( vC ).c_str( ), list( vOn ).c_str( ), list( vOff ).c_str( ),
+                    (unsigned long long)uiBytesContainer, (unsigned long long)uiBytesOn, (unsigned long long)uiBytesOff, xTimeOn.fKernels,
+                    xTimeOff.fKernels, (unsigned long long)xTimeOn.uiBatches );
+            return uiBytesContainer == uiBytesOn ? 0 : 1;
+        }
         if( argc >= 7 && ( !strcmp( argv[ 6 ], "sam" ) || bSamTags ) )
         {
             // ---- the SAM leg: n single-end reads host to host INCLUDING SAM text through (a) BatchAligner::executeFlat +

@@ -60,7 +60,8 @@ typedef struct
     int32_t report_n_best; /* 0                                  xReportN */
     int32_t max_supplementary; /* 1                              xMaxSupplementaryPerPrim */
     double max_overlap_supplementary; /* 0.1                     xMaxOverlapSupplementary */
-    /* read by the host module SmallInversions */
+    /* small inversions: search_inversions is read by the host layer only (it puts the module into the graph,
+       ma_inversions_batch into the flat paths); zdrop_inversion by ma_inversions_batch and by the host module SmallInversions */
     int32_t search_inversions; /* 0                              xSearchInversions */
     int32_t zdrop_inversion; /* 100                              xZDropInversion */
     int32_t use_paired_reads; /* 0                               xUsePairedReads (read by the host layer only: it selects the
@@ -293,6 +294,32 @@ int ma_batch_get_pairs( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, ma_alignmen
                         int32_t* other );
 int ma_batch_start_pair_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, ma_alignment* alns, uint64_t* ops, int32_t* mate,
                                   int32_t* other );
+/* ---- small inversions: SmallInversions::execute (smallInversions.h:22-221) on the device ----
+ * The module that sits between MappingQuality and PairedReads / FileWriter in the reference's graph (export.cpp:118-121), for a
+ * whole batch: replaces the host module ma_amd::SmallInversions (Alignment containers, ma_pack_extract + ma_ksw_batch round
+ * trips) on the flat paths.  ma_inversions_batch runs after ma_dp_batch / ma_align_batch / ma_batch_set_alignments on the batch's
+ * stream.  Per record of every MappingQuality list it looks for the stretches between two seeds in which the running score
+ * falls zdrop_inversion below its maximum (forAllDropPos, smallInversions.h:53-116), aligns each stretch's query against the
+ * reverse-strand window of its reference interval with the kernels of ma_ksw_batch (bandwidth_ext, zdrop, flag 0), splits the M
+ * runs into matches and mismatches and keeps the alignment if it scores more than harm_score_min * match (always with
+ * disable_heuristics): supplementary, mapping quality 0, the parent's soc_index.  It reads zdrop_inversion, zdrop, bandwidth_ext,
+ * harm_score_min, disable_heuristics and the six scores (sv_penalty through Alignment::append) of the batch's parameters and does
+ * not look at search_inversions.  It waits for the stream twice: with the read-back of the candidates' number and shapes that
+ * sizes the DP launches, and with the records and ops kept; a batch without any candidate waits once and launches one kernel.
+ * (Only a batch with more candidates than any before it on the object, or one whose ops pool has no room left, waits once more.)
+ * It fails -- with a message that names the read and the record, launching nothing more, the object stays usable -- for a stretch
+ * that ends beyond its read or whose window does not lie inside one strand of the doubled text (possible only through
+ * ma_batch_set_alignments); nothing outside a read or the text is ever read.
+ * Afterwards the lists "after MappingQuality" ARE the final lists, each kept inversion record directly behind its parent,
+ * several of one parent in the order of their stretches: ma_batch_get_mapq_alignments, ma_batch_start_mapq_download, n_alignments
+ * / n_ops of ma_batch_counts (the capacities of those downloads), ma_pair_batch, ma_sam_batch (with MA_SAM_NGMLR_TAGS too) and
+ * ma_pair_sam_batch serve them; ma_batch_get_alignments, ma_batch_get_hsets and the SoC getters serve what they served.  The
+ * call always starts from the MappingQuality output (twice gives the same lists) and drops pairs and SAM texts made before (run
+ * ma_pair_batch again); setting reads, ma_dp_batch and ma_batch_set_alignments put the MappingQuality lists back.
+ *   ma_batch_inversion_counts  drop stretches found, DP jobs among them (both sides non-empty), inversion records kept (any
+ *                              pointer may be NULL) */
+int ma_inversions_batch( ma_batch* );
+int ma_batch_inversion_counts( ma_batch*, uint64_t* n_candidates, uint64_t* n_jobs, uint64_t* n_records );
 /* ---- SAM text: FileWriter::execute (fileWriter.cpp:11-158) on the device ----
  * The single-end records of a batch as the bytes the reference's FileWriter prints for them (and ma_amd/host/ma_sam.h, the
  * yardstick, makes of the MappingQuality records), formatted by two kernels and downloaded as ONE text instead of records and

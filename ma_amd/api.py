@@ -511,6 +511,17 @@ class Batch:
     def finish_download(self):
         _chk(lib().ma_batch_finish_download(self.h))
 
+    # ---- small inversions (ma_inversions_batch)
+    def inversions(self):
+        """SmallInversions::execute for every read on the device, after align() / dp() / set_alignments(): mapq_alignments(),
+        pair(), sam() and pair_sam() then serve the lists with the inversion records behind their parents."""
+        _chk(lib().ma_inversions_batch(self.h))
+
+    def inversion_counts(self):
+        v = [C.c_uint64() for _ in range(3)]
+        _chk(lib().ma_batch_inversion_counts(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("candidates", "jobs", "records"), [x.value for x in v]))
+
     # ---- paired reads (ma_pair_batch): reads 2k and 2k+1 of the batch are the mates of pair k
     def pair(self):
         """PairedReads::execute for every pair on the device, after align() / dp()."""

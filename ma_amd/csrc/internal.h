@@ -64,6 +64,19 @@ struct DevBuf
     }
 };
 
+// prims.hip: the kernels of ma_ksw_batch over jobs, query and target bytes that are in device memory already; enqueued on
+// `stream`, nobody waits.  shapes = qlen, tlen, w per job (host).  d_ctr: KSW_BYTES_CTR_WORDS words of the call's own; afterwards
+// word KSW_BYTES_CIG_USED is the fill of the cigar pool, word KSW_BYTES_ERR holds MA_ERR_CIGAR_OVERFLOW if it was too small.
+enum : int
+{
+    KSW_BYTES_CIG_USED = 0,
+    KSW_BYTES_ERR = 3,
+    KSW_BYTES_CTR_WORDS = 32
+};
+int ksw_bytes_device( const ma_params& P, const ma_ksw_job* d_jobs, uint64_t n, const int32_t* shapes, const uint8_t* d_q, const uint8_t* d_t,
+                      ma_ez* d_ez, uint64_t* d_cig_off, uint32_t* d_cig_pool, uint64_t cigar_cap, unsigned long long* d_ctr, DevBuf& scratch,
+                      hipStream_t stream );
+
 // HIP's current device is a per-host-thread setting that defaults to 0: every entry point that takes an index or
 // a batch binds the calling thread to the device that object lives on (and restores the previous one on return), so a
 // worker thread spawned by the host graph never allocates or launches on the wrong GPU.

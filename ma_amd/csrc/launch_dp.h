@@ -52,6 +52,7 @@ int ma_dp_batch( ma_batch* b )
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads, nh = b->nHsets, nhs = b->nHseeds;
     b->sam.done = b->pairSam.done = false; // (a text printed before is of other records)
+    inv_reset( b );
     if( b->mqCnt.reserve( ( n + 1 ) * 4 ) )
         return 1;
     MA_HIP( hipMemsetAsync( b->mqCnt.p, 0, ( n + 1 ) * 4, b->stream ) );
@@ -330,6 +331,7 @@ int ma_batch_set_alignments( ma_batch* b, const uint64_t* aln_off, const ma_alig
         return fail( "ma_batch_set_alignments: null argument" );
     MA_BIND_DEVICE( b->device );
     b->sam.done = b->pairSam.done = false;
+    inv_reset( b );
     u64 no = 0;
     for( u64 i = 0; i < na; i++ )
         no += alns[ i ].n_ops;
@@ -381,6 +383,7 @@ int ma_batch_set_alignments( ma_batch* b, const uint64_t* aln_off, const ma_alig
     b->nHsets = na; // one alignment per harmonized set: the bookkeeping get_alns walks
     b->nHseeds = 0;
     b->nJobSlots = 0;
+    b->nOpsCap = no; // (the pool's fill: ma_inversions_batch appends behind it)
     b->stage_done = 4;
     return 0;
 }

@@ -39,12 +39,13 @@ PairKernelArgs pair_args( ma_batch* b )
     PairKernelArgs A;
     A.pp.P = ma_pair::params( b->P, b->idx->v.n );
     A.pp.n_pairs = (u32)( b->n_reads / 2 );
-    A.hset_off = b->hsetOff.as<u64>( );
+    const MqView V = mq_view( b );
+    A.hset_off = V.off;
     A.roff = b->d_roff;
-    A.hdr = b->hdr.as<AlnHeader>( );
+    A.hdr = V.hdr;
     A.pool = b->ops.as<u64>( );
-    A.mq_order = b->mqOrder.as<u32>( );
-    A.mq_cnt = b->mqCnt.as<u32>( );
+    A.mq_order = V.order;
+    A.mq_cnt = V.cnt;
     A.pick = b->pairPick.as<ma_pair::Pick>( );
     A.cnt = b->pairCnt.as<u64>( );
     A.nops = b->pairOps.as<u64>( );
@@ -61,7 +62,7 @@ int pair_finish_on_host( ma_batch* b, const PairKernelArgs& A )
     std::vector<u32> over( nOver ), cnt( n );
     std::vector<u64> roff( n + 1 );
     MA_HIP( hipMemcpyAsync( over.data( ), b->pairOver.p, nOver * 4ull, hipMemcpyDeviceToHost, b->stream ) );
-    MA_HIP( hipMemcpyAsync( cnt.data( ), b->mqCnt.p, n * 4, hipMemcpyDeviceToHost, b->stream ) );
+    MA_HIP( hipMemcpyAsync( cnt.data( ), mq_view( b ).cnt, n * 4, hipMemcpyDeviceToHost, b->stream ) );
     MA_HIP( hipMemcpyAsync( roff.data( ), b->d_roff, ( n + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
     if( batch_wait( b ) )
         return 1;

@@ -16,14 +16,15 @@ SamKernelArgs sam_args( ma_batch* b, u32 options )
     SamKernelArgs A;
     A.contigs = ma_sam::Contigs{ x->cnames.as<char>( ), x->cnameOff.as<u64>( ), x->v.cstart, x->v.clen, (u32)x->v.n_contigs };
     A.options = options;
+    const MqView V = mq_view( b );
     A.n_reads = (u32)b->n_reads;
-    A.hset_off = b->hsetOff.as<u64>( );
+    A.hset_off = V.off;
     A.roff = b->d_roff;
     A.reads = b->d_reads;
-    A.hdr = b->hdr.as<AlnHeader>( );
+    A.hdr = V.hdr;
     A.pool = b->ops.as<u64>( );
-    A.mq_order = b->mqOrder.as<u32>( );
-    A.mq_cnt = b->mqCnt.as<u32>( );
+    A.mq_order = V.order;
+    A.mq_cnt = V.cnt;
     A.names = b->txtNames.as<char>( );
     A.name_off = b->txtNameOff.as<u64>( );
     A.qual = b->txtHasQual ? b->txtQual.as<uint8_t>( ) : nullptr;
@@ -36,16 +37,17 @@ SamKernelArgs sam_args( ma_batch* b, u32 options )
 int sam_fail( ma_batch* b, u64 slot )
 {
     const u64 n = b->n_reads;
+    const MqView V = mq_view( b );
     std::vector<u64> hoff( n + 1 ), roff( n + 1 );
     u32 ord = 0;
     AlnHeader h;
-    MA_HIP( hipMemcpyAsync( hoff.data( ), b->hsetOff.p, ( n + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
+    MA_HIP( hipMemcpyAsync( hoff.data( ), V.off, ( n + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
     MA_HIP( hipMemcpyAsync( roff.data( ), b->d_roff, ( n + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
-    MA_HIP( hipMemcpyAsync( &ord, b->mqOrder.as<u32>( ) + slot, 4, hipMemcpyDeviceToHost, b->stream ) );
+    MA_HIP( hipMemcpyAsync( &ord, V.order + slot, 4, hipMemcpyDeviceToHost, b->stream ) );
     if( batch_wait( b ) )
         return 1;
     const u64 r = (u64)( std::upper_bound( hoff.begin( ), hoff.end( ), slot ) - hoff.begin( ) ) - 1;
-    MA_HIP( hipMemcpyAsync( &h, b->hdr.as<AlnHeader>( ) + hoff[ r ] + ord, sizeof( h ), hipMemcpyDeviceToHost, b->stream ) );
+    MA_HIP( hipMemcpyAsync( &h, V.hdr + hoff[ r ] + ord, sizeof( h ), hipMemcpyDeviceToHost, b->stream ) );
     if( batch_wait( b ) )
         return 1;
     char text[ 64 ];
@@ -69,7 +71,7 @@ int sam_tag_fail( ma_batch* b, u64 key )
         return fail( text );
     const u64 n = b->n_reads;
     std::vector<u64> hoff( n + 1 );
-    MA_HIP( hipMemcpyAsync( hoff.data( ), b->hsetOff.p, ( n + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
+    MA_HIP( hipMemcpyAsync( hoff.data( ), mq_view( b ).off, ( n + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
     if( batch_wait( b ) )
         return 1;
     const u64 r = (u64)( std::upper_bound( hoff.begin( ), hoff.end( ), slot ) - hoff.begin( ) ) - 1;
@@ -85,13 +87,14 @@ PairSamKernelArgs pair_sam_args( ma_batch* b, u32 options )
     A.options = options;
     A.n_pairs = (u32)( b->n_reads / 2 );
     A.picks_valid = b->nHsets ? 1u : 0u; // (ma_pair_batch launches nothing without harmonized sets)
-    A.hset_off = b->hsetOff.as<u64>( );
+    const MqView V = mq_view( b );
+    A.hset_off = V.off;
     A.roff = b->d_roff;
     A.reads = b->d_reads;
-    A.hdr = b->hdr.as<AlnHeader>( );
+    A.hdr = V.hdr;
     A.pool = b->ops.as<u64>( );
-    A.mq_order = b->mqOrder.as<u32>( );
-    A.mq_cnt = b->mqCnt.as<u32>( );
+    A.mq_order = V.order;
+    A.mq_cnt = V.cnt;
     A.pick = b->pairPick.as<ma_pair::Pick>( );
     A.names = b->txtNames.as<char>( );
     A.name_off = b->txtNameOff.as<u64>( );
@@ -104,10 +107,11 @@ int pair_sam_fail( ma_batch* b, u64 key )
 {
     const u64 p = key >> 32;
     const u32 k = (u32)key;
+    const MqView V = mq_view( b );
     ma_pair::Pick pick;
     u64 hoff[ 2 ], roff[ 3 ];
     MA_HIP( hipMemcpyAsync( &pick, b->pairPick.as<ma_pair::Pick>( ) + p, sizeof( pick ), hipMemcpyDeviceToHost, b->stream ) );
-    MA_HIP( hipMemcpyAsync( hoff, b->hsetOff.as<u64>( ) + 2 * p, 16, hipMemcpyDeviceToHost, b->stream ) );
+    MA_HIP( hipMemcpyAsync( hoff, V.off + 2 * p, 16, hipMemcpyDeviceToHost, b->stream ) );
     MA_HIP( hipMemcpyAsync( roff, b->d_roff + 2 * p, 24, hipMemcpyDeviceToHost, b->stream ) );
     if( batch_wait( b ) )
         return 1;
@@ -117,10 +121,10 @@ int pair_sam_fail( ma_batch* b, u64 key )
     const u64 base = hoff[ first ? 0 : 1 ];
     u32 ord = 0;
     AlnHeader h;
-    MA_HIP( hipMemcpyAsync( &ord, b->mqOrder.as<u32>( ) + base + idx, 4, hipMemcpyDeviceToHost, b->stream ) );
+    MA_HIP( hipMemcpyAsync( &ord, V.order + base + idx, 4, hipMemcpyDeviceToHost, b->stream ) );
     if( batch_wait( b ) )
         return 1;
-    MA_HIP( hipMemcpyAsync( &h, b->hdr.as<AlnHeader>( ) + base + ord, sizeof( h ), hipMemcpyDeviceToHost, b->stream ) );
+    MA_HIP( hipMemcpyAsync( &h, V.hdr + base + ord, sizeof( h ), hipMemcpyDeviceToHost, b->stream ) );
     if( batch_wait( b ) )
         return 1;
     char text[ 64 ];
@@ -141,7 +145,7 @@ int sam_text_launch( ma_batch* b, SamTextState& s, u64 n, Args A )
     if( n )
     {
         if( s.cnt.reserve( ( n + 2 ) * 8 ) || s.off.reserve( ( n + 2 ) * 8 ) || s.stat.reserve( SAM_STAT_COUNT * 8 ) ||
-            s.seqPos.reserve( ( b->nHsets + 1 ) * 8 ) )
+            s.seqPos.reserve( ( mq_view( b ).slots + 1 ) * 8 ) )
             return 1;
         const unsigned long long init[ SAM_STAT_COUNT ] = { 0, 0, ~0ull, 0 };
         MA_HIP( hipMemcpyAsync( s.stat.p, init, sizeof( init ), hipMemcpyHostToDevice, b->stream ) );

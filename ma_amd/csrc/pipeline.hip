@@ -85,6 +85,9 @@ static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0
 #include "stage_sam.h"
 #include "stage_pair_sam.h"
 
+#include "../host/ma_inv_dev.h"
+#include "stage_inv.h"
+
 // ------------------------------------------------------------------------------------------------
 // batch object
 // ------------------------------------------------------------------------------------------------
@@ -137,6 +140,13 @@ struct ma_batch
     DevBuf txtNames, txtNameOff, txtQual;
     bool txtSet = false, txtHasQual = false;
     SamTextState sam, pairSam;
+    // small inversions (ma_inversions_batch, launch_inv.h): the statistics of the call, per MappingQuality slot its candidates, per
+    // candidate its record, DP job, shape, window and result, and the FINAL lists the later stages see through mq_view
+    DevBuf invStat, invSlotCnt, invSlotFirst, invCand, invJobs, invShapes, invWin, invEz, invCigOff, invCigPool, invCtr, invHdr;
+    DevBuf finOff, finHdr, finOrder, finCnt;
+    u64 invCandCap = 0, invWinCap = 0;
+    u64 invCands = 0, invJobsN = 0, invRecs = 0, invOps = 0;
+    bool invDone = false, invFinal = false;
     u64 cigPoolCap = 0, cigPoolMin = 0, nOpsCap = 0, nJobSlots = 0;
     KswSide kswSide; // created on first use
     // double-buffered I/O (ma_batch_stage_reads / ma_batch_start_mapq_download): the next reads are uploaded into reads2 / roff2
@@ -157,6 +167,26 @@ struct ma_batch
     float hostMs[ 8 ] = { 0, 0, 0, 0, 0, 0, 0, 0 }; // wall time of the last stage calls on the host: seed, extract, chain, dp
     unsigned long long hctr[ CTR_COUNT ];
 };
+
+// The lists "after MappingQuality" as every later stage sees them -- pairing, both SAM texts, the packed download: read r's
+// records are hdr[ off[ r ] + order[ off[ r ] + k ] ], k < cnt[ r ]; slots = off[ n_reads ].  The MappingQuality arrays themselves,
+// or the final lists of a ma_inversions_batch that kept at least one record (launch_inv.h); setting reads, ma_dp_batch and
+// ma_batch_set_alignments put the view back (inv_reset).
+struct MqView
+{
+    const u64* off;
+    const AlnHeader* hdr;
+    const u32* order;
+    const u32* cnt;
+    u64 slots;
+};
+static MqView mq_view( const ma_batch* b )
+{
+    if( b->invFinal )
+        return MqView{ b->finOff.as<u64>( ), b->finHdr.as<AlnHeader>( ), b->finOrder.as<u32>( ), b->finCnt.as<u32>( ), b->nHsets + b->invRecs };
+    return MqView{ b->hsetOff.as<u64>( ), b->hdr.as<AlnHeader>( ), b->mqOrder.as<u32>( ), b->mqCnt.as<u32>( ), b->nHsets };
+}
+static void inv_reset( ma_batch* b ); // launch_inv.h
 
 // Waits for the batch's stream.  Default: hipStreamSynchronize (the runtime spins: lowest latency, one host core busy).
 // With blocking waits (ma_batch_set_blocking_sync) the host thread sleeps on an interrupt-driven event instead: the mode for
@@ -428,6 +458,7 @@ int ma_batch_use_staged_reads( ma_batch* b )
     b->reads_external = false;
     b->stage_done = 0;
     b->txtSet = b->sam.done = b->pairSam.done = false;
+    inv_reset( b );
     b->stagedPending = false;
     return 0;
 }
@@ -455,6 +486,7 @@ int ma_batch_set_reads( ma_batch* b, const uint8_t* codes, const uint64_t* offse
     b->reads_external = false;
     b->stage_done = 0;
     b->txtSet = b->sam.done = b->pairSam.done = false;
+    inv_reset( b );
     return 0;
 }
 
@@ -491,6 +523,7 @@ int ma_batch_set_reads_device( ma_batch* b, const void* d_codes, const void* d_o
     b->max_qlen = (u32)b->hctr[ 0 ];
     b->stage_done = 0;
     b->txtSet = b->sam.done = b->pairSam.done = false;
+    inv_reset( b );
     return 0;
 }
 
@@ -868,9 +901,9 @@ int ma_batch_counts( ma_batch* b, uint64_t* n_segments, uint64_t* n_seeds, uint6
     if( n_hseeds )
         *n_hseeds = b->nHseeds;
     if( n_alignments )
-        *n_alignments = b->stage_done >= 4 ? b->nHsets : 0;
-    if( n_ops ) // exact: the ops of all alignments (the MappingQuality selection has at most as many)
-        *n_ops = b->stage_done >= 4 ? b->hctr[ CTR_OPS_ALL ] : 0;
+        *n_alignments = b->stage_done >= 4 ? mq_view( b ).slots : 0;
+    if( n_ops ) // exact: the ops of all alignments (the MappingQuality selection has at most as many) and of the inversion records
+        *n_ops = b->stage_done >= 4 ? b->hctr[ CTR_OPS_ALL ] + ( b->invFinal ? b->invOps : 0 ) : 0;
     if( n_aligned_reads )
         *n_aligned_reads = b->hctr[ CTR_N_ALIGNED ];
     return 0;
@@ -1016,22 +1049,26 @@ static int get_alns( ma_batch* b, bool mq, uint64_t* aln_off, ma_alignment* alns
             memset( aln_off, 0, ( n + 1 ) * 8 );
         return 0;
     }
-    const u64 totalA = mq ? b->hctr[ CTR_ALN_MQ ] : nh, totalO = mq ? b->hctr[ CTR_OPS_MQ ] : b->hctr[ CTR_OPS_ALL ];
+    // (the MappingQuality form serves the list view: the final lists after a ma_inversions_batch that kept records)
+    const MqView V = mq_view( b );
+    const u64 invA = mq && b->invFinal ? b->invRecs : 0, invO = mq && b->invFinal ? b->invOps : 0;
+    const u64 totalA = mq ? b->hctr[ CTR_ALN_MQ ] + invA : nh, totalO = mq ? b->hctr[ CTR_OPS_MQ ] + invO : b->hctr[ CTR_OPS_ALL ];
     if( b->outCnt.reserve( ( n + 2 ) * 8 ) || b->outOps.reserve( ( n + 2 ) * 8 ) || b->outAlnOff.reserve( ( n + 2 ) * 8 ) ||
         b->outOpsOff.reserve( ( n + 2 ) * 8 ) || b->outAlns.reserve( ( totalA + 1 ) * sizeof( ma_alignment ) ) ||
         b->outOpsPairs.reserve( ( totalO + 1 ) * 16 ) )
         return 1;
-    const u32* ord = mq ? b->mqOrder.as<u32>( ) : b->order.as<u32>( );
+    const u64* off = mq ? V.off : b->hsetOff.as<u64>( );
+    const AlnHeader* hdr = mq ? V.hdr : b->hdr.as<AlnHeader>( );
+    const u32* ord = mq ? V.order : b->order.as<u32>( );
     const dim3 grid( (unsigned)( ( n + 255 ) / 256 ) ), block( 256 );
-    hipLaunchKernelGGL( k_aln_sizes, grid, block, 0, b->stream, (u32)n, b->hsetOff.as<u64>( ), b->hdr.as<AlnHeader>( ), ord,
-                        b->mqCnt.as<u32>( ), mq ? 1 : 0, b->outCnt.as<u64>( ), b->outOps.as<u64>( ) );
+    hipLaunchKernelGGL( k_aln_sizes, grid, block, 0, b->stream, (u32)n, off, hdr, ord, mq ? V.cnt : b->mqCnt.as<u32>( ), mq ? 1 : 0,
+                        b->outCnt.as<u64>( ), b->outOps.as<u64>( ) );
     MA_HIP( hipMemsetAsync( (char*)b->outCnt.p + n * 8, 0, 8, b->stream ) );
     MA_HIP( hipMemsetAsync( (char*)b->outOps.p + n * 8, 0, 8, b->stream ) );
     if( scan_exclusive<u64>( b, b->outCnt.as<u64>( ), b->outAlnOff.as<u64>( ), n + 1 ) ||
         scan_exclusive<u64>( b, b->outOps.as<u64>( ), b->outOpsOff.as<u64>( ), n + 1 ) )
         return 1;
-    hipLaunchKernelGGL( k_aln_pack, grid, block, 0, b->stream, (u32)n, b->hsetOff.as<u64>( ), b->hdr.as<AlnHeader>( ), ord,
-                        b->ops.as<u64>( ), mq ? 1 : 0, b->outAlnOff.as<u64>( ), b->outOpsOff.as<u64>( ), b->outAlns.as<ma_alignment>( ),
+    hipLaunchKernelGGL( k_aln_pack, grid, block, 0, b->stream, (u32)n, off, hdr, ord, b->ops.as<u64>( ), mq ? 1 : 0, b->outAlnOff.as<u64>( ), b->outOpsOff.as<u64>( ), b->outAlns.as<ma_alignment>( ),
                         b->outOpsPairs.as<u64>( ) );
     MA_HIP( hipGetLastError( ) );
     hipStream_t cs;
@@ -1192,3 +1229,5 @@ int ma_debug_seed_prof( unsigned long long* out )
 #include "launch_pair.h"
 
 #include "launch_sam.h"
+
+#include "launch_inv.h"

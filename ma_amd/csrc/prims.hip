@@ -128,6 +128,53 @@ enum : int
     PC_NEXT_BIG, // KSW_N_NEXT_BIG x u32
     PC_COUNT = PC_NEXT_BIG + KSW_N_NEXT_BIG / 2
 };
+static_assert( PC_CIG_USED == KSW_BYTES_CIG_USED && PC_ERR == KSW_BYTES_ERR && PC_COUNT <= KSW_BYTES_CTR_WORDS, "internal.h names these words" );
+
+// The device-resident middle of a call: n jobs whose records and bytes are in device memory (F), their result records, cigar
+// offsets and the dense cigar pool of cigar_cap words, the PC_COUNT counters of the call; everything is enqueued on `stream`
+// and nobody waits.  ctr[ PC_CIG_USED ] is the pool's fill, ctr[ PC_ERR ] holds MA_ERR_CIGAR_OVERFLOW if it did not fit.
+template <typename FETCH>
+static int ksw_bytes_launch( const FETCH& F, const KswScoring& SC, uint64_t n, const KswSizing& S, u32* lists, ma_ez* ez, u64* cig_off,
+                             u32* cig_pool, uint64_t cigar_cap, unsigned long long* ctr, DevBuf& scratch, hipStream_t stream )
+{
+    MA_HIP( hipMemsetAsync( ctr, 0, PC_COUNT * 8, stream ) );
+    MA_HIP( hipMemsetAsync( ez, 0, n * sizeof( ma_ez ), stream ) );
+    MA_HIP( hipMemsetAsync( cig_off, 0, ( n + 1 ) * 8, stream ) );
+    KswOut O;
+    O.ez = ez;
+    O.cig_off = cig_off;
+    O.cig_pool = cig_pool;
+    O.cig_pool_cap = cigar_cap;
+    O.cig_used = ctr + PC_CIG_USED;
+    O.cells = ctr + PC_CELLS;
+    O.njobs = ctr + PC_NJOBS;
+    O.err = (u32*)( ctr + PC_ERR );
+    O.path = nullptr;
+    O.cig_words = nullptr;
+    O.cig_chunk = 0; // dense pool: cigar_off[n] is the total
+    return ksw_run_all( F, SC, (u32)n, S, scratch, (unsigned int*)( ctr + PC_NEXT ), O, stream, lists, n, (unsigned int*)( ctr + PC_N_REDO ),
+                        (unsigned int*)( ctr + PC_NEXT_BIG ) );
+}
+
+// ma_ksw_batch's kernels (every ez field, no early stop) over jobs that are in device memory already: the DP of the pipeline's
+// small-inversion stage (launch_inv.h).  shapes: qlen, tlen, w of every job on the host, for the sizing of the launches.
+int ma::ksw_bytes_device( const ma_params& P, const ma_ksw_job* d_jobs, uint64_t n, const int32_t* shapes, const uint8_t* d_q,
+                          const uint8_t* d_t, ma_ez* d_ez, uint64_t* d_cig_off, uint32_t* d_cig_pool, uint64_t cigar_cap,
+                          unsigned long long* d_ctr, DevBuf& scratch, hipStream_t stream )
+{
+    KswScoring SC{ P.match, P.mismatch, P.gap, P.extend, P.gap2, P.extend2 };
+    SC.grp = ksw_grp_env( );
+    SC.band_mis = ksw_band_mis_env( );
+    SC.band_long = ksw_bandl_env( );
+    KswSizing S;
+    for( uint64_t i = 0; i < n; i++ )
+        ksw_size_job( S, shapes[ 3 * i ], shapes[ 3 * i + 1 ], shapes[ 3 * i + 2 ] );
+    ByteFetch F;
+    F.jobs = d_jobs;
+    F.qb = d_q;
+    F.tb = d_t;
+    return ksw_bytes_launch( F, SC, n, S, nullptr, d_ez, d_cig_off, d_cig_pool, cigar_cap, d_ctr, scratch, stream );
+}
 
 // FETCH::EARLY selects the pipeline semantics (extension kernel + early stop, see ksw_ext.h)
 template <typename FETCH>
@@ -179,29 +226,12 @@ static int ksw_batch_impl( const ma_params* P, const ma_ksw_job* jobs, uint64_t 
     MA_HIP( hipMemcpy( dj.p, jobs, n * sizeof( ma_ksw_job ), hipMemcpyHostToDevice ) );
     MA_HIP( hipMemcpy( dq.p, q_bytes, q_len, hipMemcpyHostToDevice ) );
     MA_HIP( hipMemcpy( dt.p, t_bytes, t_len, hipMemcpyHostToDevice ) );
-    MA_HIP( hipMemset( dctr.p, 0, PC_COUNT * 8 ) );
-    MA_HIP( hipMemset( dez.p, 0, n * sizeof( ma_ez ) ) );
-    MA_HIP( hipMemset( doff.p, 0, ( n + 1 ) * 8 ) );
-    KswOut O;
-    unsigned long long* ctr = dctr.as<unsigned long long>( );
-    O.ez = dez.as<ma_ez>( );
-    O.cig_off = doff.as<u64>( );
-    O.cig_pool = dpool.as<u32>( );
-    O.cig_pool_cap = cigar_cap;
-    O.cig_used = ctr + PC_CIG_USED;
-    O.cells = ctr + PC_CELLS;
-    O.njobs = ctr + PC_NJOBS;
-    O.err = (u32*)( ctr + PC_ERR );
-    O.path = nullptr;
-    O.cig_words = nullptr;
-    O.cig_chunk = 0; // dense pool: cigar_off[n] is the total
-    unsigned int* next = (unsigned int*)( ctr + PC_NEXT );
     FETCH F;
     F.jobs = dj.as<ma_ksw_job>( );
     F.qb = dq.as<uint8_t>( );
     F.tb = dt.as<uint8_t>( );
-    if( ksw_run_all( F, SC, (u32)n, S, dscr, next, O, 0, FETCH::EARLY ? dlists.as<u32>( ) : nullptr, n,
-                     (unsigned int*)( ctr + PC_N_REDO ), (unsigned int*)( ctr + PC_NEXT_BIG ) ) )
+    if( ksw_bytes_launch( F, SC, n, S, FETCH::EARLY ? dlists.as<u32>( ) : nullptr, dez.as<ma_ez>( ), doff.as<u64>( ), dpool.as<u32>( ), cigar_cap,
+                          dctr.as<unsigned long long>( ), dscr, 0 ) )
         return 1;
     MA_HIP( hipDeviceSynchronize( ) );
     unsigned long long h[ PC_NEXT ];

@@ -321,8 +321,9 @@ class Engine
         return run( vRefs, bStages );
     }
     // pSam: SAM mode -- the result carries the SAM text of the reads instead of their MappingQuality records; with bPairs the
-    // text of the PAIRS (PairedFileWriter's records, one vSamOff entry per pair) instead of the pair records
-    std::shared_ptr<BatchResult> run( const std::vector<ReadRef>& vReads, bool bStages, bool bPairs = false, const SamMode* pSam = nullptr )
+    // text of the PAIRS (PairedFileWriter's records, one vSamOff entry per pair) instead of the pair records; bInversions: see runFlat
+    std::shared_ptr<BatchResult> run( const std::vector<ReadRef>& vReads, bool bStages, bool bPairs = false, const SamMode* pSam = nullptr,
+                                      bool bInversions = false )
     {
         const size_t n = vReads.size( );
         auto tPack = std::chrono::steady_clock::now( );
@@ -381,7 +382,7 @@ class Engine
             }
         }
         const double fPack = secondsSince( tPack );
-        auto pRes = runFlat( pCodes, pOff, n, bStages, bPairs, xText.bOn ? &xText : nullptr );
+        auto pRes = runFlat( pCodes, pOff, n, bStages, bPairs, xText.bOn ? &xText : nullptr, bInversions );
         pRes->fPack = fPack;
         return pRes;
     }
@@ -399,8 +400,10 @@ class Engine
     // bPairs: the reads are mate pairs (2k, 2k + 1); the result carries the pair records instead of the MappingQuality ones
     // pSam: the result carries the SAM text (BatchResult::vSamOff / vSam) instead of the MappingQuality records
     // both: the pairs' SAM text (ma_pair_sam_batch), vSamOff per PAIR, instead of the pair records; bPairs and bSam are both set
+    // bInversions: "Detect Small Inversions" on the device (ma_inversions_batch) between the alignment and all of the above: the
+    // MappingQuality records, the pairs and both texts are then those of the lists with the inversion records in them
     std::shared_ptr<BatchResult> runFlat( const uint8_t* pCodes, const uint64_t* pOff, size_t n, bool bStages, bool bPairs = false,
-                                          const SamText* pSam = nullptr )
+                                          const SamText* pSam = nullptr, bool bInversions = false )
     {
         auto pRes = freshResult( );
         BatchResult& R = *pRes;
@@ -420,6 +423,8 @@ class Engine
         R.fH2D = secondsSince( t0 );
         t0 = std::chrono::steady_clock::now( );
         engineCheck( ma_align_batch( pBatch ) );
+        if( bInversions )
+            engineCheck( ma_inversions_batch( pBatch ) );
         engineCheck( ma_batch_sync( pBatch ) );
         R.fKernels = secondsSince( t0 );
         engineCheck( ma_batch_host_ms( pBatch, R.aStageMs ) );

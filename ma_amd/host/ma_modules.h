@@ -1548,11 +1548,12 @@ class BatchAligner
     // workers (host thread + engine: stream, device pools, page-locked staging), and all workers take the next batch from ONE
     // counter, so the replicas share the work by batches -- no collective, no inter-GPU traffic.  pFlat: one
     // AlignedBatch per device batch in input order (entry k covers reads [uiFrom + k * uiBatchReads, ...)); pOut: per read its
-    // Alignment containers (rOut[ i ]).  pPerIndex: phase times per replica.
+    // Alignment containers (rOut[ i ]).  pPerIndex: phase times per replica.  bInversions: "Detect Small Inversions" on the device,
+    // behind the alignment of every batch (the flat runs; execute applies the host module to its containers instead).
     void alignRangeOn( const std::vector<const ma_index*>& vIndices, const libMS::ContainerVector<std::shared_ptr<NucSeq>>& rQueries,
                        size_t uiFrom, size_t uiTo, TP_RESULT* pOut, AlignerTiming& rT, TP_FLAT* pFlat = nullptr,
                        std::shared_ptr<ReadVector> pReadsOfFlat = nullptr, std::vector<AlignerTiming>* pPerIndex = nullptr,
-                       bool bPairs = false, const uint32_t* pSamOptions = nullptr ) const
+                       bool bPairs = false, const uint32_t* pSamOptions = nullptr, bool bInversions = false ) const
     {
         if( vIndices.empty( ) )
             throw std::runtime_error( "BatchAligner: no index" );
@@ -1591,7 +1592,7 @@ class BatchAligner
                 }
                 xSam.pText = &vText, xSam.uiOptions = *pSamOptions;
             }
-            auto pRes = xEngine.run( vReads, false, bPairs, pSamOptions != nullptr ? &xSam : nullptr );
+            auto pRes = xEngine.run( vReads, false, bPairs, pSamOptions != nullptr ? &xSam : nullptr, bInversions );
             const auto t0 = std::chrono::steady_clock::now( );
             if( pFlat )
             {
@@ -1761,7 +1762,7 @@ class BatchAligner
     }
 
     // The same alignment run with the results left FLAT: one AlignedBatch per device batch, in input order (no Alignment
-    // container is built; SmallInversions needs containers and is not applied here).
+    // container is built; "Detect Small Inversions" runs on the device, ma_inversions_batch, and its records are in the lists).
     std::shared_ptr<TP_FLAT> executeFlat( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<ReadVector> pQueries )
     {
         return executeFlatOn( pFM_index->pDev->all( ), pQueries, &vLastPerIndex );
@@ -1774,9 +1775,9 @@ class BatchAligner
     }
 
     // The MA_SAM_* bits of ma_sam_batch for the writer's options.  The device serves the single-end text with every option, the
-    // NGMLR tag emulation included (MA_SAM_NGMLR_TAGS: the bases come from the index, the holes from the pack), but not with
-    // "Detect Small Inversions", which needs containers before the records are final: servesSam( ).  The paired text is not
-    // served with the tag emulation either (PairedFileWriter refuses it): servesPairSam( ).
+    // NGMLR tag emulation included (MA_SAM_NGMLR_TAGS: the bases come from the index, the holes from the pack), and with "Detect
+    // Small Inversions" (ma_inversions_batch makes the lists final on the device): servesSam( ).  The paired text is not served
+    // with the tag emulation (PairedFileWriter refuses it): servesPairSam( ).
     static uint32_t samOptionBits( const SamOptions& rO )
     {
         return ( rO.bSoftClip ? MA_SAM_SOFT_CLIP : 0u ) | ( rO.bOutputMCigar ? 0u : MA_SAM_EQX_CIGAR ) |
@@ -1785,11 +1786,11 @@ class BatchAligner
     }
     bool servesSam( ) const
     {
-        return !xP.search_inversions;
+        return true;
     }
     bool servesPairSam( ) const
     {
-        return !xP.search_inversions && !xParams.xSam.bEmulateNgmlrTags;
+        return !xParams.xSam.bEmulateNgmlrTags;
     }
     // RNAME strings and holes (Pack::vHoles, read by the NGMLR tags) of pPack on an index and its replicas
     // (ma_index_set_contig_names, ma_index_set_holes)
@@ -1836,8 +1837,6 @@ class BatchAligner
     std::shared_ptr<TP_FLAT> executeFlatSamOn( const std::vector<const ma_index*>& vIndices, std::shared_ptr<ReadVector> pQueries,
                                                std::vector<AlignerTiming>* pPerIndex )
     {
-        if( !servesSam( ) )
-            throw std::runtime_error( "BatchAligner::executeFlatSam: not with 'Detect Small Inversions' (use executeFlat and BatchFileWriter)" );
         const uint32_t uiOptions = samOptionBits( xParams.xSam );
         return runFlatOn( vIndices, pQueries, pPerIndex, false, &uiOptions );
     }
@@ -1869,14 +1868,11 @@ class BatchAligner
     // Paired mode with the results left FLAT and the pick made on the DEVICE (ma_pair_batch): both mates of all pairs go
     // through the device in batches of whole pairs, uiInflight of them in flight like executeFlat; one AlignedBatch per device
     // batch, in input order, holding the pair records (AlignedBatch::paired) -- no Alignment container, no per-read download.
-    // With "Detect Small Inversions" the inversions have to be found BEFORE pairing and SmallInversions needs containers:
-    // then this takes the container path (executePaired) and flattens what it returns into one batch of the same shape.
+    // With "Detect Small Inversions" the inversions are found on the device BEFORE pairing (ma_inversions_batch).
     std::shared_ptr<TP_FLAT> executePairedFlat( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<ReadVector> vMates )
     {
         if( vMates->size( ) % 2 )
             throw std::runtime_error( "BatchAligner::executePairedFlat: odd number of reads" );
-        if( xP.search_inversions )
-            return flattenPairs( executePaired( pFM_index, vMates ), vMates );
         return executePairedFlatOn( pFM_index->pDev->all( ), vMates, &vLastPerIndex );
     }
     std::shared_ptr<TP_FLAT> executePairedFlatOn( const std::vector<const ma_index*>& vIndices, std::shared_ptr<ReadVector> vMates,
@@ -1890,8 +1886,8 @@ class BatchAligner
     // AlignedBatch per device batch of whole pairs, in input order, that is paired( ) AND hasSamText( ) -- pair k's records are
     // samText( )[ samOffsets( )[k] .. samOffsets( )[k+1] ), the bytes PairedFileWriter::execute prints under this aligner's SAM
     // options; no download of records, ops, mate and other, no host formatting.  BatchPairedFileWriter writes such a batch with
-    // one call.  A batch whose reads only partly have qualities comes back with pair records as from executePairedFlat, and so
-    // does everything with "Detect Small Inversions" (the container path).  Not with the NGMLR tag emulation.
+    // one call.  A batch whose reads only partly have qualities comes back with pair records as from executePairedFlat.  Not with
+    // the NGMLR tag emulation.
     std::shared_ptr<TP_FLAT> executePairedFlatSam( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<ReadVector> vMates,
                                                    std::shared_ptr<Pack> pPack )
     {
@@ -1900,8 +1896,6 @@ class BatchAligner
         if( xParams.xSam.bEmulateNgmlrTags )
             throw std::runtime_error( "BatchAligner::executePairedFlatSam: not with the NGMLR tag emulation (use executePaired and "
                                       "PairedFileWriter)" );
-        if( xP.search_inversions )
-            return flattenPairs( executePaired( pFM_index, vMates ), vMates );
         nameContigs( *pFM_index->pDev, *pPack );
         return executePairedFlatSamOn( pFM_index->pDev->all( ), vMates, &vLastPerIndex );
     }
@@ -1912,64 +1906,16 @@ class BatchAligner
         if( vMates->size( ) % 2 )
             throw std::runtime_error( "BatchAligner::executePairedFlatSam: odd number of reads" );
         if( !servesPairSam( ) )
-            throw std::runtime_error( "BatchAligner::executePairedFlatSam: not with 'Detect Small Inversions' or the NGMLR tag emulation "
-                                      "(use executePairedFlat and BatchPairedFileWriter)" );
+            throw std::runtime_error( "BatchAligner::executePairedFlatSam: not with the NGMLR tag emulation (use executePairedFlat and "
+                                      "BatchPairedFileWriter)" );
         const uint32_t uiOptions = samOptionBits( xParams.xSam );
         return runFlatOn( vIndices, vMates, pPerIndex, true, &uiOptions );
-    }
-    // the pairs of executePaired as ONE paired AlignedBatch (host memory; the records keep PairedReads' changes)
-    static std::shared_ptr<TP_FLAT> flattenPairs( std::shared_ptr<TP_RESULT> pPairs, std::shared_ptr<ReadVector> vMates )
-    {
-        auto pRes = std::make_shared<detail::BatchResult>( );
-        detail::BatchResult& R = *pRes;
-        R.uiReads = vMates->size( );
-        R.bPairs = true;
-        uint64_t uiRecords = 0, uiOps = 0;
-        for( auto& pV : *pPairs )
-            for( auto& pA : *pV )
-                uiRecords++, uiOps += pA->data.size( );
-        uint64_t* pOff = R.vPairOff.need( pPairs->size( ) + 1 );
-        ma_alignment* pAlns = R.vPair.need( uiRecords + 1 );
-        uint64_t* pOps = R.vPairOps.need( 2 * uiOps + 2 );
-        int32_t *pMate = R.vPairMate.need( uiRecords + 1 ), *pOther = R.vPairOther.need( uiRecords + 1 );
-        memset( R.vMqOff.need( R.uiReads + 1 ), 0, ( R.uiReads + 1 ) * sizeof( uint64_t ) );
-        uint64_t r = 0, o = 0;
-        pOff[ 0 ] = 0;
-        for( size_t k = 0; k < pPairs->size( ); k++ )
-        {
-            const AlignmentVector& rV = *( *pPairs )[ k ];
-            for( size_t i = 0; i < rV.size( ); i++, r++ )
-            {
-                const Alignment& rA = *rV[ i ];
-                ma_alignment& rF = pAlns[ r ];
-                rF.begin_ref = (int64_t)rA.uiBeginOnRef, rF.end_ref = (int64_t)rA.uiEndOnRef;
-                rF.begin_q = (int64_t)rA.uiBeginOnQuery, rF.end_q = (int64_t)rA.uiEndOnQuery;
-                rF.score = rA.iScore, rF.soc_index = rA.index_of_strip, rF.n_ops = (uint32_t)rA.data.size( ), rF.ops_off = o;
-                rF.secondary = rA.bSecondary ? 1 : 0, rF.supplementary = rA.bSupplementary ? 1 : 0, rF.mapq = rA.fMappingQuality;
-                for( auto& rD : rA.data )
-                    pOps[ 2 * o ] = (uint64_t)rD.first, pOps[ 2 * o + 1 ] = rD.second, o++;
-                pMate[ r ] = rA.xStats.bFirst ? 1 : 0;
-                pOther[ r ] = -1;
-                auto pPartner = rA.xStats.pOther.lock( );
-                for( size_t j = 0; pPartner != nullptr && j < rV.size( ); j++ )
-                    if( rV[ j ] == pPartner )
-                        pOther[ r ] = (int32_t)j;
-            }
-            pOff[ k + 1 ] = r;
-        }
-        R.uiPairRecords = uiRecords, R.uiPairOps = uiOps;
-        auto pB = std::make_shared<AlignedBatch>( );
-        pB->pReads = vMates;
-        pB->uiFirst = 0;
-        pB->pResult = pRes;
-        auto pRet = std::make_shared<TP_FLAT>( );
-        pRet->push_back( pB );
-        return pRet;
     }
 
   private:
     // One flat run, the body of executeFlat and the ...On functions: pReads in device batches on vIndices, one AlignedBatch per
-    // batch in input order; bPairs: batches of whole pairs, paired on the device; pSamOptions: SAM text instead of records
+    // batch in input order; bPairs: batches of whole pairs, paired on the device; pSamOptions: SAM text instead of records.  With
+    // "Detect Small Inversions" every batch runs ma_inversions_batch between its alignment and its pairing / formatting / download.
     std::shared_ptr<TP_FLAT> runFlatOn( const std::vector<const ma_index*>& vIndices, std::shared_ptr<ReadVector> pReads,
                                         std::vector<AlignerTiming>* pPerIndex, bool bPairs, const uint32_t* pSamOptions )
     {
@@ -1977,7 +1923,8 @@ class BatchAligner
         xLast = AlignerTiming( );
         const auto t0 = std::chrono::steady_clock::now( );
         if( !pReads->empty( ) )
-            alignRangeOn( vIndices, *pReads, 0, pReads->size( ), nullptr, xLast, pRet.get( ), pReads, pPerIndex, bPairs, pSamOptions );
+            alignRangeOn( vIndices, *pReads, 0, pReads->size( ), nullptr, xLast, pRet.get( ), pReads, pPerIndex, bPairs, pSamOptions,
+                          xP.search_inversions != 0 );
         xLast.fWall = detail::secondsSince( t0 );
         return pRet;
     }
@@ -2123,20 +2070,16 @@ class MultiDeviceAligner
     }
 
     // BatchAligner::executePairedFlat over all replicas: batches of whole pairs rotate over them, paired on the device that
-    // aligned them.  (search_inversions: use BatchAligner::executePairedFlat, which takes the container path.)
+    // aligned them (and, with "Detect Small Inversions", looked for the inversions before).
     std::shared_ptr<BatchAligner::TP_FLAT> executePairedFlat( std::shared_ptr<ReadVector> vMates )
     {
-        if( xParams.getSelected( )->search_inversions )
-            throw std::runtime_error( "MultiDeviceAligner::executePairedFlat: not with 'Detect Small Inversions' (SmallInversions needs containers)" );
         return runFlat( &BatchAligner::executePairedFlatOn, vMates );
     }
 
     // BatchAligner::executePairedFlatSam over all replicas: every device batch of whole pairs comes back as the SAM text its
-    // device formatted.  (search_inversions: use BatchAligner::executePairedFlatSam, which takes the container path.)
+    // device formatted.
     std::shared_ptr<BatchAligner::TP_FLAT> executePairedFlatSam( std::shared_ptr<ReadVector> vMates, std::shared_ptr<Pack> pPack )
     {
-        if( xParams.getSelected( )->search_inversions )
-            throw std::runtime_error( "MultiDeviceAligner::executePairedFlatSam: not with 'Detect Small Inversions' (SmallInversions needs containers)" );
         nameContigs( *pPack );
         return runFlat( &BatchAligner::executePairedFlatSamOn, vMates );
     }
