@@ -2,13 +2,16 @@
 // `maCMD -x <genome> -i <reads> [-m <mates>] -o <out.sam> -p <preset>` needs from the hot path.  Not a re-implementation
 // of cmdMa.cpp: no option parsing beyond the four arguments, no thread pool (the batches are the parallelism).
 //
-//   ma_align [--host-sam] [--ngmlr-tags] <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam|stdout> [preset] [mates.fa|fq[.gz]]
+//   ma_align [--host-sam] [--ngmlr-tags] [--text-input] <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam|stdout> [preset] [mates.fa|fq[.gz]]
 //
 // Single-end input is printed on the device (BatchAligner::executeFlatSam: the SAM text is what comes down) whenever the
 // options are ones the device serves -- with --ngmlr-tags ("Emulate NGMLR's tag output") and with "Detect Small Inversions"
 // (found on the device, ma_inversions_batch) too; with --host-sam the records come down and FileWriter prints them.  Paired input likewise: mates are paired and their
 // records printed on the device (BatchAligner::executePairedFlatSam), or the pair records come down and
 // BatchPairedFileWriter formats them (the paired writers refuse the tag emulation).  The bytes are the same.
+// With --text-input single-end input is not parsed on the host at all: BatchTextReader cuts the file into runs of whole records
+// and the device parses them (BatchAligner::executeTextSam, ma_batch_set_reads_text).  The device serves four-line FASTQ and plain
+// FASTA only; any other file ends the program with the library's message, which names the line -- there is no silent fallback.
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_align.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
@@ -19,18 +22,18 @@ typedef libMS::ContainerVector<std::shared_ptr<NucSeq>> ReadVec;
 
 int main( int argc, char** argv )
 {
-    bool bHostSam = false, bNgmlrTags = false;
+    bool bHostSam = false, bNgmlrTags = false, bTextInput = false;
     for( int i = 1; i < argc; i++ )
-        if( std::string( argv[ i ] ) == "--host-sam" || std::string( argv[ i ] ) == "--ngmlr-tags" )
+        if( std::string( argv[ i ] ) == "--host-sam" || std::string( argv[ i ] ) == "--ngmlr-tags" || std::string( argv[ i ] ) == "--text-input" )
         {
-            ( std::string( argv[ i ] ) == "--host-sam" ? bHostSam : bNgmlrTags ) = true;
+            ( std::string( argv[ i ] ) == "--host-sam" ? bHostSam : std::string( argv[ i ] ) == "--ngmlr-tags" ? bNgmlrTags : bTextInput ) = true;
             for( int j = i; j + 1 < argc; j++ )
                 argv[ j ] = argv[ j + 1 ];
             argc--, i--;
         }
     if( argc < 4 )
     {
-        fprintf( stderr, "usage: ma_align [--host-sam] [--ngmlr-tags] <genome.fa | index prefix> <reads> <out.sam|stdout> [preset] [mates]\n" );
+        fprintf( stderr, "usage: ma_align [--host-sam] [--ngmlr-tags] [--text-input] <genome.fa | index prefix> <reads> <out.sam|stdout> [preset] [mates]\n" );
         return 2;
     }
     try
@@ -39,6 +42,11 @@ int main( int argc, char** argv )
         xParams.setSelected( argc >= 5 ? argv[ 4 ] : ( argc >= 6 ? "illuminapaired" : "default" ) );
         xParams.xSam.bEmulateNgmlrTags = bNgmlrTags;
         const bool bPaired = argc >= 6;
+        if( bTextInput && ( bPaired || bHostSam ) )
+            throw std::runtime_error( "--text-input serves single-end input printed on the device (no mates, not with --host-sam)" );
+        const std::string sReads = argv[ 2 ];
+        if( bTextInput && sReads.size( ) >= 3 && sReads.compare( sReads.size( ) - 3, 3, ".gz" ) == 0 )
+            throw std::runtime_error( "--text-input: " + sReads + " is compressed; the device parses plain text (run without the flag)" );
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         const std::string sGenome = argv[ 1 ];
@@ -53,7 +61,15 @@ int main( int argc, char** argv )
         FileReader xReader( xParams );
         auto pIn = fileStreamFromPath( argv[ 2 ] );
         const size_t uiBatch = 1000000; // reads per device batch
-        if( !bPaired && xAligner.servesSam( ) && !bHostSam )
+        if( bTextInput )
+        {
+            // the text path: the bytes of the file go to the device, which parses, aligns and prints; one write per batch
+            BatchFileWriter xWriter( xParams, std::make_shared<FileWriter>( xParams, std::string( argv[ 3 ] ), pPack ), pPack );
+            BatchTextReader xTextReader( xParams );
+            while( auto pText = xTextReader.execute( pIn ) )
+                xWriter.write( *xAligner.executeTextSam( pFM, pText, pPack ), pPack );
+        }
+        else if( !bPaired && xAligner.servesSam( ) && !bHostSam )
         {
             // the device path: records formatted by ma_sam_batch, one write per device batch behind FileWriter's header
             BatchFileWriter xWriter( xParams, std::make_shared<FileWriter>( xParams, std::string( argv[ 3 ] ), pPack ), pPack );

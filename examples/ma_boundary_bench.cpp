@@ -9,6 +9,7 @@
 // Prints one JSON line.  bench.py runs it after its timed regions and reports it as config.boundary (never as `value`).
 //
 //   ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads]
+// (further legs, one per run: paired, sam, sam-tags, text, inversions -- see the comments at their blocks in main)
 //
 // build: g++ -std=c++17 -O2 -Iinclude -Ima_amd/host examples/ma_boundary_bench.cpp -Lma_amd -lma_amd -lpthread
 #include "ma_batch_nodes.h"
@@ -17,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 
 using namespace libMA;
 using namespace libMS;
@@ -236,7 +238,7 @@ int main( int argc, char** argv )
 {
     if( argc < 6 )
     {
-        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | sam [repeats] | sam-tags [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
+        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | sam [repeats] | sam-tags [repeats] | text [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
         return 2;
     }
     try
@@ -247,7 +249,7 @@ int main( int argc, char** argv )
         maCheck( ma_set_device( atoi( argv[ 5 ] ) ) );
         maCheck( ma_host_bind_thread( atoi( argv[ 5 ] ), 0, nullptr ) ); // this thread and all it starts: the CPUs next to the GPU
         const unsigned uiHw = std::max( 1u, std::thread::hardware_concurrency( ) );
-        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
+        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "text" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         double t0 = now( );
@@ -489,6 +491,154 @@ int main( int argc, char** argv )
                     (unsigned long long)uiBytesContainer, (unsigned long long)uiBytesOn, (unsigned long long)uiBytesOff, xTimeOn.fKernels,
                     xTimeOff.fKernels, (unsigned long long)xTimeOn.uiBatches );
             return uiBytesContainer == uiBytesOn ? 0 : 1;
+        }
+        if( argc >= 7 && !strcmp( argv[ 6 ], "text" ) )
+        {
+            // ---- the text leg: the n reads as ONE FASTQ text in memory (names r<i>, seeded qualities 35 .. 126), file to SAM text
+            // through (a) StringStream -> BatchFileReader -> executeFlatSam -- records cut and parsed on the host, one NucSeq per
+            // read, gathered and uploaded as arrays -- and (b) BatchTextReader -> executeTextSam -- blocks of text cut at record
+            // starts, parsed on the device.  Both with three workers (own aligner each, one device batch of ~256 k reads at a
+            // time) that pull their batches from the ONE stream.  One warm-up of each keeps its text -- the batches put into input
+            // order by their first QNAME -- and the two files must be the same bytes; then alternating, <repeats> times each, with
+            // the texts only counted (as the sam leg's sink does) and every count checked against the file's.
+            const int iRepeats = argc >= 8 ? std::max( 1, atoi( argv[ 7 ] ) ) : 5;
+            const size_t uiWorkers = 3, uiBatchReads = std::min<size_t>( std::max<size_t>( n, 1 ), 1u << 18 );
+            std::string sFastq;
+            sFastq.reserve( n * ( 2 * uiLen + 16 ) );
+            for( size_t i = 0; i < n; i++ )
+            {
+                const NucSeq& rQ = *( *pReads )[ i ];
+                sFastq += "@" + rQ.sName + "\n";
+                for( uint8_t b : rQ.xCodes )
+                    sFastq += "ACGTN"[ b ];
+                sFastq += "\n+\n";
+                for( size_t j = 0; j < rQ.xCodes.size( ); j++ )
+                    sFastq += (char)( 35 + rnd( ) % 92 );
+                sFastq += "\n";
+            }
+            pReads->clear( );
+            BatchAligner::nameContigs( *pFM->pDev, *pPack );
+            std::vector<std::unique_ptr<BatchAligner>> vAligners;
+            for( size_t w = 0; w < uiWorkers; w++ )
+            {
+                vAligners.emplace_back( new BatchAligner( xParams ) );
+                vAligners.back( )->uiBatchReads = uiBatchReads;
+                vAligners.back( )->uiInflight = 1;
+            }
+            // runs `work( worker, keep, bytes ) -> false at the end` on the workers: every call handles the worker's next batch and adds
+            // the bytes of its SAM text; pFile (the warm-up runs): the text is kept as well and put into input order
+            typedef std::function<bool( size_t, std::string*, uint64_t& )> Work;
+            auto run = [ & ]( const Work& work, std::string* pFile, uint64_t& ruiBytes ) {
+                std::vector<std::pair<uint64_t, std::string>> vParts;
+                std::mutex xParts;
+                std::string sFailure;
+                std::atomic<uint64_t> uiBytes{ 0 };
+                const double t = now( );
+                std::vector<std::thread> vT;
+                for( size_t w = 0; w < uiWorkers; w++ )
+                    vT.emplace_back( [ &, w ]( ) {
+                        try
+                        {
+                            std::string sText;
+                            uint64_t uiMine = 0;
+                            while( work( w, pFile != nullptr ? &sText : nullptr, uiMine ) )
+                                if( pFile != nullptr )
+                                {
+                                    const uint64_t uiFirst = sText.size( ) > 1 ? strtoull( sText.c_str( ) + 1, nullptr, 10 ) : 0; // "r<i>\t..."
+                                    std::lock_guard<std::mutex> xGuard( xParts );
+                                    vParts.emplace_back( uiFirst, std::move( sText ) );
+                                    sText.clear( );
+                                }
+                            uiBytes += uiMine;
+                        }
+                        catch( const std::exception& rE )
+                        {
+                            std::lock_guard<std::mutex> xGuard( xParts );
+                            sFailure = rE.what( );
+                        }
+                    } );
+                for( auto& rT : vT )
+                    rT.join( );
+                const double f = now( ) - t;
+                if( !sFailure.empty( ) )
+                    throw std::runtime_error( sFailure );
+                ruiBytes = uiBytes.load( );
+                if( pFile != nullptr )
+                {
+                    std::sort( vParts.begin( ), vParts.end( ), []( const auto& a, const auto& b ) { return a.first < b.first; } );
+                    pFile->clear( );
+                    for( const auto& rPart : vParts )
+                        *pFile += rPart.second;
+                }
+                return f;
+            };
+            uint64_t uiBytesHost = 0, uiBytesText = 0;
+            auto host = [ & ]( std::string* pFile ) {
+                auto pStream = std::make_shared<StringStream>( sFastq );
+                BatchFileReader xReader( xParams );
+                xReader.uiBatchReads = uiBatchReads;
+                return run(
+                    [ & ]( size_t w, std::string* pKeep, uint64_t& ruiBytes ) {
+                        auto pBatch = xReader.execute( pStream );
+                        if( pBatch == nullptr )
+                            return false;
+                        std::vector<AlignerTiming> vPer;
+                        auto pFlat = vAligners[ w ]->executeFlatSamOn( pFM->pDev->all( ), pBatch, &vPer );
+                        if( pKeep != nullptr )
+                            pKeep->clear( );
+                        for( auto& pB : *pFlat )
+                        {
+                            ruiBytes += pB->samBytes( );
+                            if( pKeep != nullptr )
+                                pKeep->append( pB->samText( ), pB->samBytes( ) );
+                        }
+                        return true;
+                    },
+                    pFile, uiBytesHost );
+            };
+            auto text = [ & ]( std::string* pFile ) {
+                auto pStream = std::make_shared<StringStream>( sFastq );
+                BatchTextReader xReader( xParams );
+                xReader.uiBatchBytes = std::max<size_t>( 1, sFastq.size( ) / std::max<size_t>( n, 1 ) * uiBatchReads );
+                return run(
+                    [ & ]( size_t w, std::string* pKeep, uint64_t& ruiBytes ) {
+                        auto pBatch = xReader.execute( pStream );
+                        if( pBatch == nullptr )
+                            return false;
+                        auto pB = vAligners[ w ]->executeTextSamOn( pFM->pDev->p, pBatch );
+                        ruiBytes += pB->samBytes( );
+                        if( pKeep != nullptr )
+                            pKeep->assign( pB->samText( ), pB->samBytes( ) );
+                        return true;
+                    },
+                    pFile, uiBytesText );
+            };
+            // warm-up of both: these two runs keep their files, which must be the same bytes; the timed runs count theirs
+            std::string sFileHost, sFileText;
+            host( &sFileHost ), text( &sFileText );
+            bool bEqual = sFileHost == sFileText && !sFileHost.empty( );
+            const uint64_t uiFileBytes = sFileText.size( );
+            std::string( ).swap( sFileHost ), std::string( ).swap( sFileText );
+            std::vector<double> vH, vD;
+            for( int r = 0; r < iRepeats; r++ )
+            {
+                vH.push_back( n / host( nullptr ) ), vD.push_back( n / text( nullptr ) );
+                bEqual = bEqual && uiBytesHost == uiFileBytes && uiBytesText == uiFileBytes;
+            }
+            auto list = []( std::vector<double> v ) {
+                std::string sAll;
+                for( double f : v )
+                    sAll += ( sAll.empty( ) ? "" : ", " ) + std::to_string( f );
+                std::sort( v.begin( ), v.end( ) );
+                return "{\"median\": " + std::to_string( v[ v.size( ) / 2 ] ) + ", \"min\": " + std::to_string( v.front( ) ) +
+                       ", \"max\": " + std::to_string( v.back( ) ) + ", \"all\": [" + sAll + "]}";
+            };
+            printf( "{\"text\": {\"reads\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_reads\": %zu, \"workers\": %zu, "
+                    "\"file_reader_flat_sam_reads_per_s\": %s, \"text_reader_text_sam_reads_per_s\": %s, \"fastq_bytes\": %zu, "
+                    "\"sam_bytes\": %zu, \"equal\": %s}}\n",
+                    n, uiLen, iRepeats, uiBatchReads, uiWorkers, list( vH ).c_str( ), list( vD ).c_str( ), sFastq.size( ), (size_t)uiFileBytes,
+                    bEqual ? "true" : "false" );
+            return bEqual ? 0 : 1;
         }
         if( argc >= 7 && ( !strcmp( argv[ 6 ], "sam" ) || bSamTags ) )
         {

@@ -389,6 +389,30 @@ int ma_pair_sam_batch( ma_batch*, uint32_t options );
 int ma_batch_pair_sam_counts( ma_batch*, uint64_t* n_pairs, uint64_t* n_bytes );
 int ma_batch_get_pair_sam( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, char* text );
 int ma_batch_start_pair_sam_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, char* text );
+/* ---- read text in: FileReader::execute (fileReader.cpp:37-203) + NucSeq's translation (nucSeq.cpp:17-28) on the device ----
+ * A FASTQ or FASTA text -- a whole file, or a run of whole records cut out of one -- uploaded as it is and parsed by kernels
+ * (ma_amd/csrc/stage_text.h), byte-parallel: replaces the reader module, one NucSeq per read, the gather into code / name /
+ * quality arrays and their three uploads.  The device parses the STRICT form, stated once in ma_amd/host/ma_text_dev.h -- four-line
+ * FASTQ records, FASTA records of any number of non-empty lines, "\n" or "\r\n", names up to the first blank, bases up to a line's
+ * last IUPAC letter -- and refuses every other text with "ma_batch_set_reads_text: line <L> (byte <X>): <reason>", the lowest
+ * offending line (1-based) and the offset of its first byte.  It never guesses: the reference's reader on the host stays the path
+ * for other files.
+ *   ma_batch_set_reads_text  text: host memory, n_bytes < 2 GiB.  Uploads, parses and waits (two read-backs: the line count that
+ *                            sizes the per-line work, then reads / bases / name bytes / longest read / refusal).  Afterwards
+ *                            the batch is exactly as after ma_batch_set_reads + ma_batch_set_read_text: FASTQ gives qualities,
+ *                            FASTA none (QUAL "*"); ma_align_batch, ma_inversions_batch and ma_sam_batch run unchanged.
+ *                            n_bytes == 0 gives 0 reads.  More reads than max_reads or more bases than max_bases fail with
+ *                            "batch capacity exceeded" (*n_reads then is the number of reads the text holds; it is 0 after
+ *                            every other failure).  After ANY failure the batch holds no reads and no text and stays usable.
+ *   ma_batch_read_counts     reads, bases, name bytes (0 without text) and whether there are qualities (any pointer may be NULL)
+ *   ma_batch_get_reads       the codes (A0 C1 G2 T3, other 4; nucSeq.cpp:17-28) and CSR offsets of the batch's reads, however they
+ *                            were set (ma_batch_set_reads, ma_batch_set_reads_device, text); either pointer may be NULL
+ *   ma_batch_get_read_text   QNAME and QUAL as ma_batch_set_read_text takes them (any pointer may be NULL; qual must be NULL
+ *                            when the reads have none); fails with a message when no text was set */
+int ma_batch_set_reads_text( ma_batch*, const char* text /*host*/, uint64_t n_bytes, uint64_t* n_reads );
+int ma_batch_read_counts( ma_batch*, uint64_t* n_reads, uint64_t* n_bases, uint64_t* n_name_bytes, int32_t* has_qual );
+int ma_batch_get_reads( ma_batch*, uint64_t* offsets /*n+1*/, uint8_t* codes );
+int ma_batch_get_read_text( ma_batch*, uint64_t* name_off /*n+1*/, char* names, uint8_t* qual /*may be NULL*/ );
 /* work counters for the roofline model (same meaning as the oracle's): [0] extend_backward steps,
  * [1] distinct occ blocks touched, [2] bwt_sa LF steps, [3] SA rows, [4] DP band cells, [5] ksw jobs */
 int ma_batch_counters( ma_batch*, uint64_t out[ 8 ] );

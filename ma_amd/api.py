@@ -364,6 +364,49 @@ class Batch:
         self.n = n_reads
         self.read_off, self.n_bases = None, int(n_bases)  # (the offsets live on the device)
 
+    # ---- read text in (ma_batch_set_reads_text): a FASTQ / FASTA text parsed on the device
+    def set_reads_text(self, text):
+        """text: bytes of a FASTQ or FASTA text in the strict form (include/ma_amd.h).  Uploads and parses it on the device; the
+        batch then is as after set_reads() + set_read_text().  Returns the number of reads.  A refused text raises MaError with
+        "line <L> (byte <X>): <reason>" and leaves the batch without reads."""
+        buf = np.frombuffer(bytes(text) + b"\0", dtype=np.uint8)
+        n = C.c_uint64()
+        self.n, self.read_off, self.n_bases = 0, np.zeros(1, dtype=np.uint64), 0
+        _chk(lib().ma_batch_set_reads_text(self.h, _ptr(buf), C.c_uint64(len(buf) - 1), C.byref(n)))
+        self.n = int(n.value)
+        self.read_off, _ = self.reads(codes=False)
+        self.n_bases = int(self.read_off[-1])
+        return self.n
+
+    def read_counts(self):
+        v = [C.c_uint64() for _ in range(3)]
+        q = C.c_int32()
+        _chk(lib().ma_batch_read_counts(self.h, *[C.byref(x) for x in v], C.byref(q)))
+        return dict(zip(("reads", "bases", "name_bytes", "has_qual"), [x.value for x in v] + [q.value]))
+
+    def reads(self, codes=True):
+        """(offsets, codes) of the batch's reads, however they were set: read r is codes[offsets[r]:offsets[r + 1]]."""
+        c = self.read_counts()
+        off = np.zeros(c["reads"] + 1, dtype=np.uint64)
+        cod = np.zeros(c["bases"] + 1, dtype=np.uint8) if codes else None
+        _chk(lib().ma_batch_get_reads(self.h, _ptr(off), _ptr(cod)))
+        return off, (cod[:-1] if codes else None)
+
+    def read_text(self):
+        """(names, quals): one bytes object per read; quals None when the reads have no qualities.  Fails when no text was set."""
+        c = self.read_counts()
+        noff = np.zeros(c["reads"] + 1, dtype=np.uint64)
+        names = np.zeros(c["name_bytes"] + 1, dtype=np.uint8)
+        qual = np.zeros(c["bases"] + 1, dtype=np.uint8) if c["has_qual"] else None
+        _chk(lib().ma_batch_get_read_text(self.h, _ptr(noff), _ptr(names), _ptr(qual)))
+        nb = names.tobytes()
+        out = [nb[int(noff[r]):int(noff[r + 1])] for r in range(c["reads"])]
+        if qual is None:
+            return out, None
+        off, _ = self.reads(codes=False)
+        qb = qual.tobytes()
+        return out, [qb[int(off[r]):int(off[r + 1])] for r in range(c["reads"])]
+
     def seed(self):
         _chk(lib().ma_seed_batch(self.h))
 

@@ -266,6 +266,7 @@ int ma_batch_set_read_text( ma_batch* b, const char* names, const uint64_t* name
     if( batch_wait( b ) )
         return 1; // the caller's arrays are free again
     b->txtHasQual = qual != nullptr;
+    b->txtNameBytes = name_off[ n ];
     b->txtSet = true;
     return 0;
 }

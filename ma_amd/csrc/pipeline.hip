@@ -88,6 +88,9 @@ static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0
 #include "../host/ma_inv_dev.h"
 #include "stage_inv.h"
 
+#include "../host/ma_text_dev.h"
+#include "stage_text.h"
+
 // ------------------------------------------------------------------------------------------------
 // batch object
 // ------------------------------------------------------------------------------------------------
@@ -139,6 +142,11 @@ struct ma_batch
     // read (ma_sam_batch) and the paired-end text per pair (ma_pair_sam_batch), each all of its own: one never touches the other
     DevBuf txtNames, txtNameOff, txtQual;
     bool txtSet = false, txtHasQual = false;
+    u64 txtNameBytes = 0;
+    // read text parsed on the device (ma_batch_set_reads_text, launch_text.h), reserved on first use: the text, the statistics of
+    // the call, line feeds per workgroup, and per line its start, header flag | name bytes, bases (both scanned in place) and
+    // per record its header line
+    DevBuf txtIn, txtStat, txtBlock, txtStart, txtHdrName, txtBases, txtRecLine;
     SamTextState sam, pairSam;
     // small inversions (ma_inversions_batch, launch_inv.h): the statistics of the call, per MappingQuality slot its candidates, per
     // candidate its record, DP job, shape, window and result, and the FINAL lists the later stages see through mq_view
@@ -1231,3 +1239,5 @@ int ma_debug_seed_prof( unsigned long long* out )
 #include "launch_sam.h"
 
 #include "launch_inv.h"
+
+#include "launch_text.h"

@@ -155,6 +155,82 @@ class BatchFileReader : public libMS::Module<ReadVector, true, FileStream>
     }
 };
 
+// Volatile source of batches of TEXT out of a FASTA / FASTQ stream, for the device's parser (BatchAligner::executeTextSam):
+// about uiBatchBytes are read as a block under the stream's lock, the batch ends before the last record start in the block
+// and the tail is carried to the next call.  No line is walked but the last few of a block.  A record start is
+//   FASTQ  a line that starts with '@' whose next-but-one line starts with '+'
+//   FASTA  a line that starts with '>'
+// (the kind is that of the block's first byte).  In strict text (ma_text_dev.h) the cut is exact: a quality line that starts
+// with '@' is followed by a header and then by bases, which may not start with '+'.  In any other text the device's check
+// refuses the batch: a batch that starts at a record start and passes was consumed line by line as the reference consumes
+// it, so the next batch starts at a record start too.  A block without a record start grows; at the end of the stream the rest
+// is the batch.  A stream without block reads (gzip) throws: BatchFileReader serves it.
+class BatchTextReader : public libMS::Module<TextBatch, true, FileStream>
+{
+    std::string sCarry; // the tail of the last block (guarded by the stream's lock)
+
+  public:
+    size_t uiBatchBytes = 64u << 20;
+    BatchTextReader( const ParameterSetManager& )
+    {}
+    // offset of the last record start of rText behind offset 0, 0 if there is none
+    static size_t lastRecordStart( const std::string& rText )
+    {
+        if( rText.empty( ) || ( rText[ 0 ] != '@' && rText[ 0 ] != '>' ) )
+            return 0;
+        const bool bFastq = rText[ 0 ] == '@';
+        size_t uiNext = std::string::npos, uiNextButOne = std::string::npos; // starts of the two lines behind the one looked at
+        for( size_t uiEnd = rText.size( ); uiEnd > 0; )
+        {
+            const void* const pFeed = memrchr( rText.data( ), '\n', uiEnd );
+            if( pFeed == nullptr )
+                break;
+            const size_t uiStart = (size_t)( (const char*)pFeed - rText.data( ) ) + 1;
+            if( uiStart < rText.size( ) )
+            {
+                if( bFastq ? rText[ uiStart ] == '@' && uiNextButOne != std::string::npos && rText[ uiNextButOne ] == '+' : rText[ uiStart ] == '>' )
+                    return uiStart;
+                uiNextButOne = uiNext;
+                uiNext = uiStart;
+            }
+            uiEnd = uiStart - 1;
+        }
+        return 0;
+    }
+    virtual std::shared_ptr<TextBatch> execute( std::shared_ptr<FileStream> pStream ) override
+    {
+        auto pRet = std::make_shared<TextBatch>( );
+        std::string& rText = pRet->sText;
+        const size_t uiWant = std::max<size_t>( uiBatchBytes, 1 );
+        {
+            std::lock_guard<std::mutex> xLock( pStream->xMutex );
+            rText.reserve( sCarry.size( ) + uiWant );
+            rText.swap( sCarry );
+            sCarry.clear( );
+            for( size_t uiAsk = rText.size( ) < uiWant ? uiWant - rText.size( ) : uiWant;; uiAsk = uiWant )
+            {
+                if( !pStream->readBlock( rText, uiAsk ) )
+                    throw std::runtime_error( "BatchTextReader: the stream " + pStream->fileName( ) +
+                                              " has no block reads (compressed input?): read it with BatchFileReader" );
+                if( pStream->eof( ) )
+                    break; // the rest is the batch
+                const size_t uiCut = lastRecordStart( rText );
+                if( uiCut > 0 )
+                {
+                    sCarry.assign( rText, uiCut, std::string::npos );
+                    rText.resize( uiCut );
+                    break;
+                }
+                if( rText[ 0 ] != '@' && rText[ 0 ] != '>' )
+                    break; // neither kind: the device refuses the block as it is
+            }
+        }
+        if( rText.empty( ) )
+            return nullptr; // end of file (module.h:688-695)
+        return pRet;
+    }
+};
+
 // Volatile source over reads that already are in memory (benchmarks, callers that hold their reads): consecutive slices.
 class BatchSource : public libMS::Module<ReadVector, true>
 {

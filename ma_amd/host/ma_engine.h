@@ -509,6 +509,53 @@ class Engine
                      (void*)this, n, R.fH2D, R.fKernels, R.aStageMs[ 0 ], R.aStageMs[ 1 ], R.aStageMs[ 2 ], R.aStageMs[ 3 ], R.fD2H );
         return pRes;
     }
+    // A FASTQ / FASTA text instead of reads (ma_batch_set_reads_text: the device parses it, strict form only) through all stages to
+    // the SAM text of its reads: the result of runFlat's SAM mode (bSam, vSamOff, vSam; uiReads from the device), with no NucSeq,
+    // no gather and no separate upload of names and qualities.  A text the device refuses throws the library's message, which
+    // names the line.  The device batch is sized by the text: bases for its bytes, reads as the last texts held (a first text
+    // that holds more is parsed twice).
+    std::shared_ptr<BatchResult> runText( const char* pText, size_t uiBytes, uint32_t uiSamOptions, bool bInversions = false )
+    {
+        auto pRes = freshResult( );
+        BatchResult& R = *pRes;
+        R.bStages = R.bSocQueues = R.bPairs = false;
+        R.bSam = true;
+        R.uiSamOptions = uiSamOptions;
+        R.uiSamBytes = 0;
+        R.fPack = 0;
+        fit( std::max<uint64_t>( uiCapReads, uiBytes / 32 ), std::max<uint64_t>( uiCapBases, uiBytes ) );
+        auto t0 = std::chrono::steady_clock::now( );
+        uint64_t n = 0;
+        if( ma_batch_set_reads_text( pBatch, pText, uiBytes, &n ) != 0 )
+        {
+            if( n == 0 ) // (only "batch capacity exceeded" reports the reads of the text)
+                engineCheck( 1 );
+            fit( n, uiBytes );
+            engineCheck( ma_batch_set_reads_text( pBatch, pText, uiBytes, &n ) );
+        }
+        R.uiReads = n;
+        R.fH2D = secondsSince( t0 );
+        t0 = std::chrono::steady_clock::now( );
+        engineCheck( ma_align_batch( pBatch ) );
+        if( bInversions )
+            engineCheck( ma_inversions_batch( pBatch ) );
+        engineCheck( ma_batch_sync( pBatch ) );
+        R.fKernels = secondsSince( t0 );
+        engineCheck( ma_batch_host_ms( pBatch, R.aStageMs ) );
+        t0 = std::chrono::steady_clock::now( );
+        engineCheck( ma_batch_counts( pBatch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &R.uiAlignedReads ) );
+        engineCheck( ma_sam_batch( pBatch, uiSamOptions ) );
+        engineCheck( ma_batch_sam_counts( pBatch, &R.uiSamBytes ) );
+        engineCheck( ma_batch_get_sam( pBatch, R.vSamOff.need( n + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
+        memset( R.vMqOff.need( n + 1 ), 0, ( n + 1 ) * sizeof( uint64_t ) ); // no records in a SAM result
+        R.uiMqAlignments = R.uiMqOps = 0;
+        R.fD2H = secondsSince( t0 );
+        uiRuns++;
+        if( getenv( "MA_ENGINE_TRACE" ) ) // diagnostics: the phases of every device batch (h2d: upload, parse and its two read-backs)
+            fprintf( stderr, "engine %p: %zu bytes of text, %llu reads, h2d+parse %.4f s, stages %.4f s (seed %.1f extract %.1f chain %.1f dp %.1f ms), d2h %.4f s\n",
+                     (void*)this, uiBytes, (unsigned long long)n, R.fH2D, R.fKernels, R.aStageMs[ 0 ], R.aStageMs[ 1 ], R.aStageMs[ 2 ], R.aStageMs[ 3 ], R.fD2H );
+        return pRes;
+    }
 };
 
 // One read's place in a finished device batch.

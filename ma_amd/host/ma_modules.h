@@ -1475,6 +1475,14 @@ class AlignedBatch : public libMS::Container
     }
 };
 
+// A run of whole FASTQ / FASTA records as the bytes of the file (BatchTextReader of ma_batch_nodes.h cuts them out of a stream):
+// what BatchAligner::executeTextSam hands to the device, which parses it (ma_batch_set_reads_text).
+class TextBatch : public libMS::Container
+{
+  public:
+    std::string sText;
+};
+
 // Phase times of a throughput run (seconds, summed over the device batches; the phases of different batches overlap when
 // several are in flight, so their sum can exceed the wall time)
 struct AlignerTiming
@@ -1839,6 +1847,35 @@ class BatchAligner
     {
         const uint32_t uiOptions = samOptionBits( xParams.xSam );
         return runFlatOn( vIndices, pQueries, pPerIndex, false, &uiOptions );
+    }
+
+    // executeFlatSam for reads that still are the TEXT of their file: the device parses the text (ma_batch_set_reads_text; the
+    // strict form of ma_text_dev.h), aligns and formats; the batch comes back as executeFlatSam's (hasSamText( ); size( ) = the
+    // reads the device found), with no NucSeq behind it.  A text the device refuses throws the library's message, which names
+    // the offending line: BatchFileReader + executeFlatSam stay the path for such files.  One device batch per call; callers keep
+    // several in flight from several threads (an engine per call, reused).
+    std::shared_ptr<AlignedBatch> executeTextSam( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<TextBatch> pText,
+                                                  std::shared_ptr<Pack> pPack )
+    {
+        nameContigs( *pFM_index->pDev, *pPack );
+        return executeTextSamOn( pFM_index->pDev->p, pText );
+    }
+    // (the contigs of pIndex are named already)
+    std::shared_ptr<AlignedBatch> executeTextSamOn( const ma_index* pIndex, std::shared_ptr<TextBatch> pText )
+    {
+        auto pEngine = takeEngine( pIndex );
+        auto pRet = std::make_shared<AlignedBatch>( );
+        try
+        {
+            pRet->pResult = pEngine->runText( pText->sText.data( ), pText->sText.size( ), samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
+        }
+        catch( ... )
+        {
+            giveEngine( pIndex, std::move( pEngine ) );
+            throw;
+        }
+        giveEngine( pIndex, std::move( pEngine ) );
+        return pRet;
     }
 
     // Paired mode (setUpCompGraphPaired, export.cpp:130-202) for a batch: vMates holds the mates of pair k at 2k and

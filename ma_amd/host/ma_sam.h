@@ -923,6 +923,12 @@ class FileStream : public libMS::Container
     {
         return false;
     }
+    // Optional: appends the next uiBytes bytes of the stream to rText as they are -- fewer at its end, after which eof( ) holds --
+    // and returns true; false: the stream has no block reads (nothing was consumed).  BatchTextReader cuts batches of text with it.
+    virtual bool readBlock( std::string&, size_t )
+    {
+        return false;
+    }
     // The next line as a view that stays valid until the next call on the stream.  The default goes through safeGetLine;
     // a stream that holds its text in memory hands out a pointer into it and copies nothing.
     virtual void lineView( const char*& rpLine, size_t& ruiLength )
@@ -1005,6 +1011,34 @@ template <typename SOURCE> class BlockFileStream : public FileStream
         flushCapture( );
         pCaptured = pText;
         uiCapturedTo = uiAt;
+        return true;
+    }
+    // what is left of the current block, then the source itself (no second copy)
+    bool readBlock( std::string& rText, size_t uiBytes ) override
+    {
+        if( uiAt < uiFilled )
+        {
+            const size_t uiTake = std::min( uiBytes, uiFilled - uiAt );
+            rText.append( pBlock + uiAt, uiTake );
+            uiAt += uiTake;
+            uiBytes -= uiTake;
+        }
+        if( uiBytes == 0 )
+            return true;
+        flushCapture( );
+        size_t uiGot = 0;
+        if( !bTextAdopted )
+        {
+            const size_t uiOld = rText.size( );
+            rText.resize( uiOld + uiBytes );
+            xSource.read( &rText[ uiOld ], (std::streamsize)uiBytes );
+            uiGot = (size_t)xSource.gcount( );
+            rText.resize( uiOld + uiGot );
+            if( pCaptured != nullptr )
+                pCaptured->append( rText, uiOld, uiGot );
+        }
+        if( uiGot < uiBytes )
+            bSawEnd = true;
         return true;
     }
     bool eof( ) const override

@@ -18,7 +18,8 @@ GROUPS = [("k_seed", ["k_seed(", "k_seed<", "k_seed_long(", "k_seed_long<", "k_s
           ("k_chain", ["k_chain", "k_soc_windows", "k_soc_dump", "k_sort_seeds_wave", "k_hseed_counts", "k_hset_flatten"]),
           ("k_dp_enum", ["k_dp_enum", "k_job_cost", "k_grp_hist", "k_grp_scatter", "k_ops_caps"]),
           ("k_ksw_band", ["k_ksw_band<"]), ("k_ksw_pk", ["k_ksw_pk"]), ("k_ksw (LDS)", ["::k_ksw<"]),
-          ("k_stitch+k_finish", ["k_stitch", "k_finish"])]
+          ("k_stitch+k_finish", ["k_stitch", "k_finish"]),
+          ("k_text", ["k_text_"])]  # ma_batch_set_reads_text (stage_text.h): only in a trace of a run that parses text
 # a kernel whose name carries one of these and that matches no group is an ERROR (round 5: k_ksw_band fell through silently and the
 # DP roofline counted four of five kernel families)
 MUST_MATCH = ("k_ksw", "k_seed", "k_chain", "k_stitch", "k_soc", "k_dp_enum", "k_lf_walk")
