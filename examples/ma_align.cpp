@@ -9,9 +9,10 @@
 // (found on the device, ma_inversions_batch) too; with --host-sam the records come down and FileWriter prints them.  Paired input likewise: mates are paired and their
 // records printed on the device (BatchAligner::executePairedFlatSam), or the pair records come down and
 // BatchPairedFileWriter formats them (the paired writers refuse the tag emulation).  The bytes are the same.
-// With --text-input single-end input is not parsed on the host at all: BatchTextReader cuts the file into runs of whole records
-// and the device parses them (BatchAligner::executeTextSam, ma_batch_set_reads_text).  The device serves four-line FASTQ and plain
-// FASTA only; any other file ends the program with the library's message, which names the line -- there is no silent fallback.
+// With --text-input the input is not parsed on the host at all: BatchTextReader cuts the file into runs of whole records
+// and the device parses them (BatchAligner::executeTextSam, ma_batch_set_reads_text); with a mates file BatchPairedTextReader cuts
+// both files into runs of equally many records and the device parses, interleaves and reverse-complements them
+// (BatchAligner::executePairedTextSam, ma_batch_set_mates_text).  The device serves four-line FASTQ and plain FASTA only; any other file ends the program with the library's message, which names the line -- there is no silent fallback.
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_align.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
@@ -42,11 +43,14 @@ int main( int argc, char** argv )
         xParams.setSelected( argc >= 5 ? argv[ 4 ] : ( argc >= 6 ? "illuminapaired" : "default" ) );
         xParams.xSam.bEmulateNgmlrTags = bNgmlrTags;
         const bool bPaired = argc >= 6;
-        if( bTextInput && ( bPaired || bHostSam ) )
-            throw std::runtime_error( "--text-input serves single-end input printed on the device (no mates, not with --host-sam)" );
-        const std::string sReads = argv[ 2 ];
-        if( bTextInput && sReads.size( ) >= 3 && sReads.compare( sReads.size( ) - 3, 3, ".gz" ) == 0 )
-            throw std::runtime_error( "--text-input: " + sReads + " is compressed; the device parses plain text (run without the flag)" );
+        if( bTextInput && bHostSam )
+            throw std::runtime_error( "--text-input serves input printed on the device (not with --host-sam: the host's writers need the reads)" );
+        for( int iFile : { 2, 5 } )
+        {
+            const std::string sReads = iFile < argc ? argv[ iFile ] : "";
+            if( bTextInput && sReads.size( ) >= 3 && sReads.compare( sReads.size( ) - 3, 3, ".gz" ) == 0 )
+                throw std::runtime_error( "--text-input: " + sReads + " is compressed; the device parses plain text (run without the flag)" );
+        }
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         const std::string sGenome = argv[ 1 ];
@@ -61,7 +65,17 @@ int main( int argc, char** argv )
         FileReader xReader( xParams );
         auto pIn = fileStreamFromPath( argv[ 2 ] );
         const size_t uiBatch = 1000000; // reads per device batch
-        if( bTextInput )
+        if( bTextInput && bPaired )
+        {
+            // the paired text path: the bytes of both files go to the device, which parses, reverse-complements the mates as the
+            // parameter set says (bRevCompPairedReadMates), aligns, pairs and prints; one write per batch
+            BatchPairedFileWriter xWriter( xParams, std::make_shared<PairedFileWriter>( xParams, std::string( argv[ 3 ] ), pPack ), pPack );
+            BatchPairedTextReader xTextReader( xParams );
+            auto pStreams = std::make_shared<PairedFileStream>( pIn, fileStreamFromPath( argv[ 5 ] ) );
+            while( auto pTexts = xTextReader.execute( pStreams ) )
+                xWriter.execute( *xAligner.executePairedTextSam( pFM, pTexts, pPack ) );
+        }
+        else if( bTextInput )
         {
             // the text path: the bytes of the file go to the device, which parses, aligns and prints; one write per batch
             BatchFileWriter xWriter( xParams, std::make_shared<FileWriter>( xParams, std::string( argv[ 3 ] ), pPack ), pPack );

@@ -9,7 +9,7 @@
 // Prints one JSON line.  bench.py runs it after its timed regions and reports it as config.boundary (never as `value`).
 //
 //   ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads]
-// (further legs, one per run: paired, sam, sam-tags, text, inversions -- see the comments at their blocks in main)
+// (further legs, one per run: paired, pairtext, sam, sam-tags, text, inversions -- see the comments at their blocks in main)
 //
 // build: g++ -std=c++17 -O2 -Iinclude -Ima_amd/host examples/ma_boundary_bench.cpp -Lma_amd -lma_amd -lpthread
 #include "ma_batch_nodes.h"
@@ -238,7 +238,7 @@ int main( int argc, char** argv )
 {
     if( argc < 6 )
     {
-        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | sam [repeats] | sam-tags [repeats] | text [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
+        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | pairtext [repeats] | sam [repeats] | sam-tags [repeats] | text [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
         return 2;
     }
     try
@@ -249,7 +249,7 @@ int main( int argc, char** argv )
         maCheck( ma_set_device( atoi( argv[ 5 ] ) ) );
         maCheck( ma_host_bind_thread( atoi( argv[ 5 ] ), 0, nullptr ) ); // this thread and all it starts: the CPUs next to the GPU
         const unsigned uiHw = std::max( 1u, std::thread::hardware_concurrency( ) );
-        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "text" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
+        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "pairtext" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "text" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         double t0 = now( );
@@ -267,14 +267,8 @@ int main( int argc, char** argv )
             uiState ^= uiState << 13, uiState ^= uiState >> 7, uiState ^= uiState << 17;
             return uiState;
         };
-        if( argc >= 7 && !strcmp( argv[ 6 ], "paired" ) )
-        {
-            // ---- the paired leg: n mates (n / 2 pairs, outer distance 340 .. 460, every second pair seen from the other strand)
-            // host to host INCLUDING SAM text through (a) BatchAligner::executePaired + PairedFileWriter -- Alignment
-            // containers, PairedReads on one host thread -- and (b) executePairedFlat + BatchPairedFileWriter -- paired on the
-            // device, text from the flat pair records -- and (c) executePairedFlatSam + BatchPairedFileWriter -- paired AND
-            // printed on the device, the text is what comes down; alternating, <repeats> times each after one warm-up of each
-            const int iRepeats = argc >= 8 ? std::max( 1, atoi( argv[ 7 ] ) ) : 5;
+        // the synthetic mates of the paired legs: n / 2 pairs, outer distance 340 .. 460, every second pair seen from the other strand
+        auto makeMates = [ & ]( ) {
             auto pMates = std::make_shared<ReadVec>( );
             auto window = [ & ]( uint64_t uiPos, bool bRev, size_t uiName ) {
                 auto pQ = std::make_shared<NucSeq>( );
@@ -311,6 +305,165 @@ int main( int argc, char** argv )
                     pMates->push_back( window( uiPos + uiDist - uiLen, true, 2 * k + 1 ) );
                 }
             }
+            return pMates;
+        };
+        if( argc >= 7 && !strcmp( argv[ 6 ], "pairtext" ) )
+        {
+            // ---- the paired text leg: the mates of the paired leg as TWO FASTQ texts in memory, as a sequencer writes them (R2 on
+            // the other strand; seeded qualities 35 .. 126), files to SAM text through (a) BatchPairedTextReader ->
+            // executePairedTextSam -- blocks of both texts cut into equally many records, parsed, interleaved and reverse-complemented
+            // on the device -- and (b) PairedFileReader -> executePairedFlatSam -- one NucSeq per mate, the host's reverse
+            // complement, gathered and uploaded as arrays; what examples/ma_align runs with and without --text-input.  (a) with
+            // three workers (own aligner each, one device batch of ~256 k mates at a time) that pull their batches from the one pair
+            // stream, (b) on an aligner of its own with executePairedFlatSam's three batches in flight.  One warm-up of each keeps its text -- (a)'s
+            // batches put into input order by their first QNAME -- and the two files must be the same bytes; then alternating,
+            // <repeats> times each, with the texts only counted and every count checked against the file's.
+            const int iRepeats = argc >= 8 ? std::max( 1, atoi( argv[ 7 ] ) ) : 5;
+            auto pMates = makeMates( );
+            std::vector<uint8_t>( ).swap( vPac );
+            const size_t uiMates = pMates->size( ), uiWorkers = 3, uiBatchReads = std::min<size_t>( std::max<size_t>( uiMates, 2 ), 1u << 18 );
+            std::string asFastq[ 2 ];
+            for( size_t i = 0; i < uiMates; i++ )
+            {
+                std::string& rText = asFastq[ i & 1 ];
+                const NucSeq& rQ = *( *pMates )[ i ];
+                rText += "@" + rQ.sName + "\n";
+                if( i & 1 ) // the file holds the other strand: PairedFileReader and the device turn it back
+                    for( size_t j = rQ.xCodes.size( ); j > 0; j-- )
+                        rText += "TGCA"[ rQ.xCodes[ j - 1 ] ];
+                else
+                    for( uint8_t b : rQ.xCodes )
+                        rText += "ACGT"[ b ];
+                rText += "\n+\n";
+                for( size_t j = 0; j < rQ.xCodes.size( ); j++ )
+                    rText += (char)( 35 + rnd( ) % 92 );
+                rText += "\n";
+            }
+            pMates->clear( );
+            xParams.bRevCompPairedReadMates = true;
+            BatchAligner::nameContigs( *pFM->pDev, *pPack );
+            std::vector<std::unique_ptr<BatchAligner>> vAligners;
+            for( size_t w = 0; w <= uiWorkers; w++ ) // (the last one runs leg (b): engines of its own, so each warm-up warms its leg's)
+            {
+                vAligners.emplace_back( new BatchAligner( xParams ) );
+                vAligners.back( )->uiBatchReads = uiBatchReads;
+                vAligners.back( )->uiInflight = w == uiWorkers ? 3 : 1;
+            }
+            uint64_t uiBytesHost = 0, uiBytesText = 0;
+            auto host = [ & ]( std::string* pFile ) {
+                auto pStreams = std::make_shared<PairedFileStream>( std::make_shared<StringStream>( asFastq[ 0 ] ), std::make_shared<StringStream>( asFastq[ 1 ] ) );
+                PairedFileReader xReader( xParams );
+                const double t = now( );
+                uiBytesHost = 0;
+                if( pFile != nullptr )
+                    pFile->clear( );
+                while( true )
+                {
+                    auto pBatch = std::make_shared<ReadVec>( );
+                    while( pBatch->size( ) < 1000000 ) // (ma_align's batch)
+                    {
+                        auto pPair = xReader.execute( pStreams );
+                        if( pPair == nullptr )
+                            break;
+                        pBatch->push_back( ( *pPair )[ 0 ] );
+                        pBatch->push_back( ( *pPair )[ 1 ] );
+                    }
+                    if( pBatch->empty( ) )
+                        break;
+                    std::vector<AlignerTiming> vPer;
+                    auto pFlat = vAligners[ uiWorkers ]->executePairedFlatSamOn( pFM->pDev->all( ), pBatch, &vPer );
+                    for( auto& pB : *pFlat )
+                    {
+                        uiBytesHost += pB->samBytes( );
+                        if( pFile != nullptr )
+                            pFile->append( pB->samText( ), pB->samBytes( ) );
+                    }
+                }
+                return now( ) - t;
+            };
+            auto text = [ & ]( std::string* pFile ) {
+                auto pStreams = std::make_shared<PairedFileStream>( std::make_shared<StringStream>( asFastq[ 0 ] ), std::make_shared<StringStream>( asFastq[ 1 ] ) );
+                BatchPairedTextReader xReader( xParams );
+                xReader.uiBatchBytes = std::max<size_t>( 2, ( asFastq[ 0 ].size( ) + asFastq[ 1 ].size( ) ) / std::max<size_t>( uiMates, 1 ) * uiBatchReads );
+                std::vector<std::pair<uint64_t, std::string>> vParts;
+                std::mutex xParts;
+                std::string sFailure;
+                std::atomic<uint64_t> uiBytes{ 0 };
+                const double t = now( );
+                std::vector<std::thread> vT;
+                for( size_t w = 0; w < uiWorkers; w++ )
+                    vT.emplace_back( [ &, w ]( ) {
+                        try
+                        {
+                            while( auto pTexts = xReader.execute( pStreams ) )
+                            {
+                                auto pB = vAligners[ w ]->executePairedTextSamOn( pFM->pDev->p, pTexts );
+                                uiBytes += pB->samBytes( );
+                                if( pFile != nullptr )
+                                {
+                                    const uint64_t uiFirst = pB->samBytes( ) > 1 ? strtoull( pB->samText( ) + 1, nullptr, 10 ) : 0; // "r<i>\t..."
+                                    std::lock_guard<std::mutex> xGuard( xParts );
+                                    vParts.emplace_back( uiFirst, std::string( pB->samText( ), pB->samBytes( ) ) );
+                                }
+                            }
+                        }
+                        catch( const std::exception& rE )
+                        {
+                            std::lock_guard<std::mutex> xGuard( xParts );
+                            sFailure = rE.what( );
+                        }
+                    } );
+                for( auto& rT : vT )
+                    rT.join( );
+                const double f = now( ) - t;
+                if( !sFailure.empty( ) )
+                    throw std::runtime_error( sFailure );
+                uiBytesText = uiBytes.load( );
+                if( pFile != nullptr )
+                {
+                    std::sort( vParts.begin( ), vParts.end( ), []( const auto& a, const auto& b ) { return a.first < b.first; } );
+                    pFile->clear( );
+                    for( const auto& rPart : vParts )
+                        *pFile += rPart.second;
+                }
+                return f;
+            };
+            // warm-up of both: these two runs keep their files, which must be the same bytes; the timed runs count theirs
+            std::string sFileHost, sFileText;
+            host( &sFileHost ), text( &sFileText );
+            bool bEqual = sFileHost == sFileText && !sFileHost.empty( );
+            const uint64_t uiFileBytes = sFileText.size( );
+            std::string( ).swap( sFileHost ), std::string( ).swap( sFileText );
+            std::vector<double> vH, vD;
+            for( int r = 0; r < iRepeats; r++ )
+            {
+                vD.push_back( uiMates / text( nullptr ) ), vH.push_back( uiMates / host( nullptr ) );
+                bEqual = bEqual && uiBytesHost == uiFileBytes && uiBytesText == uiFileBytes;
+            }
+            auto list = []( std::vector<double> v ) {
+                std::string sAll;
+                for( double f : v )
+                    sAll += ( sAll.empty( ) ? "" : ", " ) + std::to_string( f );
+                std::sort( v.begin( ), v.end( ) );
+                return "{\"median\": " + std::to_string( v[ v.size( ) / 2 ] ) + ", \"min\": " + std::to_string( v.front( ) ) +
+                       ", \"max\": " + std::to_string( v.back( ) ) + ", \"all\": [" + sAll + "]}";
+            };
+            printf( "{\"pairtext\": {\"mates\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_reads\": %zu, \"workers\": %zu, "
+                    "\"paired_text_reader_paired_text_sam_reads_per_s\": %s, \"paired_file_reader_paired_flat_sam_reads_per_s\": %s, "
+                    "\"fastq_bytes\": %zu, \"sam_bytes\": %zu, \"equal\": %s}}\n",
+                    uiMates, uiLen, iRepeats, uiBatchReads, uiWorkers, list( vD ).c_str( ), list( vH ).c_str( ), asFastq[ 0 ].size( ) + asFastq[ 1 ].size( ),
+                    (size_t)uiFileBytes, bEqual ? "true" : "false" );
+            return bEqual ? 0 : 1;
+        }
+        if( argc >= 7 && !strcmp( argv[ 6 ], "paired" ) )
+        {
+            // ---- the paired leg: n mates (n / 2 pairs, outer distance 340 .. 460, every second pair seen from the other strand)
+            // host to host INCLUDING SAM text through (a) BatchAligner::executePaired + PairedFileWriter -- Alignment
+            // containers, PairedReads on one host thread -- and (b) executePairedFlat + BatchPairedFileWriter -- paired on the
+            // device, text from the flat pair records -- and (c) executePairedFlatSam + BatchPairedFileWriter -- paired AND
+            // printed on the device, the text is what comes down; alternating, <repeats> times each after one warm-up of each
+            const int iRepeats = argc >= 8 ? std::max( 1, atoi( argv[ 7 ] ) ) : 5;
+            auto pMates = makeMates( );
             std::vector<uint8_t>( ).swap( vPac );
             BatchAligner xAligner( xParams );
             xAligner.uiBatchReads = std::min<size_t>( pMates->size( ), 1u << 18 );

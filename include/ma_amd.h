@@ -413,6 +413,32 @@ int ma_batch_set_reads_text( ma_batch*, const char* text /*host*/, uint64_t n_by
 int ma_batch_read_counts( ma_batch*, uint64_t* n_reads, uint64_t* n_bases, uint64_t* n_name_bytes, int32_t* has_qual );
 int ma_batch_get_reads( ma_batch*, uint64_t* offsets /*n+1*/, uint8_t* codes );
 int ma_batch_get_read_text( ma_batch*, uint64_t* name_off /*n+1*/, char* names, uint8_t* qual /*may be NULL*/ );
+/* ---- paired read text in: PairedFileReader::execute (fileReader.h:568-617) on the device ----
+ * Two texts, the R1 and R2 file of a paired-end run or runs of whole records cut out of them, uploaded as they are and parsed
+ * by the kernels of ma_batch_set_reads_text, each by exactly its strict rules (ma_amd/host/ma_text_dev.h; ma_text::pairHost is
+ * the serial statement of this call): replaces one NucSeq per mate, the host's reverse complement of every second mate, the
+ * gather and three uploads.  Record k of text 1 becomes read 2k, record k of text 2 read 2k + 1; with R1 and R2 records there are
+ * R = min( R1, R2 ) pairs -- the shorter file ends the stream, as in the reference.  With rev_comp_mates != 0 (the reference's
+ * default, xRevCompPairedReadMates) every read 2k + 1 is reversed with its qualities (NucSeq::vReverse, nucSeq.h:373-381) and
+ * complemented (vSwitchAllBasePairsToComplement, nucSeq.h:537-543: a code below 4 becomes 3 - c, every other code 5 (sic));
+ * names are untouched.
+ *   ma_batch_set_mates_text  texts: host memory, each < 2 GiB.  Uploads, parses and waits (two read-backs: the line counts of
+ *                            both texts in one copy, then the statistics).  Afterwards the batch is exactly as after
+ *                            ma_batch_set_reads on the 2 R interleaved reads + ma_batch_set_read_text (qualities iff FASTQ):
+ *                            ma_align_batch, ma_inversions_batch, ma_pair_batch, ma_pair_sam_batch and the getters above run
+ *                            unchanged.  *n_pairs = R; consumed[i] = offset in text i of the first byte of record R (n_i when
+ *                            the text has exactly R records): a caller carries text_i + consumed[i] into its next call.
+ *                            Records beyond R are validated -- a violation anywhere refuses the call -- but count neither
+ *                            against the capacity nor into any sum.  n1 == 0 or n2 == 0 gives 0 pairs (the other text is
+ *                            still validated).  Refusals, in this order; each leaves the batch without reads and text and
+ *                            usable, *n_pairs = 0 and consumed = {0, 0} unless stated:
+ *                              "ma_batch_set_mates_text: text <1|2>: line <L> (byte <X>): <reason>"  a rule violation; text 1
+ *                                wins over text 2, within a text the lowest line, then the lowest reason
+ *                              "ma_batch_set_mates_text: the two texts differ in kind"  one FASTQ, one FASTA
+ *                              "ma_batch_set_mates_text: batch capacity exceeded"  2 R > max_reads or more paired bases than
+ *                                max_bases; *n_pairs = R then, what a caller sizes the next batch object by */
+int ma_batch_set_mates_text( ma_batch*, const char* text1 /*host*/, uint64_t n1, const char* text2 /*host*/, uint64_t n2,
+                             int32_t rev_comp_mates, uint64_t* n_pairs, uint64_t consumed[ 2 ] );
 /* work counters for the roofline model (same meaning as the oracle's): [0] extend_backward steps,
  * [1] distinct occ blocks touched, [2] bwt_sa LF steps, [3] SA rows, [4] DP band cells, [5] ksw jobs */
 int ma_batch_counters( ma_batch*, uint64_t out[ 8 ] );

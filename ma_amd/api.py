@@ -378,6 +378,27 @@ class Batch:
         self.n_bases = int(self.read_off[-1])
         return self.n
 
+    def set_mates_text(self, text1, text2, rev_comp=True):
+        """text1, text2: bytes of the two read files of a paired-end run (or runs of whole records of them), both FASTQ or both
+        FASTA in the strict form (ma_batch_set_mates_text).  Record k of text1 becomes read 2k, record k of text2 read 2k + 1,
+        reversed and complemented with rev_comp; the shorter text ends the stream.  The batch then is as after set_reads() on the
+        interleaved reads + set_read_text().  Returns (n_pairs, (consumed1, consumed2)): the offsets at which the next call goes
+        on.  A refusal raises MaError and leaves the batch without reads; after "batch capacity exceeded" the exception's n_pairs
+        is the number of pairs the texts hold."""
+        bufs = [np.frombuffer(bytes(t) + b"\0", dtype=np.uint8) for t in (text1, text2)]
+        n, consumed = C.c_uint64(), (C.c_uint64 * 2)()
+        self.n, self.read_off, self.n_bases = 0, np.zeros(1, dtype=np.uint64), 0
+        try:
+            _chk(lib().ma_batch_set_mates_text(self.h, _ptr(bufs[0]), C.c_uint64(len(bufs[0]) - 1), _ptr(bufs[1]), C.c_uint64(len(bufs[1]) - 1),
+                                               C.c_int32(1 if rev_comp else 0), C.byref(n), consumed))
+        except MaError as e:
+            e.n_pairs = int(n.value)
+            raise
+        self.n = 2 * int(n.value)
+        self.read_off, _ = self.reads(codes=False)
+        self.n_bases = int(self.read_off[-1])
+        return int(n.value), (int(consumed[0]), int(consumed[1]))
+
     def read_counts(self):
         v = [C.c_uint64() for _ in range(3)]
         q = C.c_int32()

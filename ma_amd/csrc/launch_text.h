@@ -1,5 +1,5 @@
-// launch_text.h -- ma_batch_set_reads_text and the getters of a batch's reads and read text.  Textually part of pipeline.hip;
-// the kernels are in stage_text.h, the rules in ma_amd/host/ma_text_dev.h.
+// launch_text.h -- ma_batch_set_reads_text, ma_batch_set_mates_text and the getters of a batch's reads and read text.  Textually
+// part of pipeline.hip; the kernels are in stage_text.h, the rules in ma_amd/host/ma_text_dev.h.
 
 // the batch holds no reads and no text (what a failed ma_batch_set_reads_text leaves, and what it starts from)
 static int text_no_reads( ma_batch* b )
@@ -23,6 +23,87 @@ static int text_refuse( u64 line, u64 byte, u32 reason )
     ma_text::message( msg, sizeof( msg ), line, byte, reason );
     return fail( msg );
 }
+static int mates_refuse( u32 refusal, u32 text, u64 line, u64 byte, u32 reason )
+{
+    char msg[ 256 ];
+    ma_text::messageMates( msg, sizeof( msg ), refusal, text, line, byte, reason );
+    return fail( msg );
+}
+
+// what the host sees of a text without parsing it: NO_VIOLATION, or the refusal at line 0
+static u64 text_host_key( const char* text, u64 n )
+{
+    if( n > ma_text::MAX_TEXT_BYTES )
+        return ma_text::key( 0, ma_text::ERR_TOO_LARGE );
+    if( n && text[ 0 ] != '@' && text[ 0 ] != '>' )
+        return ma_text::key( 0, ma_text::ERR_KIND );
+    return ma_text::NO_VIOLATION;
+}
+
+// The front of a parse, k_text_count .. k_text_records, of ONE text of n > 0 bytes on scratch of its own: both entry points run
+// it, ma_batch_set_mates_text once per text.  text_front_count uploads and counts, the caller reads the line feeds back
+// (stat[ TXT_FEEDS ]) and sets `feeds`, text_front_lines does the per-line work.
+struct TextFront
+{
+    const char* host;
+    u64 n;
+    char* dev; // 256-byte aligned, inside b->txtIn
+    unsigned long long* stat; // TXT_WORDS words inside b->txtStat
+    ma_batch::TextScratch* scratch;
+    u32 kind;
+    u64 nBlocks, feeds, lines;
+};
+static int text_front_count( ma_batch* b, TextFront& t )
+{
+    t.kind = t.host[ 0 ] == '@' ? ma_text::KIND_FASTQ : ma_text::KIND_FASTA;
+    t.nBlocks = ( t.n + TEXT_BLOCK_BYTES - 1 ) / TEXT_BLOCK_BYTES;
+    if( t.scratch->block.reserve( ( t.nBlocks + 1 ) * 4 ) )
+        return 1;
+    MA_HIP( hipMemcpyAsync( t.dev, t.host, t.n, hipMemcpyHostToDevice, b->stream ) );
+    MA_HIP( hipMemsetAsync( t.stat, 0, TXT_WORDS * 8, b->stream ) );
+    MA_HIP( hipMemsetAsync( t.stat + TXT_LONE_CR, 0xff, 2 * 8, b->stream ) ); // TXT_LONE_CR, TXT_VIOLATION: none
+    hipLaunchKernelGGL( k_text_count, dim3( (unsigned)t.nBlocks ), dim3( TEXT_BLOCK ), 0, b->stream, t.dev, t.n, t.scratch->block.as<u32>( ), t.stat );
+    MA_HIP( hipGetLastError( ) );
+    return 0;
+}
+static TextSide text_side( const TextFront& t, u64 hostKey )
+{
+    TextSide s;
+    s.text = t.dev;
+    s.n = t.n, s.lines = t.lines;
+    s.start = t.scratch->start.as<u32>( );
+    s.hdrName = t.scratch->hdrName.as<u64>( );
+    s.bases = t.scratch->bases.as<u32>( );
+    s.recLine = t.scratch->recLine.as<u32>( );
+    s.stat = t.stat;
+    s.hostKey = hostKey;
+    return s;
+}
+static int text_front_lines( ma_batch* b, TextFront& t )
+{
+    ma_batch::TextScratch& S = *t.scratch;
+    t.lines = ma_text::nLines( t.feeds, t.host[ t.n - 1 ] );
+    const u64 lines = t.lines;
+    if( S.start.reserve( ( lines + 2 ) * 4 ) || S.hdrName.reserve( ( lines + 2 ) * 8 ) || S.bases.reserve( ( lines + 2 ) * 4 ) ||
+        S.recLine.reserve( ( lines + 2 ) * 4 ) )
+        return 1;
+    if( scan_exclusive<u32>( b, S.block.as<u32>( ), S.block.as<u32>( ), t.nBlocks ) )
+        return 1;
+    const dim3 textGrid( (unsigned)t.nBlocks ), textBlock( TEXT_BLOCK );
+    hipLaunchKernelGGL( k_text_lines, textGrid, textBlock, 0, b->stream, t.dev, t.n, S.block.as<u32>( ), t.feeds, S.start.as<u32>( ) );
+    const dim3 lineGrid( (unsigned)( ( lines + 1 + 255 ) / 256 ) ), lineBlock( 256 );
+    hipLaunchKernelGGL( k_text_classify, lineGrid, lineBlock, 0, b->stream, t.kind, t.dev, S.start.as<u32>( ), lines, t.stat, S.hdrName.as<u64>( ),
+                        S.bases.as<u32>( ) );
+    MA_HIP( hipGetLastError( ) );
+    if( scan_exclusive<u64>( b, S.hdrName.as<u64>( ), S.hdrName.as<u64>( ), lines + 1 ) ||
+        scan_exclusive<u32>( b, S.bases.as<u32>( ), S.bases.as<u32>( ), lines + 1 ) )
+        return 1;
+    hipLaunchKernelGGL( k_text_rec_lines, lineGrid, lineBlock, 0, b->stream, lines, S.hdrName.as<u64>( ), S.recLine.as<u32>( ) );
+    hipLaunchKernelGGL( k_text_records, dim3( (unsigned)std::min<u64>( 256, ( lines + 255 ) / 256 ) ), lineBlock, 0, b->stream, t.kind, lines,
+                        S.hdrName.as<u64>( ), S.bases.as<u32>( ), S.recLine.as<u32>( ), t.stat );
+    MA_HIP( hipGetLastError( ) );
+    return 0;
+}
 
 extern "C" {
 
@@ -35,10 +116,9 @@ int ma_batch_set_reads_text( ma_batch* b, const char* text, uint64_t n, uint64_t
         *n_reads = 0;
     if( text_no_reads( b ) )
         return 1;
-    if( n > ma_text::MAX_TEXT_BYTES )
-        return batch_wait( b ) || text_refuse( 0, 0, ma_text::ERR_TOO_LARGE );
-    if( n && text[ 0 ] != '@' && text[ 0 ] != '>' )
-        return batch_wait( b ) || text_refuse( 0, 0, ma_text::ERR_KIND );
+    const u64 hostKey = text_host_key( text, n );
+    if( hostKey != ma_text::NO_VIOLATION )
+        return batch_wait( b ) || text_refuse( 0, 0, (u32)( hostKey & 0xffu ) );
     if( b->txtNameOff.reserve( ( b->max_reads + 1 ) * 8 ) )
         return 1;
     MA_HIP( hipMemsetAsync( b->txtNameOff.p, 0, 8, b->stream ) );
@@ -49,56 +129,36 @@ int ma_batch_set_reads_text( ma_batch* b, const char* text, uint64_t n, uint64_t
         b->txtSet = true;
         return 0;
     }
-    const u32 kind = text[ 0 ] == '@' ? ma_text::KIND_FASTQ : ma_text::KIND_FASTA;
-    const u64 nBlocks = ( n + TEXT_BLOCK_BYTES - 1 ) / TEXT_BLOCK_BYTES;
-    if( b->txtIn.reserve( n + 64 ) || b->txtStat.reserve( TXT_WORDS * 8 ) || b->txtBlock.reserve( ( nBlocks + 1 ) * 4 ) )
+    if( b->txtIn.reserve( n + 64 ) || b->txtStat.reserve( TXT_WORDS * 8 ) )
         return 1;
     unsigned long long* const stat = b->txtStat.as<unsigned long long>( );
     unsigned long long h[ TXT_WORDS ];
-    MA_HIP( hipMemcpyAsync( b->txtIn.p, text, n, hipMemcpyHostToDevice, b->stream ) );
-    MA_HIP( hipMemsetAsync( stat, 0, TXT_WORDS * 8, b->stream ) );
-    MA_HIP( hipMemsetAsync( stat + TXT_LONE_CR, 0xff, 2 * 8, b->stream ) ); // TXT_LONE_CR, TXT_VIOLATION: none
-    const dim3 textGrid( (unsigned)nBlocks ), textBlock( TEXT_BLOCK );
-    hipLaunchKernelGGL( k_text_count, textGrid, textBlock, 0, b->stream, b->txtIn.as<char>( ), n, b->txtBlock.as<u32>( ), stat );
-    MA_HIP( hipGetLastError( ) );
+    TextFront t{ text, n, b->txtIn.as<char>( ), stat, &b->txtOne };
+    if( text_front_count( b, t ) )
+        return 1;
     // read-back 1: the number of lines sizes the per-line scratch and launches
     MA_HIP( hipMemcpyAsync( h, stat, 8, hipMemcpyDeviceToHost, b->stream ) );
     if( batch_wait( b ) )
         return 1;
-    const u64 feeds = h[ TXT_FEEDS ], lines = ma_text::nLines( feeds, text[ n - 1 ] );
-    if( b->txtStart.reserve( ( lines + 2 ) * 4 ) || b->txtHdrName.reserve( ( lines + 2 ) * 8 ) || b->txtBases.reserve( ( lines + 2 ) * 4 ) ||
-        b->txtRecLine.reserve( ( lines + 2 ) * 4 ) || b->txtNames.reserve( n + 1 ) ||
-        ( kind == ma_text::KIND_FASTQ && b->txtQual.reserve( b->max_bases + 1 ) ) )
+    t.feeds = h[ TXT_FEEDS ];
+    if( b->txtNames.reserve( n + 1 ) || ( t.kind == ma_text::KIND_FASTQ && b->txtQual.reserve( b->max_bases + 1 ) ) || text_front_lines( b, t ) )
         return 1;
-    if( scan_exclusive<u32>( b, b->txtBlock.as<u32>( ), b->txtBlock.as<u32>( ), nBlocks ) )
-        return 1;
-    hipLaunchKernelGGL( k_text_lines, textGrid, textBlock, 0, b->stream, b->txtIn.as<char>( ), n, b->txtBlock.as<u32>( ), feeds, b->txtStart.as<u32>( ) );
-    const dim3 lineGrid( (unsigned)( ( lines + 1 + 255 ) / 256 ) ), lineBlock( 256 );
-    hipLaunchKernelGGL( k_text_classify, lineGrid, lineBlock, 0, b->stream, kind, b->txtIn.as<char>( ), b->txtStart.as<u32>( ), lines, stat,
-                        b->txtHdrName.as<u64>( ), b->txtBases.as<u32>( ) );
-    MA_HIP( hipGetLastError( ) );
-    if( scan_exclusive<u64>( b, b->txtHdrName.as<u64>( ), b->txtHdrName.as<u64>( ), lines + 1 ) ||
-        scan_exclusive<u32>( b, b->txtBases.as<u32>( ), b->txtBases.as<u32>( ), lines + 1 ) )
-        return 1;
-    hipLaunchKernelGGL( k_text_rec_lines, lineGrid, lineBlock, 0, b->stream, lines, b->txtHdrName.as<u64>( ), b->txtRecLine.as<u32>( ) );
-    hipLaunchKernelGGL( k_text_records, dim3( (unsigned)std::min<u64>( 256, ( lines + 255 ) / 256 ) ), lineBlock, 0, b->stream, kind, lines,
-                        b->txtHdrName.as<u64>( ), b->txtBases.as<u32>( ), b->txtRecLine.as<u32>( ), stat );
-    hipLaunchKernelGGL( k_text_stat, dim3( 1 ), dim3( 1 ), 0, b->stream, lines, b->txtHdrName.as<u64>( ), b->txtBases.as<u32>( ),
-                        b->txtStart.as<u32>( ), b->max_reads, b->max_bases, stat );
+    const TextSide s = text_side( t, ma_text::NO_VIOLATION );
+    hipLaunchKernelGGL( k_text_stat, dim3( 1 ), dim3( 1 ), 0, b->stream, t.lines, s.hdrName, s.bases, s.start, b->max_reads, b->max_bases, stat );
     TextEmitArgs A;
-    A.kind = kind;
-    A.text = b->txtIn.as<char>( );
-    A.n = n, A.lines = lines;
-    A.start = b->txtStart.as<u32>( );
-    A.hdrName = b->txtHdrName.as<u64>( );
-    A.bases = b->txtBases.as<u32>( );
+    A.kind = t.kind;
+    A.text = t.dev;
+    A.n = n, A.lines = t.lines;
+    A.start = s.start;
+    A.hdrName = s.hdrName;
+    A.bases = s.bases;
     A.stat = stat;
     A.roff = b->roff.as<u64>( );
     A.codes = b->reads.as<uint8_t>( );
     A.nameOff = b->txtNameOff.as<u64>( );
     A.names = b->txtNames.as<char>( );
-    A.qual = kind == ma_text::KIND_FASTQ ? b->txtQual.as<uint8_t>( ) : nullptr;
-    hipLaunchKernelGGL( k_text_emit, textGrid, textBlock, 0, b->stream, A );
+    A.qual = t.kind == ma_text::KIND_FASTQ ? b->txtQual.as<uint8_t>( ) : nullptr;
+    hipLaunchKernelGGL( k_text_emit, dim3( (unsigned)t.nBlocks ), dim3( TEXT_BLOCK ), 0, b->stream, A );
     MA_HIP( hipGetLastError( ) );
     // read-back 2: reads, bases, name bytes, the longest read, the refusal
     MA_HIP( hipMemcpyAsync( h, stat, TXT_WORDS * 8, hipMemcpyDeviceToHost, b->stream ) );
@@ -116,10 +176,125 @@ int ma_batch_set_reads_text( ma_batch* b, const char* text, uint64_t n, uint64_t
     b->n_bases = h[ TXT_BASES ];
     b->max_qlen = (u32)h[ TXT_MAX_LEN ];
     b->txtNameBytes = h[ TXT_NAME_BYTES ];
-    b->txtHasQual = kind == ma_text::KIND_FASTQ;
+    b->txtHasQual = t.kind == ma_text::KIND_FASTQ;
     b->txtSet = true;
     if( n_reads )
         *n_reads = b->n_reads;
+    return 0;
+}
+
+int ma_batch_set_mates_text( ma_batch* b, const char* text1, uint64_t n1, const char* text2, uint64_t n2, int32_t rev_comp_mates,
+                             uint64_t* n_pairs, uint64_t consumed[ 2 ] )
+{
+    if( !b || ( n1 && !text1 ) || ( n2 && !text2 ) )
+        return fail( "ma_batch_set_mates_text: null argument" );
+    MA_BIND_DEVICE( b->device );
+    if( n_pairs )
+        *n_pairs = 0;
+    if( consumed )
+        consumed[ 0 ] = consumed[ 1 ] = 0;
+    if( text_no_reads( b ) )
+        return 1;
+    // A text the host refuses at its first byte, or an empty one, is not parsed: it has no records, so there are no pairs, but
+    // the other text is validated all the same (a violation in text 1 wins over text 2's)
+    const u64 hostKey[ 2 ] = { text_host_key( text1, n1 ), text_host_key( text2, n2 ) };
+    if( hostKey[ 0 ] != ma_text::NO_VIOLATION )
+        return batch_wait( b ) || mates_refuse( ma_text::MATES_LINE, 1, 0, 0, (u32)( hostKey[ 0 ] & 0xffu ) );
+    const bool parsed[ 2 ] = { n1 > 0, n2 > 0 && hostKey[ 1 ] == ma_text::NO_VIOLATION };
+    const u64 at2 = ( n1 + 255 ) & ~(u64)255; // text 2 behind text 1 in the one upload buffer
+    if( b->txtNameOff.reserve( ( b->max_reads + 1 ) * 8 ) || b->txtIn.reserve( at2 + ( parsed[ 1 ] ? n2 : 0 ) + 64 ) ||
+        b->txtStat.reserve( ( 2 * TXT_WORDS + MT_WORDS ) * 8 ) )
+        return 1;
+    MA_HIP( hipMemsetAsync( b->txtNameOff.p, 0, 8, b->stream ) );
+    unsigned long long* const stat = b->txtStat.as<unsigned long long>( );
+    unsigned long long* const mstat = stat + 2 * TXT_WORDS;
+    MA_HIP( hipMemsetAsync( stat, 0, ( 2 * TXT_WORDS + MT_WORDS ) * 8, b->stream ) );
+    TextFront t[ 2 ] = { { text1, n1, b->txtIn.as<char>( ), stat, &b->txtOne }, { text2, n2, b->txtIn.as<char>( ) + at2, stat + TXT_WORDS, &b->txtMate } };
+    for( int i = 0; i < 2; i++ )
+    {
+        t[ i ].kind = 0, t[ i ].nBlocks = t[ i ].feeds = t[ i ].lines = 0;
+        if( parsed[ i ] && text_front_count( b, t[ i ] ) )
+            return 1;
+    }
+    unsigned long long h[ 2 * TXT_WORDS + MT_WORDS ];
+    if( parsed[ 0 ] || parsed[ 1 ] )
+    {
+        // read-back 1: the line feeds of both texts, in one copy
+        MA_HIP( hipMemcpyAsync( h, stat, ( TXT_WORDS + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
+        if( batch_wait( b ) )
+            return 1;
+    }
+    u64 most = ~0ull; // pairs at most: a FASTQ record has four lines, a FASTA record two or more
+    for( int i = 0; i < 2; i++ )
+    {
+        if( !parsed[ i ] )
+        {
+            most = 0;
+            continue;
+        }
+        t[ i ].feeds = h[ i * TXT_WORDS + TXT_FEEDS ];
+        if( text_front_lines( b, t[ i ] ) )
+            return 1;
+        most = std::min<u64>( most, t[ i ].kind == ma_text::KIND_FASTQ ? ( t[ i ].lines + 3 ) / 4 : ( t[ i ].lines + 1 ) / 2 );
+    }
+    const bool fastq = parsed[ 0 ] && parsed[ 1 ] && t[ 0 ].kind == ma_text::KIND_FASTQ && t[ 1 ].kind == ma_text::KIND_FASTQ;
+    const u32 kindsDiffer = parsed[ 0 ] && parsed[ 1 ] && t[ 0 ].kind != t[ 1 ].kind ? 1 : 0;
+    if( b->txtNames.reserve( n1 + n2 + 1 ) || ( fastq && b->txtQual.reserve( b->max_bases + 1 ) ) )
+        return 1;
+    const TextSide side[ 2 ] = { text_side( t[ 0 ], hostKey[ 0 ] ), text_side( t[ 1 ], hostKey[ 1 ] ) };
+    u64* const roff = b->roff.as<u64>( );
+    u64* const nameOff = b->txtNameOff.as<u64>( );
+    if( most > 0 )
+    {
+        // lengths of the interleaved reads, 0 behind the last pair; never more entries than the batch's arrays hold
+        const u64 entries = std::min<u64>( b->max_reads, 2 * most ) + 1;
+        hipLaunchKernelGGL( k_text_mates_plan, dim3( (unsigned)( ( ( entries + 1 ) / 2 + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream, side[ 0 ], side[ 1 ],
+                            entries, b->max_reads, roff, nameOff, mstat );
+        MA_HIP( hipGetLastError( ) );
+        if( scan_exclusive<u64>( b, roff, roff, entries ) || scan_exclusive<u64>( b, nameOff, nameOff, entries ) )
+            return 1;
+    }
+    hipLaunchKernelGGL( k_text_mates_stat, dim3( 1 ), dim3( 1 ), 0, b->stream, side[ 0 ], side[ 1 ], kindsDiffer, b->max_reads, b->max_bases, roff,
+                        nameOff, mstat );
+    if( most > 0 && !kindsDiffer )
+    {
+        MatesEmitArgs A;
+        A.kind = t[ 0 ].kind;
+        A.revComp = rev_comp_mates != 0 ? 1 : 0;
+        A.mstat = mstat;
+        A.roff = roff;
+        A.nameOff = nameOff;
+        A.codes = b->reads.as<uint8_t>( );
+        A.names = b->txtNames.as<char>( );
+        A.qual = fastq ? b->txtQual.as<uint8_t>( ) : nullptr;
+        A.s = side[ 0 ];
+        hipLaunchKernelGGL( k_text_mates_emit<0>, dim3( (unsigned)t[ 0 ].nBlocks ), dim3( TEXT_BLOCK ), 0, b->stream, A );
+        A.s = side[ 1 ];
+        hipLaunchKernelGGL( k_text_mates_emit<1>, dim3( (unsigned)t[ 1 ].nBlocks ), dim3( TEXT_BLOCK ), 0, b->stream, A );
+    }
+    MA_HIP( hipGetLastError( ) );
+    // read-back 2: pairs, sums, the longest read, the consumed bytes, the refusal
+    MA_HIP( hipMemcpyAsync( h, mstat, MT_WORDS * 8, hipMemcpyDeviceToHost, b->stream ) );
+    if( batch_wait( b ) )
+        return 1;
+    if( h[ MT_REFUSAL ] != ma_text::MATES_OK )
+    {
+        if( text_no_reads( b ) || batch_wait( b ) ) // (the offset arrays hold the plan's sums)
+            return 1;
+        if( h[ MT_REFUSAL ] == ma_text::MATES_CAPACITY && n_pairs )
+            *n_pairs = h[ MT_PAIRS ]; // (what a caller sizes the next batch object by)
+        return mates_refuse( (u32)h[ MT_REFUSAL ], (u32)h[ MT_TEXT ], h[ MT_VIOLATION ] >> 8, h[ MT_BYTE ], (u32)( h[ MT_VIOLATION ] & 0xffu ) );
+    }
+    b->n_reads = 2 * h[ MT_PAIRS ];
+    b->n_bases = h[ MT_BASES ];
+    b->max_qlen = (u32)h[ MT_MAX_LEN ];
+    b->txtNameBytes = h[ MT_NAME_BYTES ];
+    b->txtHasQual = fastq;
+    b->txtSet = true;
+    if( n_pairs )
+        *n_pairs = h[ MT_PAIRS ];
+    if( consumed )
+        consumed[ 0 ] = h[ MT_CONSUMED ], consumed[ 1 ] = h[ MT_CONSUMED + 1 ];
     return 0;
 }
 

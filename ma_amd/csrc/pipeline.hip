@@ -145,8 +145,13 @@ struct ma_batch
     u64 txtNameBytes = 0;
     // read text parsed on the device (ma_batch_set_reads_text, launch_text.h), reserved on first use: the text, the statistics of
     // the call, line feeds per workgroup, and per line its start, header flag | name bytes, bases (both scanned in place) and
-    // per record its header line
-    DevBuf txtIn, txtStat, txtBlock, txtStart, txtHdrName, txtBases, txtRecLine;
+    // per record its header line.  ma_batch_set_mates_text parses two texts: they share txtIn (the second at an aligned offset)
+    // and txtStat; the second text has its own per-workgroup and per-line scratch (txtMate)
+    DevBuf txtIn, txtStat;
+    struct TextScratch
+    {
+        DevBuf block, start, hdrName, bases, recLine;
+    } txtOne, txtMate;
     SamTextState sam, pairSam;
     // small inversions (ma_inversions_batch, launch_inv.h): the statistics of the call, per MappingQuality slot its candidates, per
     // candidate its record, DP job, shape, window and result, and the FINAL lists the later stages see through mq_view

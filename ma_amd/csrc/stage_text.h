@@ -11,7 +11,8 @@
 //   k_text_emit       16 bytes per lane again: every byte to the codes, the qualities or the names; the two offset arrays
 // A long read is one long line: nothing here walks a line's bytes in one lane but the trimming of trailing junk and the search
 // for the name's end, which real files end after one and a few dozen steps.  Reductions issue one atomic per wavefront (see
-// k_max_qlen).  No arrays indexed at run time.
+// k_max_qlen).  No arrays indexed at run time.  The kernels of ma_batch_set_mates_text (two texts interleaved into mate pairs)
+// are at the end of the file.
 
 enum : int // the statistics block of a parse (u64 words)
 {
@@ -301,5 +302,184 @@ __global__ __launch_bounds__( TEXT_BLOCK ) void k_text_emit( TextEmitArgs A )
             A.qual[ (u64)dstQual + j ] = (uint8_t)b;
         else if( t == ma_text::TO_NAMES )
             A.names[ (u64)dstName + j ] = (char)b;
+    } );
+}
+
+// ---- mate pairs out of two texts (ma_batch_set_mates_text) ------------------------------------------------------------------------
+// PairedFileReader::execute (fileReader.h:568-617) for a whole batch: both texts go through the kernels above, each on scratch of
+// its own; record k of text 1 becomes read 2k, record k of text 2 read 2k + 1 (ma_text::pairHost is the serial statement).
+//   k_text_mates_plan  one lane per pair: bases and name bytes of both mates into the batch's two offset arrays (scanned behind
+//                      it), the longest paired read
+//   k_text_mates_stat  one lane: pairs, sums, consumed bytes, the winning refusal, whether anything may be written
+//   k_text_mates_emit  16 bytes per lane over one text: every byte of a paired record to its place in the interleaved arrays; a
+//                      second mate reversed and complemented (NucSeq::vReverse + vSwitchAllBasePairsToComplement)
+enum : int // the statistics block of a paired parse (u64 words), behind the two texts' blocks
+{
+    MT_PAIRS = 0,
+    MT_BASES = 1, // over the paired records
+    MT_NAME_BYTES = 2,
+    MT_MAX_LEN = 3,
+    MT_CONSUMED = 4, // two words: offset of record R of each text (the text's size if it has none)
+    MT_REFUSAL = 6, // ma_text::MATES_*
+    MT_TEXT = 7, // MATES_LINE: 1 or 2
+    MT_VIOLATION = 8, // MATES_LINE: ma_text::key( line, reason )
+    MT_BYTE = 9, // MATES_LINE: offset of the refused line
+    MT_EMIT = 10, // 1: accepted and within the batch's capacity, k_text_mates_emit writes
+    MT_WORDS = 16
+};
+// One of the two texts as the kernels above left it.  lines == 0: an empty text, or one the host refused (hostKey): no arrays.
+struct TextSide
+{
+    const char* text;
+    u64 n, lines;
+    const u32* start;
+    const u64* hdrName; // the scans
+    const u32* bases;
+    const u32* recLine;
+    const unsigned long long* stat;
+    u64 hostKey;
+};
+__device__ __forceinline__ u64 side_records( const TextSide& s )
+{
+    return s.lines ? s.hdrName[ s.lines ] >> 32 : 0;
+}
+
+// entries: min( max_reads, 2 x the most pairs the line counts allow ) + 1 words of roff and nameOff, all written: the lengths of
+// reads 2k and 2k + 1 for k < R, 0 behind them (and everywhere when 2 R reads do not fit)
+__global__ __launch_bounds__( 256 ) void k_text_mates_plan( TextSide a, TextSide b, u64 entries, u64 max_reads, u64* roff, u64* nameOff,
+                                                            unsigned long long* mstat )
+{
+    const u64 k = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const u64 Ra = side_records( a ), Rb = side_records( b ), R = Ra < Rb ? Ra : Rb;
+    u32 len0 = 0, len1 = 0, name0 = 0, name1 = 0;
+    if( k < R && 2 * R <= max_reads )
+    {
+        const u32 la = a.recLine[ k ], lb = b.recLine[ k ];
+        len0 = a.bases[ k + 1 < Ra ? a.recLine[ k + 1 ] : a.lines ] - a.bases[ la ];
+        len1 = b.bases[ k + 1 < Rb ? b.recLine[ k + 1 ] : b.lines ] - b.bases[ lb ];
+        name0 = (u32)a.hdrName[ la + 1 ] - (u32)a.hdrName[ la ];
+        name1 = (u32)b.hdrName[ lb + 1 ] - (u32)b.hdrName[ lb ];
+    }
+    if( 2 * k < entries )
+        roff[ 2 * k ] = len0, nameOff[ 2 * k ] = name0;
+    if( 2 * k + 1 < entries )
+        roff[ 2 * k + 1 ] = len1, nameOff[ 2 * k + 1 ] = name1;
+    u32 longest = max( len0, len1 );
+    for( int m = 32; m; m >>= 1 )
+        longest = max( longest, (u32)__shfl_xor( (int)longest, m, 64 ) );
+    if( ( threadIdx.x & 63 ) == 0 && longest )
+        atomicMax( mstat + MT_MAX_LEN, (unsigned long long)longest );
+}
+
+// roff, nameOff: the scans of k_text_mates_plan's entries (word 0 alone, and 0, when a text is empty)
+__global__ void k_text_mates_stat( TextSide a, TextSide b, u32 kindsDiffer, u64 max_reads, u64 max_bases, const u64* roff, const u64* nameOff,
+                                   unsigned long long* mstat )
+{
+    const u64 Ra = side_records( a ), Rb = side_records( b ), R = Ra < Rb ? Ra : Rb;
+    const u64 keyA = a.lines ? a.stat[ TXT_VIOLATION ] : a.hostKey, keyB = b.lines ? b.stat[ TXT_VIOLATION ] : b.hostKey;
+    const bool fits = 2 * R <= max_reads;
+    const u64 B = fits ? roff[ 2 * R ] : 0, N = fits ? nameOff[ 2 * R ] : 0;
+    u64 refusal = ma_text::MATES_OK, text = 0, key = ma_text::NO_VIOLATION, byte = 0;
+    if( keyA != ma_text::NO_VIOLATION )
+        refusal = ma_text::MATES_LINE, text = 1, key = keyA, byte = a.lines ? a.start[ keyA >> 8 ] : 0;
+    else if( keyB != ma_text::NO_VIOLATION )
+        refusal = ma_text::MATES_LINE, text = 2, key = keyB, byte = b.lines ? b.start[ keyB >> 8 ] : 0;
+    else if( kindsDiffer )
+        refusal = ma_text::MATES_KIND;
+    else if( !fits || B > max_bases )
+        refusal = ma_text::MATES_CAPACITY;
+    mstat[ MT_PAIRS ] = R;
+    mstat[ MT_BASES ] = B;
+    mstat[ MT_NAME_BYTES ] = N;
+    mstat[ MT_CONSUMED ] = R < Ra ? a.start[ a.recLine[ R ] ] : a.n;
+    mstat[ MT_CONSUMED + 1 ] = R < Rb ? b.start[ b.recLine[ R ] ] : b.n;
+    mstat[ MT_REFUSAL ] = refusal;
+    mstat[ MT_TEXT ] = text;
+    mstat[ MT_VIOLATION ] = key;
+    mstat[ MT_BYTE ] = byte;
+    mstat[ MT_EMIT ] = refusal == ma_text::MATES_OK ? 1 : 0;
+}
+
+struct MatesEmitArgs
+{
+    u32 kind, revComp; // revComp: second mates are reversed and complemented
+    TextSide s;
+    const unsigned long long* mstat;
+    const u64* roff; // the scans: 2 R + 1 entries each
+    const u64* nameOff;
+    uint8_t* codes;
+    char* names;
+    uint8_t* qual; // FASTQ
+};
+// MATE: 0 over text 1, 1 over text 2.  A base's position in its record is bases[ line ] - bases[ record's header line ] + j, so
+// that a FASTA mate of several lines reverses across them.  Lanes of a reversed mate write descending addresses.
+template <int MATE> __global__ __launch_bounds__( TEXT_BLOCK ) void k_text_mates_emit( MatesEmitArgs A )
+{
+    if( !A.mstat[ MT_EMIT ] )
+        return; // refused, or more than the batch holds: nothing is written
+    const u64 base = ( (u64)blockIdx.x * TEXT_BLOCK + threadIdx.x ) * TEXT_LANE_BYTES;
+    if( base >= A.s.n )
+        return;
+    const u64 R = A.mstat[ MT_PAIRS ];
+    const bool rev = MATE == 1 && A.revComp != 0;
+    // the line of the lane's first byte: the last one that starts at or before it
+    u64 lo = 0, hi = A.s.lines - 1;
+    while( lo < hi )
+    {
+        const u64 mid = ( lo + hi + 1 ) >> 1;
+        if( A.s.start[ mid ] <= base )
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    u64 line = lo;
+    u32 from = 0, to = 0, at = 0, len = 0; // of `line`, loaded when the walk enters it; at: bases of the record before the line
+    u64 dst = 0, dstName = 0;
+    ma_text::Line x;
+    bool loaded = false, paired = false;
+    const TextChunk c = text_chunk( A.s.text, A.s.n, base );
+    text_each( c, [ & ]( int k, u32 b ) {
+        const u64 pos = base + k;
+        if( pos >= A.s.n )
+            return;
+        if( loaded && pos >= to )
+            line++, loaded = false;
+        if( !loaded )
+        {
+            from = A.s.start[ line ], to = A.s.start[ line + 1 ];
+            const u64 h0 = A.s.hdrName[ line ], h1 = A.s.hdrName[ line + 1 ];
+            const u32 lineBases = A.s.bases[ line ];
+            x.uiLen = ma_text::content( A.s.text, from, to );
+            x.uiBases = A.s.bases[ line + 1 ] - lineBases;
+            x.uiName = (u32)h1 - (u32)h0;
+            x.uiKind = A.kind == ma_text::KIND_FASTQ ? (u32)( line & 3u ) : ( h1 >> 32 ) != ( h0 >> 32 ) ? ma_text::LINE_HEADER : ma_text::LINE_BASES;
+            x.uiReason = ma_text::OK;
+            // headers before the line: a header line is the record of that number, any other line belongs to the one before
+            const u64 rec = ( h0 >> 32 ) - ( x.uiKind == ma_text::LINE_HEADER ? 0 : 1 );
+            paired = ( x.uiKind == ma_text::LINE_HEADER || ( h0 >> 32 ) > 0 ) && rec < R;
+            if( paired )
+            {
+                const u64 entry = 2 * rec + MATE;
+                dst = A.roff[ entry ];
+                len = (u32)( A.roff[ entry + 1 ] - dst );
+                dstName = A.nameOff[ entry ];
+                at = x.uiKind == ma_text::LINE_BASES ? lineBases - A.s.bases[ A.s.recLine[ rec ] ] : 0; // (a quality line mirrors its one bases line)
+            }
+            loaded = true;
+        }
+        if( !paired )
+            return; // a record beyond the shorter text: validated, dropped
+        u32 j;
+        const u32 t = ma_text::byteTarget( x, (u32)( pos - from ), &j );
+        const u32 p = at + j;
+        if( ( t == ma_text::TO_CODES || t == ma_text::TO_QUAL ) && p >= len )
+            return; // (never in a text that passed: a record's bytes lie inside the record)
+        const u64 where = dst + ( rev ? len - 1 - p : p );
+        if( t == ma_text::TO_CODES )
+            A.codes[ where ] = rev ? ma_text::mateCode( ma_text::code( (uint8_t)b ) ) : ma_text::code( (uint8_t)b );
+        else if( t == ma_text::TO_QUAL )
+            A.qual[ where ] = (uint8_t)b;
+        else if( t == ma_text::TO_NAMES )
+            A.names[ dstName + j ] = (char)b;
     } );
 }

@@ -231,6 +231,121 @@ class BatchTextReader : public libMS::Module<TextBatch, true, FileStream>
     }
 };
 
+// BatchTextReader for mate pairs, the source of BatchAligner::executePairedTextSam: about half of uiBatchBytes are read from each
+// of the two streams under the pair stream's lock and cut at BatchTextReader::lastRecordStart; then the two record counts are made
+// equal on the host, so that a batch always holds whole pairs (ma_batch_set_mates_text consumes both texts entirely).  Records
+// are counted at memchr speed -- FASTQ: lines / 4, FASTA: lines that start with '>' -- and the surplus of the block with more of
+// them is moved to that stream's carry by walking back from the block's end.  When the stream with fewer records is at its end
+// the rests go out as they are and the pair stream ends: the device drops the surplus records, as PairedFileReader does
+// (fileReader.h:590-600).  In text that is not strict the counts mean nothing and the device refuses the batch.  A stream
+// without block reads (gzip) throws: PairedFileReader serves it.
+class BatchPairedTextReader : public libMS::Module<MatesTextBatch, true, PairedFileStream>
+{
+    std::string asCarry[ 2 ]; // the tails of the last blocks (guarded by the pair stream's lock)
+    bool bDone = false; // one of the streams has ended
+
+  public:
+    size_t uiBatchBytes = 64u << 20;
+    BatchPairedTextReader( const ParameterSetManager& )
+    {}
+    // records of a run of whole records
+    static size_t countRecords( const std::string& rText )
+    {
+        if( rText.empty( ) )
+            return 0;
+        const bool bFastq = rText[ 0 ] == '@';
+        size_t uiLines = 0, uiHeaders = rText[ 0 ] == '>' ? 1 : 0;
+        const char *p = rText.data( ), *const pEnd = p + rText.size( );
+        while( const char* pFeed = (const char*)memchr( p, '\n', (size_t)( pEnd - p ) ) )
+        {
+            uiLines++;
+            p = pFeed + 1;
+            if( p < pEnd && *p == '>' )
+                uiHeaders++;
+        }
+        if( p < pEnd )
+            uiLines++; // the last line lacks its end
+        return bFastq ? uiLines / 4 : uiHeaders;
+    }
+    // offset at which the last uiRecords records of a run of whole records start (0: it has no more than that)
+    static size_t startOfLastRecords( const std::string& rText, size_t uiRecords )
+    {
+        const bool bFastq = !rText.empty( ) && rText[ 0 ] == '@';
+        size_t uiNeed = bFastq ? 4 * uiRecords : uiRecords, uiEnd = rText.size( );
+        if( uiEnd > 0 && rText[ uiEnd - 1 ] == '\n' )
+            uiEnd--;
+        while( uiNeed > 0 )
+        {
+            const void* const pFeed = uiEnd > 0 ? memrchr( rText.data( ), '\n', uiEnd ) : nullptr;
+            const size_t uiStart = pFeed != nullptr ? (size_t)( (const char*)pFeed - rText.data( ) ) + 1 : 0;
+            if( bFastq || rText[ uiStart ] == '>' )
+                uiNeed--;
+            if( uiStart == 0 || uiNeed == 0 )
+                return uiStart;
+            uiEnd = uiStart - 1;
+        }
+        return rText.size( );
+    }
+    virtual std::shared_ptr<MatesTextBatch> execute( std::shared_ptr<PairedFileStream> pStreams ) override
+    {
+        auto pRet = std::make_shared<MatesTextBatch>( );
+        std::string* const apText[ 2 ] = { &pRet->sText1, &pRet->sText2 };
+        const std::shared_ptr<FileStream> apStream[ 2 ] = { pStreams->first, pStreams->second };
+        const size_t uiWant = std::max<size_t>( uiBatchBytes / 2, 1 );
+        std::lock_guard<std::mutex> xLock( pStreams->xMutex );
+        if( bDone )
+            return nullptr;
+        bool abEnd[ 2 ] = { false, false };
+        for( int i = 0; i < 2; i++ )
+        {
+            std::string& rText = *apText[ i ];
+            rText.reserve( asCarry[ i ].size( ) + uiWant );
+            rText.swap( asCarry[ i ] );
+            asCarry[ i ].clear( );
+            for( size_t uiAsk = rText.size( ) < uiWant ? uiWant - rText.size( ) : uiWant;; uiAsk = uiWant )
+            {
+                if( !apStream[ i ]->readBlock( rText, uiAsk ) )
+                    throw std::runtime_error( "BatchTextReader: the stream " + apStream[ i ]->fileName( ) +
+                                              " has no block reads (compressed input?): read it with BatchFileReader" );
+                if( apStream[ i ]->eof( ) )
+                {
+                    abEnd[ i ] = true; // the rest is the batch
+                    break;
+                }
+                const size_t uiCut = BatchTextReader::lastRecordStart( rText );
+                if( uiCut > 0 )
+                {
+                    asCarry[ i ].assign( rText, uiCut, std::string::npos );
+                    rText.resize( uiCut );
+                    break;
+                }
+                if( rText[ 0 ] != '@' && rText[ 0 ] != '>' )
+                    break; // neither kind: the device refuses the block as it is
+            }
+        }
+        if( apText[ 0 ]->empty( ) || apText[ 1 ]->empty( ) )
+        {
+            bDone = true;
+            return nullptr; // the shorter file ends the pair stream (module.h:688-695)
+        }
+        const size_t auiRecords[ 2 ] = { countRecords( *apText[ 0 ] ), countRecords( *apText[ 1 ] ) };
+        const int iFewer = auiRecords[ 0 ] <= auiRecords[ 1 ] ? 0 : 1, iMore = 1 - iFewer;
+        if( abEnd[ iFewer ] )
+            bDone = true; // the rests as they are: the device drops the surplus
+        else if( auiRecords[ iMore ] > auiRecords[ iFewer ] )
+        {
+            std::string& rText = *apText[ iMore ];
+            const size_t uiCut = startOfLastRecords( rText, auiRecords[ iMore ] - auiRecords[ iFewer ] );
+            if( uiCut > 0 ) // (0: text that is not strict; the device refuses it)
+            {
+                asCarry[ iMore ].insert( 0, rText, uiCut, std::string::npos );
+                rText.resize( uiCut );
+            }
+        }
+        return pRet;
+    }
+};
+
 // Volatile source over reads that already are in memory (benchmarks, callers that hold their reads): consecutive slices.
 class BatchSource : public libMS::Module<ReadVector, true>
 {

@@ -556,6 +556,60 @@ class Engine
                      (void*)this, uiBytes, (unsigned long long)n, R.fH2D, R.fKernels, R.aStageMs[ 0 ], R.aStageMs[ 1 ], R.aStageMs[ 2 ], R.aStageMs[ 3 ], R.fD2H );
         return pRes;
     }
+    // runText for mate pairs: the texts of the two read files (ma_batch_set_mates_text: the device parses both, interleaves the
+    // mates and, with bRevCompMates, reverse-complements every second one) through all stages, the pairing and the pairs'
+    // formatting: the result of runFlat's paired SAM mode (bPairs, bSam, vSamOff per PAIR, vSam; uiReads = 2 x the pairs the device
+    // found).  Records one text has beyond the other's are dropped as PairedFileReader drops them.  Sized like runText.
+    std::shared_ptr<BatchResult> runMatesText( const char* pText1, size_t uiBytes1, const char* pText2, size_t uiBytes2, bool bRevCompMates,
+                                               uint32_t uiSamOptions, bool bInversions = false )
+    {
+        auto pRes = freshResult( );
+        BatchResult& R = *pRes;
+        R.bStages = R.bSocQueues = false;
+        R.bPairs = R.bSam = true;
+        R.uiSamOptions = uiSamOptions;
+        R.uiSamBytes = 0;
+        R.fPack = 0;
+        const size_t uiBytes = uiBytes1 + uiBytes2;
+        fit( std::max<uint64_t>( uiCapReads, uiBytes / 32 ), std::max<uint64_t>( uiCapBases, uiBytes ) );
+        auto t0 = std::chrono::steady_clock::now( );
+        uint64_t nPairs = 0, aConsumed[ 2 ];
+        if( ma_batch_set_mates_text( pBatch, pText1, uiBytes1, pText2, uiBytes2, bRevCompMates ? 1 : 0, &nPairs, aConsumed ) != 0 )
+        {
+            if( nPairs == 0 ) // (only "batch capacity exceeded" reports the pairs of the texts)
+                engineCheck( 1 );
+            fit( 2 * nPairs, uiBytes );
+            engineCheck( ma_batch_set_mates_text( pBatch, pText1, uiBytes1, pText2, uiBytes2, bRevCompMates ? 1 : 0, &nPairs, aConsumed ) );
+        }
+        const uint64_t n = 2 * nPairs;
+        R.uiReads = n;
+        R.fH2D = secondsSince( t0 );
+        t0 = std::chrono::steady_clock::now( );
+        engineCheck( ma_align_batch( pBatch ) );
+        if( bInversions )
+            engineCheck( ma_inversions_batch( pBatch ) );
+        engineCheck( ma_batch_sync( pBatch ) );
+        R.fKernels = secondsSince( t0 );
+        engineCheck( ma_batch_host_ms( pBatch, R.aStageMs ) );
+        t0 = std::chrono::steady_clock::now( );
+        engineCheck( ma_batch_counts( pBatch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &R.uiAlignedReads ) );
+        R.uiPairRecords = R.uiPairOps = 0;
+        engineCheck( ma_pair_batch( pBatch ) );
+        engineCheck( ma_batch_pair_counts( pBatch, &nPairs, nullptr, nullptr, &R.uiPairsOnHost ) );
+        engineCheck( ma_pair_sam_batch( pBatch, uiSamOptions ) );
+        engineCheck( ma_batch_pair_sam_counts( pBatch, &nPairs, &R.uiSamBytes ) );
+        engineCheck( ma_batch_get_pair_sam( pBatch, R.vSamOff.need( nPairs + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
+        memset( R.vPairOff.need( nPairs + 1 ), 0, ( nPairs + 1 ) * sizeof( uint64_t ) ); // no pair records in a SAM result
+        memset( R.vMqOff.need( n + 1 ), 0, ( n + 1 ) * sizeof( uint64_t ) ); // no per-read records either
+        R.uiMqAlignments = R.uiMqOps = 0;
+        R.fD2H = secondsSince( t0 );
+        uiRuns++;
+        if( getenv( "MA_ENGINE_TRACE" ) ) // diagnostics: the phases of every device batch (h2d: upload, parse and its two read-backs)
+            fprintf( stderr, "engine %p: %zu + %zu bytes of mate text, %llu pairs, h2d+parse %.4f s, stages %.4f s (seed %.1f extract %.1f chain %.1f dp %.1f ms), d2h %.4f s\n",
+                     (void*)this, uiBytes1, uiBytes2, (unsigned long long)nPairs, R.fH2D, R.fKernels, R.aStageMs[ 0 ], R.aStageMs[ 1 ], R.aStageMs[ 2 ],
+                     R.aStageMs[ 3 ], R.fD2H );
+        return pRes;
+    }
 };
 
 // One read's place in a finished device batch.

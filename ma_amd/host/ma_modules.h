@@ -1482,6 +1482,13 @@ class TextBatch : public libMS::Container
   public:
     std::string sText;
 };
+// The same for mate pairs: runs of whole records of the two read files (BatchPairedTextReader cuts them so that both hold equally
+// many records, except at the end of a stream): what BatchAligner::executePairedTextSam hands to ma_batch_set_mates_text.
+class MatesTextBatch : public libMS::Container
+{
+  public:
+    std::string sText1, sText2;
+};
 
 // Phase times of a throughput run (seconds, summed over the device batches; the phases of different batches overlap when
 // several are in flight, so their sum can exceed the wall time)
@@ -1947,6 +1954,43 @@ class BatchAligner
                                       "BatchPairedFileWriter)" );
         const uint32_t uiOptions = samOptionBits( xParams.xSam );
         return runFlatOn( vIndices, vMates, pPerIndex, true, &uiOptions );
+    }
+
+    // executePairedFlatSam for mates that still are the TEXT of their two files: the device parses both texts, interleaves the
+    // mates, reverse-complements every second one if the parameter set says so (ma_batch_set_mates_text; the strict form of
+    // ma_text_dev.h), aligns, pairs and formats; the batch comes back as executePairedFlatSam's (paired( ) and hasSamText( );
+    // size( ) = 2 x the pairs the device found), with no NucSeq behind it.  Texts the device refuses throw the library's message,
+    // which names the text and the line: PairedFileReader + executePairedFlatSam stay the path for such files.  One device batch
+    // per call.  Not with the NGMLR tag emulation.
+    std::shared_ptr<AlignedBatch> executePairedTextSam( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<MatesTextBatch> pTexts,
+                                                        std::shared_ptr<Pack> pPack )
+    {
+        if( xParams.xSam.bEmulateNgmlrTags )
+            throw std::runtime_error( "BatchAligner::executePairedTextSam: not with the NGMLR tag emulation (use executePaired and "
+                                      "PairedFileWriter)" );
+        nameContigs( *pFM_index->pDev, *pPack );
+        return executePairedTextSamOn( pFM_index->pDev->p, pTexts );
+    }
+    // (the contigs of pIndex are named already)
+    std::shared_ptr<AlignedBatch> executePairedTextSamOn( const ma_index* pIndex, std::shared_ptr<MatesTextBatch> pTexts )
+    {
+        if( !servesPairSam( ) )
+            throw std::runtime_error( "BatchAligner::executePairedTextSam: not with the NGMLR tag emulation (use executePairedFlat and "
+                                      "BatchPairedFileWriter)" );
+        auto pEngine = takeEngine( pIndex );
+        auto pRet = std::make_shared<AlignedBatch>( );
+        try
+        {
+            pRet->pResult = pEngine->runMatesText( pTexts->sText1.data( ), pTexts->sText1.size( ), pTexts->sText2.data( ), pTexts->sText2.size( ),
+                                                   xParams.bRevCompPairedReadMates, samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
+        }
+        catch( ... )
+        {
+            giveEngine( pIndex, std::move( pEngine ) );
+            throw;
+        }
+        giveEngine( pIndex, std::move( pEngine ) );
+        return pRet;
     }
 
   private:

@@ -4,6 +4,9 @@
 //   - parseHost( ) below runs the same functions serially: the statement of the rules the CPU tests (tests/emul/text_dev_test.cpp)
 //     compare with the yardstick, FileReader::parseRecord of ma_sam.h (fileReader.cpp:37-203), and the GPU tests with the kernels;
 //   - libma_amd.so words a refusal with errorText( ) / message( ).
+// The rules of ma_batch_set_mates_text -- two such texts interleaved into mate pairs -- follow at the end: pairHost( ), the serial
+// statement the k_text_mates_* kernels are compared with (tests/emul/mates_text_test.cpp compares it with PairedFileReader of
+// ma_sam.h), and messageMates( ).
 // No reference headers, no containers, no strings: include/ma_amd.h only.
 //
 // The reference's record grammar is a serial state machine; the device serves the two plain shapes real read files have (the
@@ -35,6 +38,8 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
 
 #if defined( __HIPCC__ )
 #define MA_TEXT_HD __host__ __device__ __forceinline__
@@ -389,5 +394,152 @@ inline int parseHost( const char* pText, uint64_t n, uint32_t* pStart, uint64_t*
     if( pNameOff )
         pNameOff[ uiRead ] = uiName;
     return 0;
+}
+
+// ---- mate pairs out of two texts (ma_batch_set_mates_text) -----------------------------------------------------------------------
+// PairedFileReader::execute (fileReader.h:568-617) over two texts in the strict form: record k of text 1 becomes read 2k, record
+// k of text 2 read 2k + 1; the shorter text ends the stream (R = min( R1, R2 ) pairs), the surplus records of the longer one are
+// validated and dropped.  With iRevComp every read 2k + 1 is reversed with its qualities (NucSeq::vReverse, nucSeq.h:373-381)
+// and complemented (vSwitchAllBasePairsToComplement, nucSeq.h:537-543: a code below 4 becomes 3 - c, every other code 5 (sic)).
+MA_TEXT_HD uint8_t mateCode( uint8_t c ) // the complement of a code
+{
+    return c < 4 ? (uint8_t)( 3 - c ) : (uint8_t)5;
+}
+enum : uint32_t // why a call is refused, in the order of precedence
+{
+    MATES_OK = 0u,
+    MATES_LINE = 1u, // a rule violation in text uiText (text 1 wins over text 2; within a text as parseHost)
+    MATES_KIND = 2u, // one FASTQ and one FASTA text
+    MATES_CAPACITY = 3u // more pairs or bases than the batch holds (the library's check; pairHost knows no batch)
+};
+struct PairResult
+{
+    uint64_t uiPairs, uiBases, uiNameBytes, uiMaxLen; // over the paired records only
+    uint64_t aConsumed[ 2 ]; // offset of the first byte of record R of each text (its size when it has exactly R records)
+    int32_t iHasQual;
+    uint32_t uiRefusal; // MATES_*
+    uint32_t uiText, uiReason; // MATES_LINE: 1 or 2, and the reason
+    uint64_t uiLine, uiByte; // MATES_LINE: 0-based line, offset of its first byte
+};
+// "ma_batch_set_mates_text: text <1|2>: line <L> (byte <X>): <reason>" and the two other refusals; uiLine is 0-based here
+inline void messageMates( char* pOut, size_t uiCap, uint32_t uiRefusal, uint32_t uiText, uint64_t uiLine, uint64_t uiByte, uint32_t uiReason )
+{
+    if( uiRefusal == MATES_LINE )
+        snprintf( pOut, uiCap, "ma_batch_set_mates_text: text %u: line %llu (byte %llu): %s", (unsigned)uiText, (unsigned long long)( uiLine + 1 ),
+                  (unsigned long long)uiByte, errorText( uiReason ) );
+    else
+        snprintf( pOut, uiCap, "ma_batch_set_mates_text: %s",
+                  uiRefusal == MATES_KIND ? "the two texts differ in kind" : uiRefusal == MATES_CAPACITY ? "batch capacity exceeded" : "no error" );
+}
+// offset of the first byte of record uiRecord of an ACCEPTED text with the line starts parseHost left in pStart (n if the text
+// has no such record)
+inline uint64_t recordStartHost( const char* pText, uint64_t n, const uint32_t* pStart, uint64_t uiRecord )
+{
+    if( n == 0 )
+        return 0;
+    const uint32_t uiKind = pText[ 0 ] == '@' ? KIND_FASTQ : KIND_FASTA;
+    uint64_t uiFeeds = 0;
+    for( uint64_t p = 0; p < n; p++ )
+        uiFeeds += pText[ p ] == '\n' ? 1 : 0;
+    const uint64_t uiLines = nLines( uiFeeds, pText[ n - 1 ] );
+    uint64_t uiSeen = 0;
+    for( uint64_t i = 0; i < uiLines; i++ )
+        if( lineKind( uiKind, i, pText + pStart[ i ], content( pText, pStart[ i ], pStart[ i + 1 ] ) ) == LINE_HEADER && uiSeen++ == uiRecord )
+            return pStart[ i ];
+    return n;
+}
+// The serial statement of ma_batch_set_mates_text: parseHost on each text, interleave, reverse complement.  Returns 0 and fills
+// *pResult and the arrays that are not NULL (pOffsets / pNameOff: 2 R + 1 entries, pCodes / pQual: bases, pNames: name bytes;
+// call with NULLs first for the sizes), or returns 1 with the refusal in *pResult (messageMates( ) words it) and the arrays
+// untouched.  An empty text is a text of no records: 0 pairs, the other text is validated all the same.
+inline int pairHost( const char* pText1, uint64_t n1, const char* pText2, uint64_t n2, int32_t iRevComp, uint64_t* pOffsets, uint8_t* pCodes,
+                     uint64_t* pNameOff, char* pNames, uint8_t* pQual, PairResult* pResult )
+{
+    PairResult r = { 0, 0, 0, 0, { 0, 0 }, 0, MATES_OK, 0, OK, 0, 0 };
+    *pResult = r;
+    const char* const apText[ 2 ] = { pText1, pText2 };
+    const uint64_t aN[ 2 ] = { n1, n2 };
+    uint32_t* apStart[ 2 ] = { NULL, NULL };
+    uint64_t *apOff[ 2 ] = { NULL, NULL }, *apNameOff[ 2 ] = { NULL, NULL };
+    uint8_t *apCodes[ 2 ] = { NULL, NULL }, *apQual[ 2 ] = { NULL, NULL };
+    char* apNames[ 2 ] = { NULL, NULL };
+    Result aParsed[ 2 ];
+    int iRet = 0;
+    for( int t = 0; t < 2; t++ )
+    {
+        apStart[ t ] = (uint32_t*)malloc( ( aN[ t ] + 2 ) * sizeof( uint32_t ) );
+        if( parseHost( apText[ t ], aN[ t ], apStart[ t ], NULL, NULL, NULL, NULL, NULL, &aParsed[ t ] ) && iRet == 0 )
+        {
+            r.uiRefusal = MATES_LINE;
+            r.uiText = (uint32_t)t + 1;
+            r.uiReason = aParsed[ t ].uiReason, r.uiLine = aParsed[ t ].uiLine, r.uiByte = aParsed[ t ].uiByte;
+            iRet = 1;
+        }
+    }
+    if( iRet == 0 && n1 > 0 && n2 > 0 && aParsed[ 0 ].iHasQual != aParsed[ 1 ].iHasQual )
+    {
+        r.uiRefusal = MATES_KIND;
+        iRet = 1;
+    }
+    if( iRet == 0 )
+    {
+        const uint64_t R = aParsed[ 0 ].uiReads < aParsed[ 1 ].uiReads ? aParsed[ 0 ].uiReads : aParsed[ 1 ].uiReads;
+        r.uiPairs = R;
+        r.iHasQual = n1 > 0 && n2 > 0 ? aParsed[ 0 ].iHasQual : 0; // (an empty text has no kind: no reads, no qualities)
+        for( int t = 0; t < 2; t++ )
+        {
+            const Result& p = aParsed[ t ];
+            apOff[ t ] = (uint64_t*)malloc( ( p.uiReads + 1 ) * sizeof( uint64_t ) );
+            apNameOff[ t ] = (uint64_t*)malloc( ( p.uiReads + 1 ) * sizeof( uint64_t ) );
+            apCodes[ t ] = (uint8_t*)malloc( p.uiBases + 1 );
+            apQual[ t ] = (uint8_t*)malloc( p.uiBases + 1 );
+            apNames[ t ] = (char*)malloc( p.uiNameBytes + 1 );
+            Result xAgain;
+            parseHost( apText[ t ], aN[ t ], apStart[ t ], apOff[ t ], apCodes[ t ], apNameOff[ t ], apNames[ t ], p.iHasQual ? apQual[ t ] : NULL, &xAgain );
+            r.aConsumed[ t ] = R < p.uiReads ? recordStartHost( apText[ t ], aN[ t ], apStart[ t ], R ) : aN[ t ];
+        }
+        uint64_t uiBase = 0, uiName = 0;
+        for( uint64_t k = 0; k < 2 * R; k++ )
+        {
+            const int t = (int)( k & 1 );
+            const uint64_t uiRec = k >> 1, uiFrom = apOff[ t ][ uiRec ], uiLen = apOff[ t ][ uiRec + 1 ] - uiFrom;
+            const uint64_t uiNameFrom = apNameOff[ t ][ uiRec ], uiNameLen = apNameOff[ t ][ uiRec + 1 ] - uiNameFrom;
+            const bool bRev = t == 1 && iRevComp != 0;
+            if( pOffsets )
+                pOffsets[ k ] = uiBase;
+            if( pNameOff )
+                pNameOff[ k ] = uiName;
+            for( uint64_t j = 0; j < uiLen; j++ )
+            {
+                const uint64_t uiSrc = uiFrom + ( bRev ? uiLen - 1 - j : j );
+                if( pCodes )
+                    pCodes[ uiBase + j ] = bRev ? mateCode( apCodes[ t ][ uiSrc ] ) : apCodes[ t ][ uiSrc ];
+                if( pQual && r.iHasQual )
+                    pQual[ uiBase + j ] = apQual[ t ][ uiSrc ];
+            }
+            if( pNames )
+                memcpy( pNames + uiName, apNames[ t ] + uiNameFrom, uiNameLen );
+            uiBase += uiLen;
+            uiName += uiNameLen;
+            if( uiLen > r.uiMaxLen )
+                r.uiMaxLen = uiLen;
+        }
+        if( pOffsets )
+            pOffsets[ 2 * R ] = uiBase;
+        if( pNameOff )
+            pNameOff[ 2 * R ] = uiName;
+        r.uiBases = uiBase, r.uiNameBytes = uiName;
+    }
+    for( int t = 0; t < 2; t++ )
+    {
+        free( apStart[ t ] );
+        free( apOff[ t ] );
+        free( apNameOff[ t ] );
+        free( apCodes[ t ] );
+        free( apQual[ t ] );
+        free( apNames[ t ] );
+    }
+    *pResult = r;
+    return iRet;
 }
 } // namespace ma_text
