@@ -12,7 +12,9 @@
 // With --text-input the input is not parsed on the host at all: BatchTextReader cuts the file into runs of whole records
 // and the device parses them (BatchAligner::executeTextSam, ma_batch_set_reads_text); with a mates file BatchPairedTextReader cuts
 // both files into runs of equally many records and the device parses, interleaves and reverse-complements them
-// (BatchAligner::executePairedTextSam, ma_batch_set_mates_text).  The device serves four-line FASTQ and plain FASTA only; any other file ends the program with the library's message, which names the line -- there is no silent fallback.
+// (BatchAligner::executePairedTextSam, ma_batch_set_mates_text).  A single-end reads file that bgzip wrote (BGZF, told by its first
+// bytes) goes up compressed: BatchBgzfReader cuts it at member borders and the device inflates it in front of its parser
+// (BatchAligner::executeBgzfSam, ma_batch_set_reads_bgzf); plain gzip is not served with the flag.  The device serves four-line FASTQ and plain FASTA only; any other file ends the program with the library's message, which names the line -- there is no silent fallback.
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_align.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
@@ -45,11 +47,26 @@ int main( int argc, char** argv )
         const bool bPaired = argc >= 6;
         if( bTextInput && bHostSam )
             throw std::runtime_error( "--text-input serves input printed on the device (not with --host-sam: the host's writers need the reads)" );
+        // a single-end reads file that starts with a BGZF member (what bgzip writes; told by its first 18 bytes, not by its name)
+        // is inflated on the device; any other compressed file is not served with the flag
+        bool bBgzf = false;
+        if( bTextInput && !bPaired )
+        {
+            uint8_t aFirst[ ma_bgzf::MIN_PROBE_BYTES ];
+            std::ifstream xProbe( argv[ 2 ], std::ios::binary );
+            xProbe.read( (char*)aFirst, sizeof( aFirst ) );
+            ma_bgzf::Member xMember;
+            const uint32_t uiReason = xProbe.gcount( ) == (std::streamsize)sizeof( aFirst ) ? ma_bgzf::header( aFirst, sizeof( aFirst ), 0, &xMember )
+                                                                                             : (uint32_t)ma_bgzf::ERR_NOT_BGZF;
+            bBgzf = uiReason == ma_bgzf::OK || uiReason == ma_bgzf::ERR_TRUNCATED; // (truncated: the member goes on behind the 18 bytes)
+        }
         for( int iFile : { 2, 5 } )
         {
             const std::string sReads = iFile < argc ? argv[ iFile ] : "";
-            if( bTextInput && sReads.size( ) >= 3 && sReads.compare( sReads.size( ) - 3, 3, ".gz" ) == 0 )
-                throw std::runtime_error( "--text-input: " + sReads + " is compressed; the device parses plain text (run without the flag)" );
+            if( bTextInput && !( iFile == 2 && bBgzf ) && sReads.size( ) >= 3 && sReads.compare( sReads.size( ) - 3, 3, ".gz" ) == 0 )
+                throw std::runtime_error( "--text-input: " + sReads +
+                                          " is compressed; the device parses plain text, and inflates single-end reads that bgzip wrote (BGZF), "
+                                          "but no plain gzip (run without the flag)" );
         }
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
@@ -63,7 +80,7 @@ int main( int argc, char** argv )
         }
         BatchAligner xAligner( xParams );
         FileReader xReader( xParams );
-        auto pIn = fileStreamFromPath( argv[ 2 ] );
+        std::shared_ptr<FileStream> pIn = bBgzf ? std::make_shared<StdFileStream>( argv[ 2 ] ) : fileStreamFromPath( argv[ 2 ] ); // (BGZF: its bytes as they are)
         const size_t uiBatch = 1000000; // reads per device batch
         if( bTextInput && bPaired )
         {
@@ -74,6 +91,14 @@ int main( int argc, char** argv )
             auto pStreams = std::make_shared<PairedFileStream>( pIn, fileStreamFromPath( argv[ 5 ] ) );
             while( auto pTexts = xTextReader.execute( pStreams ) )
                 xWriter.execute( *xAligner.executePairedTextSam( pFM, pTexts, pPack ) );
+        }
+        else if( bBgzf )
+        {
+            // the compressed text path: the members go to the device, which inflates, parses, aligns and prints
+            BatchFileWriter xWriter( xParams, std::make_shared<FileWriter>( xParams, std::string( argv[ 3 ] ), pPack ), pPack );
+            BatchBgzfReader xBgzfReader( xParams );
+            while( auto pMembers = xBgzfReader.execute( pIn ) )
+                xWriter.write( *xAligner.executeBgzfSam( pFM, pMembers, pPack ), pPack );
         }
         else if( bTextInput )
         {

@@ -9,9 +9,9 @@
 // Prints one JSON line.  bench.py runs it after its timed regions and reports it as config.boundary (never as `value`).
 //
 //   ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads]
-// (further legs, one per run: paired, pairtext, sam, sam-tags, text, inversions -- see the comments at their blocks in main)
+// (further legs, one per run: paired, pairtext, sam, sam-tags, text, bgzf, inversions -- see the comments at their blocks in main)
 //
-// build: g++ -std=c++17 -O2 -Iinclude -Ima_amd/host examples/ma_boundary_bench.cpp -Lma_amd -lma_amd -lpthread
+// build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_boundary_bench.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
 #include <atomic>
 #include <chrono>
@@ -238,7 +238,7 @@ int main( int argc, char** argv )
 {
     if( argc < 6 )
     {
-        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | pairtext [repeats] | sam [repeats] | sam-tags [repeats] | text [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
+        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | pairtext [repeats] | sam [repeats] | sam-tags [repeats] | text [repeats] | bgzf [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
         return 2;
     }
     try
@@ -249,7 +249,7 @@ int main( int argc, char** argv )
         maCheck( ma_set_device( atoi( argv[ 5 ] ) ) );
         maCheck( ma_host_bind_thread( atoi( argv[ 5 ] ), 0, nullptr ) ); // this thread and all it starts: the CPUs next to the GPU
         const unsigned uiHw = std::max( 1u, std::thread::hardware_concurrency( ) );
-        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "pairtext" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "text" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
+        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "pairtext" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "text" ) && strcmp( argv[ 6 ], "bgzf" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         double t0 = now( );
@@ -645,8 +645,15 @@ int main( int argc, char** argv )
                     xTimeOff.fKernels, (unsigned long long)xTimeOn.uiBatches );
             return uiBytesContainer == uiBytesOn ? 0 : 1;
         }
-        if( argc >= 7 && !strcmp( argv[ 6 ], "text" ) )
+        const bool bBgzfLeg = argc >= 7 && !strcmp( argv[ 6 ], "bgzf" );
+        if( argc >= 7 && ( !strcmp( argv[ 6 ], "text" ) || bBgzfLeg ) )
         {
+            // ---- the bgzf leg (the workload, workers and checks of the text leg, described below): the FASTQ text written once as
+            // BGZF through zlib at the default level, 65 280 bytes of text per member as bgzip cuts them, to a file next to the
+            // index; file to SAM text through (a) BatchBgzfReader -> executeBgzfSam -- the compressed bytes cut at member borders,
+            // inflated and parsed on the device --, (b) GzFileStream -> BatchFileReader -> executeFlatSam -- what a compressed file
+            // gets without it: zlib's gzread a byte at a time, then one NucSeq per read -- and (c) the text leg's (b) on the
+            // uncompressed text, the ceiling.  All three must write the same bytes.  (Needs -DMA_WITH_ZLIB -lz.)
             // ---- the text leg: the n reads as ONE FASTQ text in memory (names r<i>, seeded qualities 35 .. 126), file to SAM text
             // through (a) StringStream -> BatchFileReader -> executeFlatSam -- records cut and parsed on the host, one NucSeq per
             // read, gathered and uploaded as arrays -- and (b) BatchTextReader -> executeTextSam -- blocks of text cut at record
@@ -766,6 +773,115 @@ int main( int argc, char** argv )
                     },
                     pFile, uiBytesText );
             };
+            if( bBgzfLeg )
+            {
+#ifdef MA_WITH_ZLIB
+                std::string sBgzf;
+                for( size_t uiAt = 0; uiAt <= sFastq.size( ); uiAt += 65280 ) // (the last turn writes the rest or the end-of-file marker)
+                {
+                    const size_t uiText = std::min<size_t>( 65280, sFastq.size( ) - uiAt );
+                    z_stream z;
+                    memset( &z, 0, sizeof( z ) );
+                    if( deflateInit2( &z, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY ) != Z_OK )
+                        throw std::runtime_error( "deflateInit2" );
+                    std::string sOut( deflateBound( &z, (uLong)uiText ) + 64, '\0' );
+                    z.next_in = (Bytef*)( sFastq.data( ) + uiAt ), z.avail_in = (uInt)uiText;
+                    z.next_out = (Bytef*)&sOut[ 0 ], z.avail_out = (uInt)sOut.size( );
+                    if( deflate( &z, Z_FINISH ) != Z_STREAM_END )
+                        throw std::runtime_error( "deflate" );
+                    sOut.resize( z.total_out );
+                    deflateEnd( &z );
+                    const uint32_t uiCrc = (uint32_t)crc32( crc32( 0L, Z_NULL, 0 ), (const Bytef*)( sFastq.data( ) + uiAt ), (uInt)uiText );
+                    auto le = [ & ]( uint32_t v, int nBytes ) {
+                        for( int i = 0; i < nBytes; i++ )
+                            sBgzf += (char)( ( v >> ( 8 * i ) ) & 0xff );
+                    };
+                    sBgzf += std::string( "\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0", 16 );
+                    le( (uint32_t)sOut.size( ) + 25, 2 );
+                    sBgzf += sOut;
+                    le( uiCrc, 4 ), le( (uint32_t)uiText, 4 );
+                    if( uiText == 0 )
+                        break;
+                }
+                const std::string sPath = std::string( argv[ 1 ] ) + ".boundary_bench.fq.gz";
+                {
+                    std::ofstream xOut( sPath, std::ios::binary );
+                    xOut.write( sBgzf.data( ), (std::streamsize)sBgzf.size( ) );
+                    if( !xOut )
+                        throw std::runtime_error( "cannot write " + sPath );
+                }
+                uint64_t uiBytesBgzf = 0, uiBytesGz = 0;
+                auto bgzf = [ & ]( std::string* pFile ) {
+                    auto pStream = std::make_shared<StringStream>( sBgzf );
+                    BatchBgzfReader xReader( xParams );
+                    xReader.uiBatchBytes = std::max<size_t>( 1, sBgzf.size( ) / std::max<size_t>( n, 1 ) * uiBatchReads );
+                    return run(
+                        [ & ]( size_t w, std::string* pKeep, uint64_t& ruiBytes ) {
+                            auto pBatch = xReader.execute( pStream );
+                            if( pBatch == nullptr )
+                                return false;
+                            auto pB = vAligners[ w ]->executeBgzfSamOn( pFM->pDev->p, pBatch );
+                            ruiBytes += pB->samBytes( );
+                            if( pKeep != nullptr )
+                                pKeep->assign( pB->samText( ), pB->samBytes( ) );
+                            return true;
+                        },
+                        pFile, uiBytesBgzf );
+                };
+                auto gz = [ & ]( std::string* pFile ) {
+                    std::shared_ptr<FileStream> pStream = std::make_shared<GzFileStream>( sPath );
+                    BatchFileReader xReader( xParams );
+                    xReader.uiBatchReads = uiBatchReads;
+                    return run(
+                        [ & ]( size_t w, std::string* pKeep, uint64_t& ruiBytes ) {
+                            auto pBatch = xReader.execute( pStream );
+                            if( pBatch == nullptr )
+                                return false;
+                            std::vector<AlignerTiming> vPer;
+                            auto pFlat = vAligners[ w ]->executeFlatSamOn( pFM->pDev->all( ), pBatch, &vPer );
+                            if( pKeep != nullptr )
+                                pKeep->clear( );
+                            for( auto& pB : *pFlat )
+                            {
+                                ruiBytes += pB->samBytes( );
+                                if( pKeep != nullptr )
+                                    pKeep->append( pB->samText( ), pB->samBytes( ) );
+                            }
+                            return true;
+                        },
+                        pFile, uiBytesGz );
+                };
+                // warm-up of all three: these runs keep their files, which must be the same bytes; the timed runs count theirs
+                std::string sFileGz, sFileBgzf, sFilePlain;
+                gz( &sFileGz ), bgzf( &sFileBgzf ), text( &sFilePlain );
+                bool bSame = sFileGz == sFileBgzf && sFileGz == sFilePlain && !sFileGz.empty( );
+                const uint64_t uiSamBytes = sFileGz.size( );
+                std::string( ).swap( sFileGz ), std::string( ).swap( sFileBgzf ), std::string( ).swap( sFilePlain );
+                std::vector<double> vA, vB, vC;
+                for( int r = 0; r < iRepeats; r++ )
+                {
+                    vA.push_back( n / bgzf( nullptr ) ), vB.push_back( n / gz( nullptr ) ), vC.push_back( n / text( nullptr ) );
+                    bSame = bSame && uiBytesBgzf == uiSamBytes && uiBytesGz == uiSamBytes && uiBytesText == uiSamBytes;
+                }
+                remove( sPath.c_str( ) );
+                auto stats = []( std::vector<double> v ) {
+                    std::string sAll;
+                    for( double f : v )
+                        sAll += ( sAll.empty( ) ? "" : ", " ) + std::to_string( f );
+                    std::sort( v.begin( ), v.end( ) );
+                    return "{\"median\": " + std::to_string( v[ v.size( ) / 2 ] ) + ", \"min\": " + std::to_string( v.front( ) ) +
+                           ", \"max\": " + std::to_string( v.back( ) ) + ", \"all\": [" + sAll + "]}";
+                };
+                printf( "{\"bgzf\": {\"reads\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_reads\": %zu, \"workers\": %zu, "
+                        "\"bgzf_reader_bgzf_sam_reads_per_s\": %s, \"gz_stream_file_reader_flat_sam_reads_per_s\": %s, "
+                        "\"text_reader_text_sam_reads_per_s\": %s, \"fastq_bytes\": %zu, \"bgzf_bytes\": %zu, \"sam_bytes\": %zu, \"equal\": %s}}\n",
+                        n, uiLen, iRepeats, uiBatchReads, uiWorkers, stats( vA ).c_str( ), stats( vB ).c_str( ), stats( vC ).c_str( ), sFastq.size( ),
+                        sBgzf.size( ), (size_t)uiSamBytes, bSame ? "true" : "false" );
+                return bSame ? 0 : 1;
+#else
+                throw std::runtime_error( "the bgzf leg writes its file through zlib: build with -DMA_WITH_ZLIB -lz" );
+#endif
+            }
             // warm-up of both: these two runs keep their files, which must be the same bytes; the timed runs count theirs
             std::string sFileHost, sFileText;
             host( &sFileHost ), text( &sFileText );

@@ -439,6 +439,40 @@ int ma_batch_get_read_text( ma_batch*, uint64_t* name_off /*n+1*/, char* names, 
  *                                max_bases; *n_pairs = R then, what a caller sizes the next batch object by */
 int ma_batch_set_mates_text( ma_batch*, const char* text1 /*host*/, uint64_t n1, const char* text2 /*host*/, uint64_t n2,
                              int32_t rev_comp_mates, uint64_t* n_pairs, uint64_t consumed[ 2 ] );
+/* ---- compressed read text in: BGZF members inflated on the device ----
+ * BGZF (what bgzip and htslib write, and what every zlib reader reads as ordinary gzip) is a chain of independent gzip members
+ * of at most 64 KiB of text each, every one with its compressed size in its header.  The compressed bytes are uploaded as they
+ * are, every member is inflated by a lane of its own (ma_amd/csrc/stage_bgzf.h) into the buffer the parser of
+ * ma_batch_set_reads_text reads, and that call's kernels run behind it unchanged.  The STRICT member form and the deflate
+ * streams accepted -- exactly zlib's -- are stated once in ma_amd/host/ma_bgzf_dev.h (ma_bgzf::inflateHost is the serial
+ * statement): bytes 1f 8b 08 04, one BC subfield of SLEN 2 among the extra field's subfields, BSIZE + 1 inside the data,
+ * ISIZE <= 65536, a deflate stream that fills its bytes exactly, inflates to ISIZE bytes and has the trailer's CRC32; a member
+ * of ISIZE 0 (the 28-byte end-of-file marker) may stand anywhere.  A file that is ONE gzip member has no such parallelism and
+ * is refused by name: it stays with the host's gzip stream.
+ *   ma_batch_set_reads_bgzf  head: n_head bytes of text (host, may be NULL with n_head 0); members: n_bytes of whole members
+ *                            (host).  The text T is head followed by what the members inflate to, in order, minus its last
+ *                            n_drop bytes: head and n_drop let a caller cut a compressed stream into runs of whole records by
+ *                            inflating only the last member of a chunk on the host -- the bytes it drops are the next call's
+ *                            head -- so that no batch waits for the one before it.  T must be a run of whole records in the
+ *                            strict form of ma_batch_set_reads_text; afterwards the batch is exactly as after that call on T.
+ *                            Uploads, inflates, parses and waits: TWO read-backs (the line feeds, the inflate's verdict and
+ *                            T's first and last byte in one copy; then the statistics, as ma_batch_set_reads_text's second).
+ *                            n_bytes == 0 parses the head alone; nothing at all gives 0 reads.  Refusals; each leaves the
+ *                            batch without reads and text and usable, and *n_reads = 0 unless stated:
+ *                              "ma_batch_set_reads_bgzf: member <k> (byte <X>): <reason>"  member k (0-based), whose first
+ *                                byte is at offset X of `members`: the first bad header (found on the host: nothing is
+ *                                launched), else the lowest member whose stream or trailer is refused.  The reasons: not
+ *                                BGZF ("a gzip member without the BGZF size field: single-member gzip stays with
+ *                                GzFileStream ..."), truncated member, ISIZE too large, one per deflate violation, length
+ *                                mismatch, CRC mismatch
+ *                              "ma_batch_set_reads_bgzf: n_drop is larger than the inflated part of the text"
+ *                              "ma_batch_set_reads_bgzf: text: line <L> (byte <X>): <reason>"  a violation in T, L and X as
+ *                                in ma_batch_set_reads_text but counted in T, the reasons that call's (a T of 2 GiB or more:
+ *                                its "too large")
+ *                              "ma_batch_set_reads_bgzf: batch capacity exceeded"  *n_reads = the reads T holds
+ *                            With ma_batch_enable_timing, ma_batch_kernel_ms [6] is the time of the two inflate kernels. */
+int ma_batch_set_reads_bgzf( ma_batch*, const char* head /*host, may be NULL*/, uint64_t n_head, const void* members /*host*/,
+                             uint64_t n_bytes, uint64_t n_drop, uint64_t* n_reads );
 /* work counters for the roofline model (same meaning as the oracle's): [0] extend_backward steps,
  * [1] distinct occ blocks touched, [2] bwt_sa LF steps, [3] SA rows, [4] DP band cells, [5] ksw jobs */
 int ma_batch_counters( ma_batch*, uint64_t out[ 8 ] );
@@ -446,7 +480,7 @@ int ma_batch_counters( ma_batch*, uint64_t out[ 8 ] );
  * qlen, tlen, w, zdrop, flag, ez.zdropped, ez.max_q, ez.max_t (shapes may be NULL to only count) */
 int ma_batch_get_dp_jobs( ma_batch*, uint64_t* n_jobs, int32_t* shapes, uint64_t cap );
 /* per-kernel HIP-event times of the last stage calls in ms: [0] seeding [1] sa-lookup [2] chaining
- * [3] dp-jobs [4] ksw [5] stitch; requires ma_batch_enable_timing(b,1) */
+ * [3] dp-jobs [4] ksw [5] stitch; [6] the inflate of the last ma_batch_set_reads_bgzf; requires ma_batch_enable_timing(b,1) */
 int ma_batch_enable_timing( ma_batch*, int on );
 int ma_batch_kernel_ms( ma_batch*, float out[ 8 ] );
 /* host wall time in ms of the stage calls of the last ma_align_batch: [0] seed [1] extract [2] chain [3] dp (launches,

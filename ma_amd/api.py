@@ -378,6 +378,27 @@ class Batch:
         self.n_bases = int(self.read_off[-1])
         return self.n
 
+    def set_reads_bgzf(self, members, head=b"", drop=0):
+        """members: bytes of whole BGZF members (what bgzip writes; the strict form of include/ma_amd.h).  The text is head
+        followed by what the members inflate to, minus its last drop bytes; the device inflates the members, one per lane, and
+        parses the text as set_reads_text() does.  Returns the number of reads.  A refusal raises MaError -- "member <k> (byte
+        <X>): <reason>" or "text: line <L> (byte <X>): <reason>" -- and leaves the batch without reads; after "batch capacity
+        exceeded" the exception's n_reads is the number of reads the text holds."""
+        data = np.frombuffer(bytes(members) + b"\0", dtype=np.uint8)
+        front = np.frombuffer(bytes(head) + b"\0", dtype=np.uint8)
+        n = C.c_uint64()
+        self.n, self.read_off, self.n_bases = 0, np.zeros(1, dtype=np.uint64), 0
+        try:
+            _chk(lib().ma_batch_set_reads_bgzf(self.h, _ptr(front), C.c_uint64(len(front) - 1), _ptr(data), C.c_uint64(len(data) - 1),
+                                               C.c_uint64(drop), C.byref(n)))
+        except MaError as e:
+            e.n_reads = int(n.value)
+            raise
+        self.n = int(n.value)
+        self.read_off, _ = self.reads(codes=False)
+        self.n_bases = int(self.read_off[-1])
+        return self.n
+
     def set_mates_text(self, text1, text2, rev_comp=True):
         """text1, text2: bytes of the two read files of a paired-end run (or runs of whole records of them), both FASTQ or both
         FASTA in the strict form (ma_batch_set_mates_text).  Record k of text1 becomes read 2k, record k of text2 read 2k + 1,

@@ -17,10 +17,11 @@ static int text_no_reads( ma_batch* b )
     return 0;
 }
 
-static int text_refuse( u64 line, u64 byte, u32 reason )
+// who: the words in front of "line <L> ..." ("ma_batch_set_reads_text", "ma_batch_set_reads_bgzf: text")
+static int text_refuse( u64 line, u64 byte, u32 reason, const char* who = "ma_batch_set_reads_text" )
 {
     char msg[ 256 ];
-    ma_text::message( msg, sizeof( msg ), line, byte, reason );
+    ma_text::messageOf( msg, sizeof( msg ), who, line, byte, reason );
     return fail( msg );
 }
 static int mates_refuse( u32 refusal, u32 text, u64 line, u64 byte, u32 reason )
@@ -42,24 +43,35 @@ static u64 text_host_key( const char* text, u64 n )
 
 // The front of a parse, k_text_count .. k_text_records, of ONE text of n > 0 bytes on scratch of its own: both entry points run
 // it, ma_batch_set_mates_text once per text.  text_front_count uploads and counts, the caller reads the line feeds back
-// (stat[ TXT_FEEDS ]) and sets `feeds`, text_front_lines does the per-line work.
+// (stat[ TXT_FEEDS ]) and sets `feeds`, text_front_lines does the per-line work.  A text that is on the device already
+// (ma_batch_set_reads_bgzf inflates it there) has no `host`: nothing is uploaded, and the caller sets `first`, `last` and `kind`
+// behind the read-back that brings the two bytes with the line feeds.
 struct TextFront
 {
-    const char* host;
+    const char* host; // NULL: the text is in `dev` already
     u64 n;
     char* dev; // 256-byte aligned, inside b->txtIn
     unsigned long long* stat; // TXT_WORDS words inside b->txtStat
     ma_batch::TextScratch* scratch;
     u32 kind;
     u64 nBlocks, feeds, lines;
+    char first, last; // the text's first and last byte
 };
+static u32 text_kind( char first )
+{
+    return first == '@' ? ma_text::KIND_FASTQ : ma_text::KIND_FASTA;
+}
 static int text_front_count( ma_batch* b, TextFront& t )
 {
-    t.kind = t.host[ 0 ] == '@' ? ma_text::KIND_FASTQ : ma_text::KIND_FASTA;
     t.nBlocks = ( t.n + TEXT_BLOCK_BYTES - 1 ) / TEXT_BLOCK_BYTES;
     if( t.scratch->block.reserve( ( t.nBlocks + 1 ) * 4 ) )
         return 1;
-    MA_HIP( hipMemcpyAsync( t.dev, t.host, t.n, hipMemcpyHostToDevice, b->stream ) );
+    if( t.host )
+    {
+        t.first = t.host[ 0 ], t.last = t.host[ t.n - 1 ];
+        t.kind = text_kind( t.first );
+        MA_HIP( hipMemcpyAsync( t.dev, t.host, t.n, hipMemcpyHostToDevice, b->stream ) );
+    }
     MA_HIP( hipMemsetAsync( t.stat, 0, TXT_WORDS * 8, b->stream ) );
     MA_HIP( hipMemsetAsync( t.stat + TXT_LONE_CR, 0xff, 2 * 8, b->stream ) ); // TXT_LONE_CR, TXT_VIOLATION: none
     hipLaunchKernelGGL( k_text_count, dim3( (unsigned)t.nBlocks ), dim3( TEXT_BLOCK ), 0, b->stream, t.dev, t.n, t.scratch->block.as<u32>( ), t.stat );
@@ -82,7 +94,7 @@ static TextSide text_side( const TextFront& t, u64 hostKey )
 static int text_front_lines( ma_batch* b, TextFront& t )
 {
     ma_batch::TextScratch& S = *t.scratch;
-    t.lines = ma_text::nLines( t.feeds, t.host[ t.n - 1 ] );
+    t.lines = ma_text::nLines( t.feeds, t.last );
     const u64 lines = t.lines;
     if( S.start.reserve( ( lines + 2 ) * 4 ) || S.hdrName.reserve( ( lines + 2 ) * 8 ) || S.bases.reserve( ( lines + 2 ) * 4 ) ||
         S.recLine.reserve( ( lines + 2 ) * 4 ) )
@@ -102,6 +114,55 @@ static int text_front_lines( ma_batch* b, TextFront& t )
     hipLaunchKernelGGL( k_text_records, dim3( (unsigned)std::min<u64>( 256, ( lines + 255 ) / 256 ) ), lineBlock, 0, b->stream, t.kind, lines,
                         S.hdrName.as<u64>( ), S.bases.as<u32>( ), S.recLine.as<u32>( ), t.stat );
     MA_HIP( hipGetLastError( ) );
+    return 0;
+}
+
+// The rest of a single text's parse behind the read-back of its line feeds (t.feeds is set): the per-line kernels, k_text_stat,
+// k_text_emit, the read-back of the statistics into h (TXT_WORDS words) and the batch's new state.  who / whoText: the call's
+// name, and the words in front of "line <L> ..." in a refusal.
+static int text_single_rest( ma_batch* b, TextFront& t, unsigned long long* h, const char* who, const char* whoText, uint64_t* n_reads )
+{
+    const u64 n = t.n;
+    unsigned long long* const stat = t.stat;
+    if( b->txtNames.reserve( n + 1 ) || ( t.kind == ma_text::KIND_FASTQ && b->txtQual.reserve( b->max_bases + 1 ) ) || text_front_lines( b, t ) )
+        return 1;
+    const TextSide s = text_side( t, ma_text::NO_VIOLATION );
+    hipLaunchKernelGGL( k_text_stat, dim3( 1 ), dim3( 1 ), 0, b->stream, t.lines, s.hdrName, s.bases, s.start, b->max_reads, b->max_bases, stat );
+    TextEmitArgs A;
+    A.kind = t.kind;
+    A.text = t.dev;
+    A.n = n, A.lines = t.lines;
+    A.start = s.start;
+    A.hdrName = s.hdrName;
+    A.bases = s.bases;
+    A.stat = stat;
+    A.roff = b->roff.as<u64>( );
+    A.codes = b->reads.as<uint8_t>( );
+    A.nameOff = b->txtNameOff.as<u64>( );
+    A.names = b->txtNames.as<char>( );
+    A.qual = t.kind == ma_text::KIND_FASTQ ? b->txtQual.as<uint8_t>( ) : nullptr;
+    hipLaunchKernelGGL( k_text_emit, dim3( (unsigned)t.nBlocks ), dim3( TEXT_BLOCK ), 0, b->stream, A );
+    MA_HIP( hipGetLastError( ) );
+    // the last read-back: reads, bases, name bytes, the longest read, the refusal
+    MA_HIP( hipMemcpyAsync( h, stat, TXT_WORDS * 8, hipMemcpyDeviceToHost, b->stream ) );
+    if( batch_wait( b ) )
+        return 1;
+    if( h[ TXT_VIOLATION ] != ma_text::NO_VIOLATION )
+        return text_refuse( h[ TXT_VIOLATION ] >> 8, h[ TXT_BYTE ], (u32)( h[ TXT_VIOLATION ] & 0xffu ), whoText );
+    if( !h[ TXT_EMIT ] )
+    {
+        if( n_reads )
+            *n_reads = h[ TXT_READS ]; // (what a caller sizes the next batch object by)
+        return fail( std::string( who ) + ": batch capacity exceeded" );
+    }
+    b->n_reads = h[ TXT_READS ];
+    b->n_bases = h[ TXT_BASES ];
+    b->max_qlen = (u32)h[ TXT_MAX_LEN ];
+    b->txtNameBytes = h[ TXT_NAME_BYTES ];
+    b->txtHasQual = t.kind == ma_text::KIND_FASTQ;
+    b->txtSet = true;
+    if( n_reads )
+        *n_reads = b->n_reads;
     return 0;
 }
 
@@ -141,46 +202,7 @@ int ma_batch_set_reads_text( ma_batch* b, const char* text, uint64_t n, uint64_t
     if( batch_wait( b ) )
         return 1;
     t.feeds = h[ TXT_FEEDS ];
-    if( b->txtNames.reserve( n + 1 ) || ( t.kind == ma_text::KIND_FASTQ && b->txtQual.reserve( b->max_bases + 1 ) ) || text_front_lines( b, t ) )
-        return 1;
-    const TextSide s = text_side( t, ma_text::NO_VIOLATION );
-    hipLaunchKernelGGL( k_text_stat, dim3( 1 ), dim3( 1 ), 0, b->stream, t.lines, s.hdrName, s.bases, s.start, b->max_reads, b->max_bases, stat );
-    TextEmitArgs A;
-    A.kind = t.kind;
-    A.text = t.dev;
-    A.n = n, A.lines = t.lines;
-    A.start = s.start;
-    A.hdrName = s.hdrName;
-    A.bases = s.bases;
-    A.stat = stat;
-    A.roff = b->roff.as<u64>( );
-    A.codes = b->reads.as<uint8_t>( );
-    A.nameOff = b->txtNameOff.as<u64>( );
-    A.names = b->txtNames.as<char>( );
-    A.qual = t.kind == ma_text::KIND_FASTQ ? b->txtQual.as<uint8_t>( ) : nullptr;
-    hipLaunchKernelGGL( k_text_emit, dim3( (unsigned)t.nBlocks ), dim3( TEXT_BLOCK ), 0, b->stream, A );
-    MA_HIP( hipGetLastError( ) );
-    // read-back 2: reads, bases, name bytes, the longest read, the refusal
-    MA_HIP( hipMemcpyAsync( h, stat, TXT_WORDS * 8, hipMemcpyDeviceToHost, b->stream ) );
-    if( batch_wait( b ) )
-        return 1;
-    if( h[ TXT_VIOLATION ] != ma_text::NO_VIOLATION )
-        return text_refuse( h[ TXT_VIOLATION ] >> 8, h[ TXT_BYTE ], (u32)( h[ TXT_VIOLATION ] & 0xffu ) );
-    if( !h[ TXT_EMIT ] )
-    {
-        if( n_reads )
-            *n_reads = h[ TXT_READS ]; // (what a caller sizes the next batch object by)
-        return fail( "ma_batch_set_reads_text: batch capacity exceeded" );
-    }
-    b->n_reads = h[ TXT_READS ];
-    b->n_bases = h[ TXT_BASES ];
-    b->max_qlen = (u32)h[ TXT_MAX_LEN ];
-    b->txtNameBytes = h[ TXT_NAME_BYTES ];
-    b->txtHasQual = t.kind == ma_text::KIND_FASTQ;
-    b->txtSet = true;
-    if( n_reads )
-        *n_reads = b->n_reads;
-    return 0;
+    return text_single_rest( b, t, h, "ma_batch_set_reads_text", "ma_batch_set_reads_text", n_reads );
 }
 
 int ma_batch_set_mates_text( ma_batch* b, const char* text1, uint64_t n1, const char* text2, uint64_t n2, int32_t rev_comp_mates,

@@ -91,6 +91,9 @@ static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0
 #include "../host/ma_text_dev.h"
 #include "stage_text.h"
 
+#include "../host/ma_bgzf_dev.h"
+#include "stage_bgzf.h"
+
 // ------------------------------------------------------------------------------------------------
 // batch object
 // ------------------------------------------------------------------------------------------------
@@ -152,6 +155,9 @@ struct ma_batch
     {
         DevBuf block, start, hdrName, bases, recLine;
     } txtOne, txtMate;
+    // BGZF members inflated into txtIn (ma_batch_set_reads_bgzf, launch_bgzf.h): the compressed bytes and the member table; the
+    // call's statistics follow the parse's in txtStat
+    DevBuf bgzIn, bgzMembers;
     SamTextState sam, pairSam;
     // small inversions (ma_inversions_batch, launch_inv.h): the statistics of the call, per MappingQuality slot its candidates, per
     // candidate its record, DP job, shape, window and result, and the FINAL lists the later stages see through mq_view
@@ -1246,3 +1252,5 @@ int ma_debug_seed_prof( unsigned long long* out )
 #include "launch_inv.h"
 
 #include "launch_text.h"
+
+#include "launch_bgzf.h"

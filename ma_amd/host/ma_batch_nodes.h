@@ -13,6 +13,7 @@
 // binarySeeding.h:575-584).  Every graph thread that calls BatchAlign::execute gets its own engine (stream + device batch),
 // so the number of graph threads IS the number of device batches in flight.
 #pragma once
+#include "ma_bgzf_dev.h"
 #include "ma_flat_sam.h"
 #include "ma_sam.h"
 #include <atomic>
@@ -226,6 +227,164 @@ class BatchTextReader : public libMS::Module<TextBatch, true, FileStream>
             }
         }
         if( rText.empty( ) )
+            return nullptr; // end of file (module.h:688-695)
+        return pRet;
+    }
+};
+
+// BatchTextReader over the COMPRESSED bytes of a BGZF file (what bgzip and htslib write: a chain of independent gzip members, the
+// strict form of ma_bgzf_dev.h), the source of BatchAligner::executeBgzfSam.  About uiBatchBytes of the file are read as a block
+// behind the carried compressed tail, under the stream's lock, and cut at the last whole member by walking the member headers;
+// the rest is carried.  The text is not inflated here but for the LAST member(s): BatchTextReader::lastRecordStart is local and
+// exact in strict text, so the last record start of the chunk's text is found in the text of its last member, or of its last
+// two, ... -- one member more while none is found, with the carried head when the walk goes all the way back.  The batch is
+//   sHead     the text carried from the last batch (what lay behind its cut)
+//   sMembers  the members up to and including the one that holds the cut
+//   uiDrop    the bytes of that member's text behind the cut: they become the next batch's sHead
+// and the members behind that one are carried as they are.  No batch waits for anything the device makes of the one before it.
+// At the end of the file the rest is the batch, uiDrop = 0.  A chunk without a record start grows.  A stream that is not BGZF
+// -- plain gzip has no size field in its header -- throws with the reason's text, which names GzFileStream.  No zlib.
+class BatchBgzfReader : public libMS::Module<BgzfBatch, true, FileStream>
+{
+    std::string sCarry, sHeadCarry; // compressed bytes and text behind the last cut (guarded by the stream's lock)
+    char cKind = '\0'; // the first byte of the file's text
+
+    [[noreturn]] static void refuse( FileStream& rStream, const std::string& sWhat, uint32_t uiReason )
+    {
+        throw std::runtime_error( "BatchBgzfReader: the stream " + rStream.fileName( ) + ": " + sWhat + ": " + ma_bgzf::errorText( uiReason ) );
+    }
+    // the text of member rM of rData behind rText
+    static void inflateBehind( FileStream& rStream, const std::string& rData, const ma_bgzf::Member& rM, std::string& rText )
+    {
+        const size_t uiOld = rText.size( );
+        rText.resize( uiOld + rM.uiIsize );
+        const uint32_t uiReason = ma_bgzf::inflateMember( (const uint8_t*)rData.data( ), rM, (uint8_t*)&rText[ uiOld ] );
+        if( uiReason != ma_bgzf::OK )
+            refuse( rStream, "the member at byte " + std::to_string( rM.uiIn ) + " of a chunk", uiReason );
+    }
+
+  public:
+    size_t uiBatchBytes = 16u << 20; // of the compressed file
+    BatchBgzfReader( const ParameterSetManager& )
+    {}
+    // the text of a batch, inflated on the host (tests, and callers without a device)
+    static std::string textOf( const BgzfBatch& rBatch )
+    {
+        ma_bgzf::Result xResult;
+        const uint8_t* const pData = (const uint8_t*)rBatch.sMembers.data( );
+        char aMessage[ 320 ];
+        if( ma_bgzf::inflateHost( pData, rBatch.sMembers.size( ), nullptr, &xResult ) == 0 )
+        {
+            std::string sText( xResult.uiBytes, '\0' );
+            if( ma_bgzf::inflateHost( pData, rBatch.sMembers.size( ), (uint8_t*)&sText[ 0 ], &xResult ) == 0 && rBatch.uiDrop <= sText.size( ) )
+            {
+                sText.resize( sText.size( ) - rBatch.uiDrop );
+                return rBatch.sHead + sText;
+            }
+        }
+        ma_bgzf::message( aMessage, sizeof( aMessage ), xResult.uiMember, xResult.uiByte, xResult.uiReason );
+        throw std::runtime_error( aMessage );
+    }
+    virtual std::shared_ptr<BgzfBatch> execute( std::shared_ptr<FileStream> pStream ) override
+    {
+        auto pRet = std::make_shared<BgzfBatch>( );
+        std::string& rData = pRet->sMembers;
+        const size_t uiWant = std::max<size_t>( uiBatchBytes, 1 );
+        std::lock_guard<std::mutex> xLock( pStream->xMutex );
+        rData.reserve( sCarry.size( ) + uiWant );
+        rData.swap( sCarry );
+        sCarry.clear( );
+        pRet->sHead.swap( sHeadCarry );
+        sHeadCarry.clear( );
+        std::vector<ma_bgzf::Member> vMembers; // the whole members of rData, which end at uiWalked
+        size_t uiWalked = 0;
+        // (a chunk that has to grow doubles: every attempt inflates its last members again)
+        for( size_t uiAsk = rData.size( ) < uiWant ? uiWant - rData.size( ) : uiWant;; uiAsk = std::max( uiWant, rData.size( ) ) )
+        {
+            if( !pStream->readBlock( rData, uiAsk ) )
+                throw std::runtime_error( "BatchBgzfReader: the stream " + pStream->fileName( ) + " has no block reads" );
+            while( uiWalked < rData.size( ) )
+            {
+                ma_bgzf::Member xM;
+                const uint32_t uiReason = ma_bgzf::header( (const uint8_t*)rData.data( ), rData.size( ), uiWalked, &xM );
+                if( uiReason == ma_bgzf::ERR_TRUNCATED && !pStream->eof( ) )
+                    break; // the rest of the member comes with the next block
+                if( uiReason != ma_bgzf::OK )
+                    refuse( *pStream, "the member at byte " + std::to_string( uiWalked ) + " of a chunk", uiReason );
+                vMembers.push_back( xM );
+                uiWalked += xM.uiBytes;
+            }
+            if( cKind == '\0' ) // the first byte of the file's text tells FASTQ from FASTA
+                for( size_t i = 0; i < vMembers.size( ) && cKind == '\0'; i++ )
+                    if( vMembers[ i ].uiIsize > 0 )
+                    {
+                        std::string sFirst;
+                        inflateBehind( *pStream, rData, vMembers[ i ], sFirst );
+                        cKind = sFirst[ 0 ];
+                    }
+            if( pStream->eof( ) )
+                break; // the rest is the batch
+            if( cKind != '\0' && cKind != '@' && cKind != '>' )
+                break; // neither kind: the device refuses the chunk as it is
+            // the last record start of the chunk's text, looked for in the text of its last members
+            std::string sTail;
+            size_t uiFrom = vMembers.size( ), uiCut = 0; // sTail: the text of members uiFrom .. ; uiCut: offset of the cut in it
+            while( uiFrom > 0 && uiCut == 0 )
+            {
+                std::string sOne;
+                inflateBehind( *pStream, rData, vMembers[ --uiFrom ], sOne );
+                sTail.insert( 0, sOne );
+                if( uiFrom > 0 || pRet->sHead.empty( ) )
+                {
+                    // (the rule reads the kind off the first byte and looks at line starts behind offset 0 only)
+                    const size_t uiAt = BatchTextReader::lastRecordStart( std::string( 1, cKind ) + sTail );
+                    uiCut = uiAt > 0 ? uiAt - 1 : 0;
+                }
+            }
+            size_t uiHeadKept = pRet->sHead.size( );
+            if( uiCut == 0 && !vMembers.empty( ) && !pRet->sHead.empty( ) )
+            {
+                const size_t uiAt = BatchTextReader::lastRecordStart( pRet->sHead + sTail );
+                if( uiAt >= pRet->sHead.size( ) )
+                    uiCut = uiAt - pRet->sHead.size( ); // (0: exactly behind the head)
+                else if( uiAt > 0 )
+                    uiHeadKept = uiAt; // inside the head: the batch is the head's front, no member
+                if( uiAt == 0 )
+                    continue; // no record start yet: the chunk grows
+            }
+            else if( uiCut == 0 )
+                continue;
+            // members uiFrom .. uiLast - 1 hold the text before the cut
+            size_t uiLast = uiFrom, uiBefore = 0; // uiBefore: text of sTail before member uiLast
+            if( uiHeadKept == pRet->sHead.size( ) )
+                while( uiLast < vMembers.size( ) && uiBefore < uiCut )
+                    uiBefore += vMembers[ uiLast++ ].uiIsize;
+            else
+                uiLast = 0;
+            const size_t uiKeep = uiLast > 0 ? (size_t)( vMembers[ uiLast - 1 ].uiIn + vMembers[ uiLast - 1 ].uiBytes ) : 0;
+            if( uiHeadKept < pRet->sHead.size( ) )
+            {
+                sHeadCarry.assign( pRet->sHead, uiHeadKept, std::string::npos );
+                pRet->sHead.resize( uiHeadKept );
+            }
+            else
+            {
+                pRet->uiDrop = uiBefore - uiCut;
+                sHeadCarry.assign( sTail, uiCut, pRet->uiDrop );
+            }
+            sCarry.assign( rData, uiKeep, std::string::npos );
+            rData.resize( uiKeep );
+            return pRet;
+        }
+        if( uiWalked != rData.size( ) ) // (never at the end of the file: a truncated member is refused there)
+        {
+            sCarry.assign( rData, uiWalked, std::string::npos );
+            rData.resize( uiWalked );
+        }
+        bool bText = !pRet->sHead.empty( );
+        for( const ma_bgzf::Member& rM : vMembers )
+            bText = bText || rM.uiIsize > 0;
+        if( !bText )
             return nullptr; // end of file (module.h:688-695)
         return pRet;
     }

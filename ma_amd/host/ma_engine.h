@@ -13,6 +13,7 @@
 // std::runtime_error like in the module wrappers.
 #pragma once
 #include "../../include/ma_amd.h"
+#include "ma_bgzf_dev.h"
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -516,6 +517,25 @@ class Engine
     // that holds more is parsed twice).
     std::shared_ptr<BatchResult> runText( const char* pText, size_t uiBytes, uint32_t uiSamOptions, bool bInversions = false )
     {
+        return runTextBy( uiBytes, uiSamOptions, bInversions,
+                          [ & ]( uint64_t* pReads ) { return ma_batch_set_reads_text( pBatch, pText, uiBytes, pReads ); } );
+    }
+    // runText for a batch of a BGZF-compressed file: the text is pHead followed by what the members inflate to, minus its last
+    // uiDrop bytes (ma_batch_set_reads_bgzf: the device inflates the members and parses the text).  The member headers are walked
+    // here as well, for the size of the text the device batch is sized by.
+    std::shared_ptr<BatchResult> runBgzf( const char* pHead, size_t uiHeadBytes, const char* pMembers, size_t uiMemberBytes, uint64_t uiDrop,
+                                          uint32_t uiSamOptions, bool bInversions = false )
+    {
+        ma_bgzf::Result xWalk;
+        ma_bgzf::inflateHost( (const uint8_t*)pMembers, uiMemberBytes, nullptr, &xWalk ); // (a bad header: the library refuses it by name)
+        const size_t uiBytes = uiHeadBytes + xWalk.uiBytes - std::min<uint64_t>( uiDrop, xWalk.uiBytes );
+        return runTextBy( uiBytes, uiSamOptions, bInversions, [ & ]( uint64_t* pReads ) {
+            return ma_batch_set_reads_bgzf( pBatch, pHead, uiHeadBytes, pMembers, uiMemberBytes, uiDrop, pReads );
+        } );
+    }
+    // uiBytes of text that rSet puts into pBatch (it returns the library's status and the reads it found)
+    template <typename SET> std::shared_ptr<BatchResult> runTextBy( size_t uiBytes, uint32_t uiSamOptions, bool bInversions, SET&& rSet )
+    {
         auto pRes = freshResult( );
         BatchResult& R = *pRes;
         R.bStages = R.bSocQueues = R.bPairs = false;
@@ -526,12 +546,12 @@ class Engine
         fit( std::max<uint64_t>( uiCapReads, uiBytes / 32 ), std::max<uint64_t>( uiCapBases, uiBytes ) );
         auto t0 = std::chrono::steady_clock::now( );
         uint64_t n = 0;
-        if( ma_batch_set_reads_text( pBatch, pText, uiBytes, &n ) != 0 )
+        if( rSet( &n ) != 0 )
         {
             if( n == 0 ) // (only "batch capacity exceeded" reports the reads of the text)
                 engineCheck( 1 );
             fit( n, uiBytes );
-            engineCheck( ma_batch_set_reads_text( pBatch, pText, uiBytes, &n ) );
+            engineCheck( rSet( &n ) );
         }
         R.uiReads = n;
         R.fH2D = secondsSince( t0 );

@@ -1482,6 +1482,15 @@ class TextBatch : public libMS::Container
   public:
     std::string sText;
 };
+// The same out of a BGZF-compressed file (BatchBgzfReader of ma_batch_nodes.h): the text is sHead followed by what the whole
+// members of sMembers inflate to, minus its last uiDrop bytes -- what BatchAligner::executeBgzfSam hands to the device, which
+// inflates and parses it (ma_batch_set_reads_bgzf).  The host inflated only the last member(s), to find the cut.
+class BgzfBatch : public libMS::Container
+{
+  public:
+    std::string sHead, sMembers;
+    uint64_t uiDrop = 0;
+};
 // The same for mate pairs: runs of whole records of the two read files (BatchPairedTextReader cuts them so that both hold equally
 // many records, except at the end of a stream): what BatchAligner::executePairedTextSam hands to ma_batch_set_mates_text.
 class MatesTextBatch : public libMS::Container
@@ -1875,6 +1884,34 @@ class BatchAligner
         try
         {
             pRet->pResult = pEngine->runText( pText->sText.data( ), pText->sText.size( ), samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
+        }
+        catch( ... )
+        {
+            giveEngine( pIndex, std::move( pEngine ) );
+            throw;
+        }
+        giveEngine( pIndex, std::move( pEngine ) );
+        return pRet;
+    }
+
+    // executeTextSam for a batch of a BGZF-compressed file (BatchBgzfReader): the device inflates the members, one per lane, into
+    // the buffer its parser reads (ma_batch_set_reads_bgzf; the strict forms of ma_bgzf_dev.h and ma_text_dev.h) and goes on as
+    // for text.  Members or a text the device refuses throw the library's message, which names the member or the line.
+    std::shared_ptr<AlignedBatch> executeBgzfSam( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<BgzfBatch> pBatch,
+                                                  std::shared_ptr<Pack> pPack )
+    {
+        nameContigs( *pFM_index->pDev, *pPack );
+        return executeBgzfSamOn( pFM_index->pDev->p, pBatch );
+    }
+    // (the contigs of pIndex are named already)
+    std::shared_ptr<AlignedBatch> executeBgzfSamOn( const ma_index* pIndex, std::shared_ptr<BgzfBatch> pBatch )
+    {
+        auto pEngine = takeEngine( pIndex );
+        auto pRet = std::make_shared<AlignedBatch>( );
+        try
+        {
+            pRet->pResult = pEngine->runBgzf( pBatch->sHead.data( ), pBatch->sHead.size( ), pBatch->sMembers.data( ), pBatch->sMembers.size( ),
+                                              pBatch->uiDrop, samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
         }
         catch( ... )
         {

@@ -104,11 +104,16 @@ MA_TEXT_HD const char* errorText( uint32_t uiReason )
     }
 }
 
-// "ma_batch_set_reads_text: line <L> (byte <X>): <reason>" into pOut (at least 192 bytes); uiLine is 0-based here
+// "<who>: line <L> (byte <X>): <reason>" into pOut (at least 192 bytes); uiLine is 0-based here.  (ma_batch_set_reads_bgzf words
+// a violation in its inflated text with it.)
+inline void messageOf( char* pOut, size_t uiCap, const char* pWho, uint64_t uiLine, uint64_t uiByte, uint32_t uiReason )
+{
+    snprintf( pOut, uiCap, "%s: line %llu (byte %llu): %s", pWho, (unsigned long long)( uiLine + 1 ), (unsigned long long)uiByte, errorText( uiReason ) );
+}
+// "ma_batch_set_reads_text: line <L> (byte <X>): <reason>"
 inline void message( char* pOut, size_t uiCap, uint64_t uiLine, uint64_t uiByte, uint32_t uiReason )
 {
-    snprintf( pOut, uiCap, "ma_batch_set_reads_text: line %llu (byte %llu): %s", (unsigned long long)( uiLine + 1 ), (unsigned long long)uiByte,
-              errorText( uiReason ) );
+    messageOf( pOut, uiCap, "ma_batch_set_reads_text", uiLine, uiByte, uiReason );
 }
 
 // ---- character classes ------------------------------------------------------------------------------------------------
