@@ -217,6 +217,14 @@ int ma_stream_destroy( const ma_index*, void* hip_stream );
  * call replaces the output of the preceding stage (CSR offsets per read, records as the get functions return them). */
 int ma_batch_set_segments( ma_batch*, const uint64_t* seg_off /*n+1*/, const ma_segment* segs ); /* -> ma_extract_seeds_batch */
 int ma_batch_set_seeds( ma_batch*, const uint64_t* seed_off /*n+1*/, const ma_seed* seeds ); /* -> ma_chain_batch */
+/* Harmonized seed sets from elsewhere (layout of ma_batch_get_hsets): the sets of read r are hset_off[r] .. hset_off[r+1], the
+ * seeds of set s are hseeds[hseed_off[s] .. hseed_off[s+1]), hset_soc[s] is its xStats.index_of_strip.  -> ma_dp_batch.
+ * Contract, checked on the host before anything is uploaded: hset_off and hseed_off start at 0 and never decrease; no seed
+ * has a negative field; q_start + len <= the length of the set's read; r_start + len <= the length of the doubled text
+ * (reverse-strand seeds carry positions >= the forward length).  A violation fails the call with "ma_batch_set_hsets: ..."
+ * naming the read and the set; the batch then holds no harmonized sets (as before ma_chain_batch) and stays usable.
+ * The order of the seeds inside a set is NOT checked: NeedlemanWunsch::execute_one walks them as given, and so does
+ * ma_dp_batch; Harmonization hands them over ordered by q_start.  Empty sets and seeds of length 0 are allowed. */
 int ma_batch_set_hsets( ma_batch*, const uint64_t* hset_off /*n+1*/, const uint64_t* hseed_off /*n_hsets+1*/,
                         const uint32_t* hset_soc, const ma_seed* hseeds ); /* -> ma_dp_batch */
 /* A SoC queue per read that was swept elsewhere (SoCPriorityQueue soc.h:96-420 as StripOfConsideration::execute returns

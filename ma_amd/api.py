@@ -521,6 +521,16 @@ class Batch:
         seeds = np.ascontiguousarray(np.concatenate([seeds, np.zeros(1, dtype=SEED_DT)]))
         _chk(lib().ma_batch_set_seeds(self.h, _ptr(off), _ptr(seeds)))
 
+    def set_hsets(self, hset_off, hseed_off, hset_soc, seeds):
+        """Harmonized sets from elsewhere (the layout of hsets()) -> dp().  ma_batch_set_hsets checks them on the host and
+        raises MaError("ma_batch_set_hsets: ...") for a seed beyond its read or the text, a negative field or a decreasing
+        offset array; the batch then holds no sets and stays usable."""
+        hset_off = np.ascontiguousarray(hset_off, dtype=np.uint64)
+        hseed_off = np.ascontiguousarray(np.concatenate([np.asarray(hseed_off, dtype=np.uint64), np.zeros(1, dtype=np.uint64)]))
+        hset_soc = np.ascontiguousarray(np.concatenate([np.asarray(hset_soc, dtype=np.uint32), np.zeros(1, dtype=np.uint32)]))
+        seeds = np.ascontiguousarray(np.concatenate([np.asarray(seeds, dtype=SEED_DT), np.zeros(1, dtype=SEED_DT)]))
+        _chk(lib().ma_batch_set_hsets(self.h, _ptr(hset_off), _ptr(hseed_off), _ptr(hset_soc), _ptr(seeds)))
+
     def socs(self, heap=False):
         """The SoC queue of every read: strips in pop order, or (heap=True) the queue's array as the sweep leaves it;
         returns (soc_off, socs, seed_off, seeds re-sorted by reference position)."""

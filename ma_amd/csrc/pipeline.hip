@@ -691,18 +691,79 @@ int ma_batch_set_soc_heap( ma_batch* b, const uint64_t* soc_off, const ma_soc* s
     return 0;
 }
 
+// What ma_dp_batch relies on in sets handed in (include/ma_amd.h): checked on the host, before anything is uploaded -- a seed
+// beyond its read or beyond the text would be an out-of-bounds read of k_dp_enum and the ksw kernels.  A refusal leaves the batch
+// without harmonized sets (as before ma_chain_batch) and otherwise usable.
+static int hsets_refuse( ma_batch* b, const std::string& what )
+{
+    b->nHsets = b->nHseeds = 0;
+    b->nJobSlots = 0;
+    if( b->stage_done > 2 )
+        b->stage_done = 2;
+    return fail( "ma_batch_set_hsets: " + what );
+}
+static int hsets_check( ma_batch* b, const u64* roff, const uint64_t* hset_off, const uint64_t* hseed_off, const uint32_t* hset_soc, const ma_seed* hseeds )
+{
+    const u64 n = b->n_reads, textLen = b->idx->v.n;
+    if( hset_off[ 0 ] != 0 )
+        return hsets_refuse( b, "hset_off does not start at 0" );
+    for( u64 r = 0; r < n; r++ )
+        if( hset_off[ r + 1 ] < hset_off[ r ] )
+            return hsets_refuse( b, "hset_off decreases at read " + std::to_string( r ) );
+    const u64 nh = hset_off[ n ];
+    if( nh == 0 )
+        return 0;
+    if( !hseed_off || !hset_soc )
+        return fail( "ma_batch_set_hsets: null argument" );
+    if( nh > 0xffffffffull )
+        return hsets_refuse( b, "more than 2^32 - 1 sets" );
+    if( hseed_off[ 0 ] != 0 )
+        return hsets_refuse( b, "hseed_off does not start at 0" );
+    for( u64 r = 0; r < n; r++ )
+    {
+        const u64 qlen = roff[ r + 1 ] - roff[ r ];
+        for( u64 s = hset_off[ r ]; s < hset_off[ r + 1 ]; s++ )
+        {
+            const std::string where = "read " + std::to_string( r ) + ", set " + std::to_string( s - hset_off[ r ] );
+            if( hseed_off[ s + 1 ] < hseed_off[ s ] )
+                return hsets_refuse( b, "hseed_off decreases (" + where + ")" );
+            if( hseed_off[ s + 1 ] - hseed_off[ s ] > 0x7fffffffull )
+                return hsets_refuse( b, "too many seeds (" + where + ")" );
+            if( hseed_off[ s + 1 ] > hseed_off[ s ] && !hseeds )
+                return fail( "ma_batch_set_hsets: null argument" );
+            for( u64 k = hseed_off[ s ]; k < hseed_off[ s + 1 ]; k++ )
+            {
+                const ma_seed& x = hseeds[ k ];
+                const std::string seed = where + ", seed " + std::to_string( k - hseed_off[ s ] ) + ")";
+                if( x.q_start < 0 || x.len < 0 || x.r_start < 0 || x.delta < 0 )
+                    return hsets_refuse( b, "negative field (" + seed );
+                if( (u64)x.q_start > qlen || (u64)x.len > qlen - (u64)x.q_start )
+                    return hsets_refuse( b, "seed ends beyond its read of " + std::to_string( qlen ) + " bases (" + seed );
+                if( (u64)x.r_start > textLen || (u64)x.len > textLen - (u64)x.r_start )
+                    return hsets_refuse( b, "seed ends beyond the doubled text of " + std::to_string( textLen ) + " bases (" + seed );
+            }
+        }
+    }
+    return 0;
+}
+
 int ma_batch_set_hsets( ma_batch* b, const uint64_t* hset_off, const uint64_t* hseed_off, const uint32_t* hset_soc,
                         const ma_seed* hseeds )
 {
     if( !b || !b->d_roff || !hset_off )
         return fail( "ma_batch_set_hsets: no reads set or null argument" );
-    const u64 n = b->n_reads, nh = hset_off[ n ];
-    if( nh && ( !hseed_off || !hset_soc ) )
-        return fail( "ma_batch_set_hsets: null argument" );
-    const u64 nhs = nh ? hseed_off[ nh ] : 0;
-    if( nhs && !hseeds )
-        return fail( "ma_batch_set_hsets: null argument" );
+    const u64 n = b->n_reads;
     MA_BIND_DEVICE( b->device );
+    // the reads' lengths: the offsets live on the device, however the reads were set (this call is no part of the aligned path: a
+    // small copy and a wait more do not matter here, a host copy of the offsets per ma_batch_set_reads would)
+    std::vector<u64> roff( n + 1, 0 );
+    MA_HIP( hipMemcpyAsync( roff.data( ), b->d_roff, ( n + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
+    if( batch_wait( b ) )
+        return 1;
+    if( hsets_check( b, roff.data( ), hset_off, hseed_off, hset_soc, hseeds ) )
+        return 1;
+    const u64 nh = hset_off[ n ];
+    const u64 nhs = nh ? hseed_off[ nh ] : 0;
     std::vector<HSet> flat( nh + 1 );
     std::vector<u32> rd( nh + 1 );
     for( u64 r = 0; r < n; r++ )

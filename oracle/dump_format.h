@@ -4,6 +4,11 @@
 // MACASE01: magic[8] | u32 n_contigs | { u32 name_len, name, u64 len, codes[len] (0..3, >=4 = N) }*
 //           | u32 n_reads | { u32 len, codes[len] (0..4) }*
 // KSWCAS01: magic[8] | u32 n | { i32 qlen, i32 tlen, i32 w, i32 zdrop, i32 flag, q[qlen], t[tlen] }*
+// NWSETS01: magic[8] | u64 n_reads | u64 n_sets | u64 n_seeds | u64 hset_off[n_reads + 1] | u64 hseed_off[n_sets + 1]
+//           | u32 hset_soc[n_sets] | { i64 q_start, i64 len, i64 r_start, i64 delta, u32 ambiguity, u32 on_forward }[n_seeds]
+//           harmonized seed sets for the reads of a MACASE01 file, in the layout of ma_batch_get_hsets / ma_batch_set_hsets: the
+//           sets of read r are hset_off[r] .. hset_off[r + 1], the seeds of set s are hseed_off[s] .. hseed_off[s + 1] (records
+//           in ma_seed layout, positions on the doubled text), hset_soc[s] is its index_of_strip (writer: tests/nw_sets.py)
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -23,6 +28,18 @@ struct KswCase
 {
     int w, zdrop, flag;
     std::vector<uint8_t> q, t;
+};
+
+struct NwSetsSeed
+{
+    int64_t q_start, len, r_start, delta;
+    uint32_t ambiguity, on_forward;
+};
+struct NwSetsFile
+{
+    std::vector<uint64_t> hsetOff, hseedOff;
+    std::vector<uint32_t> hsetSoc;
+    std::vector<NwSetsSeed> seeds;
 };
 
 namespace dumpfmt
@@ -72,6 +89,37 @@ inline CaseFile readCase( const char* sPath )
     }
     fclose( f );
     return c;
+}
+
+inline NwSetsFile readNwSets( const char* sPath )
+{
+    FILE* f = fopen( sPath, "rb" );
+    if( !f )
+        throw std::runtime_error( std::string( "cannot open " ) + sPath );
+    char magic[ 8 ];
+    dumpfmt::rd( f, magic, 8 );
+    if( memcmp( magic, "NWSETS01", 8 ) )
+        throw std::runtime_error( "bad sets magic" );
+    const uint64_t nReads = dumpfmt::rdv<uint64_t>( f ), nSets = dumpfmt::rdv<uint64_t>( f ), nSeeds = dumpfmt::rdv<uint64_t>( f );
+    NwSetsFile s;
+    s.hsetOff.resize( nReads + 1 );
+    s.hseedOff.resize( nSets + 1 );
+    s.hsetSoc.resize( nSets );
+    s.seeds.resize( nSeeds );
+    dumpfmt::rd( f, s.hsetOff.data( ), 8 * ( nReads + 1 ) );
+    dumpfmt::rd( f, s.hseedOff.data( ), 8 * ( nSets + 1 ) );
+    dumpfmt::rd( f, s.hsetSoc.data( ), 4 * nSets );
+    dumpfmt::rd( f, s.seeds.data( ), sizeof( NwSetsSeed ) * nSeeds );
+    fclose( f );
+    if( s.hsetOff[ 0 ] != 0 || s.hsetOff[ nReads ] != nSets || s.hseedOff[ 0 ] != 0 || s.hseedOff[ nSets ] != nSeeds )
+        throw std::runtime_error( "sets file: offsets and counts disagree" );
+    for( uint64_t i = 0; i < nReads; i++ )
+        if( s.hsetOff[ i + 1 ] < s.hsetOff[ i ] )
+            throw std::runtime_error( "sets file: hset_off decreases" );
+    for( uint64_t i = 0; i < nSets; i++ )
+        if( s.hseedOff[ i + 1 ] < s.hseedOff[ i ] )
+            throw std::runtime_error( "sets file: hseed_off decreases" );
+    return s;
 }
 
 inline std::vector<KswCase> readKswCases( const char* sPath )

@@ -132,6 +132,12 @@ inline void cnt( int i, u64 x = 1 )
     if( tlsCnt )
         tlsCnt->v[ i ] += x;
 }
+// the kswcpp calls of a run, in call order (ma_or_nw_sets): qlen, tlen, w, zdrop, flag
+struct KswCall
+{
+    int32_t qlen, tlen, w, zdrop, flag;
+};
+thread_local std::vector<KswCall>* tlsCalls = nullptr;
 
 // ---- suffix sorting of T' $ for the oracle's own index builder (any correct suffix sort yields the
 // reference's BWT; is.cpp / bwt_large.cpp are merely the reference's choice of algorithm) ----

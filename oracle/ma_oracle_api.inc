@@ -489,6 +489,117 @@ const void* ma_or_chain_res_array( const ma_or_chain_result* r, int32_t which, u
     return nullptr;
 }
 
+// ---- the NeedlemanWunsch + MappingQuality stage alone, from given harmonized sets (tests of the product's walk on chosen sets) ----
+struct ma_or_nw_result
+{
+    std::vector<u64> alnOff, mqOff, ops, mqOps, jobOff, nAligned;
+    std::vector<ma_or_alignment> alns, mq;
+    std::vector<ma_or_ksw_call> jobs;
+};
+
+static ma_or_alignment toAlnRec( const Aln& a, std::vector<u64>& ops, bool flags )
+{
+    ma_or_alignment r;
+    r.begin_ref = (i64)a.bRef;
+    r.end_ref = (i64)a.eRef;
+    r.begin_q = (i64)a.bQ;
+    r.end_q = (i64)a.eQ;
+    r.score = a.score;
+    r.soc_index = a.socIndex;
+    r.n_ops = (uint32_t)a.data.size( );
+    r.ops_off = ops.size( ) / 2;
+    r.secondary = flags && a.secondary ? 1 : 0;
+    r.supplementary = flags && a.supplementary ? 1 : 0;
+    r.mapq = flags ? a.mapq : 0;
+    for( auto& d : a.data )
+    {
+        ops.push_back( (u64)d.first );
+        ops.push_back( d.second );
+    }
+    return r;
+}
+
+ma_or_nw_result* ma_or_nw_sets( const ma_or_index* x, const ma_or_params* P, const uint8_t* reads, const uint64_t* read_off,
+                                uint64_t n, const uint64_t* hset_off, const uint64_t* hseed_off, const uint32_t* hset_soc,
+                                const ma_or_seed* hseeds )
+{
+    ma_or_nw_result* res = new ma_or_nw_result( );
+    Ctx c{ *x, *P };
+    res->alnOff.push_back( 0 );
+    res->mqOff.push_back( 0 );
+    res->jobOff.push_back( 0 );
+    res->nAligned.push_back( 0 );
+    std::vector<KswCall> calls;
+    for( u64 i = 0; i < n; i++ )
+    {
+        const u64 qlen = read_off[ i + 1 ] - read_off[ i ];
+        std::vector<uint8_t> Q( reads + read_off[ i ], reads + read_off[ i + 1 ] );
+        std::vector<Aln> alns;
+        for( u64 s = hset_off[ i ]; s < hset_off[ i + 1 ]; s++ )
+        {
+            SeedSet set;
+            set.socIndex = hset_soc[ s ];
+            for( u64 k = hseed_off[ s ]; k < hseed_off[ s + 1 ]; k++ )
+            {
+                Seed sd;
+                sd.q = (u64)hseeds[ k ].q_start;
+                sd.len = (u64)hseeds[ k ].len;
+                sd.r = (u64)hseeds[ k ].r_start;
+                sd.delta = (u64)hseeds[ k ].delta;
+                sd.amb = hseeds[ k ].ambiguity;
+                sd.fwd = hseeds[ k ].on_forward != 0;
+                set.v.push_back( sd );
+            }
+            calls.clear( );
+            tlsCalls = &calls; // the kswcpp calls of this set, in call order
+            alns.push_back( executeOne( c, set, Q ) );
+            tlsCalls = nullptr;
+            for( const KswCall& k : calls )
+                res->jobs.push_back( ma_or_ksw_call{ k.qlen, k.tlen, k.w, k.zdrop, k.flag } );
+            res->jobOff.push_back( res->jobs.size( ) );
+        }
+        nwSort( alns ); // NeedlemanWunsch::execute's final sort (needlemanWunsch.h:131-132)
+        for( const Aln& a : alns )
+            res->alns.push_back( toAlnRec( a, res->ops, false ) );
+        res->alnOff.push_back( res->alns.size( ) );
+        std::vector<Aln> tmp = alns, mq;
+        mappingQuality( c, qlen, tmp, mq );
+        for( const Aln& a : mq )
+            res->mq.push_back( toAlnRec( a, res->mqOps, true ) );
+        res->mqOff.push_back( res->mq.size( ) );
+        if( !mq.empty( ) )
+            res->nAligned[ 0 ]++;
+    }
+    return res;
+}
+void ma_or_nw_result_free( ma_or_nw_result* r )
+{
+    delete r;
+}
+const void* ma_or_nw_res_array( const ma_or_nw_result* r, int32_t which, uint64_t* count )
+{
+#define MA_OR_ARR( v )                                                                                                 \
+    {                                                                                                                  \
+        *count = r->v.size( );                                                                                         \
+        return r->v.data( );                                                                                           \
+    }
+    switch( which )
+    {
+        case MA_OR_NW_ALN_OFF: MA_OR_ARR( alnOff )
+        case MA_OR_NW_ALNS: MA_OR_ARR( alns )
+        case MA_OR_NW_OPS: MA_OR_ARR( ops )
+        case MA_OR_NW_MQ_OFF: MA_OR_ARR( mqOff )
+        case MA_OR_NW_MQ: MA_OR_ARR( mq )
+        case MA_OR_NW_MQ_OPS: MA_OR_ARR( mqOps )
+        case MA_OR_NW_JOB_OFF: MA_OR_ARR( jobOff )
+        case MA_OR_NW_JOBS: MA_OR_ARR( jobs )
+        case MA_OR_NW_N_ALIGNED: MA_OR_ARR( nAligned )
+    }
+#undef MA_OR_ARR
+    *count = 0;
+    return nullptr;
+}
+
 int ma_or_dump_pipe( const ma_or_index* x, const ma_or_params* P, const uint8_t* reads, const uint64_t* off,
                      uint64_t n, const char* out_path )
 {

@@ -413,6 +413,8 @@ static void kswDispatch( int qlen, const uint8_t* q, int tlen, const uint8_t* t,
                          int zdrop, int flag, Ez& ez )
 {
     cnt( 5 );
+    if( tlsCalls )
+        tlsCalls->push_back( KswCall{ qlen, tlen, w, zdrop, flag } );
     int minScr = std::min( { P.mismatch > 0 ? -P.mismatch : P.mismatch, -P.gap, -P.extend, -P.gap2, -P.extend2 } );
     int maxSc = P.match < 0 ? -P.match : P.match;
     i64 sz = std::max( qlen, tlen );

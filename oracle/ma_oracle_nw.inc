@@ -498,13 +498,9 @@ inline bool alnLarger( const Aln& a, const Aln& b )
     return a.score > b.score;
 }
 
-// NeedlemanWunsch::execute (needlemanWunsch.h:111-134)
-static void nwExecute( const Ctx& c, const std::vector<SeedSet>& sets, const uint8_t* q, u64 qlen, std::vector<Aln>& out )
+// the final sort of NeedlemanWunsch::execute (needlemanWunsch.h:131-132)
+static void nwSort( std::vector<Aln>& out )
 {
-    out.clear( );
-    std::vector<uint8_t> Q( q, q + qlen );
-    for( const SeedSet& s : sets )
-        out.push_back( executeOne( c, s, Q ) );
     // the reference sorts shared_ptrs; sorting indices reproduces the same permutation
     std::vector<size_t> idx( out.size( ) );
     for( size_t i = 0; i < idx.size( ); i++ )
@@ -514,6 +510,16 @@ static void nwExecute( const Ctx& c, const std::vector<SeedSet>& sets, const uin
     for( size_t i : idx )
         tmp.push_back( std::move( out[ i ] ) );
     out.swap( tmp );
+}
+
+// NeedlemanWunsch::execute (needlemanWunsch.h:111-134)
+static void nwExecute( const Ctx& c, const std::vector<SeedSet>& sets, const uint8_t* q, u64 qlen, std::vector<Aln>& out )
+{
+    out.clear( );
+    std::vector<uint8_t> Q( q, q + qlen );
+    for( const SeedSet& s : sets )
+        out.push_back( executeOne( c, s, Q ) );
+    nwSort( out );
 }
 
 // Alignment::overlap (alignment.h:659-735)

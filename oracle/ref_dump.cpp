@@ -15,6 +15,8 @@
 //   ref_dump readpair <in1> <in2> <out> <revcomp mate 0|1> -> mate pairs of the PairedFileReader
 //   ref_dump f4    <case> <preset> <seed> <out> <inversions 0|1> <paired 0|1> <zdrop_inversion> [<out.sam> [<sam options>]]
 //                                                      -> SmallInversions / PairedReads lists (+ SAM of the (Paired)FileWriter)
+//   ref_dump nwsets <case> <preset> <sets file> <out> [match mismatch gap extend gap2 extend2]
+//                                                      -> NeedlemanWunsch + MappingQuality on GIVEN harmonized sets (NWSETS01)
 #include "ma/container/fMIndex.h"
 #include "ma/container/pack.h"
 #include "ma/module/binarySeeding.h"
@@ -171,6 +173,65 @@ static int cmdPipe( const char* sCase, const char* sPreset, unsigned uiSeed, con
                      (unsigned long long)pA->uiEndOnRef, (unsigned long long)pA->uiBeginOnQuery,
                      (unsigned long long)pA->uiEndOnQuery, (long long)pA->iScore, (int)pA->bSecondary,
                      (int)pA->bSupplementary, pA->fMappingQuality );
+    }
+    fclose( f );
+    return 0;
+}
+
+// NeedlemanWunsch::execute + MappingQuality::execute on harmonized sets handed in (NWSETS01, dump_format.h): the SeedsSets are
+// built from the file, xStats.index_of_strip from hset_soc; the ALN and MQ lines are cmdPipe's
+static int cmdNwSets( const char* sCase, const char* sPreset, const char* sSets, const char* sOut )
+{
+    CaseFile c = readCase( sCase );
+    NwSetsFile s = readNwSets( sSets );
+    if( s.hsetOff.size( ) != c.reads.size( ) + 1 )
+        throw std::runtime_error( "sets file and case differ in their number of reads" );
+    RefIndex idx = buildIndex( c );
+    ParameterSetManager xParams;
+    selectPreset( xParams, sPreset );
+    NeedlemanWunsch xDp( xParams );
+    MappingQuality xMq( xParams );
+    FILE* f = fopen( sOut, "w" );
+    for( size_t i = 0; i < c.reads.size( ); i++ )
+    {
+        auto pQ = mkSeq( c.reads[ i ] );
+        pQ->sName = "r" + std::to_string( i );
+        fprintf( f, "R %zu %zu\n", i, c.reads[ i ].size( ) );
+        auto pHarm = std::make_shared<libMS::ContainerVector<std::shared_ptr<Seeds>>>( );
+        for( uint64_t k = s.hsetOff[ i ]; k < s.hsetOff[ i + 1 ]; k++ )
+        {
+            auto pS = std::make_shared<Seeds>( );
+            for( uint64_t j = s.hseedOff[ k ]; j < s.hseedOff[ k + 1 ]; j++ )
+            {
+                const NwSetsSeed& x = s.seeds[ j ];
+                Seed xSeed( (nucSeqIndex)x.q_start, (nucSeqIndex)x.len, (nucSeqIndex)x.r_start, x.ambiguity, x.on_forward != 0 );
+                xSeed.uiDelta = (nucSeqIndex)x.delta;
+                pS->push_back( xSeed );
+            }
+            pS->xStats.index_of_strip = s.hsetSoc[ k ];
+            pS->bConsistent = true;
+            pHarm->push_back( pS );
+        }
+        auto pAlns = xDp.execute( pHarm, pQ, idx.pPack );
+        fprintf( f, "ALN %zu\n", pAlns->size( ) );
+        for( auto& pA : *pAlns )
+        {
+            fprintf( f, "a %llu %llu %llu %llu %lld %u %zu", (unsigned long long)pA->uiBeginOnRef,
+                     (unsigned long long)pA->uiEndOnRef, (unsigned long long)pA->uiBeginOnQuery,
+                     (unsigned long long)pA->uiEndOnQuery, (long long)pA->iScore, pA->xStats.index_of_strip,
+                     pA->data.size( ) );
+            for( auto& d : pA->data )
+                fprintf( f, " %d:%llu", (int)d.first, (unsigned long long)d.second );
+            fprintf( f, "\n" );
+        }
+        auto pMq = xMq.execute( pQ, pAlns );
+        fprintf( f, "MQ %zu\n", pMq->size( ) );
+        for( auto& pA : *pMq )
+            fprintf( f, "m %llu %llu %llu %llu %lld %d %d %.17g\n", (unsigned long long)pA->uiBeginOnRef,
+                     (unsigned long long)pA->uiEndOnRef, (unsigned long long)pA->uiBeginOnQuery,
+                     (unsigned long long)pA->uiEndOnQuery, (long long)pA->iScore, (int)pA->bSecondary,
+                     (int)pA->bSupplementary, pA->fMappingQuality );
+        fflush( f ); // (a case the reference dies on shows as the last read of the file)
     }
     fclose( f );
     return 0;
@@ -527,6 +588,17 @@ int main( int argc, char** argv )
         pGlobalParams->iGap2->set( atoi( argv[ 10 ] ) );
         pGlobalParams->iExtend2->set( atoi( argv[ 11 ] ) );
     }
+    if( argc >= 12 && !strcmp( argv[ 1 ], "nwsets" ) ) // nwsets <case> <preset> <sets> <out> match mismatch gap extend gap2 extend2
+    {
+        pGlobalParams->iMatch->set( atoi( argv[ 6 ] ) );
+        pGlobalParams->iMissMatch->set( atoi( argv[ 7 ] ) );
+        pGlobalParams->iGap->set( atoi( argv[ 8 ] ) );
+        pGlobalParams->iExtend->set( atoi( argv[ 9 ] ) );
+        pGlobalParams->iGap2->set( atoi( argv[ 10 ] ) );
+        pGlobalParams->iExtend2->set( atoi( argv[ 11 ] ) );
+    }
+    if( argc >= 6 && !strcmp( argv[ 1 ], "nwsets" ) )
+        return cmdNwSets( argv[ 2 ], argv[ 3 ], argv[ 4 ], argv[ 5 ] );
     if( argc >= 6 && !strcmp( argv[ 1 ], "pipe" ) )
         return cmdPipe( argv[ 2 ], argv[ 3 ], (unsigned)atoi( argv[ 4 ] ), argv[ 5 ] );
     if( argc >= 6 && !strcmp( argv[ 1 ], "sam" ) )
@@ -569,6 +641,6 @@ int main( int argc, char** argv )
                 aSc[ i ] = atoi( argv[ 5 + i ] );
         return cmdKsw( argv[ 2 ], argv[ 3 ], argc >= 5 && !strcmp( argv[ 4 ], "dirty" ), aSc );
     }
-    fprintf( stderr, "usage: ref_dump index|pipe|sam|f4|read|ext|ksw ...\n" );
+    fprintf( stderr, "usage: ref_dump index|pipe|sam|f4|nwsets|read|ext|ksw ...\n" );
     return 2;
 }

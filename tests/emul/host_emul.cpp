@@ -261,6 +261,12 @@ int main( int argc, char** argv )
     if( std::string( argv[ 2 ] ).find( "+mems" ) != std::string::npos ) // the preset with the MEMs seeding technique
         OP.seeding_technique = 2;
     OP.srand_seed = (u32)atoi( argv[ 3 ] );
+    if( const char* e = getenv( "MA_EMUL_SCORING" ) ) // "match,mismatch,gap,extend,gap2,extend2" instead of the preset's
+        if( sscanf( e, "%d,%d,%d,%d,%d,%d", &OP.match, &OP.mismatch, &OP.gap, &OP.extend, &OP.gap2, &OP.extend2 ) != 6 )
+        {
+            fprintf( stderr, "MA_EMUL_SCORING: six numbers expected\n" );
+            return 1;
+        }
     SeedParams SP;
     SP.technique = OP.seeding_technique;
     SP.min_seed_len = OP.min_seed_len;
@@ -338,12 +344,153 @@ int main( int argc, char** argv )
             return 1;
         }
     }
+    // MA_EMUL_HSETS=<file> (NWSETS01, dump_format.h): the DP stage alone from given harmonized sets (Batch.set_hsets -> dp()):
+    // nothing is seeded or chained, the dump has the HARM, ALN and MQ blocks and the jobs of every set
+    NwSetsFile givenSets;
+    const bool hsetsGiven = getenv( "MA_EMUL_HSETS" ) != nullptr;
+    if( hsetsGiven )
+    {
+        givenSets = readNwSets( getenv( "MA_EMUL_HSETS" ) );
+        if( givenSets.hsetOff.size( ) != cs.reads.size( ) + 1 )
+        {
+            fprintf( stderr, "MA_EMUL_HSETS: %s is not for %zu reads\n", getenv( "MA_EMUL_HSETS" ), cs.reads.size( ) );
+            return 1;
+        }
+    }
     FILE* f = fopen( argv[ 4 ], "w" );
+    // ---- DP: enumerate, answer with the oracle's ksw, stitch, finish.  exact: the ops capacity the product gives a set (k_ops_caps)
+    // instead of a generous one, and the jobs of every set in the dump ("j" lines) -- the form MA_EMUL_HSETS runs
+    auto dpStage = [ & ]( const std::vector<uint8_t>& q, const HSet* sets, u32 nsets, const ma_seed* hpool, bool exact ) -> int {
+        const u32 qlen = (u32)q.size( );
+        u32 err = 0;
+        std::vector<AlnHeader> hdr( nsets );
+        std::vector<std::vector<u64>> opsv( nsets );
+        std::vector<u64> opsPool;
+        std::vector<uint8_t> Q( q );
+        for( u32 s = 0; s < nsets; s++ )
+        {
+            const ma_seed* S = hpool + sets[ s ].off;
+            AlnHeader h;
+            memset( &h, 0, sizeof( h ) );
+            h.soc_index = sets[ s ].soc;
+            h.mapq = NAN;
+            const NwWindow W = nw_window( X, NP, S, sets[ s ].cnt );
+            std::vector<u64> ops( qlen + 100000 );
+            h.ops_cap = (u32)ops.size( );
+            std::vector<DpJob> setJobs;
+            if( W.valid )
+            {
+                std::vector<DpJob> jobs;
+                HostSink sink{ &jobs, W.begin_ref };
+                NwWalk<HostSink> walk{ X, NP, sink, Q.data( ), W.begin_ref, AlnBuilder{ nullptr, nullptr, nullptr } };
+                walk.run( S, sets[ s ].cnt, qlen, W );
+                std::vector<ma_or_ez> ez( jobs.size( ) );
+                std::vector<std::vector<u32>> cig( jobs.size( ) );
+                for( size_t j = 0; j < jobs.size( ); j++ )
+                {
+                    const DpJob& J = jobs[ j ];
+                    std::vector<uint8_t> qq, tt;
+                    for( u32 i = J.q_from; i < J.q_to; i++ )
+                        qq.push_back( Q[ i ] );
+                    for( u32 i = J.r_from; i < J.r_to; i++ )
+                        tt.push_back( (uint8_t)text_base( X, J.win_begin + i ) );
+                    if( J.rev )
+                    {
+                        std::reverse( qq.begin( ), qq.end( ) );
+                        std::reverse( tt.begin( ), tt.end( ) );
+                    }
+                    cig[ j ].resize( qq.size( ) + tt.size( ) + 4 );
+                    int nc = ma_or_ksw( (int)qq.size( ), qq.data( ), (int)tt.size( ), tt.data( ), J.w, J.zdrop, J.flag, &OP,
+                                        &ez[ j ], cig[ j ].data( ), (int)cig[ j ].size( ) );
+                    cig[ j ].resize( nc );
+                }
+                if( exact )
+                {
+                    u64 cap = (u64)qlen + 8ull * sets[ s ].cnt + 16;
+                    for( auto& c : cig )
+                        cap += c.size( );
+                    ops.assign( cap, 0 );
+                    ops.shrink_to_fit( ); // (a write behind the capacity is a heap overflow the address sanitizer reports)
+                    h.ops_cap = (u32)cap;
+                    if( jobs.size( ) > 2 * (size_t)sets[ s ].cnt )
+                    {
+                        fprintf( stderr, "set %u: %zu jobs for %u seeds\n", s, jobs.size( ), sets[ s ].cnt );
+                        return 1;
+                    }
+                }
+                setJobs = jobs;
+                h.begin_ref = h.end_ref = W.begin_ref;
+                HostStitch st{ &ez, &cig, 0 };
+                NwWalk<HostStitch> w2{ X, NP, st, Q.data( ), W.begin_ref, AlnBuilder{ &h, ops.data( ), &err } };
+                w2.run( S, sets[ s ].cnt, qlen, W );
+            }
+            h.ops_off = opsPool.size( );
+            for( u32 k = 0; k < h.n_ops; k++ )
+                opsPool.push_back( ops[ k ] );
+            hdr[ s ] = h;
+            if( exact )
+                for( const DpJob& J : setJobs )
+                    fprintf( f, "j %u %u %u %d %d %d\n", s, J.q_to - J.q_from, J.r_to - J.r_from, J.w, J.zdrop, J.flag );
+        }
+        std::vector<u32> order( nsets + 1 ), mq( nsets + 1 );
+        const u32 nmq = finish_read( NP, hdr.data( ), opsPool.data( ), nsets, qlen, order.data( ), mq.data( ) );
+        fprintf( f, "ALN %u\n", nsets );
+        for( u32 k = 0; k < nsets; k++ )
+        {
+            const AlnHeader& h = hdr[ order[ k ] ];
+            fprintf( f, "a %llu %llu %llu %llu %lld %u %u", (unsigned long long)h.begin_ref,
+                     (unsigned long long)h.end_ref, (unsigned long long)h.begin_q, (unsigned long long)h.end_q,
+                     (long long)h.score, h.soc_index, h.n_ops );
+            for( u32 j = 0; j < h.n_ops; j++ )
+                fprintf( f, " %u:%llu", op_type( opsPool[ h.ops_off + j ] ),
+                         (unsigned long long)op_len( opsPool[ h.ops_off + j ] ) );
+            fprintf( f, "\n" );
+        }
+        fprintf( f, "MQ %u\n", nmq );
+        for( u32 k = 0; k < nmq; k++ )
+        {
+            const AlnHeader& h = hdr[ mq[ k ] ];
+            fprintf( f, "m %llu %llu %llu %llu %lld %d %d %.17g\n", (unsigned long long)h.begin_ref,
+                     (unsigned long long)h.end_ref, (unsigned long long)h.begin_q, (unsigned long long)h.end_q,
+                     (long long)h.score, (int)h.secondary, (int)h.supplementary, h.mapq );
+        }
+        if( err )
+        {
+            fprintf( stderr, "dp overflow %u\n", err );
+            return 1;
+        }
+        return 0;
+    };
     for( size_t ri = 0; ri < cs.reads.size( ); ri++ )
     {
         const std::vector<uint8_t>& q = cs.reads[ ri ];
         const u32 qlen = (u32)q.size( );
         fprintf( f, "R %zu %u\n", ri, qlen );
+        if( hsetsGiven )
+        {
+            // exactly the arrays ma_batch_set_hsets uploads: the seeds back to back, one HSet per set
+            const u64 s0 = givenSets.hsetOff[ ri ], s1 = givenSets.hsetOff[ ri + 1 ], k0 = givenSets.hseedOff[ s0 ];
+            std::vector<HSet> hs( s1 - s0 + 1 );
+            std::vector<ma_seed> pool( givenSets.hseedOff[ s1 ] - k0 );
+            for( u64 k = k0; k < givenSets.hseedOff[ s1 ]; k++ )
+            {
+                const NwSetsSeed& x = givenSets.seeds[ k ];
+                ma_seed& d = pool[ k - k0 ];
+                d.q_start = x.q_start, d.len = x.len, d.r_start = x.r_start, d.delta = x.delta;
+                d.ambiguity = x.ambiguity, d.on_forward = x.on_forward;
+            }
+            fprintf( f, "HARM %llu\n", (unsigned long long)( s1 - s0 ) );
+            for( u64 s = s0; s < s1; s++ )
+            {
+                hs[ s - s0 ].off = givenSets.hseedOff[ s ] - k0;
+                hs[ s - s0 ].cnt = (u32)( givenSets.hseedOff[ s + 1 ] - givenSets.hseedOff[ s ] );
+                hs[ s - s0 ].soc = givenSets.hsetSoc[ s ];
+                fprintf( f, "h %u %u\n", hs[ s - s0 ].soc, hs[ s - s0 ].cnt );
+            }
+            if( dpStage( q, hs.data( ), (u32)( s1 - s0 ), pool.data( ), true ) )
+                return 1;
+            continue;
+        }
         // ---- seeding
         const u32 seg_cap = 6 * qlen + 8;
         std::vector<ma_segment> stage( seg_cap ), sa( qlen + 2 ), sb( qlen + 2 );
@@ -489,79 +636,8 @@ int main( int argc, char** argv )
             for( u32 k = 0; k < sets[ s ].cnt; k++ )
                 dumpSeed( f, "g", hpool[ sets[ s ].off + k ] );
         }
-        // ---- DP: enumerate, answer with the oracle's ksw, stitch
-        std::vector<AlnHeader> hdr( nsets );
-        std::vector<std::vector<u64>> opsv( nsets );
-        std::vector<u64> opsPool;
-        std::vector<uint8_t> Q( q );
-        for( u32 s = 0; s < nsets; s++ )
-        {
-            const ma_seed* S = hpool.data( ) + sets[ s ].off;
-            AlnHeader h;
-            memset( &h, 0, sizeof( h ) );
-            h.soc_index = sets[ s ].soc;
-            h.mapq = NAN;
-            const NwWindow W = nw_window( X, NP, S, sets[ s ].cnt );
-            std::vector<u64> ops( qlen + 100000 );
-            h.ops_cap = (u32)ops.size( );
-            if( W.valid )
-            {
-                std::vector<DpJob> jobs;
-                HostSink sink{ &jobs, W.begin_ref };
-                NwWalk<HostSink> walk{ X, NP, sink, Q.data( ), W.begin_ref, AlnBuilder{ nullptr, nullptr, nullptr } };
-                walk.run( S, sets[ s ].cnt, qlen, W );
-                std::vector<ma_or_ez> ez( jobs.size( ) );
-                std::vector<std::vector<u32>> cig( jobs.size( ) );
-                for( size_t j = 0; j < jobs.size( ); j++ )
-                {
-                    const DpJob& J = jobs[ j ];
-                    std::vector<uint8_t> qq, tt;
-                    for( u32 i = J.q_from; i < J.q_to; i++ )
-                        qq.push_back( Q[ i ] );
-                    for( u32 i = J.r_from; i < J.r_to; i++ )
-                        tt.push_back( (uint8_t)text_base( X, J.win_begin + i ) );
-                    if( J.rev )
-                    {
-                        std::reverse( qq.begin( ), qq.end( ) );
-                        std::reverse( tt.begin( ), tt.end( ) );
-                    }
-                    cig[ j ].resize( qq.size( ) + tt.size( ) + 4 );
-                    int nc = ma_or_ksw( (int)qq.size( ), qq.data( ), (int)tt.size( ), tt.data( ), J.w, J.zdrop, J.flag, &OP,
-                                        &ez[ j ], cig[ j ].data( ), (int)cig[ j ].size( ) );
-                    cig[ j ].resize( nc );
-                }
-                h.begin_ref = h.end_ref = W.begin_ref;
-                HostStitch st{ &ez, &cig, 0 };
-                NwWalk<HostStitch> w2{ X, NP, st, Q.data( ), W.begin_ref, AlnBuilder{ &h, ops.data( ), &err } };
-                w2.run( S, sets[ s ].cnt, qlen, W );
-            }
-            h.ops_off = opsPool.size( );
-            for( u32 k = 0; k < h.n_ops; k++ )
-                opsPool.push_back( ops[ k ] );
-            hdr[ s ] = h;
-        }
-        std::vector<u32> order( nsets + 1 ), mq( nsets + 1 );
-        const u32 nmq = finish_read( NP, hdr.data( ), opsPool.data( ), nsets, qlen, order.data( ), mq.data( ) );
-        fprintf( f, "ALN %u\n", nsets );
-        for( u32 k = 0; k < nsets; k++ )
-        {
-            const AlnHeader& h = hdr[ order[ k ] ];
-            fprintf( f, "a %llu %llu %llu %llu %lld %u %u", (unsigned long long)h.begin_ref,
-                     (unsigned long long)h.end_ref, (unsigned long long)h.begin_q, (unsigned long long)h.end_q,
-                     (long long)h.score, h.soc_index, h.n_ops );
-            for( u32 j = 0; j < h.n_ops; j++ )
-                fprintf( f, " %u:%llu", op_type( opsPool[ h.ops_off + j ] ),
-                         (unsigned long long)op_len( opsPool[ h.ops_off + j ] ) );
-            fprintf( f, "\n" );
-        }
-        fprintf( f, "MQ %u\n", nmq );
-        for( u32 k = 0; k < nmq; k++ )
-        {
-            const AlnHeader& h = hdr[ mq[ k ] ];
-            fprintf( f, "m %llu %llu %llu %llu %lld %d %d %.17g\n", (unsigned long long)h.begin_ref,
-                     (unsigned long long)h.end_ref, (unsigned long long)h.begin_q, (unsigned long long)h.end_q,
-                     (long long)h.score, (int)h.secondary, (int)h.supplementary, h.mapq );
-        }
+        if( dpStage( q, sets.data( ), nsets, hpool.data( ), false ) )
+            return 1;
     }
     fclose( f );
     return 0;

@@ -382,6 +382,8 @@ OR_ALN_DT = np.dtype([("begin_ref", "<i8"), ("end_ref", "<i8"), ("begin_q", "<i8
                       ("soc_index", "<u4"), ("n_ops", "<u4"), ("ops_off", "<u8"), ("secondary", "<u4"),
                       ("supplementary", "<u4"), ("mapq", "<f8")])
 
+OR_KSW_CALL_DT = np.dtype([(k, "<i4") for k in ("qlen", "tlen", "w", "zdrop", "flag")])
+
 _orlib = None
 
 
@@ -403,6 +405,8 @@ def orlib():
         L.ma_or_bwt_sa.restype = C.c_int64
         L.ma_or_chain_seeds.restype = C.c_void_p
         L.ma_or_chain_res_array.restype = C.c_void_p
+        L.ma_or_nw_sets.restype = C.c_void_p
+        L.ma_or_nw_res_array.restype = C.c_void_p
         _orlib = L
     return _orlib
 
@@ -540,6 +544,36 @@ class OrIndex:
             ptr = L.ma_or_chain_res_array(r, C.c_int32(which), C.byref(cnt))
             res[name] = _np_from(ptr, int(cnt.value), dt)
         L.ma_or_chain_result_free(r)
+        return res
+
+    def nw_sets(self, reads, hset_off, hseed_off, hset_soc, seeds, params):
+        """NeedlemanWunsch::execute + MappingQuality::execute on GIVEN harmonized sets (the layout of the product's Batch.hsets()).
+        Returns aln_off / alns / ops in the layout of Batch.alignments(), mq_off / mq / mq_ops in that of Batch.mapq_alignments(),
+        job_off (per set) / jobs: the kswcpp calls every set issued in call order, and n_aligned."""
+        off = np.zeros(len(reads) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(r) for r in reads])
+        cat = np.ascontiguousarray(np.concatenate([np.asarray(r, dtype=np.uint8) for r in reads] + [np.zeros(1, dtype=np.uint8)]))
+        hset_off = np.ascontiguousarray(hset_off, dtype=np.uint64)
+        nh = int(hset_off[-1])
+        hseed_off = np.ascontiguousarray(np.concatenate([np.asarray(hseed_off, dtype=np.uint64), np.zeros(1, dtype=np.uint64)]))
+        hset_soc = np.ascontiguousarray(np.concatenate([np.asarray(hset_soc, dtype=np.uint32), np.zeros(1, dtype=np.uint32)]))
+        assert len(hset_off) == len(reads) + 1 and len(hseed_off) == nh + 2 and len(hset_soc) == nh + 1
+        assert int(hseed_off[nh]) == len(seeds)
+        seeds = np.ascontiguousarray(np.concatenate([np.asarray(seeds, dtype=OR_SEED_DT), np.zeros(1, dtype=OR_SEED_DT)]))
+        L = orlib()
+        r = C.c_void_p(L.ma_or_nw_sets(self.h, C.byref(params), cat.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p),
+                                       C.c_uint64(len(reads)), hset_off.ctypes.data_as(C.c_void_p),
+                                       hseed_off.ctypes.data_as(C.c_void_p), hset_soc.ctypes.data_as(C.c_void_p),
+                                       seeds.ctypes.data_as(C.c_void_p)))
+        res = {}
+        for which, (name, dt) in enumerate((("aln_off", np.uint64), ("alns", OR_ALN_DT), ("ops", np.uint64), ("mq_off", np.uint64),
+                                            ("mq", OR_ALN_DT), ("mq_ops", np.uint64), ("job_off", np.uint64),
+                                            ("jobs", OR_KSW_CALL_DT), ("n_aligned", np.uint64))):
+            cnt = C.c_uint64()
+            ptr = L.ma_or_nw_res_array(r, C.c_int32(which), C.byref(cnt))
+            res[name] = _np_from(ptr, int(cnt.value), dt)
+        res["n_aligned"] = int(res["n_aligned"][0])
+        L.ma_or_nw_result_free(r)
         return res
 
 
