@@ -112,12 +112,7 @@ int ma_batch_set_reads_bgzf( ma_batch* b, const char* head, uint64_t n_head, con
         t.first = head[ 0 ], t.last = head[ n - 1 ];
     }
     if( n == 0 )
-    {
-        if( batch_wait( b ) )
-            return 1;
-        b->txtSet = true;
-        return 0;
-    }
+        return text_empty( b );
     if( t.first != '@' && t.first != '>' )
         return text_refuse( 0, 0, ma_text::ERR_KIND, "ma_batch_set_reads_bgzf: text" );
     t.kind = text_kind( t.first );

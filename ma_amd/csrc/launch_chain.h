@@ -43,13 +43,13 @@ static u32 lanes_per_wave( u64 items )
 
 int ma_chain_batch( ma_batch* b )
 {
-    if( !b || b->stage_done < 2 )
+    if( !b || b->stage_done < STAGE_EXTRACTED )
         return fail( "ma_chain_batch: run ma_extract_seeds_batch first" );
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads;
     if( n == 0 )
     {
-        b->stage_done = 3;
+        b->stage_done = STAGE_CHAINED;
         return 0;
     }
     const u64 ts = b->nSeeds + 1;
@@ -177,6 +177,6 @@ int ma_chain_batch( ma_batch* b )
                         b->hseedOff.as<u64>( ), b->seedOff.as<u64>( ), b->hlocal.as<ma_seed>( ), b->hpool.as<ma_seed>( ),
                         b->hdense.as<ma_seed>( ), b->hsetFlat.as<HSet>( ), b->hsetRead.as<u32>( ) );
     MA_HIP( hipGetLastError( ) );
-    b->stage_done = 3;
+    b->stage_done = STAGE_CHAINED;
     return 0;
 }

@@ -47,12 +47,11 @@ static bool dp_one_stream( )
 
 int ma_dp_batch( ma_batch* b )
 {
-    if( !b || b->stage_done < 3 )
+    if( !b || b->stage_done < STAGE_CHAINED )
         return fail( "ma_dp_batch: run ma_chain_batch first" );
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads, nh = b->nHsets, nhs = b->nHseeds;
-    b->sam.done = b->pairSam.done = false; // (a text printed before is of other records)
-    inv_reset( b );
+    batch_results_changed( b );
     if( b->mqCnt.reserve( ( n + 1 ) * 4 ) )
         return 1;
     MA_HIP( hipMemsetAsync( b->mqCnt.p, 0, ( n + 1 ) * 4, b->stream ) );
@@ -64,7 +63,7 @@ int ma_dp_batch( ma_batch* b )
     if( n == 0 || nh == 0 )
     {
         b->nJobSlots = 0;
-        b->stage_done = 4;
+        b->stage_done = STAGE_ALIGNED;
         return read_ctr( b );
     }
     const u64 nSlots = 2 * nhs;
@@ -313,7 +312,7 @@ int ma_dp_batch( ma_batch* b )
                             b->ctr.as<unsigned long long>( ), 1 );
     }
     MA_HIP( hipGetLastError( ) );
-    b->stage_done = 4;
+    b->stage_done = STAGE_ALIGNED;
     return 0;
 }
 
@@ -330,8 +329,7 @@ int ma_batch_set_alignments( ma_batch* b, const uint64_t* aln_off, const ma_alig
     if( na && !alns )
         return fail( "ma_batch_set_alignments: null argument" );
     MA_BIND_DEVICE( b->device );
-    b->sam.done = b->pairSam.done = false;
-    inv_reset( b );
+    batch_results_changed( b );
     u64 no = 0;
     for( u64 i = 0; i < na; i++ )
         no += alns[ i ].n_ops;
@@ -384,6 +382,6 @@ int ma_batch_set_alignments( ma_batch* b, const uint64_t* aln_off, const ma_alig
     b->nHseeds = 0;
     b->nJobSlots = 0;
     b->nOpsCap = no; // (the pool's fill: ma_inversions_batch appends behind it)
-    b->stage_done = 4;
+    b->stage_done = STAGE_ALIGNED;
     return 0;
 }

@@ -1,13 +1,13 @@
 // launch_extract.h -- host side of seed extraction: ma_extract_seeds_batch (C ABI).  Textually part of pipeline.hip.
 int ma_extract_seeds_batch( ma_batch* b )
 {
-    if( !b || b->stage_done < 1 )
+    if( !b || b->stage_done < STAGE_SEEDED )
         return fail( "ma_extract_seeds_batch: run ma_seed_batch first" );
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads;
     if( n == 0 )
     {
-        b->socGiven = false, b->stage_done = 2;
+        b->socGiven = false, b->stage_done = STAGE_EXTRACTED;
         return 0;
     }
     if( read_ctr( b ) || check_err( b, "ma_seed_batch" ) )
@@ -54,7 +54,7 @@ int ma_extract_seeds_batch( ma_batch* b )
                             b->seeds.as<ma_seed>( ), c );
     }
     MA_HIP( hipGetLastError( ) );
-    b->socGiven = false, b->stage_done = 2;
+    b->socGiven = false, b->stage_done = STAGE_EXTRACTED;
     return 0;
 }
 

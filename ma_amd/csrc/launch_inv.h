@@ -77,13 +77,12 @@ int ma_inversions_batch( ma_batch* b )
 {
     if( !b )
         return fail( "ma_inversions_batch: null batch" );
-    if( b->stage_done < 4 )
+    if( b->stage_done < STAGE_ALIGNED )
         return fail( "ma_inversions_batch: no MappingQuality output to scan (run ma_dp_batch / ma_align_batch / ma_batch_set_alignments first)" );
     MA_BIND_DEVICE( b->device );
     // pairs and texts made before are of other lists
-    inv_reset( b );
-    b->stage_done = 4;
-    b->sam.done = b->pairSam.done = false;
+    batch_results_changed( b );
+    b->stage_done = STAGE_ALIGNED;
     const u64 n = b->n_reads, nh = b->nHsets;
     if( n == 0 || nh == 0 )
     {

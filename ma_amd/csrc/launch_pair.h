@@ -100,7 +100,7 @@ int ma_pair_batch( ma_batch* b )
 {
     if( !b )
         return fail( "ma_pair_batch: null batch" );
-    if( b->stage_done < 4 )
+    if( b->stage_done < STAGE_ALIGNED )
         return fail( "ma_pair_batch: no MappingQuality output to pair (run ma_dp_batch / ma_align_batch first)" );
     if( b->n_reads % 2 )
         return fail( "ma_pair_batch: odd number of reads (" + std::to_string( b->n_reads ) +
@@ -110,7 +110,7 @@ int ma_pair_batch( ma_batch* b )
     b->pairOnHost = 0;
     b->pairRecs = b->pairNOps = 0;
     b->pairSam.done = false; // (a text printed before is of other picks)
-    b->stage_done = 4;
+    b->stage_done = STAGE_ALIGNED;
     if( np && b->nHsets )
     {
         if( b->pairPick.reserve( np * sizeof( ma_pair::Pick ) ) || b->pairCnt.reserve( ( np + 2 ) * 8 ) || b->pairOps.reserve( ( np + 2 ) * 8 ) ||
@@ -130,13 +130,13 @@ int ma_pair_batch( ma_batch* b )
         b->pairRecs = b->hctr[ CTR_PAIR_RECS ];
         b->pairNOps = b->hctr[ CTR_PAIR_OPS ];
     }
-    b->stage_done = 5;
+    b->stage_done = STAGE_PAIRED;
     return 0;
 }
 
 int ma_batch_pair_counts( ma_batch* b, uint64_t* n_pairs, uint64_t* n_records, uint64_t* n_ops, uint64_t* n_host_pairs )
 {
-    if( !b || b->stage_done < 5 )
+    if( !b || b->stage_done < STAGE_PAIRED )
         return fail( "ma_batch_pair_counts: run ma_pair_batch first" );
     if( n_pairs )
         *n_pairs = b->n_reads / 2;
@@ -153,7 +153,7 @@ int ma_batch_pair_counts( ma_batch* b, uint64_t* n_pairs, uint64_t* n_records, u
 // async: see get_alns
 static int get_pairs( ma_batch* b, uint64_t* pair_off, ma_alignment* alns, uint64_t* ops, int32_t* mate, int32_t* other, bool async )
 {
-    if( !b || b->stage_done < 5 )
+    if( !b || b->stage_done < STAGE_PAIRED )
         return fail( "ma_batch_get_pairs: run ma_pair_batch first" );
     MA_BIND_DEVICE( b->device );
     if( download_begin( b, async, "ma_batch_start_pair_download" ) )

@@ -275,7 +275,7 @@ int ma_sam_batch( ma_batch* b, uint32_t options )
 {
     if( !b )
         return fail( "ma_sam_batch: null batch" );
-    if( b->stage_done < 4 )
+    if( b->stage_done < STAGE_ALIGNED )
         return fail( "ma_sam_batch: no MappingQuality output to print (run ma_dp_batch / ma_align_batch / ma_batch_set_alignments first)" );
     if( options & ~(uint32_t)ma_sam::ALL_OPTIONS )
         return fail( "ma_sam_batch: unknown option bits " + std::to_string( options & ~(uint32_t)ma_sam::ALL_OPTIONS ) );
@@ -293,7 +293,7 @@ int ma_pair_sam_batch( ma_batch* b, uint32_t options )
 {
     if( !b )
         return fail( "ma_pair_sam_batch: null batch" );
-    if( b->stage_done < 5 )
+    if( b->stage_done < STAGE_PAIRED )
         return fail( "ma_pair_sam_batch: no pairs to print (run ma_pair_batch first)" );
     if( options & ~(uint32_t)ma_sam::PAIR_OPTIONS ) // (the tag emulation is the single-end writer's)
         return fail( "ma_pair_sam_batch: unknown option bits " + std::to_string( options & ~(uint32_t)ma_sam::PAIR_OPTIONS ) );

@@ -75,7 +75,7 @@ static int seed_mems( ma_batch* b )
     if( batch_wait( b ) )
         return 1;
     MA_HIP( hipGetLastError( ) );
-    b->stage_done = 1;
+    b->stage_done = STAGE_SEEDED;
     return 0;
 }
 
@@ -210,7 +210,7 @@ static int seed_tasks( ma_batch* b )
     hipLaunchKernelGGL( k_task_finish, dim3( (unsigned)( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream, b->idx->v, seed_params( b->P ),
                         b->d_roff, (u32)n, b->segPool.as<ma_segment>( ), b->segOff.as<u64>( ), b->segCnt.as<u32>( ) );
     MA_HIP( hipGetLastError( ) );
-    b->stage_done = 1;
+    b->stage_done = STAGE_SEEDED;
     return 0;
 }
 
@@ -225,7 +225,7 @@ int ma_seed_batch( ma_batch* b )
     b->segMarked = false;
     if( n == 0 )
     {
-        b->stage_done = 1;
+        b->stage_done = STAGE_SEEDED;
         return 0;
     }
     if( b->P.seeding_technique == 2 )
@@ -364,6 +364,6 @@ int ma_seed_batch( ma_batch* b )
             break; // surfaces as an error in the next stage
         MA_HIP( hipMemsetAsync( b->ctr.p, 0, CTR_COUNT * 8, b->stream ) );
     }
-    b->stage_done = 1;
+    b->stage_done = STAGE_SEEDED;
     return 0;
 }

@@ -6,14 +6,18 @@ static int text_no_reads( ma_batch* b )
 {
     b->n_reads = b->n_bases = 0;
     b->max_qlen = 0;
-    b->d_reads = b->reads.as<uint8_t>( );
-    b->d_roff = b->roff.as<u64>( );
-    b->reads_external = false;
-    b->stage_done = 0;
-    b->txtSet = b->txtHasQual = b->sam.done = b->pairSam.done = false;
-    b->txtNameBytes = 0;
-    inv_reset( b );
+    batch_own_reads( b );
+    batch_reads_changed( b );
     MA_HIP( hipMemsetAsync( b->roff.p, 0, 8, b->stream ) );
+    return 0;
+}
+
+// an empty text (behind text_no_reads and the first name offset): no reads, with names -- none
+static int text_empty( ma_batch* b )
+{
+    if( batch_wait( b ) )
+        return 1;
+    b->txtSet = true;
     return 0;
 }
 
@@ -184,12 +188,7 @@ int ma_batch_set_reads_text( ma_batch* b, const char* text, uint64_t n, uint64_t
         return 1;
     MA_HIP( hipMemsetAsync( b->txtNameOff.p, 0, 8, b->stream ) );
     if( n == 0 )
-    {
-        if( batch_wait( b ) )
-            return 1;
-        b->txtSet = true;
-        return 0;
-    }
+        return text_empty( b );
     if( b->txtIn.reserve( n + 64 ) || b->txtStat.reserve( TXT_WORDS * 8 ) )
         return 1;
     unsigned long long* const stat = b->txtStat.as<unsigned long long>( );

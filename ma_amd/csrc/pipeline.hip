@@ -106,6 +106,9 @@ struct SamTextState
     u64 bytes = 0;
 };
 
+// how far a batch's reads have come (ma_batch::stage_done), in order; ALIGNED: DP + MappingQuality, or lists handed in
+enum Stage { STAGE_NONE, STAGE_SEEDED, STAGE_EXTRACTED, STAGE_CHAINED, STAGE_ALIGNED, STAGE_PAIRED };
+
 struct ma_batch
 {
     const ma_index* idx = nullptr;
@@ -176,7 +179,7 @@ struct ma_batch
     bool stagedPending = false, downPending = false;
     u64 stN = 0, stBases = 0;
     u32 stMaxQ = 0;
-    int stage_done = 0; // 0 none, 1 seeded, 2 extracted, 3 chained, 4 dp, 5 paired
+    int stage_done = STAGE_NONE; // a Stage
     bool timing = false;
     bool blocking = false; // batch_wait: sleep on an event instead of spinning
     hipEvent_t waitEv = nullptr;
@@ -223,6 +226,41 @@ static int batch_wait( ma_batch* b )
     MA_HIP( hipEventRecord( b->waitEv, b->stream ) );
     MA_HIP( hipEventSynchronize( b->waitEv ) );
     return 0;
+}
+
+// The alignment lists changed (ma_dp_batch, ma_batch_set_alignments; ma_inversions_batch, which also puts the stage back to
+// STAGE_ALIGNED): both SAM texts are of other records, and the list view goes back to the MappingQuality arrays.
+// ma_pair_batch is NOT one of them: it changes the picks only, so it drops pairSam alone and the single-end text stays.
+static void batch_results_changed( ma_batch* b )
+{
+    b->sam.done = b->pairSam.done = false;
+    inv_reset( b );
+}
+
+// The batch has new reads, however they came (host arrays, a staged upload, caller-owned device arrays, a text, a refused text):
+// no stage has run on them, they have no names (txtHasQual and txtNameBytes are only read behind txtSet), and every SAM text,
+// pair and inversion record is of other reads.
+static void batch_reads_changed( ma_batch* b )
+{
+    b->stage_done = STAGE_NONE;
+    b->txtSet = b->txtHasQual = false;
+    b->txtNameBytes = 0;
+    batch_results_changed( b );
+}
+
+static void batch_own_reads( ma_batch* b )
+{
+    b->d_reads = b->reads.as<uint8_t>( );
+    b->d_roff = b->roff.as<u64>( );
+    b->reads_external = false;
+}
+
+static u32 longest_read( const uint64_t* offsets, u64 n )
+{
+    u32 mq = 0;
+    for( u64 i = 0; i < n; i++ )
+        mq = std::max<u32>( mq, (u32)( offsets[ i + 1 ] - offsets[ i ] ) );
+    return mq;
 }
 
 static int read_ctr( ma_batch* b )
@@ -442,10 +480,7 @@ int ma_batch_stage_reads( ma_batch* b, const uint8_t* codes, const uint64_t* off
         return fail( "ma_batch_stage_reads: the reads staged before were not taken (ma_batch_use_staged_reads)" );
     if( io_init( b ) || b->reads2.reserve( b->max_bases + 64 ) || b->roff2.reserve( ( b->max_reads + 1 ) * 8 ) )
         return 1;
-    u32 mq = 0;
-    for( u64 i = 0; i < n; i++ )
-        mq = std::max<u32>( mq, (u32)( offsets[ i + 1 ] - offsets[ i ] ) );
-    b->stN = n, b->stBases = offsets[ n ], b->stMaxQ = mq;
+    b->stN = n, b->stBases = offsets[ n ], b->stMaxQ = longest_read( offsets, n );
     // the second buffer held the reads of the step before the current one: everything that was enqueued on the batch's stream
     // up to the last swap may still read it
     if( b->evReadsFree )
@@ -472,12 +507,8 @@ int ma_batch_use_staged_reads( ma_batch* b )
     b->n_reads = b->stN;
     b->n_bases = b->stBases;
     b->max_qlen = b->stMaxQ;
-    b->d_reads = b->reads.as<uint8_t>( );
-    b->d_roff = b->roff.as<u64>( );
-    b->reads_external = false;
-    b->stage_done = 0;
-    b->txtSet = b->sam.done = b->pairSam.done = false;
-    inv_reset( b );
+    batch_own_reads( b );
+    batch_reads_changed( b );
     b->stagedPending = false;
     return 0;
 }
@@ -491,21 +522,14 @@ int ma_batch_set_reads( ma_batch* b, const uint8_t* codes, const uint64_t* offse
         return fail( "ma_batch_set_reads: batch capacity exceeded" );
     b->n_reads = n;
     b->n_bases = offsets[ n ];
-    u32 mq = 0;
-    for( u64 i = 0; i < n; i++ )
-        mq = std::max<u32>( mq, (u32)( offsets[ i + 1 ] - offsets[ i ] ) );
-    b->max_qlen = mq;
+    b->max_qlen = longest_read( offsets, n );
     if( b->n_bases )
         MA_HIP( hipMemcpyAsync( b->reads.p, codes, b->n_bases, hipMemcpyHostToDevice, b->stream ) );
     MA_HIP( hipMemcpyAsync( b->roff.p, offsets, ( n + 1 ) * 8, hipMemcpyHostToDevice, b->stream ) );
     if( batch_wait( b ) )
         return 1;
-    b->d_reads = b->reads.as<uint8_t>( );
-    b->d_roff = b->roff.as<u64>( );
-    b->reads_external = false;
-    b->stage_done = 0;
-    b->txtSet = b->sam.done = b->pairSam.done = false;
-    inv_reset( b );
+    batch_own_reads( b );
+    batch_reads_changed( b );
     return 0;
 }
 
@@ -540,9 +564,7 @@ int ma_batch_set_reads_device( ma_batch* b, const void* d_codes, const void* d_o
     if( read_ctr( b ) )
         return 1;
     b->max_qlen = (u32)b->hctr[ 0 ];
-    b->stage_done = 0;
-    b->txtSet = b->sam.done = b->pairSam.done = false;
-    inv_reset( b );
+    batch_reads_changed( b );
     return 0;
 }
 
@@ -626,7 +648,7 @@ int ma_batch_set_segments( ma_batch* b, const uint64_t* seg_off, const ma_segmen
         return 1; // the host vectors go out of scope
     b->nSegs = ns;
     b->nSeeds = b->nHsets = b->nHseeds = 0;
-    b->stage_done = 1;
+    b->stage_done = STAGE_SEEDED;
     return 0;
 }
 
@@ -651,7 +673,7 @@ int ma_batch_set_seeds( ma_batch* b, const uint64_t* seed_off, const ma_seed* se
     b->nSeeds = total;
     b->nHsets = b->nHseeds = 0;
     b->socGiven = false;
-    b->stage_done = 2;
+    b->stage_done = STAGE_EXTRACTED;
     return 0;
 }
 
@@ -698,8 +720,8 @@ static int hsets_refuse( ma_batch* b, const std::string& what )
 {
     b->nHsets = b->nHseeds = 0;
     b->nJobSlots = 0;
-    if( b->stage_done > 2 )
-        b->stage_done = 2;
+    if( b->stage_done > STAGE_EXTRACTED )
+        b->stage_done = STAGE_EXTRACTED;
     return fail( "ma_batch_set_hsets: " + what );
 }
 static int hsets_check( ma_batch* b, const u64* roff, const uint64_t* hset_off, const uint64_t* hseed_off, const uint32_t* hset_soc, const ma_seed* hseeds )
@@ -789,7 +811,7 @@ int ma_batch_set_hsets( ma_batch* b, const uint64_t* hset_off, const uint64_t* h
         return 1;
     b->nHsets = nh;
     b->nHseeds = nhs;
-    b->stage_done = 3;
+    b->stage_done = STAGE_CHAINED;
     return 0;
 }
 
@@ -808,7 +830,7 @@ int ma_batch_get_soc_heap( ma_batch* b, uint64_t* n_socs, uint64_t* soc_off, ma_
 static int get_socs( ma_batch* b, int heap_layout, uint64_t* n_socs, uint64_t* soc_off, ma_soc* socs, uint64_t* seed_off,
                      ma_seed* sorted_seeds )
 {
-    if( !b || b->stage_done < 2 )
+    if( !b || b->stage_done < STAGE_EXTRACTED )
         return fail( "ma_batch_get_socs: run ma_extract_seeds_batch first" );
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads, ts = b->nSeeds + 1;
@@ -970,7 +992,7 @@ int ma_batch_counts( ma_batch* b, uint64_t* n_segments, uint64_t* n_seeds, uint6
 {
     if( ma_batch_sync( b ) )
         return 1;
-    if( b->stage_done >= 1 && b->nSegs == 0 )
+    if( b->stage_done >= STAGE_SEEDED && b->nSegs == 0 )
         b->nSegs = b->hctr[ CTR_SEG_USED ];
     if( n_segments )
         *n_segments = b->nSegs;
@@ -981,9 +1003,9 @@ int ma_batch_counts( ma_batch* b, uint64_t* n_segments, uint64_t* n_seeds, uint6
     if( n_hseeds )
         *n_hseeds = b->nHseeds;
     if( n_alignments )
-        *n_alignments = b->stage_done >= 4 ? mq_view( b ).slots : 0;
+        *n_alignments = b->stage_done >= STAGE_ALIGNED ? mq_view( b ).slots : 0;
     if( n_ops ) // exact: the ops of all alignments (the MappingQuality selection has at most as many) and of the inversion records
-        *n_ops = b->stage_done >= 4 ? b->hctr[ CTR_OPS_ALL ] + ( b->invFinal ? b->invOps : 0 ) : 0;
+        *n_ops = b->stage_done >= STAGE_ALIGNED ? b->hctr[ CTR_OPS_ALL ] + ( b->invFinal ? b->invOps : 0 ) : 0;
     if( n_aligned_reads )
         *n_aligned_reads = b->hctr[ CTR_N_ALIGNED ];
     return 0;
@@ -1007,7 +1029,7 @@ static int seg_materialise( ma_batch* b, u64 ns )
 // Downloads gather the per-read ranges (pools are in completion order) into read-order CSR arrays.
 int ma_batch_get_segments( ma_batch* b, uint64_t* seg_off, ma_segment* segs )
 {
-    if( !b || b->stage_done < 1 )
+    if( !b || b->stage_done < STAGE_SEEDED )
         return fail( "ma_batch_get_segments: stage not run" );
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )
@@ -1042,7 +1064,7 @@ int ma_batch_get_segments( ma_batch* b, uint64_t* seg_off, ma_segment* segs )
 
 int ma_batch_get_seeds( ma_batch* b, uint64_t* seed_off, ma_seed* seeds )
 {
-    if( !b || b->stage_done < 2 )
+    if( !b || b->stage_done < STAGE_EXTRACTED )
         return fail( "ma_batch_get_seeds: stage not run" );
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )
@@ -1075,7 +1097,7 @@ int ma_batch_get_seeds( ma_batch* b, uint64_t* seed_off, ma_seed* seeds )
 
 int ma_batch_get_hsets( ma_batch* b, uint64_t* hset_off, uint64_t* hseed_off, uint32_t* hset_soc, ma_seed* hseeds )
 {
-    if( !b || b->stage_done < 3 )
+    if( !b || b->stage_done < STAGE_CHAINED )
         return fail( "ma_batch_get_hsets: stage not run" );
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )
@@ -1111,7 +1133,7 @@ int ma_batch_get_hsets( ma_batch* b, uint64_t* hset_off, uint64_t* hseed_off, ui
 // async = the double-buffered form: the copies go to the I/O stream behind the pack kernels and nobody waits here
 static int get_alns( ma_batch* b, bool mq, uint64_t* aln_off, ma_alignment* alns, uint64_t* ops, bool async = false )
 {
-    if( !b || b->stage_done < 4 )
+    if( !b || b->stage_done < STAGE_ALIGNED )
         return fail( "ma_batch_get_alignments: stage not run" );
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )
@@ -1189,7 +1211,7 @@ int ma_batch_get_mapq_alignments( ma_batch* b, uint64_t* aln_off, ma_alignment* 
 
 int ma_batch_get_dp_jobs( ma_batch* b, uint64_t* n_jobs, int32_t* shapes /* 8 x i32 per job */, uint64_t cap )
 {
-    if( !b || b->stage_done < 4 )
+    if( !b || b->stage_done < STAGE_ALIGNED )
         return fail( "ma_batch_get_dp_jobs: stage not run" );
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )

@@ -406,108 +406,30 @@ class Engine
     std::shared_ptr<BatchResult> runFlat( const uint8_t* pCodes, const uint64_t* pOff, size_t n, bool bStages, bool bPairs = false,
                                           const SamText* pSam = nullptr, bool bInversions = false )
     {
-        auto pRes = freshResult( );
+        const uint32_t uiSamOptions = pSam != nullptr ? pSam->uiOptions : 0;
+        auto pRes = beginRun( bStages, bPairs, pSam != nullptr, uiSamOptions );
         BatchResult& R = *pRes;
         R.uiReads = n;
-        R.bStages = bStages;
-        R.bSocQueues = false;
-        R.bPairs = bPairs;
-        R.bSam = pSam != nullptr;
-        R.uiSamOptions = pSam != nullptr ? pSam->uiOptions : 0;
-        R.uiSamBytes = 0;
-        R.fPack = 0;
         fit( n, pOff[ n ] );
         auto t0 = std::chrono::steady_clock::now( );
         engineCheck( ma_batch_set_reads( pBatch, pCodes, pOff, n ) );
         if( pSam != nullptr )
             engineCheck( ma_batch_set_read_text( pBatch, pSam->pNames, pSam->pNameOff, pSam->pQual ) );
         R.fH2D = secondsSince( t0 );
-        t0 = std::chrono::steady_clock::now( );
-        engineCheck( ma_align_batch( pBatch ) );
-        if( bInversions )
-            engineCheck( ma_inversions_batch( pBatch ) );
-        engineCheck( ma_batch_sync( pBatch ) );
-        R.fKernels = secondsSince( t0 );
-        engineCheck( ma_batch_host_ms( pBatch, R.aStageMs ) );
-        t0 = std::chrono::steady_clock::now( );
+        t0 = runStages( R, bInversions );
         uint64_t nSeg = 0, nSeed = 0, nHset = 0, nHseed = 0, nAln = 0, nOps = 0;
         engineCheck( ma_batch_counts( pBatch, &nSeg, &nSeed, &nHset, &nHseed, &nAln, &nOps, &R.uiAlignedReads ) );
         if( bStages )
-        {
-            R.vSegOff.resize( n + 1 );
-            R.vSegs.resize( nSeg + 1 );
-            engineCheck( ma_batch_get_segments( pBatch, R.vSegOff.data( ), R.vSegs.data( ) ) );
-            R.vSeedOff.resize( n + 1 );
-            R.vSeeds.resize( nSeed + 1 );
-            engineCheck( ma_batch_get_seeds( pBatch, R.vSeedOff.data( ), R.vSeeds.data( ) ) );
-            R.vHsetOff.resize( n + 1 );
-            R.vHseedOff.resize( nHset + 1 );
-            R.vHsetSoc.resize( nHset + 1 );
-            R.vHseeds.resize( nHseed + 1 );
-            engineCheck( ma_batch_get_hsets( pBatch, R.vHsetOff.data( ), R.vHseedOff.data( ), R.vHsetSoc.data( ), R.vHseeds.data( ) ) );
-            if( bFetchSocQueues )
-            {
-                uint64_t nSocs = 0;
-                engineCheck( ma_batch_get_soc_heap( pBatch, &nSocs, nullptr, nullptr, nullptr, nullptr ) );
-                R.vSocOff.resize( n + 1 );
-                R.vSocHeap.resize( nSocs + 1 );
-                R.vSortedSeeds.resize( nSeed + 1 );
-                std::vector<uint64_t> vSeedOffAgain( n + 1 );
-                engineCheck( ma_batch_get_soc_heap( pBatch, &nSocs, R.vSocOff.data( ), R.vSocHeap.data( ), vSeedOffAgain.data( ),
-                                                    R.vSortedSeeds.data( ) ) );
-                R.bSocQueues = true;
-            }
-            R.vAlnOff.resize( n + 1 );
-            R.vAlns.resize( nAln + 1 );
-            R.vAlnOps.resize( 2 * nOps + 2 );
-            engineCheck( ma_batch_get_alignments( pBatch, R.vAlnOff.data( ), R.vAlns.data( ), R.vAlnOps.data( ) ) );
-        }
-        uint64_t* pMqOff = R.vMqOff.need( n + 1 );
+            fetchStageRecords( R, nSeg, nSeed, nHset, nHseed, nAln, nOps );
         if( bPairs && pSam != nullptr )
-        {
-            // pairing and formatting behind the alignment: the text replaces the download of records, ops, mate and other
-            uint64_t nPairs = 0;
-            R.uiPairRecords = R.uiPairOps = 0;
-            engineCheck( ma_pair_batch( pBatch ) );
-            engineCheck( ma_batch_pair_counts( pBatch, &nPairs, nullptr, nullptr, &R.uiPairsOnHost ) );
-            engineCheck( ma_pair_sam_batch( pBatch, pSam->uiOptions ) );
-            engineCheck( ma_batch_pair_sam_counts( pBatch, &nPairs, &R.uiSamBytes ) );
-            engineCheck( ma_batch_get_pair_sam( pBatch, R.vSamOff.need( nPairs + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
-            memset( R.vPairOff.need( nPairs + 1 ), 0, ( nPairs + 1 ) * sizeof( uint64_t ) ); // no pair records either (a recycled result)
-            memset( pMqOff, 0, ( n + 1 ) * sizeof( uint64_t ) ); // no records in a SAM result
-        }
+            fetchPairSam( R, uiSamOptions );
         else if( bPairs )
-        {
-            uint64_t nPairs = 0;
-            engineCheck( ma_pair_batch( pBatch ) );
-            engineCheck( ma_batch_pair_counts( pBatch, &nPairs, &R.uiPairRecords, &R.uiPairOps, &R.uiPairsOnHost ) );
-            engineCheck( ma_batch_get_pairs( pBatch, R.vPairOff.need( nPairs + 1 ), R.vPair.need( R.uiPairRecords + 1 ),
-                                             R.vPairOps.need( 2 * R.uiPairOps + 2 ), R.vPairMate.need( R.uiPairRecords + 1 ),
-                                             R.vPairOther.need( R.uiPairRecords + 1 ) ) );
-            memset( pMqOff, 0, ( n + 1 ) * sizeof( uint64_t ) ); // no per-read records in a paired result
-        }
+            fetchPairRecords( R );
         else if( pSam != nullptr )
-        {
-            // the text replaces the record download: ma_sam_batch waits once for the size, then one copy of offsets + bytes
-            engineCheck( ma_sam_batch( pBatch, pSam->uiOptions ) );
-            engineCheck( ma_batch_sam_counts( pBatch, &R.uiSamBytes ) );
-            engineCheck( ma_batch_get_sam( pBatch, R.vSamOff.need( n + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
-            memset( pMqOff, 0, ( n + 1 ) * sizeof( uint64_t ) ); // no records in a SAM result
-        }
+            fetchSam( R, uiSamOptions );
         else
-            engineCheck( ma_batch_get_mapq_alignments( pBatch, pMqOff, R.vMq.need( nAln + 1 ), R.vMqOps.need( 2 * nOps + 2 ) ) );
-        R.uiMqAlignments = n ? pMqOff[ n ] : 0;
-        R.uiMqOps = 0;
-        if( R.uiMqAlignments )
-        {
-            const ma_alignment& rLast = R.vMq[ R.uiMqAlignments - 1 ];
-            R.uiMqOps = rLast.ops_off + rLast.n_ops;
-        }
-        R.fD2H = secondsSince( t0 );
-        uiRuns++;
-        if( getenv( "MA_ENGINE_TRACE" ) ) // diagnostics: the phases of every device batch
-            fprintf( stderr, "engine %p: %zu reads, h2d %.4f s, stages %.4f s (seed %.1f extract %.1f chain %.1f dp %.1f ms), d2h %.4f s\n",
-                     (void*)this, n, R.fH2D, R.fKernels, R.aStageMs[ 0 ], R.aStageMs[ 1 ], R.aStageMs[ 2 ], R.aStageMs[ 3 ], R.fD2H );
+            fetchMqRecords( R, nAln, nOps );
+        endRun( R, t0, [ & ]( char* p, size_t c ) { snprintf( p, c, "%zu reads, h2d", n ); } );
         return pRes;
     }
     // A FASTQ / FASTA text instead of reads (ma_batch_set_reads_text: the device parses it, strict form only) through all stages to
@@ -533,49 +455,6 @@ class Engine
             return ma_batch_set_reads_bgzf( pBatch, pHead, uiHeadBytes, pMembers, uiMemberBytes, uiDrop, pReads );
         } );
     }
-    // uiBytes of text that rSet puts into pBatch (it returns the library's status and the reads it found)
-    template <typename SET> std::shared_ptr<BatchResult> runTextBy( size_t uiBytes, uint32_t uiSamOptions, bool bInversions, SET&& rSet )
-    {
-        auto pRes = freshResult( );
-        BatchResult& R = *pRes;
-        R.bStages = R.bSocQueues = R.bPairs = false;
-        R.bSam = true;
-        R.uiSamOptions = uiSamOptions;
-        R.uiSamBytes = 0;
-        R.fPack = 0;
-        fit( std::max<uint64_t>( uiCapReads, uiBytes / 32 ), std::max<uint64_t>( uiCapBases, uiBytes ) );
-        auto t0 = std::chrono::steady_clock::now( );
-        uint64_t n = 0;
-        if( rSet( &n ) != 0 )
-        {
-            if( n == 0 ) // (only "batch capacity exceeded" reports the reads of the text)
-                engineCheck( 1 );
-            fit( n, uiBytes );
-            engineCheck( rSet( &n ) );
-        }
-        R.uiReads = n;
-        R.fH2D = secondsSince( t0 );
-        t0 = std::chrono::steady_clock::now( );
-        engineCheck( ma_align_batch( pBatch ) );
-        if( bInversions )
-            engineCheck( ma_inversions_batch( pBatch ) );
-        engineCheck( ma_batch_sync( pBatch ) );
-        R.fKernels = secondsSince( t0 );
-        engineCheck( ma_batch_host_ms( pBatch, R.aStageMs ) );
-        t0 = std::chrono::steady_clock::now( );
-        engineCheck( ma_batch_counts( pBatch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &R.uiAlignedReads ) );
-        engineCheck( ma_sam_batch( pBatch, uiSamOptions ) );
-        engineCheck( ma_batch_sam_counts( pBatch, &R.uiSamBytes ) );
-        engineCheck( ma_batch_get_sam( pBatch, R.vSamOff.need( n + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
-        memset( R.vMqOff.need( n + 1 ), 0, ( n + 1 ) * sizeof( uint64_t ) ); // no records in a SAM result
-        R.uiMqAlignments = R.uiMqOps = 0;
-        R.fD2H = secondsSince( t0 );
-        uiRuns++;
-        if( getenv( "MA_ENGINE_TRACE" ) ) // diagnostics: the phases of every device batch (h2d: upload, parse and its two read-backs)
-            fprintf( stderr, "engine %p: %zu bytes of text, %llu reads, h2d+parse %.4f s, stages %.4f s (seed %.1f extract %.1f chain %.1f dp %.1f ms), d2h %.4f s\n",
-                     (void*)this, uiBytes, (unsigned long long)n, R.fH2D, R.fKernels, R.aStageMs[ 0 ], R.aStageMs[ 1 ], R.aStageMs[ 2 ], R.aStageMs[ 3 ], R.fD2H );
-        return pRes;
-    }
     // runText for mate pairs: the texts of the two read files (ma_batch_set_mates_text: the device parses both, interleaves the
     // mates and, with bRevCompMates, reverse-complements every second one) through all stages, the pairing and the pairs'
     // formatting: the result of runFlat's paired SAM mode (bPairs, bSam, vSamOff per PAIR, vSam; uiReads = 2 x the pairs the device
@@ -583,52 +462,171 @@ class Engine
     std::shared_ptr<BatchResult> runMatesText( const char* pText1, size_t uiBytes1, const char* pText2, size_t uiBytes2, bool bRevCompMates,
                                                uint32_t uiSamOptions, bool bInversions = false )
     {
+        auto pRes = beginRun( false, true, true, uiSamOptions );
+        BatchResult& R = *pRes;
+        auto t0 = std::chrono::steady_clock::now( );
+        uint64_t aConsumed[ 2 ];
+        const uint64_t nPairs = setText( uiBytes1 + uiBytes2, 2, [ & ]( uint64_t* pPairs ) {
+            return ma_batch_set_mates_text( pBatch, pText1, uiBytes1, pText2, uiBytes2, bRevCompMates ? 1 : 0, pPairs, aConsumed );
+        } );
+        R.uiReads = 2 * nPairs;
+        R.fH2D = secondsSince( t0 );
+        t0 = runStages( R, bInversions );
+        engineCheck( ma_batch_counts( pBatch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &R.uiAlignedReads ) );
+        fetchPairSam( R, uiSamOptions );
+        endRun( R, t0, [ & ]( char* p, size_t c ) { snprintf( p, c, "%zu + %zu bytes of mate text, %llu pairs, h2d+parse", uiBytes1, uiBytes2, (unsigned long long)nPairs ); } );
+        return pRes;
+    }
+
+  private:
+    // uiBytes of text that rSet puts into pBatch (it returns the library's status and the reads it found)
+    template <typename SET> std::shared_ptr<BatchResult> runTextBy( size_t uiBytes, uint32_t uiSamOptions, bool bInversions, SET&& rSet )
+    {
+        auto pRes = beginRun( false, false, true, uiSamOptions );
+        BatchResult& R = *pRes;
+        auto t0 = std::chrono::steady_clock::now( );
+        R.uiReads = setText( uiBytes, 1, rSet );
+        R.fH2D = secondsSince( t0 );
+        t0 = runStages( R, bInversions );
+        engineCheck( ma_batch_counts( pBatch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &R.uiAlignedReads ) );
+        fetchSam( R, uiSamOptions );
+        endRun( R, t0, [ & ]( char* p, size_t c ) { snprintf( p, c, "%zu bytes of text, %llu reads, h2d+parse", uiBytes, (unsigned long long)R.uiReads ); } );
+        return pRes;
+    }
+
+    // ---- the pieces of a run: beginRun, the form's input, runStages, the form's output (fetch...), endRun ----
+    std::shared_ptr<BatchResult> beginRun( bool bStages, bool bPairs, bool bSam, uint32_t uiSamOptions )
+    {
         auto pRes = freshResult( );
         BatchResult& R = *pRes;
-        R.bStages = R.bSocQueues = false;
-        R.bPairs = R.bSam = true;
+        R.bStages = bStages, R.bPairs = bPairs, R.bSam = bSam;
+        R.bSocQueues = false;
         R.uiSamOptions = uiSamOptions;
         R.uiSamBytes = 0;
         R.fPack = 0;
-        const size_t uiBytes = uiBytes1 + uiBytes2;
-        fit( std::max<uint64_t>( uiCapReads, uiBytes / 32 ), std::max<uint64_t>( uiCapBases, uiBytes ) );
-        auto t0 = std::chrono::steady_clock::now( );
-        uint64_t nPairs = 0, aConsumed[ 2 ];
-        if( ma_batch_set_mates_text( pBatch, pText1, uiBytes1, pText2, uiBytes2, bRevCompMates ? 1 : 0, &nPairs, aConsumed ) != 0 )
+        return pRes;
+    }
+    // rLead writes the front of the MA_ENGINE_TRACE line, up to and including the name of the first phase (h2d+parse: the upload of
+    // a text, its parse and the parse's two read-backs)
+    template <typename LEAD> void endRun( BatchResult& R, const std::chrono::steady_clock::time_point& tD2H, LEAD&& rLead )
+    {
+        R.fD2H = secondsSince( tD2H );
+        uiRuns++;
+        if( getenv( "MA_ENGINE_TRACE" ) ) // diagnostics: the phases of every device batch
         {
-            if( nPairs == 0 ) // (only "batch capacity exceeded" reports the pairs of the texts)
-                engineCheck( 1 );
-            fit( 2 * nPairs, uiBytes );
-            engineCheck( ma_batch_set_mates_text( pBatch, pText1, uiBytes1, pText2, uiBytes2, bRevCompMates ? 1 : 0, &nPairs, aConsumed ) );
+            char aLead[ 160 ];
+            rLead( aLead, sizeof( aLead ) );
+            fprintf( stderr, "engine %p: %s %.4f s, stages %.4f s (seed %.1f extract %.1f chain %.1f dp %.1f ms), d2h %.4f s\n", (void*)this, aLead,
+                     R.fH2D, R.fKernels, R.aStageMs[ 0 ], R.aStageMs[ 1 ], R.aStageMs[ 2 ], R.aStageMs[ 3 ], R.fD2H );
         }
-        const uint64_t n = 2 * nPairs;
-        R.uiReads = n;
-        R.fH2D = secondsSince( t0 );
-        t0 = std::chrono::steady_clock::now( );
+    }
+    // A text form's input: the device batch sized by the text, then rSet, which returns the library's status and the count it
+    // found (reads, or pairs: uiReadsPerCount reads each).  Only "batch capacity exceeded" fails WITH a count: the batch is then
+    // made to hold it and rSet runs again; every other failure throws the library's message.
+    template <typename SET> uint64_t setText( size_t uiBytes, uint64_t uiReadsPerCount, SET&& rSet )
+    {
+        fit( std::max<uint64_t>( uiCapReads, uiBytes / 32 ), std::max<uint64_t>( uiCapBases, uiBytes ) );
+        uint64_t n = 0;
+        if( rSet( &n ) != 0 )
+        {
+            if( n == 0 )
+                engineCheck( 1 );
+            fit( uiReadsPerCount * n, uiBytes );
+            engineCheck( rSet( &n ) );
+        }
+        return n;
+    }
+    // the device stages of every form; returns the start of the download phase
+    std::chrono::steady_clock::time_point runStages( BatchResult& R, bool bInversions )
+    {
+        const auto t0 = std::chrono::steady_clock::now( );
         engineCheck( ma_align_batch( pBatch ) );
         if( bInversions )
             engineCheck( ma_inversions_batch( pBatch ) );
         engineCheck( ma_batch_sync( pBatch ) );
         R.fKernels = secondsSince( t0 );
         engineCheck( ma_batch_host_ms( pBatch, R.aStageMs ) );
-        t0 = std::chrono::steady_clock::now( );
-        engineCheck( ma_batch_counts( pBatch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &R.uiAlignedReads ) );
+        return std::chrono::steady_clock::now( );
+    }
+    // no per-read records in this result (pairs, either text): a recycled result may hold old offsets
+    void noMqRecords( BatchResult& R )
+    {
+        memset( R.vMqOff.need( R.uiReads + 1 ), 0, ( R.uiReads + 1 ) * sizeof( uint64_t ) );
+        R.uiMqAlignments = R.uiMqOps = 0;
+    }
+    void fetchStageRecords( BatchResult& R, uint64_t nSeg, uint64_t nSeed, uint64_t nHset, uint64_t nHseed, uint64_t nAln, uint64_t nOps )
+    {
+        const size_t n = R.uiReads;
+        R.vSegOff.resize( n + 1 );
+        R.vSegs.resize( nSeg + 1 );
+        engineCheck( ma_batch_get_segments( pBatch, R.vSegOff.data( ), R.vSegs.data( ) ) );
+        R.vSeedOff.resize( n + 1 );
+        R.vSeeds.resize( nSeed + 1 );
+        engineCheck( ma_batch_get_seeds( pBatch, R.vSeedOff.data( ), R.vSeeds.data( ) ) );
+        R.vHsetOff.resize( n + 1 );
+        R.vHseedOff.resize( nHset + 1 );
+        R.vHsetSoc.resize( nHset + 1 );
+        R.vHseeds.resize( nHseed + 1 );
+        engineCheck( ma_batch_get_hsets( pBatch, R.vHsetOff.data( ), R.vHseedOff.data( ), R.vHsetSoc.data( ), R.vHseeds.data( ) ) );
+        if( bFetchSocQueues )
+        {
+            uint64_t nSocs = 0;
+            engineCheck( ma_batch_get_soc_heap( pBatch, &nSocs, nullptr, nullptr, nullptr, nullptr ) );
+            R.vSocOff.resize( n + 1 );
+            R.vSocHeap.resize( nSocs + 1 );
+            R.vSortedSeeds.resize( nSeed + 1 );
+            std::vector<uint64_t> vSeedOffAgain( n + 1 );
+            engineCheck( ma_batch_get_soc_heap( pBatch, &nSocs, R.vSocOff.data( ), R.vSocHeap.data( ), vSeedOffAgain.data( ),
+                                                R.vSortedSeeds.data( ) ) );
+            R.bSocQueues = true;
+        }
+        R.vAlnOff.resize( n + 1 );
+        R.vAlns.resize( nAln + 1 );
+        R.vAlnOps.resize( 2 * nOps + 2 );
+        engineCheck( ma_batch_get_alignments( pBatch, R.vAlnOff.data( ), R.vAlns.data( ), R.vAlnOps.data( ) ) );
+    }
+    void fetchMqRecords( BatchResult& R, uint64_t nAln, uint64_t nOps )
+    {
+        uint64_t* pMqOff = R.vMqOff.need( R.uiReads + 1 );
+        engineCheck( ma_batch_get_mapq_alignments( pBatch, pMqOff, R.vMq.need( nAln + 1 ), R.vMqOps.need( 2 * nOps + 2 ) ) );
+        R.uiMqAlignments = R.uiReads ? pMqOff[ R.uiReads ] : 0;
+        R.uiMqOps = 0;
+        if( R.uiMqAlignments )
+        {
+            const ma_alignment& rLast = R.vMq[ R.uiMqAlignments - 1 ];
+            R.uiMqOps = rLast.ops_off + rLast.n_ops;
+        }
+    }
+    void fetchPairRecords( BatchResult& R )
+    {
+        uint64_t nPairs = 0;
+        engineCheck( ma_pair_batch( pBatch ) );
+        engineCheck( ma_batch_pair_counts( pBatch, &nPairs, &R.uiPairRecords, &R.uiPairOps, &R.uiPairsOnHost ) );
+        engineCheck( ma_batch_get_pairs( pBatch, R.vPairOff.need( nPairs + 1 ), R.vPair.need( R.uiPairRecords + 1 ),
+                                         R.vPairOps.need( 2 * R.uiPairOps + 2 ), R.vPairMate.need( R.uiPairRecords + 1 ),
+                                         R.vPairOther.need( R.uiPairRecords + 1 ) ) );
+        noMqRecords( R );
+    }
+    // the text replaces the record download: ma_sam_batch waits once for the size, then one copy of offsets + bytes
+    void fetchSam( BatchResult& R, uint32_t uiSamOptions )
+    {
+        engineCheck( ma_sam_batch( pBatch, uiSamOptions ) );
+        engineCheck( ma_batch_sam_counts( pBatch, &R.uiSamBytes ) );
+        engineCheck( ma_batch_get_sam( pBatch, R.vSamOff.need( R.uiReads + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
+        noMqRecords( R );
+    }
+    // pairing and formatting behind the alignment: the text replaces the download of records, ops, mate and other
+    void fetchPairSam( BatchResult& R, uint32_t uiSamOptions )
+    {
+        uint64_t nPairs = 0;
         R.uiPairRecords = R.uiPairOps = 0;
         engineCheck( ma_pair_batch( pBatch ) );
         engineCheck( ma_batch_pair_counts( pBatch, &nPairs, nullptr, nullptr, &R.uiPairsOnHost ) );
         engineCheck( ma_pair_sam_batch( pBatch, uiSamOptions ) );
         engineCheck( ma_batch_pair_sam_counts( pBatch, &nPairs, &R.uiSamBytes ) );
         engineCheck( ma_batch_get_pair_sam( pBatch, R.vSamOff.need( nPairs + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
-        memset( R.vPairOff.need( nPairs + 1 ), 0, ( nPairs + 1 ) * sizeof( uint64_t ) ); // no pair records in a SAM result
-        memset( R.vMqOff.need( n + 1 ), 0, ( n + 1 ) * sizeof( uint64_t ) ); // no per-read records either
-        R.uiMqAlignments = R.uiMqOps = 0;
-        R.fD2H = secondsSince( t0 );
-        uiRuns++;
-        if( getenv( "MA_ENGINE_TRACE" ) ) // diagnostics: the phases of every device batch (h2d: upload, parse and its two read-backs)
-            fprintf( stderr, "engine %p: %zu + %zu bytes of mate text, %llu pairs, h2d+parse %.4f s, stages %.4f s (seed %.1f extract %.1f chain %.1f dp %.1f ms), d2h %.4f s\n",
-                     (void*)this, uiBytes1, uiBytes2, (unsigned long long)nPairs, R.fH2D, R.fKernels, R.aStageMs[ 0 ], R.aStageMs[ 1 ], R.aStageMs[ 2 ],
-                     R.aStageMs[ 3 ], R.fD2H );
-        return pRes;
+        memset( R.vPairOff.need( nPairs + 1 ), 0, ( nPairs + 1 ) * sizeof( uint64_t ) ); // no pair records either (a recycled result)
+        noMqRecords( R );
     }
 };
 

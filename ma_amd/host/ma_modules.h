@@ -1551,6 +1551,24 @@ class BatchAligner
         std::lock_guard<std::mutex> xGuard( xEngineMutex );
         vIdleEngines.emplace_back( pIndex, std::move( pEngine ) );
     }
+    // One device batch on an engine of pIndex: rRun( engine ) gives its result, and the engine goes back to the idle ones whether rRun
+    // returns or throws.  (alignRangeOn and warmUp hand their engines back themselves: the order decides which a later call reuses.)
+    template <typename RUN> std::shared_ptr<AlignedBatch> withEngine( const ma_index* pIndex, RUN&& rRun ) const
+    {
+        auto pEngine = takeEngine( pIndex );
+        auto pRet = std::make_shared<AlignedBatch>( );
+        try
+        {
+            pRet->pResult = rRun( *pEngine );
+        }
+        catch( ... )
+        {
+            giveEngine( pIndex, std::move( pEngine ) );
+            throw;
+        }
+        giveEngine( pIndex, std::move( pEngine ) );
+        return pRet;
+    }
 
   public:
     typedef libMS::ContainerVector<std::shared_ptr<AlignmentVector>> TP_RESULT;
@@ -1879,19 +1897,9 @@ class BatchAligner
     // (the contigs of pIndex are named already)
     std::shared_ptr<AlignedBatch> executeTextSamOn( const ma_index* pIndex, std::shared_ptr<TextBatch> pText )
     {
-        auto pEngine = takeEngine( pIndex );
-        auto pRet = std::make_shared<AlignedBatch>( );
-        try
-        {
-            pRet->pResult = pEngine->runText( pText->sText.data( ), pText->sText.size( ), samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
-        }
-        catch( ... )
-        {
-            giveEngine( pIndex, std::move( pEngine ) );
-            throw;
-        }
-        giveEngine( pIndex, std::move( pEngine ) );
-        return pRet;
+        return withEngine( pIndex, [ & ]( detail::Engine& rEngine ) {
+            return rEngine.runText( pText->sText.data( ), pText->sText.size( ), samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
+        } );
     }
 
     // executeTextSam for a batch of a BGZF-compressed file (BatchBgzfReader): the device inflates the members, one per lane, into
@@ -1906,20 +1914,10 @@ class BatchAligner
     // (the contigs of pIndex are named already)
     std::shared_ptr<AlignedBatch> executeBgzfSamOn( const ma_index* pIndex, std::shared_ptr<BgzfBatch> pBatch )
     {
-        auto pEngine = takeEngine( pIndex );
-        auto pRet = std::make_shared<AlignedBatch>( );
-        try
-        {
-            pRet->pResult = pEngine->runBgzf( pBatch->sHead.data( ), pBatch->sHead.size( ), pBatch->sMembers.data( ), pBatch->sMembers.size( ),
-                                              pBatch->uiDrop, samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
-        }
-        catch( ... )
-        {
-            giveEngine( pIndex, std::move( pEngine ) );
-            throw;
-        }
-        giveEngine( pIndex, std::move( pEngine ) );
-        return pRet;
+        return withEngine( pIndex, [ & ]( detail::Engine& rEngine ) {
+            return rEngine.runBgzf( pBatch->sHead.data( ), pBatch->sHead.size( ), pBatch->sMembers.data( ), pBatch->sMembers.size( ), pBatch->uiDrop,
+                                    samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
+        } );
     }
 
     // Paired mode (setUpCompGraphPaired, export.cpp:130-202) for a batch: vMates holds the mates of pair k at 2k and
@@ -2014,20 +2012,10 @@ class BatchAligner
         if( !servesPairSam( ) )
             throw std::runtime_error( "BatchAligner::executePairedTextSam: not with the NGMLR tag emulation (use executePairedFlat and "
                                       "BatchPairedFileWriter)" );
-        auto pEngine = takeEngine( pIndex );
-        auto pRet = std::make_shared<AlignedBatch>( );
-        try
-        {
-            pRet->pResult = pEngine->runMatesText( pTexts->sText1.data( ), pTexts->sText1.size( ), pTexts->sText2.data( ), pTexts->sText2.size( ),
-                                                   xParams.bRevCompPairedReadMates, samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
-        }
-        catch( ... )
-        {
-            giveEngine( pIndex, std::move( pEngine ) );
-            throw;
-        }
-        giveEngine( pIndex, std::move( pEngine ) );
-        return pRet;
+        return withEngine( pIndex, [ & ]( detail::Engine& rEngine ) {
+            return rEngine.runMatesText( pTexts->sText1.data( ), pTexts->sText1.size( ), pTexts->sText2.data( ), pTexts->sText2.size( ),
+                                         xParams.bRevCompPairedReadMates, samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
+        } );
     }
 
   private:

@@ -1,0 +1,186 @@
+"""What a batch forgets, and when (ma_amd/csrc/pipeline.hip: batch_reads_changed, batch_results_changed).  Every form of "this
+batch has new reads" -- the host arrays, the staged upload, caller-owned device arrays, a text, a refused text, mate texts, BGZF
+members -- puts a batch that has been through every stage back to the start: no stage output, no SAM text, no pairs, no names
+unless the form brings them, and the next pass computes what a fresh batch computes.  Every call that changes the alignment
+lists (ma_dp_batch, ma_batch_set_alignments, ma_inversions_batch) drops both SAM texts and the pairs; ma_pair_batch drops only
+the pairs' text."""
+import numpy as np
+import pytest
+
+from ma_testlib import rand_genome, revcomp, sample_reads
+from test_gpu_bgzf import END, member
+
+pytestmark = pytest.mark.gpu
+NO_READS = dict(reads=0, bases=0, name_bytes=0, has_qual=0)
+
+
+def params():
+    import ma_amd
+    P = ma_amd.Params.preset("default")
+    P.srand_seed = 1
+    return P
+
+
+def names_of(reads):
+    return ["r%d" % i for i in range(len(reads))]
+
+
+def fastq(reads, names=None):
+    names = names or names_of(reads)
+    return b"".join(("@%s\n%s\n+\n%s\n" % (nm, "".join("ACGT"[int(x)] for x in r), "I" * len(r))).encode() for nm, r in zip(names, reads))
+
+
+def full_pass(b, reads, text_is_set):
+    """every stage and both texts; returns the MappingQuality records (after the inversions) as bytes"""
+    b.align()
+    if not text_is_set:
+        b.set_read_text(names_of(reads))
+    b.inversions()
+    b.pair()
+    assert b.sam() >= 0 and b.pair_sam() >= 0
+    b.sam_bytes(), b.pair_sam_bytes(), b.pair_counts()  # all there
+    return tuple(x.tobytes() for x in b.mapq_alignments())
+
+
+@pytest.fixture(scope="module")
+def world(gpu_device):
+    import ma_amd
+    g = rand_genome(41, [20000])
+    reads = sample_reads(g, 8, 100, 42, sub=0.01)  # the reads of the pass before each form, as 4 pairs
+    fresh = sample_reads(g, 8, 100, 43, sub=0.01)  # the reads each form brings
+    idx = ma_amd.Index.build(g)
+    idx.set_contig_names(["chr1"])
+    b = ma_amd.Batch(idx, params(), 64, 8192)
+    want = {}
+    for key, rs in (("fresh", fresh), ("none", [])):  # what a fresh batch computes for them
+        f = ma_amd.Batch(idx, params(), 64, 8192)
+        f.set_reads(rs)
+        want[key] = full_pass(f, rs, False)
+        f.close()
+    yield b, reads, fresh, want
+    b.close()
+    idx.close()
+
+
+def flat(reads):
+    off = np.zeros(len(reads) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(r) for r in reads])
+    return np.ascontiguousarray(np.concatenate(reads + [np.zeros(1, dtype=np.uint8)])), off
+
+
+def by_set_reads(b, reads):
+    b.set_reads(reads)
+
+
+def by_staged_reads(b, reads):
+    import ma_amd
+    cat, off = flat(reads)
+    codes, offs = ma_amd.HostArray(len(cat), np.uint8), ma_amd.HostArray(len(off), np.uint64)
+    codes.a[:], offs.a[:] = cat, off
+    b.stage_reads_flat(codes.ptr, offs.ptr, len(reads))
+    b.use_staged_reads()  # (waits for the upload: the host arrays are free again)
+    codes.close()
+    offs.close()
+
+
+def by_set_reads_device(b, reads):
+    import torch
+    cat, off = flat(reads)
+    b.keep = (torch.from_numpy(cat).cuda(), torch.from_numpy(off.astype(np.int64)).cuda())  # the caller owns them while they are set
+    b.set_reads_device(b.keep[0].data_ptr(), b.keep[1].data_ptr(), len(reads), int(off[-1]))
+
+
+def by_text(b, reads):
+    assert b.set_reads_text(fastq(reads)) == len(reads)
+
+
+def by_refused_text(b, reads):
+    import ma_amd
+    with pytest.raises(ma_amd.MaError, match="ma_batch_set_reads_text: line 1"):
+        b.set_reads_text(b"x")
+
+
+def by_mates_text(b, reads):
+    nm = names_of(reads)
+    n, _ = b.set_mates_text(fastq(reads[0::2], nm[0::2]), fastq([revcomp(r) for r in reads[1::2]], nm[1::2]))
+    assert 2 * n == len(reads)
+
+
+def by_bgzf(b, reads):
+    text = fastq(reads)
+    assert b.set_reads_bgzf(member(text[:700]) + member(text[700:]) + END) == len(reads)
+
+
+FORMS = [("set_reads", by_set_reads, "array"), ("stage_reads_flat + use_staged_reads", by_staged_reads, "array"),
+         ("set_reads_device", by_set_reads_device, "array"), ("set_reads_text", by_text, "text"),
+         ("set_reads_text, refused", by_refused_text, "refused"), ("set_mates_text", by_mates_text, "text"),
+         ("set_reads_bgzf", by_bgzf, "text")]
+
+
+@pytest.mark.parametrize("name,form,kind", FORMS, ids=[f[0] for f in FORMS])
+def test_new_reads_put_the_batch_back_to_the_start(world, name, form, kind):
+    """after a complete pass (align, names, inversions, pairs, both texts) each form of new reads leaves: dp() without chains, no
+    SAM text, no pairs' text, no pairs; read_counts() of the new reads with names only where the form brings them; and a pass
+    that computes the MappingQuality records of a fresh batch with the same reads, byte for byte"""
+    import ma_amd
+    b, reads, fresh, want = world
+    b.set_reads(reads)
+    full_pass(b, reads, False)
+    form(b, fresh)
+    for call, message in ((b.dp, "ma_dp_batch: run ma_chain_batch first"), (b.sam_bytes, "ma_batch_sam_counts: run ma_sam_batch first"),
+                          (b.pair_sam_bytes, "ma_batch_pair_sam_counts: run ma_pair_sam_batch first"),
+                          (b.pair_counts, "ma_batch_pair_counts: run ma_pair_batch first")):
+        with pytest.raises(ma_amd.MaError) as e:
+            call()
+        assert str(e.value) == message, name
+    n_bases = sum(len(r) for r in fresh)
+    if kind == "array":
+        assert b.read_counts() == dict(reads=len(fresh), bases=n_bases, name_bytes=0, has_qual=0)
+    elif kind == "text":
+        assert b.read_counts() == dict(reads=len(fresh), bases=n_bases, name_bytes=sum(len(x) for x in names_of(fresh)), has_qual=1)
+        assert b.read_text()[0] == [x.encode() for x in names_of(fresh)]
+    else:
+        assert b.read_counts() == NO_READS
+    after = [] if kind == "refused" else fresh
+    assert full_pass(b, after, kind == "text") == want["none" if kind == "refused" else "fresh"]
+    b.keep = None
+
+
+def gone(call, message):
+    import ma_amd
+    with pytest.raises(ma_amd.MaError) as e:
+        call()
+    assert str(e.value) == message
+
+
+def test_changed_lists_drop_the_texts_and_the_pairs(world):
+    """a second dp(), set_alignments with the records just downloaded, and inversions() each drop both SAM texts and the pairs
+    of the lists before; pair() again drops only the pairs' text -- the single-end text does not read the picks and stays"""
+    b, reads, fresh, want = world
+    changes = [("dp", lambda: b.dp()), ("set_alignments", lambda: b.set_alignments(*b.alignments())), ("inversions", lambda: b.inversions())]
+    for name, change in changes:
+        b.set_reads(reads)
+        full_pass(b, reads, False)
+        change()
+        gone(b.sam_bytes, "ma_batch_sam_counts: run ma_sam_batch first")
+        gone(b.pair_sam_bytes, "ma_batch_pair_sam_counts: run ma_pair_sam_batch first")
+        gone(b.pair_counts, "ma_batch_pair_counts: run ma_pair_batch first")
+    b.set_reads(reads)
+    full_pass(b, reads, False)
+    single = b.sam_bytes()
+    b.pair()  # the one asymmetry
+    gone(b.pair_sam_bytes, "ma_batch_pair_sam_counts: run ma_pair_sam_batch first")
+    assert b.sam_bytes() == single > 0
+    assert b.pair_counts()["pairs"] == len(reads) // 2
+
+
+def test_empty_input(world):
+    """an empty text and no BGZF members at all: a batch of zero reads, which align() takes"""
+    b, reads, fresh, want = world
+    for empty in (lambda: b.set_reads_text(b""), lambda: b.set_reads_bgzf(b"")):
+        b.set_reads(reads)
+        full_pass(b, reads, False)
+        assert empty() == 0
+        assert b.read_counts() == NO_READS
+        b.align()
+        b.sync()
