@@ -2,7 +2,7 @@
 // `maCMD -x <genome> -i <reads> [-m <mates>] -o <out.sam> -p <preset>` needs from the hot path.  Not a re-implementation
 // of cmdMa.cpp: no option parsing beyond the four arguments, no thread pool (the batches are the parallelism).
 //
-//   ma_align [--host-sam] [--ngmlr-tags] [--text-input] <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam|stdout> [preset] [mates.fa|fq[.gz]]
+//   ma_align [--host-sam] [--ngmlr-tags] [--text-input] [--bgzf-output] <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam[.gz]|stdout> [preset] [mates.fa|fq[.gz]]
 //
 // Single-end input is printed on the device (BatchAligner::executeFlatSam: the SAM text is what comes down) whenever the
 // options are ones the device serves -- with --ngmlr-tags ("Emulate NGMLR's tag output") and with "Detect Small Inversions"
@@ -15,6 +15,10 @@
 // (BatchAligner::executePairedTextSam, ma_batch_set_mates_text).  A single-end reads file that bgzip wrote (BGZF, told by its first
 // bytes) goes up compressed: BatchBgzfReader cuts it at member borders and the device inflates it in front of its parser
 // (BatchAligner::executeBgzfSam, ma_batch_set_reads_bgzf); plain gzip is not served with the flag.  The device serves four-line FASTQ and plain FASTA only; any other file ends the program with the library's message, which names the line -- there is no silent fallback.
+// With --bgzf-output, or an output name that ends in .gz, the output is BGZF (SamOptions::bBgzf; what bgzip writes: samtools, zcat
+// and gzip read it): on the device paths every batch's text is deflated where it was printed (ma_sam_bgzf_batch) and only its
+// members come down; the header, and with --host-sam every byte, goes through the host statement of the same rules
+// (ma_bgzf::deflateHost).  The file inflates to the bytes of the run without the option.
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_align.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
@@ -25,18 +29,22 @@ typedef libMS::ContainerVector<std::shared_ptr<NucSeq>> ReadVec;
 
 int main( int argc, char** argv )
 {
-    bool bHostSam = false, bNgmlrTags = false, bTextInput = false;
+    bool bHostSam = false, bNgmlrTags = false, bTextInput = false, bBgzfOutput = false;
     for( int i = 1; i < argc; i++ )
-        if( std::string( argv[ i ] ) == "--host-sam" || std::string( argv[ i ] ) == "--ngmlr-tags" || std::string( argv[ i ] ) == "--text-input" )
+        if( std::string( argv[ i ] ) == "--host-sam" || std::string( argv[ i ] ) == "--ngmlr-tags" || std::string( argv[ i ] ) == "--text-input" ||
+            std::string( argv[ i ] ) == "--bgzf-output" )
         {
-            ( std::string( argv[ i ] ) == "--host-sam" ? bHostSam : std::string( argv[ i ] ) == "--ngmlr-tags" ? bNgmlrTags : bTextInput ) = true;
+            ( std::string( argv[ i ] ) == "--host-sam"     ? bHostSam
+              : std::string( argv[ i ] ) == "--ngmlr-tags" ? bNgmlrTags
+              : std::string( argv[ i ] ) == "--text-input" ? bTextInput
+                                                           : bBgzfOutput ) = true;
             for( int j = i; j + 1 < argc; j++ )
                 argv[ j ] = argv[ j + 1 ];
             argc--, i--;
         }
     if( argc < 4 )
     {
-        fprintf( stderr, "usage: ma_align [--host-sam] [--ngmlr-tags] [--text-input] <genome.fa | index prefix> <reads> <out.sam|stdout> [preset] [mates]\n" );
+        fprintf( stderr, "usage: ma_align [--host-sam] [--ngmlr-tags] [--text-input] [--bgzf-output] <genome.fa | index prefix> <reads> <out.sam[.gz]|stdout> [preset] [mates]\n" );
         return 2;
     }
     try
@@ -44,6 +52,8 @@ int main( int argc, char** argv )
         ParameterSetManager xParams;
         xParams.setSelected( argc >= 5 ? argv[ 4 ] : ( argc >= 6 ? "illuminapaired" : "default" ) );
         xParams.xSam.bEmulateNgmlrTags = bNgmlrTags;
+        const std::string sOutName = argv[ 3 ];
+        xParams.xSam.bBgzf = bBgzfOutput || ( sOutName.size( ) >= 3 && sOutName.compare( sOutName.size( ) - 3, 3, ".gz" ) == 0 );
         const bool bPaired = argc >= 6;
         if( bTextInput && bHostSam )
             throw std::runtime_error( "--text-input serves input printed on the device (not with --host-sam: the host's writers need the reads)" );

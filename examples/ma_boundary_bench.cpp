@@ -9,7 +9,7 @@
 // Prints one JSON line.  bench.py runs it after its timed regions and reports it as config.boundary (never as `value`).
 //
 //   ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads]
-// (further legs, one per run: paired, pairtext, sam, sam-tags, text, bgzf, inversions -- see the comments at their blocks in main)
+// (further legs, one per run: paired, pairtext, sam, sam-tags, sam-bgzf, text, bgzf, inversions -- see the comments at their blocks in main)
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_boundary_bench.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
@@ -238,7 +238,7 @@ int main( int argc, char** argv )
 {
     if( argc < 6 )
     {
-        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | pairtext [repeats] | sam [repeats] | sam-tags [repeats] | text [repeats] | bgzf [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
+        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | pairtext [repeats] | sam [repeats] | sam-tags [repeats] | sam-bgzf [repeats] | text [repeats] | bgzf [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
         return 2;
     }
     try
@@ -249,7 +249,7 @@ int main( int argc, char** argv )
         maCheck( ma_set_device( atoi( argv[ 5 ] ) ) );
         maCheck( ma_host_bind_thread( atoi( argv[ 5 ] ), 0, nullptr ) ); // this thread and all it starts: the CPUs next to the GPU
         const unsigned uiHw = std::max( 1u, std::thread::hardware_concurrency( ) );
-        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "pairtext" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "text" ) && strcmp( argv[ 6 ], "bgzf" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
+        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "pairtext" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "sam-bgzf" ) && strcmp( argv[ 6 ], "text" ) && strcmp( argv[ 6 ], "bgzf" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         double t0 = now( );
@@ -908,6 +908,121 @@ int main( int argc, char** argv )
                     n, uiLen, iRepeats, uiBatchReads, uiWorkers, list( vH ).c_str( ), list( vD ).c_str( ), sFastq.size( ), (size_t)uiFileBytes,
                     bEqual ? "true" : "false" );
             return bEqual ? 0 : 1;
+        }
+        if( argc >= 7 && !strcmp( argv[ 6 ], "sam-bgzf" ) )
+        {
+            // ---- the compressed SAM leg: n single-end reads host to a FILE through BatchAligner::executeFlatSam + BatchFileWriter,
+            // (a) plain: the text comes down and is written as it is; (b) SamOptions::bBgzf on aligner and writer: the text is
+            // deflated on the device (ma_sam_bgzf_batch) and only its members come down and are written; (c) bBgzf on the writer
+            // alone: the text comes down and up to 16 writer threads deflate it with the host statement of the same rules
+            // (ma_bgzf::deflateHost) -- what a caller had before.  Alternating, <repeats> times each after one warm-up of each.
+            // One more device run with ma_batch_enable_timing on an engine of its own gives the kernels' own time per batch.
+            const int iRepeats = argc >= 8 ? std::max( 1, atoi( argv[ 7 ] ) ) : 5;
+            ParameterSetManager xPacked = xParams;
+            xPacked.xSam.bBgzf = true;
+            BatchAligner xPlainAligner( xParams ), xPackedAligner( xPacked );
+            for( BatchAligner* pA : { &xPlainAligner, &xPackedAligner } )
+            {
+                pA->uiBatchReads = std::min<size_t>( pReads->size( ), 1u << 18 );
+                pA->uiInflight = 3;
+                pA->warmUp( pFM, pReads );
+            }
+            // (MA_BOUNDARY_SAM_FILE: the file's name; it then stays, holding the last run's bytes -- the host-deflate variant's)
+            const char* const sKeep = getenv( "MA_BOUNDARY_SAM_FILE" );
+            const std::string sFile = sKeep != nullptr ? std::string( sKeep ) : "/tmp/ma_boundary_bench." + std::to_string( (long)getpid( ) ) + ".sam";
+            struct Run
+            {
+                double fSeconds = 0, fWriter = 0;
+                uint64_t uiFileBytes = 0, uiTextBytes = 0;
+                AlignerTiming xTiming;
+            };
+            auto run = [ & ]( BatchAligner& rAligner, const ParameterSetManager& rWriterParams ) {
+                Run r;
+                const double t = now( );
+                {
+                    BatchFileWriter xWriter( rWriterParams, std::make_shared<FileWriter>( rWriterParams, sFile, pPack ), pPack );
+                    xWriter.uiFormatThreads = std::min( 16u, uiHw );
+                    auto pFlat = rAligner.executeFlatSam( pFM, pReads, pPack );
+                    const double tW = now( );
+                    for( auto& pB : *pFlat )
+                        xWriter.write( *pB, pPack );
+                    r.uiTextBytes = xWriter.uiBytes.load( );
+                    r.fWriter = now( ) - tW;
+                } // (the stream closes: the end-of-file marker)
+                r.fSeconds = now( ) - t;
+                r.xTiming = rAligner.xLast;
+                std::ifstream xSize( sFile, std::ios::binary | std::ios::ate );
+                r.uiFileBytes = (uint64_t)xSize.tellg( );
+                return r;
+            };
+            Run xPlain = run( xPlainAligner, xParams ), xDevice = run( xPackedAligner, xPacked ), xHost = run( xPlainAligner, xPacked ); // warm-up
+            std::vector<double> vP, vD, vH;
+            for( int r = 0; r < iRepeats; r++ )
+            {
+                xPlain = run( xPlainAligner, xParams ), vP.push_back( n / xPlain.fSeconds );
+                xDevice = run( xPackedAligner, xPacked ), vD.push_back( n / xDevice.fSeconds );
+                xHost = run( xPlainAligner, xPacked ), vH.push_back( n / xHost.fSeconds );
+            }
+            if( sKeep == nullptr )
+                remove( sFile.c_str( ) );
+            // the kernels' own time: one batch of at most 2^18 reads on a batch object with timing on
+            float aMs[ 8 ] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+            double fSamMs = 0;
+            uint64_t uiOneText = 0, uiOneMembers = 0, uiOnePacked = 0;
+            {
+                const size_t uiOne = std::min<size_t>( pReads->size( ), 1u << 18 );
+                std::vector<uint8_t> vCodes;
+                std::vector<uint64_t> vOff( 1, 0 ), vNameOff( 1, 0 );
+                std::string sNames;
+                for( size_t i = 0; i < uiOne; i++ )
+                {
+                    const NucSeq& rQ = *( *pReads )[ i ];
+                    vCodes.insert( vCodes.end( ), rQ.xCodes.begin( ), rQ.xCodes.end( ) );
+                    vOff.push_back( vCodes.size( ) );
+                    sNames += rQ.sName;
+                    vNameOff.push_back( sNames.size( ) );
+                }
+                ma_batch* pB = nullptr;
+                maCheck( ma_batch_create( pFM->pDev->p, &xParams.xSelected, uiOne, vCodes.size( ) + 64, &pB ) );
+                maCheck( ma_batch_enable_timing( pB, 1 ) );
+                maCheck( ma_batch_set_reads( pB, vCodes.data( ), vOff.data( ), uiOne ) );
+                maCheck( ma_batch_set_read_text( pB, sNames.data( ), vNameOff.data( ), nullptr ) );
+                maCheck( ma_align_batch( pB ) );
+                maCheck( ma_batch_sync( pB ) );
+                for( int k = 0; k < 2; k++ ) // (the second pass is the measured one)
+                {
+                    const double tS = now( );
+                    maCheck( ma_sam_batch( pB, BatchAligner::samOptionBits( xParams.xSam ) ) );
+                    maCheck( ma_batch_sync( pB ) );
+                    fSamMs = 1e3 * ( now( ) - tS );
+                    maCheck( ma_sam_bgzf_batch( pB, 0 ) );
+                }
+                maCheck( ma_batch_kernel_ms( pB, aMs ) );
+                maCheck( ma_batch_sam_counts( pB, &uiOneText ) );
+                maCheck( ma_batch_sam_bgzf_counts( pB, 0, &uiOneMembers, &uiOnePacked ) );
+                maCheck( ma_batch_destroy( pB ) );
+            }
+            auto list = []( std::vector<double> v ) {
+                std::sort( v.begin( ), v.end( ) );
+                return "{\"median\": " + std::to_string( v[ v.size( ) / 2 ] ) + ", \"min\": " + std::to_string( v.front( ) ) +
+                       ", \"max\": " + std::to_string( v.back( ) ) + "}";
+            };
+            auto phases = []( const Run& rR ) {
+                char buf[ 320 ];
+                snprintf( buf, sizeof( buf ), "{\"wall_s\": %.4f, \"batches\": %llu, \"h2d_s\": %.4f, \"stages_s\": %.4f, \"d2h_s\": %.4f, "
+                          "\"writer_s\": %.4f, \"file_bytes\": %llu, \"text_bytes\": %llu}", rR.fSeconds, (unsigned long long)rR.xTiming.uiBatches,
+                          rR.xTiming.fH2D, rR.xTiming.fKernels, rR.xTiming.fD2H, rR.fWriter, (unsigned long long)rR.uiFileBytes,
+                          (unsigned long long)rR.uiTextBytes );
+                return std::string( buf );
+            };
+            printf( "{\"sam_bgzf\": {\"reads\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_reads\": %zu, \"in_flight\": 3, \"writer_threads\": %u, "
+                    "\"plain_reads_per_s\": %s, \"device_deflate_reads_per_s\": %s, \"host_deflate_reads_per_s\": %s, \"phases_plain\": %s, "
+                    "\"phases_device_deflate\": %s, \"phases_host_deflate\": %s, \"one_batch\": {\"reads\": %zu, \"text_bytes\": %llu, \"members\": %llu, "
+                    "\"member_bytes\": %llu, \"sam_stage_ms\": %.3f, \"deflate_kernels_ms\": %.3f}}}\n",
+                    n, uiLen, iRepeats, xPlainAligner.uiBatchReads, std::min( 16u, uiHw ), list( vP ).c_str( ), list( vD ).c_str( ), list( vH ).c_str( ),
+                    phases( xPlain ).c_str( ), phases( xDevice ).c_str( ), phases( xHost ).c_str( ), std::min<size_t>( pReads->size( ), 1u << 18 ),
+                    (unsigned long long)uiOneText, (unsigned long long)uiOneMembers, (unsigned long long)uiOnePacked, fSamMs, aMs[ 7 ] );
+            return xDevice.uiTextBytes == xPlain.uiTextBytes && xHost.uiFileBytes == xDevice.uiFileBytes ? 0 : 1;
         }
         if( argc >= 7 && ( !strcmp( argv[ 6 ], "sam" ) || bSamTags ) )
         {

@@ -481,6 +481,36 @@ int ma_batch_set_mates_text( ma_batch*, const char* text1 /*host*/, uint64_t n1,
  *                            With ma_batch_enable_timing, ma_batch_kernel_ms [6] is the time of the two inflate kernels. */
 int ma_batch_set_reads_bgzf( ma_batch*, const char* head /*host, may be NULL*/, uint64_t n_head, const void* members /*host*/,
                              uint64_t n_bytes, uint64_t n_drop, uint64_t* n_reads );
+/* ---- compressed SAM text out: the text of a batch deflated on the device into BGZF members ----
+ * The SAM text of the last ma_sam_batch / ma_pair_sam_batch is cut at fixed offsets -- member k holds text[65280 k ..
+ * min(65280 (k+1), n)), so ceil(n / 65280) members and none for an empty text -- and every member is deflated by a wavefront
+ * of its own (ma_amd/csrc/stage_deflate.h): one dynamic-Huffman block over an LZ77 parse, or one stored block where that is
+ * not smaller, in the member form htslib writes (18 header bytes with BSIZE, the stream, CRC32, ISIZE), which is the strict
+ * form ma_batch_set_reads_bgzf accepts.  The cuts, the parse, the codes and so every byte are stated once in
+ * ma_amd/host/ma_deflate_dev.h; ma_bgzf::deflateHost is the serial statement and gives the same bytes.  Records may straddle
+ * members, so the members of consecutive batches, written one after the other and closed with the 28-byte end-of-file marker,
+ * are a file samtools, zcat and gzip read.  No member is larger than its text + 31 bytes.
+ *   ma_sam_bgzf_batch                 pair == 0: the text of the last ma_sam_batch, else of the last ma_pair_sam_batch; on the
+ *                                     batch's stream; waits once, with the one read-back of the compressed size.  Fails with a
+ *                                     message when that text has not been made.  The text itself stays (ma_batch_get_sam /
+ *                                     ma_batch_get_pair_sam still serve it); making a SAM text again, or setting reads, drops
+ *                                     the members.
+ *   ma_batch_sam_bgzf_counts          members and their bytes
+ *   ma_batch_get_sam_bgzf             the members packed back to back; member k is bytes[member_off[k] .. member_off[k+1])
+ *                                     (either pointer may be NULL)
+ *   ma_batch_start_sam_bgzf_download  the same without the wait, completed by ma_batch_finish_download (one download can be
+ *                                     pending per object: a second one is refused under this call's name)
+ *   ma_bgzf_deflate                   the primitive: n_bytes of any host bytes through the same kernels on the index's device
+ *                                     (the index only names it).  out == NULL only counts (*n_members, *n_out); else cap is the
+ *                                     room behind out, and one that is too small fails with the size needed in the message.
+ * With ma_batch_enable_timing, ma_batch_kernel_ms [7] is the time of the deflate kernels of the last ma_sam_bgzf_batch (the call
+ * then also waits for their end). */
+int ma_sam_bgzf_batch( ma_batch*, int32_t pair );
+int ma_batch_sam_bgzf_counts( ma_batch*, int32_t pair, uint64_t* n_members, uint64_t* n_bytes );
+int ma_batch_get_sam_bgzf( ma_batch*, int32_t pair, uint64_t* member_off /*n_members+1*/, void* bytes );
+int ma_batch_start_sam_bgzf_download( ma_batch*, int32_t pair, uint64_t* member_off /*n_members+1*/, void* bytes );
+int ma_bgzf_deflate( const ma_index*, const void* text /*host*/, uint64_t n_bytes, uint64_t* n_members, uint64_t* n_out,
+                     uint64_t* member_off /*may be NULL*/, void* out /*may be NULL*/, uint64_t cap );
 /* work counters for the roofline model (same meaning as the oracle's): [0] extend_backward steps,
  * [1] distinct occ blocks touched, [2] bwt_sa LF steps, [3] SA rows, [4] DP band cells, [5] ksw jobs */
 int ma_batch_counters( ma_batch*, uint64_t out[ 8 ] );
@@ -488,7 +518,7 @@ int ma_batch_counters( ma_batch*, uint64_t out[ 8 ] );
  * qlen, tlen, w, zdrop, flag, ez.zdropped, ez.max_q, ez.max_t (shapes may be NULL to only count) */
 int ma_batch_get_dp_jobs( ma_batch*, uint64_t* n_jobs, int32_t* shapes, uint64_t cap );
 /* per-kernel HIP-event times of the last stage calls in ms: [0] seeding [1] sa-lookup [2] chaining
- * [3] dp-jobs [4] ksw [5] stitch; [6] the inflate of the last ma_batch_set_reads_bgzf; requires ma_batch_enable_timing(b,1) */
+ * [3] dp-jobs [4] ksw [5] stitch; [6] the inflate of the last ma_batch_set_reads_bgzf; [7] the deflate of the last ma_sam_bgzf_batch; requires ma_batch_enable_timing(b,1) */
 int ma_batch_enable_timing( ma_batch*, int on );
 int ma_batch_kernel_ms( ma_batch*, float out[ 8 ] );
 /* host wall time in ms of the stage calls of the last ma_align_batch: [0] seed [1] extract [2] chain [3] dp (launches,

@@ -6,8 +6,8 @@ device and raises MaError otherwise.
 """
 from .api import (MaError, Params, Index, Batch, HostArray, lib, lib_path, device_count, set_device, bind_host_thread,
                   ksw_batch, SEGMENT_DT, SEED_DT, EZ_DT, ALIGNMENT_DT, KSW_JOB_DT, SAM_SOFT_CLIP, SAM_EQX_CIGAR, SAM_NO_SECONDARY,
-                  SAM_NO_SUPPLEMENTARY, SAM_NO_CG_TAG, SAM_NGMLR_TAGS, debug_ngmlr_floats)
+                  SAM_NO_SUPPLEMENTARY, SAM_NO_CG_TAG, SAM_NGMLR_TAGS, debug_ngmlr_floats, bgzf_deflate)
 
 __all__ = ["MaError", "Params", "Index", "Batch", "HostArray", "lib", "lib_path", "device_count", "set_device", "bind_host_thread",
            "ksw_batch", "SEGMENT_DT", "SEED_DT", "EZ_DT", "ALIGNMENT_DT", "KSW_JOB_DT", "SAM_SOFT_CLIP", "SAM_EQX_CIGAR",
-           "SAM_NO_SECONDARY", "SAM_NO_SUPPLEMENTARY", "SAM_NO_CG_TAG", "SAM_NGMLR_TAGS", "debug_ngmlr_floats"]
+           "SAM_NO_SECONDARY", "SAM_NO_SUPPLEMENTARY", "SAM_NO_CG_TAG", "SAM_NGMLR_TAGS", "debug_ngmlr_floats", "bgzf_deflate"]

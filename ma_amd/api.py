@@ -316,6 +316,20 @@ def ksw_batch(params, cases, cigar_cap=None, pipeline_semantics=False):
     return ez, cigs
 
 
+def bgzf_deflate(index, data):
+    """(member_off, bytes): data (any bytes) deflated on index's device into BGZF members of 65 280 bytes of text each
+    (ma_bgzf_deflate: the kernels of Batch.sam_bgzf); member k is bytes[member_off[k]:member_off[k + 1]].  The bytes followed by
+    the 28-byte end-of-file marker are a file gzip reads."""
+    buf = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+    nm, nb = C.c_uint64(), C.c_uint64()
+    _chk(lib().ma_bgzf_deflate(index.h, _ptr(buf), C.c_uint64(len(buf) - 1), C.byref(nm), C.byref(nb), None, None, C.c_uint64(0)))
+    off = np.zeros(nm.value + 1, dtype=np.uint64)
+    out = np.zeros(nb.value + 1, dtype=np.uint8)
+    _chk(lib().ma_bgzf_deflate(index.h, _ptr(buf), C.c_uint64(len(buf) - 1), C.byref(nm), C.byref(nb), _ptr(off), _ptr(out),
+                               C.c_uint64(nb.value)))
+    return off, out[:-1].tobytes()
+
+
 class Batch:
     """Device-resident batch of reads and stage outputs (ma_batch*)."""
 
@@ -727,6 +741,38 @@ class Batch:
             return None
         _chk(lib().ma_batch_start_pair_sam_download(self.h, C.c_void_p(off.ptr), C.c_void_p(text.ptr)))
         return nb
+
+    # ---- BGZF members of a SAM text (ma_sam_bgzf_batch): the text of sam() / pair_sam() deflated on the device
+    def sam_bgzf_counts(self, pair=False):
+        """(members, bytes) of the last sam_bgzf_members() / sam_bgzf()"""
+        nm, nb = C.c_uint64(), C.c_uint64()
+        _chk(lib().ma_batch_sam_bgzf_counts(self.h, C.c_int32(1 if pair else 0), C.byref(nm), C.byref(nb)))
+        return nm.value, nb.value
+
+    def sam_bgzf_members(self, pair=False):
+        """(member_off, bytes): the text of the last sam() (pair: of the last pair_sam()) as BGZF members of 65 280 bytes of text
+        each, packed back to back; member k is bytes[member_off[k]:member_off[k + 1]].  sam_text() / pair_sam_text() stay."""
+        _chk(lib().ma_sam_bgzf_batch(self.h, C.c_int32(1 if pair else 0)))
+        nm, nb = self.sam_bgzf_counts(pair)
+        off = np.zeros(nm + 1, dtype=np.uint64)
+        out = np.zeros(nb + 1, dtype=np.uint8)
+        _chk(lib().ma_batch_get_sam_bgzf(self.h, C.c_int32(1 if pair else 0), _ptr(off), _ptr(out)))
+        return off, out[:-1].tobytes()
+
+    def sam_bgzf(self, pair=False):
+        """the bytes of all members: written behind a header's members and closed with the 28-byte end-of-file marker they are a
+        .sam.gz that samtools, zcat and gzip read"""
+        return self.sam_bgzf_members(pair)[1]
+
+    def start_sam_bgzf_download(self, off, out, pair=False):
+        """deflates (ma_sam_bgzf_batch) and starts sam_bgzf_members() into caller-owned HostArrays (u64[members + 1], u8[bytes])
+        without the wait: None when they are too small, else (members, bytes); complete after finish_download()."""
+        _chk(lib().ma_sam_bgzf_batch(self.h, C.c_int32(1 if pair else 0)))
+        nm, nb = self.sam_bgzf_counts(pair)
+        if off.n < nm + 1 or out.n < nb:
+            return None
+        _chk(lib().ma_batch_start_sam_bgzf_download(self.h, C.c_int32(1 if pair else 0), C.c_void_p(off.ptr), C.c_void_p(out.ptr)))
+        return nm, nb
 
     def close(self):
         if self.h:

@@ -140,7 +140,7 @@ int sam_text_launch( ma_batch* b, SamTextState& s, u64 n, Args A )
 {
     if( download_wait( b ) ) // the text of the last call may still be on its way down
         return 1;
-    s.done = false;
+    s.done = s.zDone = false; // (the members of ma_sam_bgzf_batch are of the text before)
     s.bytes = 0;
     if( n )
     {

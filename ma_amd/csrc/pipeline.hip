@@ -93,17 +93,34 @@ static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0
 
 #include "../host/ma_bgzf_dev.h"
 #include "stage_bgzf.h"
+// the device deflate of the SAM texts into BGZF members: ma_sam_bgzf_batch (launch_deflate.h)
+#include "../host/ma_deflate_dev.h"
+#include "stage_deflate.h"
 
 // ------------------------------------------------------------------------------------------------
 // batch object
 // ------------------------------------------------------------------------------------------------
 // One SAM text of a batch (launch_sam.h): per item -- a read, or a pair -- the bytes of its records and their scan, where SEQ
 // of every record goes, the text, the statistics of the one read-back (SAM_STAT_*)
+// What a deflate needs beside the text (launch_deflate.h), sized by the members (slots, sizes, flags) and by the grid (tokens),
+// and the members of one text: their offsets (members + 1) and their bytes
+struct DeflateBufs
+{
+    DevBuf tokens, slots, sizes, flags, cub;
+};
+struct DeflateMembers
+{
+    DevBuf off, bytes;
+};
+// z*: the text's BGZF members (ma_sam_bgzf_batch), valid while done and zDone: making the text again drops them
 struct SamTextState
 {
     DevBuf cnt, off, seqPos, text, stat;
     bool done = false;
     u64 bytes = 0;
+    DeflateMembers z;
+    bool zDone = false;
+    u64 zMembers = 0, zBytes = 0;
 };
 
 // how far a batch's reads have come (ma_batch::stage_done), in order; ALIGNED: DP + MappingQuality, or lists handed in
@@ -162,6 +179,7 @@ struct ma_batch
     // call's statistics follow the parse's in txtStat
     DevBuf bgzIn, bgzMembers;
     SamTextState sam, pairSam;
+    DeflateBufs zScratch; // of ma_sam_bgzf_batch, shared by both texts
     // small inversions (ma_inversions_batch, launch_inv.h): the statistics of the call, per MappingQuality slot its candidates, per
     // candidate its record, DP job, shape, window and result, and the FINAL lists the later stages see through mq_view
     DevBuf invStat, invSlotCnt, invSlotFirst, invCand, invJobs, invShapes, invWin, invEz, invCigOff, invCigPool, invCtr, invHdr;
@@ -1337,3 +1355,5 @@ int ma_debug_seed_prof( unsigned long long* out )
 #include "launch_text.h"
 
 #include "launch_bgzf.h"
+
+#include "launch_deflate.h"

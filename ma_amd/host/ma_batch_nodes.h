@@ -555,7 +555,8 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
         const size_t n = pReads->size( );
         if( pAligned->size( ) != n )
             throw std::runtime_error( "BatchFileWriter: the batch of alignments does not belong to these reads" );
-        if( pAligned->hasSamText( ) ) // formatted on the device (BatchAligner::executeFlatSam): the batch's text as it is
+        // formatted on the device (BatchAligner::executeFlatSam): the batch's text, or its members, as they are
+        if( pAligned->hasSamText( ) || pAligned->hasSamBgzf( ) )
         {
             write( *pAligned );
             return std::make_shared<libMS::Container>( );
@@ -602,23 +603,81 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
             rT.join( );
         if( !sFailure.empty( ) )
             throw std::runtime_error( sFailure );
-        uint64_t uiTotal = 0;
-        {
-            std::lock_guard<std::mutex> xGuard( *pPerRead->pLock );
-            for( const auto& rArena : vArenas )
-            {
-                pPerRead->pOut->write( rArena.data( ), rArena.size( ) );
-                uiTotal += rArena.size( );
-            }
-        }
-        uiBytes += uiTotal, uiReads += n;
+        uiBytes += writeArenas( *pPerRead, vArenas ), uiReads += n;
         return std::make_shared<libMS::Container>( );
+    }
+    // The arenas of a batch, in order, under one acquisition of the writer's lock.  On a BGZF stream (SamOptions::bBgzf) every
+    // arena is deflated first (ma_bgzf::deflateHost), by a thread of its own like the formatting before: the lock is held for
+    // the writes of the members alone.  Returns the bytes of text.
+    static uint64_t writeArenas( const SamSink& rSink, const std::vector<ma_amd::flat::Arena>& vArenas )
+    {
+        uint64_t uiTotal = 0;
+        const auto pBgzf = rSink.bgzf( );
+        std::vector<std::vector<uint8_t>> vMembers( pBgzf != nullptr ? vArenas.size( ) : 0 );
+        if( pBgzf != nullptr )
+        {
+            std::vector<std::thread> vT;
+            for( size_t t = 1; t < vArenas.size( ); t++ )
+                vT.emplace_back( [ &, t ]( ) { vMembers[ t ] = bgzfMembersOf( vArenas[ t ].data( ), vArenas[ t ].size( ) ); } );
+            vMembers[ 0 ] = bgzfMembersOf( vArenas[ 0 ].data( ), vArenas[ 0 ].size( ) );
+            for( auto& rT : vT )
+                rT.join( );
+        }
+        std::lock_guard<std::mutex> xGuard( *rSink.pLock );
+        for( size_t t = 0; t < vArenas.size( ); t++ )
+        {
+            if( pBgzf != nullptr )
+                pBgzf->writeMembers( vMembers[ t ].data( ), vMembers[ t ].size( ) );
+            else
+                rSink.pOut->write( vArenas[ t ].data( ), vArenas[ t ].size( ) );
+            uiTotal += vArenas[ t ].size( );
+        }
+        return uiTotal;
+    }
+    // The text of a batch the device formatted, with one write.  On a BGZF stream (the writer has SamOptions::bBgzf, the aligner
+    // has not) the text is cut at multiples of a member's 65 280 bytes into up to uiThreads pieces, every piece is deflated by a
+    // thread of its own (ma_bgzf::deflateHost) and the members go out in order: the members of the whole text.
+    static void writeDeviceText( const SamSink& rSink, const char* pText, size_t uiBytes, size_t uiThreads )
+    {
+        const auto pBgzf = rSink.bgzf( );
+        if( pBgzf == nullptr )
+        {
+            std::lock_guard<std::mutex> xGuard( *rSink.pLock );
+            rSink.pOut->write( pText, uiBytes );
+            return;
+        }
+        const size_t uiChunks = ( uiBytes + ma_bgzf::DEFLATE_CHUNK - 1 ) / ma_bgzf::DEFLATE_CHUNK;
+        const size_t uiPieces = std::max<size_t>( 1, std::min( uiThreads, uiChunks ) );
+        std::vector<std::vector<uint8_t>> vMembers( uiPieces );
+        auto piece = [ & ]( size_t t ) {
+            const size_t uiFrom = std::min( uiBytes, uiChunks * t / uiPieces * ma_bgzf::DEFLATE_CHUNK );
+            const size_t uiTo = std::min( uiBytes, uiChunks * ( t + 1 ) / uiPieces * ma_bgzf::DEFLATE_CHUNK );
+            vMembers[ t ] = bgzfMembersOf( pText + uiFrom, uiTo - uiFrom );
+        };
+        std::vector<std::thread> vT;
+        for( size_t t = 1; t < uiPieces; t++ )
+            vT.emplace_back( piece, t );
+        piece( 0 );
+        for( auto& rT : vT )
+            rT.join( );
+        std::lock_guard<std::mutex> xGuard( *rSink.pLock );
+        for( const auto& rMembers : vMembers )
+            pBgzf->writeMembers( rMembers.data( ), rMembers.size( ) );
+    }
+    // the members of a batch the device deflated, as they are: only onto a BGZF stream
+    static void writeDeviceMembers( const SamSink& rSink, const AlignedBatch& rBatch, const char* sWho )
+    {
+        const auto pBgzf = rSink.bgzf( );
+        if( pBgzf == nullptr )
+            throw std::runtime_error( std::string( sWho ) + ": the batch carries BGZF members, the writer's stream is plain (SamOptions::bBgzf)" );
+        std::lock_guard<std::mutex> xGuard( *rSink.pLock );
+        pBgzf->writeMembers( rBatch.samBgzf( ), rBatch.samBgzfBytes( ) );
     }
     // A batch of BatchAligner::executeFlat / executeFlatSam outside of a graph: device text goes out with ONE write, records
     // are formatted as in execute( ).
     void write( const AlignedBatch& rBatch, std::shared_ptr<Pack> pPack = nullptr )
     {
-        if( !rBatch.hasSamText( ) )
+        if( !rBatch.hasSamText( ) && !rBatch.hasSamBgzf( ) )
         {
             if( pPack == nullptr && pPerRead->xOptions.bEmulateNgmlrTags )
                 throw std::runtime_error( "BatchFileWriter::write: the NGMLR tags need the pack" );
@@ -633,10 +692,13 @@ class BatchFileWriter : public libMS::Module<libMS::Container, false, ReadVector
             throw std::runtime_error( "BatchFileWriter: device text carries no NGMLR tags" );
         if( !pPerRead->xOptions.bEmulateNgmlrTags && ( rBatch.samOptions( ) & MA_SAM_NGMLR_TAGS ) )
             throw std::runtime_error( "BatchFileWriter: device text carries NGMLR tags the writer's options do not ask for" );
+        if( rBatch.hasSamBgzf( ) )
         {
-            std::lock_guard<std::mutex> xGuard( *pPerRead->pLock );
-            pPerRead->pOut->write( rBatch.samText( ), rBatch.samBytes( ) );
+            writeDeviceMembers( *pPerRead, rBatch, "BatchFileWriter" );
+            uiBytes += rBatch.samBytes( ), uiReads += rBatch.size( );
+            return;
         }
+        writeDeviceText( *pPerRead, rBatch.samText( ), rBatch.samBytes( ), uiFormatThreads );
         uiBytes += rBatch.samBytes( ), uiReads += rBatch.size( );
     }
     virtual bool requiresLock( ) const
@@ -677,12 +739,15 @@ class BatchPairedFileWriter
         if( !rBatch.paired( ) )
             throw std::runtime_error( "BatchPairedFileWriter: not a paired batch" );
         const size_t n = rBatch.pairs( );
+        if( rBatch.hasSamBgzf( ) ) // formatted and deflated on the device: the batch's members as they are
+        {
+            BatchFileWriter::writeDeviceMembers( *pPerPair, rBatch, "BatchPairedFileWriter" );
+            uiBytes += rBatch.samBytes( ), uiReads += 2 * n;
+            return;
+        }
         if( rBatch.hasSamText( ) ) // formatted on the device (BatchAligner::executePairedFlatSam): the batch's text as it is
         {
-            {
-                std::lock_guard<std::mutex> xGuard( *pPerPair->pLock );
-                pPerPair->pOut->write( rBatch.samText( ), rBatch.samBytes( ) );
-            }
+            BatchFileWriter::writeDeviceText( *pPerPair, rBatch.samText( ), rBatch.samBytes( ), uiFormatThreads );
             uiBytes += rBatch.samBytes( ), uiReads += 2 * n;
             return;
         }
@@ -721,16 +786,7 @@ class BatchPairedFileWriter
             rT.join( );
         if( !sFailure.empty( ) )
             throw std::runtime_error( sFailure );
-        uint64_t uiTotal = 0;
-        {
-            std::lock_guard<std::mutex> xGuard( *pPerPair->pLock );
-            for( const auto& rArena : vArenas )
-            {
-                pPerPair->pOut->write( rArena.data( ), rArena.size( ) );
-                uiTotal += rArena.size( );
-            }
-        }
-        uiBytes += uiTotal, uiReads += 2 * n;
+        uiBytes += BatchFileWriter::writeArenas( *pPerPair, vArenas ), uiReads += 2 * n;
     }
 };
 } // namespace libMA

@@ -59,6 +59,14 @@ struct ReadText
     const uint8_t* pQuality = nullptr;
 };
 // SAM mode of Engine::run: the text of the batch's reads (one entry per read) and the MA_SAM_* bits of ma_sam_batch
+// Beside the MA_SAM_* bits in a run's SAM options: the text stays on the device, is deflated there (ma_sam_bgzf_batch) and only its
+// BGZF members come down (BatchResult::bSamBgzf).  The bit is the host layer's: it never reaches the library.
+static const uint32_t SAM_AS_BGZF = 0x80000000u;
+// (The three calls behind the bit are weak references: a program that stands in for the library without them still links --
+// tests/emul/engine_calls_test.cpp stubs exactly the calls its golden trace holds -- and the bit then throws.)
+#pragma weak ma_sam_bgzf_batch
+#pragma weak ma_batch_sam_bgzf_counts
+#pragma weak ma_batch_get_sam_bgzf
 struct SamMode
 {
     const std::vector<ReadText>* pText = nullptr;
@@ -222,6 +230,11 @@ struct BatchResult
     HostBuf<uint64_t> vSamOff; // uiReads + 1 (pairs: uiReads / 2 + 1)
     HostBuf<char> vSam;
     uint64_t uiSamBytes = 0;
+    // with SAM_AS_BGZF among the options: INSTEAD of the text its BGZF members as the device deflated them, packed back to back
+    // (uiSamBytes is still the size of the text; vSamOff and vSam are not filled)
+    bool bSamBgzf = false;
+    HostBuf<uint8_t> vSamBgzf;
+    uint64_t uiSamBgzfBytes = 0, uiSamBgzfMembers = 0;
     double fPack = 0, fH2D = 0, fKernels = 0, fD2H = 0; // seconds: gathering the reads, upload, all stages, download
     float aStageMs[ 8 ] = { 0, 0, 0, 0, 0, 0, 0, 0 }; // host wall time of seed / extract / chain / dp (ma_batch_host_ms)
 };
@@ -503,6 +516,8 @@ class Engine
         R.bSocQueues = false;
         R.uiSamOptions = uiSamOptions;
         R.uiSamBytes = 0;
+        R.bSamBgzf = false;
+        R.uiSamBgzfBytes = R.uiSamBgzfMembers = 0;
         R.fPack = 0;
         return pRes;
     }
@@ -610,10 +625,23 @@ class Engine
     // the text replaces the record download: ma_sam_batch waits once for the size, then one copy of offsets + bytes
     void fetchSam( BatchResult& R, uint32_t uiSamOptions )
     {
-        engineCheck( ma_sam_batch( pBatch, uiSamOptions ) );
+        engineCheck( ma_sam_batch( pBatch, uiSamOptions & ~SAM_AS_BGZF ) );
         engineCheck( ma_batch_sam_counts( pBatch, &R.uiSamBytes ) );
-        engineCheck( ma_batch_get_sam( pBatch, R.vSamOff.need( R.uiReads + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
+        if( uiSamOptions & SAM_AS_BGZF )
+            fetchSamBgzf( R, 0 );
+        else
+            engineCheck( ma_batch_get_sam( pBatch, R.vSamOff.need( R.uiReads + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
         noMqRecords( R );
+    }
+    // the text deflated where it is: only its members come down
+    void fetchSamBgzf( BatchResult& R, int32_t iPair )
+    {
+        if( &ma_sam_bgzf_batch == nullptr || &ma_batch_sam_bgzf_counts == nullptr || &ma_batch_get_sam_bgzf == nullptr )
+            throw std::runtime_error( "Engine: SAM_AS_BGZF without ma_sam_bgzf_batch in the library" );
+        engineCheck( ma_sam_bgzf_batch( pBatch, iPair ) );
+        engineCheck( ma_batch_sam_bgzf_counts( pBatch, iPair, &R.uiSamBgzfMembers, &R.uiSamBgzfBytes ) );
+        engineCheck( ma_batch_get_sam_bgzf( pBatch, iPair, nullptr, R.vSamBgzf.need( R.uiSamBgzfBytes + 1 ) ) );
+        R.bSamBgzf = true;
     }
     // pairing and formatting behind the alignment: the text replaces the download of records, ops, mate and other
     void fetchPairSam( BatchResult& R, uint32_t uiSamOptions )
@@ -622,9 +650,12 @@ class Engine
         R.uiPairRecords = R.uiPairOps = 0;
         engineCheck( ma_pair_batch( pBatch ) );
         engineCheck( ma_batch_pair_counts( pBatch, &nPairs, nullptr, nullptr, &R.uiPairsOnHost ) );
-        engineCheck( ma_pair_sam_batch( pBatch, uiSamOptions ) );
+        engineCheck( ma_pair_sam_batch( pBatch, uiSamOptions & ~SAM_AS_BGZF ) );
         engineCheck( ma_batch_pair_sam_counts( pBatch, &nPairs, &R.uiSamBytes ) );
-        engineCheck( ma_batch_get_pair_sam( pBatch, R.vSamOff.need( nPairs + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
+        if( uiSamOptions & SAM_AS_BGZF )
+            fetchSamBgzf( R, 1 );
+        else
+            engineCheck( ma_batch_get_pair_sam( pBatch, R.vSamOff.need( nPairs + 1 ), R.vSam.need( R.uiSamBytes + 1 ) ) );
         memset( R.vPairOff.need( nPairs + 1 ), 0, ( nPairs + 1 ) * sizeof( uint64_t ) ); // no pair records either (a recycled result)
         noMqRecords( R );
     }

@@ -51,6 +51,9 @@ struct SamOptions
     bool bOutputMCigar = true; // "Use M in CIGAR"
     bool bCGTag = true; // "Output long cigars in CG tag"
     bool bSoftClip = false; // "Soft clip"
+    // not the reference's: the writers' stream is BGZF (.sam.gz, what bgzip writes) from its first byte, and the ...Sam paths of
+    // BatchAligner deflate a batch's text on the device (ma_sam_bgzf_batch) and return its members (AlignedBatch::hasSamBgzf)
+    bool bBgzf = false;
 };
 
 // ParameterSetManager (parameter.h:1067-1201) reduced to the preset selection the path reads
@@ -1449,7 +1452,23 @@ class AlignedBatch : public libMS::Container
     // Such a batch has no pair records: pairOffsets( ) are all 0, the other pair accessors are not valid on it.
     bool hasSamText( ) const
     {
-        return pResult != nullptr && pResult->bSam;
+        return pResult != nullptr && pResult->bSam && !pResult->bSamBgzf;
+    }
+    // With SamOptions::bBgzf the batch holds, INSTEAD of the text, the text's BGZF members as the device deflated them
+    // (ma_sam_bgzf_batch), packed back to back: samBgzf( )[ 0 .. samBgzfBytes( ) ); samBytes( ) is the size of the text they
+    // inflate to.  Records may straddle members, so there are no offsets per read.  The writers put the members on their stream
+    // as they are.
+    bool hasSamBgzf( ) const
+    {
+        return pResult != nullptr && pResult->bSam && pResult->bSamBgzf;
+    }
+    const uint8_t* samBgzf( ) const
+    {
+        return pResult->vSamBgzf.data( );
+    }
+    uint64_t samBgzfBytes( ) const
+    {
+        return pResult->uiSamBgzfBytes;
     }
     const uint64_t* samOffsets( ) const
     {
@@ -1824,7 +1843,8 @@ class BatchAligner
     {
         return ( rO.bSoftClip ? MA_SAM_SOFT_CLIP : 0u ) | ( rO.bOutputMCigar ? 0u : MA_SAM_EQX_CIGAR ) |
                ( rO.bNoSecondary ? MA_SAM_NO_SECONDARY : 0u ) | ( rO.bNoSupplementary ? MA_SAM_NO_SUPPLEMENTARY : 0u ) |
-               ( rO.bCGTag ? 0u : MA_SAM_NO_CG_TAG ) | ( rO.bEmulateNgmlrTags ? MA_SAM_NGMLR_TAGS : 0u );
+               ( rO.bCGTag ? 0u : MA_SAM_NO_CG_TAG ) | ( rO.bEmulateNgmlrTags ? MA_SAM_NGMLR_TAGS : 0u ) |
+               ( rO.bBgzf ? detail::SAM_AS_BGZF : 0u ); // (the host layer's own bit: Engine::fetchSam)
     }
     bool servesSam( ) const
     {

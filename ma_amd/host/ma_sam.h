@@ -9,6 +9,7 @@
 // PairedFileWriter refuses it.
 #pragma once
 #include "ma_modules.h"
+#include "ma_deflate_dev.h"
 
 #ifdef MA_WITH_ZLIB
 #include <zlib.h>
@@ -544,8 +545,92 @@ class StringOutStream : public OutStream // convenience for tests and in-memory 
     }
 };
 
+// A sink that turns everything written to it into BGZF on the sink behind it (SamOptions::bBgzf: the writers put it in front of
+// their stream themselves).  Text -- the header, the per-read writers' lines, a batch's formatted records -- is collected and
+// goes out as members of 65 280 bytes of text through ma_bgzf::deflateHost, the host statement of the device's deflate;
+// members made elsewhere (writeMembers: a batch the device deflated, arenas the batch writers' threads deflated) go out as they
+// are, behind what text is still pending.  finish( ) -- or the destructor -- writes the pending text and then, ONCE, the 28-byte
+// end-of-file marker.  Like every sink it is written to under the writers' lock.
+class BgzfOutStream : public OutStream
+{
+    const std::shared_ptr<OutStream> pInner;
+    std::string sPending;
+    std::vector<uint8_t> vMembers;
+    bool bFinished = false;
+
+    void deflatePending( size_t uiBytes ) // the first uiBytes of sPending
+    {
+        if( uiBytes == 0 )
+            return;
+        vMembers.resize( ma_bgzf::deflateBound( uiBytes ) );
+        const uint64_t n = ma_bgzf::deflateHost( (const uint8_t*)sPending.data( ), uiBytes, vMembers.data( ), nullptr );
+        pInner->write( (const char*)vMembers.data( ), n );
+        sPending.erase( 0, uiBytes );
+    }
+
+  protected:
+    void put( const char* p, size_t n ) override
+    {
+        if( bFinished )
+            throw std::runtime_error( "BgzfOutStream: written to after the end-of-file marker" );
+        sPending.append( p, n );
+        if( sPending.size( ) >= 4 * ma_bgzf::DEFLATE_CHUNK )
+            deflatePending( sPending.size( ) / ma_bgzf::DEFLATE_CHUNK * ma_bgzf::DEFLATE_CHUNK );
+    }
+
+  public:
+    explicit BgzfOutStream( std::shared_ptr<OutStream> pInner ) : pInner( pInner )
+    {}
+    void write( const char* p, size_t n ) override
+    {
+        put( p, n );
+    }
+    // whole BGZF members
+    void writeMembers( const void* p, size_t n )
+    {
+        if( bFinished )
+            throw std::runtime_error( "BgzfOutStream: written to after the end-of-file marker" );
+        deflatePending( sPending.size( ) );
+        pInner->write( (const char*)p, n );
+    }
+    void finish( )
+    {
+        if( bFinished )
+            return;
+        deflatePending( sPending.size( ) );
+        uint8_t aEof[ ma_bgzf::EOF_BYTES ];
+        ma_bgzf::writeEof( aEof );
+        pInner->write( (const char*)aEof, sizeof( aEof ) );
+        bFinished = true;
+    }
+    ~BgzfOutStream( ) override
+    {
+        try
+        {
+            finish( );
+        }
+        catch( ... )
+        {}
+    }
+};
+// the members of a text (the batch writers' threads deflate their arenas with it)
+inline std::vector<uint8_t> bgzfMembersOf( const char* pText, size_t uiBytes )
+{
+    std::vector<uint8_t> vOut( ma_bgzf::deflateBound( uiBytes ) );
+    vOut.resize( ma_bgzf::deflateHost( (const uint8_t*)pText, uiBytes, vOut.data( ), nullptr ) );
+    return vOut;
+}
+
 namespace sam
 {
+// the sink of a writer: with SamOptions::bBgzf a BgzfOutStream in front of pOut, unless pOut is one already (a second writer on
+// the same stream)
+inline std::shared_ptr<OutStream> sinkFor( std::shared_ptr<OutStream> pOut, const SamOptions& rOptions )
+{
+    if( !rOptions.bBgzf || std::dynamic_pointer_cast<BgzfOutStream>( pOut ) != nullptr )
+        return pOut;
+    return std::make_shared<BgzfOutStream>( pOut );
+}
 // "stdout" or a file (fileWriter.h:385-400)
 inline std::shared_ptr<OutStream> openSink( const std::string& sFileName )
 {
@@ -615,7 +700,7 @@ class SamSink
 
   protected:
     SamSink( std::shared_ptr<OutStream> pOut, std::shared_ptr<std::mutex> pLock, const SamOptions& rOptions )
-        : pOut( pOut ), pLock( pLock ), xOptions( rOptions )
+        : pOut( sam::sinkFor( pOut, rOptions ) ), pLock( pLock ), xOptions( rOptions )
     {}
     ~SamSink( )
     {
@@ -643,6 +728,22 @@ class SamSink
     }
 
   public:
+    // the BGZF sink of a writer with SamOptions::bBgzf, or nullptr
+    std::shared_ptr<BgzfOutStream> bgzf( ) const
+    {
+        return std::dynamic_pointer_cast<BgzfOutStream>( pOut );
+    }
+    // flush( ), and with SamOptions::bBgzf the pending text and the end-of-file marker: the stream is complete (the sink's
+    // destructor does the same when the last writer on it is gone); nothing may be written afterwards
+    void finishStream( ) const
+    {
+        flush( );
+        if( auto pBgzf = bgzf( ) )
+        {
+            std::lock_guard<std::mutex> xTurn( *pLock );
+            pBgzf->finish( );
+        }
+    }
     // writes what the threads' buffers still hold (uiBufferBytes > 0); not to be called while other threads emit
     void flush( ) const
     {
