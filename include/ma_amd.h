@@ -187,7 +187,20 @@ int ma_ksw_ext_batch( const ma_params*, const ma_ksw_job* jobs, uint64_t n, cons
                       uint64_t cigar_cap );
 
 /* ---- batch pipeline: BinarySeeding -> StripOfConsideration -> Harmonization -> NeedlemanWunsch -> MappingQuality
- *      as wired in libMA::setUpCompGraph (libs/ma/src/util/export.cpp:104-108) ---- */
+ *      as wired in libMA::setUpCompGraph (libs/ma/src/util/export.cpp:104-108) ----
+ * What a call invalidates.  A batch holds products that are made of one another:
+ *
+ *   reads - names
+ *   reads - SEEDED - EXTRACTED - CHAINED - ALIGNED - inversion view -+- single-end text (needs names) - its BGZF members
+ *                                                                    +- pairs - pairs' text (needs names) - its BGZF members
+ *
+ * A call that makes a product (a stage, a stage input handed in, ma_batch_set_read_text, ma_inversions_batch, ma_pair_batch,
+ * a SAM text, its members) first drops that product and everything to its right, and marks it valid when it succeeds; new reads
+ * in any form drop everything.  So after a stage call or a stage-input call the products of LATER stages are gone -- their
+ * getters fail with "run ... first" until they are made again --, a call that returns 1 leaves the batch at the product before
+ * it, and the two that keep something to their left do so on purpose: ma_inversions_batch keeps ALIGNED, ma_pair_batch keeps the
+ * single-end text and the inversion view.  A stage input handed in makes the batch jump to that stage; what the earlier stages
+ * held is then unspecified.  The rules are written once, in ma_amd/host/ma_batch_state.h. */
 int ma_batch_create( const ma_index*, const ma_params*, uint64_t max_reads, uint64_t max_bases, ma_batch** out );
 int ma_batch_destroy( ma_batch* );
 /* stream: a hipStream_t (as void*) all stage kernels of this batch are launched on; NULL = default stream */
@@ -197,6 +210,7 @@ int ma_batch_set_stream( ma_batch*, void* hip_stream );
 int ma_batch_set_blocking_sync( ma_batch*, int on );
 /* reads as 1 byte/base codes, CSR offsets[n+1]; host or device pointers */
 int ma_batch_set_reads( ma_batch*, const uint8_t* codes, const uint64_t* offsets, uint64_t n_reads );
+/* the caller's device arrays, which stay the caller's; a call that fails leaves the reads that were set before in place */
 int ma_batch_set_reads_device( ma_batch*, const void* d_codes, const void* d_offsets, uint64_t n_reads,
                                uint64_t n_bases );
 /* stages (asynchronous on the batch stream; each requires the previous one) */
@@ -322,8 +336,7 @@ int ma_batch_start_pair_download( ma_batch*, uint64_t* pair_off /*n_pairs+1*/, m
  * several of one parent in the order of their stretches: ma_batch_get_mapq_alignments, ma_batch_start_mapq_download, n_alignments
  * / n_ops of ma_batch_counts (the capacities of those downloads), ma_pair_batch, ma_sam_batch (with MA_SAM_NGMLR_TAGS too) and
  * ma_pair_sam_batch serve them; ma_batch_get_alignments, ma_batch_get_hsets and the SoC getters serve what they served.  The
- * call always starts from the MappingQuality output (twice gives the same lists) and drops pairs and SAM texts made before (run
- * ma_pair_batch again); setting reads, ma_dp_batch and ma_batch_set_alignments put the MappingQuality lists back.
+ * call always starts from the MappingQuality output (twice gives the same lists).
  *   ma_batch_inversion_counts  drop stretches found, DP jobs among them (both sides non-empty), inversion records kept (any
  *                              pointer may be NULL) */
 int ma_inversions_batch( ma_batch* );
@@ -347,7 +360,7 @@ int ma_batch_inversion_counts( ma_batch*, uint64_t* n_candidates, uint64_t* n_jo
  *   ma_batch_set_read_text       QNAME (NucSeq::sName) and QUAL (NucSeq::pxQualityValues / fastaq quality, nucSeq.h:697-709) of
  *                                the batch's reads, after the reads were set: read r's name is names[name_off[r] ..
  *                                name_off[r+1]), qual is NULL (QUAL "*") or holds one character per base in the reads' CSR.
- *                                Setting reads again drops the text; without it ma_sam_batch fails with a message.
+ *                                Without it ma_sam_batch fails with a message.
  *   ma_sam_batch                 after ma_dp_batch / ma_align_batch / ma_batch_set_alignments on the batch's stream; options =
  *                                MA_SAM_* (the members of FileWriter's settings it serves).  Waits for the stream with the one
  *                                read-back that sizes the download.  A record that ends beyond its read (possible only through
@@ -493,8 +506,7 @@ int ma_batch_set_reads_bgzf( ma_batch*, const char* head /*host, may be NULL*/, 
  *   ma_sam_bgzf_batch                 pair == 0: the text of the last ma_sam_batch, else of the last ma_pair_sam_batch; on the
  *                                     batch's stream; waits once, with the one read-back of the compressed size.  Fails with a
  *                                     message when that text has not been made.  The text itself stays (ma_batch_get_sam /
- *                                     ma_batch_get_pair_sam still serve it); making a SAM text again, or setting reads, drops
- *                                     the members.
+ *                                     ma_batch_get_pair_sam still serve it).
  *   ma_batch_sam_bgzf_counts          members and their bytes
  *   ma_batch_get_sam_bgzf             the members packed back to back; member k is bytes[member_off[k] .. member_off[k+1])
  *                                     (either pointer may be NULL)

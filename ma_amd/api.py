@@ -529,6 +529,12 @@ class Batch:
         _chk(lib().ma_batch_get_hsets(self.h, _ptr(hoff), _ptr(soff), _ptr(soc), _ptr(seeds)))
         return hoff, soff, soc, seeds[: int(soff[-1])]
 
+    def set_segments(self, off, segs):
+        """Segments from elsewhere (CSR per read, the layout of segments()) -> extract()."""
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        segs = np.ascontiguousarray(np.concatenate([segs, np.zeros(1, dtype=SEGMENT_DT)]))
+        _chk(lib().ma_batch_set_segments(self.h, _ptr(off), _ptr(segs)))
+
     def set_seeds(self, off, seeds):
         """Extracted seeds from elsewhere (CSR per read) -> chain()."""
         off = np.ascontiguousarray(off, dtype=np.uint64)

@@ -43,16 +43,17 @@ static u32 lanes_per_wave( u64 items )
 
 int ma_chain_batch( ma_batch* b )
 {
-    if( !b || b->stage_done < STAGE_EXTRACTED )
+    if( !b || !b->st.has( ma_state::EXTRACTED ) )
         return fail( "ma_chain_batch: run ma_extract_seeds_batch first" );
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads;
+    b->st.drop( ma_state::CHAINED );
     if( n == 0 )
     {
-        b->stage_done = STAGE_CHAINED;
+        b->st.finish( ma_state::CHAINED );
         return 0;
     }
-    const u64 ts = b->nSeeds + 1;
+    const u64 ts = b->st.nSeeds + 1;
     const u32 set_cap = 2 * (u32)b->P.max_num_soc;
     b->hpoolCap = 3 * ts + 1024;
     if( b->cWork.reserve( ts * sizeof( ma_seed ) ) || b->cMax.reserve( ts * sizeof( SoCEntry ) ) ||
@@ -94,8 +95,8 @@ int ma_chain_batch( ma_batch* b )
     A.set_cap = set_cap;
     A.nsets = b->nsets.as<u32>( );
     A.ctr = b->ctr.as<unsigned long long>( );
-    A.queue = b->socGiven ? b->socIn.as<ma_soc>( ) : nullptr;
-    A.queue_cnt = b->socGiven ? b->socInCnt.as<u32>( ) : nullptr;
+    A.queue = b->st.socGiven ? b->socIn.as<ma_soc>( ) : nullptr;
+    A.queue_cnt = b->st.socGiven ? b->socInCnt.as<u32>( ) : nullptr;
     A.pre_nmx = nullptr;
     A.pre_sorted = nullptr;
     // long reads (thousands of seeds per read): the sweep's two std::sort calls run as wave-cooperative kernels on arrays in
@@ -104,7 +105,7 @@ int ma_chain_batch( ma_batch* b )
         const char* e = getenv( "MA_CHAIN_WAVE_SORT" );
         return !e || atoi( e ) != 0;
     }( );
-    const bool waveSort = waveSortOn && !b->socGiven && b->max_qlen > 254 && b->nSeeds >= 64;
+    const bool waveSort = waveSortOn && !b->st.socGiven && b->max_qlen > 254 && b->st.nSeeds >= 64;
     {
         EvTimer t( b, 2 );
         A.lanes = lanes_per_wave( n );
@@ -167,8 +168,8 @@ int ma_chain_batch( ma_batch* b )
     MA_HIP( hipMemcpyAsync( &nhs, (char*)b->hseedOff.p + n * 8, 8, hipMemcpyDeviceToHost, b->stream ) );
     if( read_ctr( b ) || check_err( b, "ma_chain_batch" ) )
         return 1;
-    b->nHsets = nh;
-    b->nHseeds = nhs;
+    b->st.nHsets = nh;
+    b->st.nHseeds = nhs;
     if( b->hsetFlat.reserve( ( nh + 1 ) * sizeof( HSet ) ) || b->hsetRead.reserve( ( nh + 1 ) * 4 ) ||
         b->hdense.reserve( ( nhs + 1 ) * sizeof( ma_seed ) ) )
         return 1;
@@ -177,6 +178,6 @@ int ma_chain_batch( ma_batch* b )
                         b->hseedOff.as<u64>( ), b->seedOff.as<u64>( ), b->hlocal.as<ma_seed>( ), b->hpool.as<ma_seed>( ),
                         b->hdense.as<ma_seed>( ), b->hsetFlat.as<HSet>( ), b->hsetRead.as<u32>( ) );
     MA_HIP( hipGetLastError( ) );
-    b->stage_done = STAGE_CHAINED;
+    b->st.finish( ma_state::CHAINED );
     return 0;
 }

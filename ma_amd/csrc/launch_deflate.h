@@ -47,9 +47,9 @@ int sam_bgzf_state( ma_batch* b, int32_t pair, const char* who, bool needMembers
     if( !b )
         return fail( std::string( who ) + ": null batch" );
     *s = pair ? &b->pairSam : &b->sam;
-    if( !( *s )->done )
+    if( !b->st.has( ( *s )->id ) )
         return fail( std::string( who ) + ": no SAM text to deflate (run " + ( pair ? "ma_pair_sam_batch" : "ma_sam_batch" ) + " first)" );
-    if( needMembers && !( *s )->zDone )
+    if( needMembers && !b->st.has( ma_state::membersOf( ( *s )->id ) ) )
         return fail( std::string( who ) + ": run ma_sam_bgzf_batch first (making the SAM text again drops the members)" );
     return 0;
 }
@@ -63,7 +63,8 @@ int get_sam_bgzf( ma_batch* b, int32_t pair, uint64_t* member_off, void* bytes, 
     MA_BIND_DEVICE( b->device );
     if( download_begin( b, async, "ma_batch_start_sam_bgzf_download" ) )
         return 1;
-    if( s->zMembers == 0 )
+    const ma_state::TextCounts& c = b->st.text( s->id );
+    if( c.zMembers == 0 )
     {
         if( member_off )
             member_off[ 0 ] = 0;
@@ -73,9 +74,9 @@ int get_sam_bgzf( ma_batch* b, int32_t pair, uint64_t* member_off, void* bytes, 
     if( download_stream( b, async, &cs ) )
         return 1;
     if( member_off )
-        MA_HIP( hipMemcpyAsync( member_off, s->z.off.p, ( s->zMembers + 1 ) * 8, hipMemcpyDeviceToHost, cs ) );
+        MA_HIP( hipMemcpyAsync( member_off, s->z.off.p, ( c.zMembers + 1 ) * 8, hipMemcpyDeviceToHost, cs ) );
     if( bytes )
-        MA_HIP( hipMemcpyAsync( bytes, s->z.bytes.p, s->zBytes, hipMemcpyDeviceToHost, cs ) );
+        MA_HIP( hipMemcpyAsync( bytes, s->z.bytes.p, c.zBytes, hipMemcpyDeviceToHost, cs ) );
     return download_end( b, async, cs );
 }
 } // namespace
@@ -90,18 +91,18 @@ int ma_sam_bgzf_batch( ma_batch* b, int32_t pair )
     MA_BIND_DEVICE( b->device );
     if( download_wait( b ) ) // the members of the last call may still be on their way down
         return 1;
-    s->zDone = false;
-    s->zMembers = s->zBytes = 0;
-    if( s->bytes )
+    b->st.drop( ma_state::membersOf( s->id ) );
+    ma_state::TextCounts& c = b->st.text( s->id );
+    if( c.bytes )
     {
         unsigned long long total = 0;
         if( b->timing )
             (void)hipEventRecord( b->ev[ 14 ], b->stream );
-        if( deflate_front( b->stream, s->text.as<uint8_t>( ), s->bytes, b->zScratch, s->z, &total ) )
+        if( deflate_front( b->stream, s->text.as<uint8_t>( ), c.bytes, b->zScratch, s->z, &total ) )
             return 1;
         if( batch_wait( b ) )
             return 1;
-        if( deflate_rest( b->stream, s->text.as<uint8_t>( ), s->bytes, b->zScratch, s->z, total ) )
+        if( deflate_rest( b->stream, s->text.as<uint8_t>( ), c.bytes, b->zScratch, s->z, total ) )
             return 1;
         if( b->timing )
         {
@@ -110,10 +111,10 @@ int ma_sam_bgzf_batch( ma_batch* b, int32_t pair )
             if( hipEventSynchronize( b->ev[ 15 ] ) == hipSuccess && hipEventElapsedTime( &ms, b->ev[ 14 ], b->ev[ 15 ] ) == hipSuccess )
                 b->kms[ 7 ] = ms;
         }
-        s->zMembers = ma_bgzf::deflateMembers( s->bytes );
-        s->zBytes = total;
+        c.zMembers = ma_bgzf::deflateMembers( c.bytes );
+        c.zBytes = total;
     }
-    s->zDone = true;
+    b->st.finish( ma_state::membersOf( s->id ) );
     return 0;
 }
 
@@ -123,9 +124,9 @@ int ma_batch_sam_bgzf_counts( ma_batch* b, int32_t pair, uint64_t* n_members, ui
     if( sam_bgzf_state( b, pair, "ma_batch_sam_bgzf_counts", true, &s ) )
         return 1;
     if( n_members )
-        *n_members = s->zMembers;
+        *n_members = b->st.text( s->id ).zMembers;
     if( n_bytes )
-        *n_bytes = s->zBytes;
+        *n_bytes = b->st.text( s->id ).zBytes;
     return 0;
 }
 

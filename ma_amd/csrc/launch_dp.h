@@ -47,11 +47,11 @@ static bool dp_one_stream( )
 
 int ma_dp_batch( ma_batch* b )
 {
-    if( !b || b->stage_done < STAGE_CHAINED )
+    if( !b || !b->st.has( ma_state::CHAINED ) )
         return fail( "ma_dp_batch: run ma_chain_batch first" );
     MA_BIND_DEVICE( b->device );
-    const u64 n = b->n_reads, nh = b->nHsets, nhs = b->nHseeds;
-    batch_results_changed( b );
+    const u64 n = b->n_reads, nh = b->st.nHsets, nhs = b->st.nHseeds;
+    b->st.drop( ma_state::ALIGNED );
     if( b->mqCnt.reserve( ( n + 1 ) * 4 ) )
         return 1;
     MA_HIP( hipMemsetAsync( b->mqCnt.p, 0, ( n + 1 ) * 4, b->stream ) );
@@ -62,12 +62,13 @@ int ma_dp_batch( ma_batch* b )
     MA_HIP( hipMemsetAsync( b->ctr.as<unsigned long long>( ) + CTR_OPS_ALL, 0, ( CTR_COUNT - CTR_OPS_ALL ) * 8, b->stream ) );
     if( n == 0 || nh == 0 )
     {
-        b->nJobSlots = 0;
-        b->stage_done = STAGE_ALIGNED;
-        return read_ctr( b );
+        if( read_ctr( b ) )
+            return 1;
+        b->st.finish( ma_state::ALIGNED );
+        return 0;
     }
     const u64 nSlots = 2 * nhs;
-    b->nJobSlots = nSlots;
+    b->st.nJobSlots = nSlots;
     if( b->jobs.reserve( ( nSlots + 2 ) * sizeof( DpJob ) ) || b->info.reserve( nh * sizeof( SetInfo ) ) ||
         b->ez.reserve( ( nSlots + 2 ) * sizeof( ma_ez ) ) || b->clsLists.reserve( ( ( KSW_N_CLASSES + 2 ) * nSlots + 2 ) * 4 ) || b->cigOff.reserve( ( nSlots + 2 ) * 8 ) ||
         b->opsCap.reserve( ( nh + 1 ) * 8 ) || b->opsOff.reserve( ( nh + 2 ) * 8 ) ||
@@ -312,7 +313,7 @@ int ma_dp_batch( ma_batch* b )
                             b->ctr.as<unsigned long long>( ), 1 );
     }
     MA_HIP( hipGetLastError( ) );
-    b->stage_done = STAGE_ALIGNED;
+    b->st.finish( ma_state::ALIGNED );
     return 0;
 }
 
@@ -329,7 +330,6 @@ int ma_batch_set_alignments( ma_batch* b, const uint64_t* aln_off, const ma_alig
     if( na && !alns )
         return fail( "ma_batch_set_alignments: null argument" );
     MA_BIND_DEVICE( b->device );
-    batch_results_changed( b );
     u64 no = 0;
     for( u64 i = 0; i < na; i++ )
         no += alns[ i ].n_ops;
@@ -359,6 +359,7 @@ int ma_batch_set_alignments( ma_batch* b, const uint64_t* aln_off, const ma_alig
             pk[ w++ ] = op_pack( (u32)t, l );
         }
     }
+    b->st.drop( ma_state::ALIGNED );
     if( reset_ctr( b ) || b->hsetOff.reserve( ( n + 2 ) * 8 ) || b->hdr.reserve( ( na + 1 ) * sizeof( AlnHeader ) ) ||
         b->ops.reserve( ( no + 2 ) * 8 ) || b->order.reserve( ( na + 1 ) * 4 ) || b->mqOrder.reserve( ( na + 1 ) * 4 ) ||
         b->mqCnt.reserve( ( n + 1 ) * 4 ) )
@@ -378,10 +379,9 @@ int ma_batch_set_alignments( ma_batch* b, const uint64_t* aln_off, const ma_alig
     MA_HIP( hipGetLastError( ) );
     if( batch_wait( b ) )
         return 1; // the host vectors go out of scope
-    b->nHsets = na; // one alignment per harmonized set: the bookkeeping get_alns walks
-    b->nHseeds = 0;
-    b->nJobSlots = 0;
+    b->st.nHsets = na; // one alignment per harmonized set: the bookkeeping get_alns walks
+    b->st.nHseeds = 0;
     b->nOpsCap = no; // (the pool's fill: ma_inversions_batch appends behind it)
-    b->stage_done = STAGE_ALIGNED;
+    b->st.finish( ma_state::ALIGNED );
     return 0;
 }

@@ -1,19 +1,20 @@
 // launch_extract.h -- host side of seed extraction: ma_extract_seeds_batch (C ABI).  Textually part of pipeline.hip.
 int ma_extract_seeds_batch( ma_batch* b )
 {
-    if( !b || b->stage_done < STAGE_SEEDED )
+    if( !b || !b->st.has( ma_state::SEEDED ) )
         return fail( "ma_extract_seeds_batch: run ma_seed_batch first" );
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads;
+    b->st.drop( ma_state::EXTRACTED );
     if( n == 0 )
     {
-        b->socGiven = false, b->stage_done = STAGE_EXTRACTED;
+        b->st.finish( ma_state::EXTRACTED );
         return 0;
     }
     if( read_ctr( b ) || check_err( b, "ma_seed_batch" ) )
         return 1;
-    b->nSegs = b->hctr[ CTR_SEG_USED ];
-    const u64 ns = b->nSegs;
+    b->st.nSegs = b->hctr[ CTR_SEG_USED ];
+    const u64 ns = b->st.nSegs;
     if( b->segSeedCnt.reserve( ( ns + 1 ) * 8 ) || b->segSeedOff.reserve( ( ns + 2 ) * 8 ) ||
         b->seedOff.reserve( n * 8 ) || b->seedCnt.reserve( n * 4 ) )
         return 1;
@@ -31,7 +32,7 @@ int ma_extract_seeds_batch( ma_batch* b )
         if( batch_wait( b ) )
         return 1;
     }
-    b->nSeeds = total;
+    b->st.nSeeds = total;
     if( b->seeds.reserve( ( total + 1 ) * sizeof( ma_seed ) ) )
         return 1;
     hipLaunchKernelGGL( k_read_seed_ranges, dim3( (unsigned)( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream,
@@ -54,7 +55,7 @@ int ma_extract_seeds_batch( ma_batch* b )
                             b->seeds.as<ma_seed>( ), c );
     }
     MA_HIP( hipGetLastError( ) );
-    b->socGiven = false, b->stage_done = STAGE_EXTRACTED;
+    b->st.finish( ma_state::EXTRACTED );
     return 0;
 }
 

@@ -25,7 +25,7 @@ InvKernelArgs inv_args( ma_batch* b )
     A.P = ma_inv::params( b->P );
     A.NP = nw_params( b->P );
     A.n_reads = (u32)b->n_reads;
-    A.n_slots = b->nHsets;
+    A.n_slots = b->st.nHsets;
     A.off = b->hsetOff.as<u64>( ); // always the MappingQuality output itself, never the final lists of a call before
     A.hdr = b->hdr.as<AlnHeader>( );
     A.order = b->mqOrder.as<u32>( );
@@ -64,29 +64,21 @@ int inv_fail( ma_batch* b, u64 key )
 }
 } // namespace
 
-// puts the list view (mq_view) back on the MappingQuality arrays
-static void inv_reset( ma_batch* b )
-{
-    b->invDone = b->invFinal = false;
-    b->invCands = b->invJobsN = b->invRecs = b->invOps = 0;
-}
-
 extern "C" {
 
 int ma_inversions_batch( ma_batch* b )
 {
     if( !b )
         return fail( "ma_inversions_batch: null batch" );
-    if( b->stage_done < STAGE_ALIGNED )
+    if( !b->st.has( ma_state::ALIGNED ) )
         return fail( "ma_inversions_batch: no MappingQuality output to scan (run ma_dp_batch / ma_align_batch / ma_batch_set_alignments first)" );
     MA_BIND_DEVICE( b->device );
-    // pairs and texts made before are of other lists
-    batch_results_changed( b );
-    b->stage_done = STAGE_ALIGNED;
-    const u64 n = b->n_reads, nh = b->nHsets;
+    // pairs and texts made before are of other lists; the list view (mq_view) is back on the MappingQuality arrays
+    b->st.drop( ma_state::INVERSIONS );
+    const u64 n = b->n_reads, nh = b->st.nHsets;
     if( n == 0 || nh == 0 )
     {
-        b->invDone = true;
+        b->st.finish( ma_state::INVERSIONS );
         return 0;
     }
     if( b->invStat.reserve( INV_STAT_COUNT * 8 ) || b->invSlotCnt.reserve( ( nh + 1 ) * 4 ) || b->invSlotFirst.reserve( ( nh + 1 ) * 8 ) )
@@ -120,11 +112,11 @@ int ma_inversions_batch( ma_batch* b )
         b->invWinCap = std::max<u64>( b->invWinCap, stat[ INV_STAT_WIN ] + stat[ INV_STAT_WIN ] / 4 );
     }
     const u64 nc = stat[ INV_STAT_CAND ];
-    b->invCands = nc;
-    b->invJobsN = stat[ INV_STAT_JOBS ];
+    b->st.invCands = nc;
+    b->st.invJobsN = stat[ INV_STAT_JOBS ];
     if( nc == 0 ) // nothing found: the view stays on the MappingQuality arrays
     {
-        b->invDone = true;
+        b->st.finish( ma_state::INVERSIONS );
         return 0;
     }
     // the DP of all candidates at once: kswcpp_dispatch( ..., uiBandwidth, uiZDrop, 0, ... ) (smallInversions.h:131-133)
@@ -186,23 +178,22 @@ int ma_inversions_batch( ma_batch* b )
         return fail( "obtained wierd symbol from ksw" ); // (the host module's text, smallInversions.h:167)
     if( stat[ INV_STAT_FLAGS ] )
         return fail( "ma_inversions_batch: device capacity overflow: alignment-ops" );
-    b->invRecs = stat[ INV_STAT_RECS ];
-    b->invOps = stat[ INV_STAT_REC_OPS ];
-    b->invFinal = b->invRecs != 0; // (no record kept: the final lists would be the MappingQuality lists)
-    b->invDone = true;
+    b->st.invRecs = stat[ INV_STAT_RECS ];
+    b->st.invOps = stat[ INV_STAT_REC_OPS ];
+    b->st.finish( ma_state::INVERSIONS ); // (no record kept: the view stays on the MappingQuality lists, BatchState::invFinal)
     return 0;
 }
 
 int ma_batch_inversion_counts( ma_batch* b, uint64_t* n_candidates, uint64_t* n_jobs, uint64_t* n_records )
 {
-    if( !b || !b->invDone )
+    if( !b || !b->st.has( ma_state::INVERSIONS ) )
         return fail( "ma_batch_inversion_counts: run ma_inversions_batch first" );
     if( n_candidates )
-        *n_candidates = b->invCands;
+        *n_candidates = b->st.invCands;
     if( n_jobs )
-        *n_jobs = b->invJobsN;
+        *n_jobs = b->st.invJobsN;
     if( n_records )
-        *n_records = b->invRecs;
+        *n_records = b->st.invRecs;
     return 0;
 }
 } // extern "C"

@@ -100,18 +100,15 @@ int ma_pair_batch( ma_batch* b )
 {
     if( !b )
         return fail( "ma_pair_batch: null batch" );
-    if( b->stage_done < STAGE_ALIGNED )
+    if( !b->st.has( ma_state::ALIGNED ) )
         return fail( "ma_pair_batch: no MappingQuality output to pair (run ma_dp_batch / ma_align_batch first)" );
     if( b->n_reads % 2 )
         return fail( "ma_pair_batch: odd number of reads (" + std::to_string( b->n_reads ) +
                      "): reads 2k and 2k+1 of a batch are the mates of pair k" );
     MA_BIND_DEVICE( b->device );
     const u64 np = b->n_reads / 2;
-    b->pairOnHost = 0;
-    b->pairRecs = b->pairNOps = 0;
-    b->pairSam.done = false; // (a text printed before is of other picks)
-    b->stage_done = STAGE_ALIGNED;
-    if( np && b->nHsets )
+    b->st.drop( ma_state::PAIRS ); // (a pairs' text printed before is of other picks; the single-end text does not read them)
+    if( np && b->st.nHsets )
     {
         if( b->pairPick.reserve( np * sizeof( ma_pair::Pick ) ) || b->pairCnt.reserve( ( np + 2 ) * 8 ) || b->pairOps.reserve( ( np + 2 ) * 8 ) ||
             b->pairOver.reserve( ( np + 1 ) * 4 ) )
@@ -124,28 +121,28 @@ int ma_pair_batch( ma_batch* b )
             return 1;
         if( b->hctr[ CTR_PAIR_ERR ] )
             return fail( ma_pair::noCandidateText( ) );
-        b->pairOnHost = b->hctr[ CTR_PAIR_OVER ];
-        if( b->pairOnHost && pair_finish_on_host( b, A ) )
+        b->st.pairOnHost = b->hctr[ CTR_PAIR_OVER ];
+        if( b->st.pairOnHost && pair_finish_on_host( b, A ) )
             return 1;
-        b->pairRecs = b->hctr[ CTR_PAIR_RECS ];
-        b->pairNOps = b->hctr[ CTR_PAIR_OPS ];
+        b->st.pairRecs = b->hctr[ CTR_PAIR_RECS ];
+        b->st.pairNOps = b->hctr[ CTR_PAIR_OPS ];
     }
-    b->stage_done = STAGE_PAIRED;
+    b->st.finish( ma_state::PAIRS );
     return 0;
 }
 
 int ma_batch_pair_counts( ma_batch* b, uint64_t* n_pairs, uint64_t* n_records, uint64_t* n_ops, uint64_t* n_host_pairs )
 {
-    if( !b || b->stage_done < STAGE_PAIRED )
+    if( !b || !b->st.has( ma_state::PAIRS ) )
         return fail( "ma_batch_pair_counts: run ma_pair_batch first" );
     if( n_pairs )
         *n_pairs = b->n_reads / 2;
     if( n_records )
-        *n_records = b->pairRecs;
+        *n_records = b->st.pairRecs;
     if( n_ops )
-        *n_ops = b->pairNOps;
+        *n_ops = b->st.pairNOps;
     if( n_host_pairs )
-        *n_host_pairs = b->pairOnHost;
+        *n_host_pairs = b->st.pairOnHost;
     return 0;
 }
 } // extern "C"
@@ -153,12 +150,12 @@ int ma_batch_pair_counts( ma_batch* b, uint64_t* n_pairs, uint64_t* n_records, u
 // async: see get_alns
 static int get_pairs( ma_batch* b, uint64_t* pair_off, ma_alignment* alns, uint64_t* ops, int32_t* mate, int32_t* other, bool async )
 {
-    if( !b || b->stage_done < STAGE_PAIRED )
+    if( !b || !b->st.has( ma_state::PAIRS ) )
         return fail( "ma_batch_get_pairs: run ma_pair_batch first" );
     MA_BIND_DEVICE( b->device );
     if( download_begin( b, async, "ma_batch_start_pair_download" ) )
         return 1;
-    const u64 np = b->n_reads / 2, totalA = b->pairRecs, totalO = b->pairNOps;
+    const u64 np = b->n_reads / 2, totalA = b->st.pairRecs, totalO = b->st.pairNOps;
     if( totalA == 0 )
     {
         if( pair_off )

@@ -27,7 +27,7 @@ SamKernelArgs sam_args( ma_batch* b, u32 options )
     A.mq_cnt = V.cnt;
     A.names = b->txtNames.as<char>( );
     A.name_off = b->txtNameOff.as<u64>( );
-    A.qual = b->txtHasQual ? b->txtQual.as<uint8_t>( ) : nullptr;
+    A.qual = b->st.hasQual ? b->txtQual.as<uint8_t>( ) : nullptr;
     A.ref = ma_sam::Ref{ x->v.pac, x->holeStart.as<u64>( ), x->holeLen.as<u64>( ), x->nHoles, x->v.F };
     return A;
 }
@@ -86,7 +86,7 @@ PairSamKernelArgs pair_sam_args( ma_batch* b, u32 options )
     A.contigs = ma_sam::Contigs{ x->cnames.as<char>( ), x->cnameOff.as<u64>( ), x->v.cstart, x->v.clen, (u32)x->v.n_contigs };
     A.options = options;
     A.n_pairs = (u32)( b->n_reads / 2 );
-    A.picks_valid = b->nHsets ? 1u : 0u; // (ma_pair_batch launches nothing without harmonized sets)
+    A.picks_valid = b->st.nHsets ? 1u : 0u; // (ma_pair_batch launches nothing without harmonized sets)
     const MqView V = mq_view( b );
     A.hset_off = V.off;
     A.roff = b->d_roff;
@@ -98,7 +98,7 @@ PairSamKernelArgs pair_sam_args( ma_batch* b, u32 options )
     A.pick = b->pairPick.as<ma_pair::Pick>( );
     A.names = b->txtNames.as<char>( );
     A.name_off = b->txtNameOff.as<u64>( );
-    A.qual = b->txtHasQual ? b->txtQual.as<uint8_t>( ) : nullptr;
+    A.qual = b->st.hasQual ? b->txtQual.as<uint8_t>( ) : nullptr;
     return A;
 }
 
@@ -140,8 +140,7 @@ int sam_text_launch( ma_batch* b, SamTextState& s, u64 n, Args A )
 {
     if( download_wait( b ) ) // the text of the last call may still be on its way down
         return 1;
-    s.done = s.zDone = false; // (the members of ma_sam_bgzf_batch are of the text before)
-    s.bytes = 0;
+    b->st.drop( s.id ); // (the members of ma_sam_bgzf_batch are of the text before)
     if( n )
     {
         if( s.cnt.reserve( ( n + 2 ) * 8 ) || s.off.reserve( ( n + 2 ) * 8 ) || s.stat.reserve( SAM_STAT_COUNT * 8 ) ||
@@ -172,9 +171,9 @@ int sam_text_launch( ma_batch* b, SamTextState& s, u64 n, Args A )
         A.text = s.text.as<char>( );
         hipLaunchKernelGGL( WriteKernel, grid, block, 0, b->stream, A );
         MA_HIP( hipGetLastError( ) );
-        s.bytes = stat[ SAM_STAT_BYTES ];
+        b->st.text( s.id ).bytes = stat[ SAM_STAT_BYTES ];
     }
-    s.done = true;
+    b->st.finish( s.id );
     return 0;
 }
 } // namespace
@@ -255,7 +254,7 @@ int ma_batch_set_read_text( ma_batch* b, const char* names, const uint64_t* name
         if( name_off[ i + 1 ] < name_off[ i ] )
             return fail( "ma_batch_set_read_text: offsets decrease" );
     MA_BIND_DEVICE( b->device );
-    b->txtSet = b->sam.done = b->pairSam.done = false;
+    b->st.drop( ma_state::NAMES ); // (both texts were printed with the names before)
     if( b->txtNames.reserve( name_off[ n ] + 1 ) || b->txtNameOff.reserve( ( n + 1 ) * 8 ) || ( qual && b->txtQual.reserve( b->n_bases + 1 ) ) )
         return 1;
     if( name_off[ n ] )
@@ -265,9 +264,9 @@ int ma_batch_set_read_text( ma_batch* b, const char* names, const uint64_t* name
         MA_HIP( hipMemcpyAsync( b->txtQual.p, qual, b->n_bases, hipMemcpyHostToDevice, b->stream ) );
     if( batch_wait( b ) )
         return 1; // the caller's arrays are free again
-    b->txtHasQual = qual != nullptr;
-    b->txtNameBytes = name_off[ n ];
-    b->txtSet = true;
+    b->st.hasQual = qual != nullptr;
+    b->st.nameBytes = name_off[ n ];
+    b->st.finish( ma_state::NAMES );
     return 0;
 }
 
@@ -275,13 +274,13 @@ int ma_sam_batch( ma_batch* b, uint32_t options )
 {
     if( !b )
         return fail( "ma_sam_batch: null batch" );
-    if( b->stage_done < STAGE_ALIGNED )
+    if( !b->st.has( ma_state::ALIGNED ) )
         return fail( "ma_sam_batch: no MappingQuality output to print (run ma_dp_batch / ma_align_batch / ma_batch_set_alignments first)" );
     if( options & ~(uint32_t)ma_sam::ALL_OPTIONS )
         return fail( "ma_sam_batch: unknown option bits " + std::to_string( options & ~(uint32_t)ma_sam::ALL_OPTIONS ) );
     if( !b->idx->namesSet )
         return fail( "ma_sam_batch: the index has no contig names (ma_index_set_contig_names)" );
-    if( !b->txtSet )
+    if( !b->st.has( ma_state::NAMES ) )
         return fail( "ma_sam_batch: the reads have no names (ma_batch_set_read_text after the reads were set)" );
     MA_BIND_DEVICE( b->device );
     if( options & ma_sam::NGMLR_TAGS )
@@ -293,13 +292,13 @@ int ma_pair_sam_batch( ma_batch* b, uint32_t options )
 {
     if( !b )
         return fail( "ma_pair_sam_batch: null batch" );
-    if( b->stage_done < STAGE_PAIRED )
+    if( !b->st.has( ma_state::PAIRS ) )
         return fail( "ma_pair_sam_batch: no pairs to print (run ma_pair_batch first)" );
     if( options & ~(uint32_t)ma_sam::PAIR_OPTIONS ) // (the tag emulation is the single-end writer's)
         return fail( "ma_pair_sam_batch: unknown option bits " + std::to_string( options & ~(uint32_t)ma_sam::PAIR_OPTIONS ) );
     if( !b->idx->namesSet )
         return fail( "ma_pair_sam_batch: the index has no contig names (ma_index_set_contig_names)" );
-    if( !b->txtSet )
+    if( !b->st.has( ma_state::NAMES ) )
         return fail( "ma_pair_sam_batch: the reads have no names (ma_batch_set_read_text after the reads were set)" );
     MA_BIND_DEVICE( b->device );
     return sam_text_launch<PairSamKernelArgs, k_pair_sam_size, k_pair_sam_write, pair_sam_fail>( b, b->pairSam, b->n_reads / 2,
@@ -308,21 +307,21 @@ int ma_pair_sam_batch( ma_batch* b, uint32_t options )
 
 int ma_batch_sam_counts( ma_batch* b, uint64_t* n_bytes )
 {
-    if( !b || !b->sam.done )
+    if( !b || !b->st.has( ma_state::SAM ) )
         return fail( "ma_batch_sam_counts: run ma_sam_batch first" );
     if( n_bytes )
-        *n_bytes = b->sam.bytes;
+        *n_bytes = b->st.sam.bytes;
     return 0;
 }
 
 int ma_batch_pair_sam_counts( ma_batch* b, uint64_t* n_pairs, uint64_t* n_bytes )
 {
-    if( !b || !b->pairSam.done )
+    if( !b || !b->st.has( ma_state::PAIR_SAM ) )
         return fail( "ma_batch_pair_sam_counts: run ma_pair_sam_batch first" );
     if( n_pairs )
         *n_pairs = b->n_reads / 2;
     if( n_bytes )
-        *n_bytes = b->pairSam.bytes;
+        *n_bytes = b->st.pairSam.bytes;
     return 0;
 }
 } // extern "C"
@@ -331,6 +330,7 @@ int ma_batch_pair_sam_counts( ma_batch* b, uint64_t* n_pairs, uint64_t* n_bytes 
 static int get_sam_text( ma_batch* b, const SamTextState& s, u64 n, const char* start, uint64_t* off, char* text, bool async )
 {
     MA_BIND_DEVICE( b->device );
+    const u64 bytes = b->st.text( s.id ).bytes;
     if( download_begin( b, async, start ) )
         return 1;
     if( n == 0 )
@@ -344,20 +344,20 @@ static int get_sam_text( ma_batch* b, const SamTextState& s, u64 n, const char* 
         return 1;
     if( off )
         MA_HIP( hipMemcpyAsync( off, s.off.p, ( n + 1 ) * 8, hipMemcpyDeviceToHost, cs ) );
-    if( text && s.bytes )
-        MA_HIP( hipMemcpyAsync( text, s.text.p, s.bytes, hipMemcpyDeviceToHost, cs ) );
+    if( text && bytes )
+        MA_HIP( hipMemcpyAsync( text, s.text.p, bytes, hipMemcpyDeviceToHost, cs ) );
     return download_end( b, async, cs );
 }
 
 static int get_sam( ma_batch* b, uint64_t* rec_off, char* text, bool async )
 {
-    if( !b || !b->sam.done )
+    if( !b || !b->st.has( ma_state::SAM ) )
         return fail( "ma_batch_get_sam: run ma_sam_batch first" );
     return get_sam_text( b, b->sam, b->n_reads, "ma_batch_start_sam_download", rec_off, text, async );
 }
 static int get_pair_sam( ma_batch* b, uint64_t* pair_off, char* text, bool async )
 {
-    if( !b || !b->pairSam.done )
+    if( !b || !b->st.has( ma_state::PAIR_SAM ) )
         return fail( "ma_batch_get_pair_sam: run ma_pair_sam_batch first" );
     return get_sam_text( b, b->pairSam, b->n_reads / 2, "ma_batch_start_pair_sam_download", pair_off, text, async );
 }

@@ -75,7 +75,6 @@ static int seed_mems( ma_batch* b )
     if( batch_wait( b ) )
         return 1;
     MA_HIP( hipGetLastError( ) );
-    b->stage_done = STAGE_SEEDED;
     return 0;
 }
 
@@ -210,24 +209,16 @@ static int seed_tasks( ma_batch* b )
     hipLaunchKernelGGL( k_task_finish, dim3( (unsigned)( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream, b->idx->v, seed_params( b->P ),
                         b->d_roff, (u32)n, b->segPool.as<ma_segment>( ), b->segOff.as<u64>( ), b->segCnt.as<u32>( ) );
     MA_HIP( hipGetLastError( ) );
-    b->stage_done = STAGE_SEEDED;
     return 0;
 }
 
-int ma_seed_batch( ma_batch* b )
+// the stage itself, by one of its three launch paths; ma_seed_batch keeps the state around it
+static int seed_run( ma_batch* b )
 {
-    if( !b || !b->d_roff )
-        return fail( "ma_seed_batch: no reads set" );
-    MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads;
     MA_HIP( hipMemsetAsync( b->ctr.p, 0, CTR_COUNT * 8, b->stream ) );
-    b->nSegs = b->nSeeds = b->nHsets = b->nHseeds = 0;
-    b->segMarked = false;
     if( n == 0 )
-    {
-        b->stage_done = STAGE_SEEDED;
         return 0;
-    }
     if( b->P.seeding_technique == 2 )
         return seed_mems( b );
     // few long reads: one lane per AREA of the recursion instead of one per read.  With >= 128 k reads in the batch the
@@ -330,7 +321,7 @@ int ma_seed_batch( ma_batch* b )
                 text = text && atoi( e ) != 0;
             if( text )
             {
-                b->segMarked = true;
+                b->st.markSegments( true );
                 hipLaunchKernelGGL( ( k_seed<false, true> ), dim3( (unsigned)( lanes / 256 ) ), dim3( 256 ), A.q_lds * 256, b->stream, A );
             }
             else if( A.q_lds )
@@ -364,6 +355,17 @@ int ma_seed_batch( ma_batch* b )
             break; // surfaces as an error in the next stage
         MA_HIP( hipMemsetAsync( b->ctr.p, 0, CTR_COUNT * 8, b->stream ) );
     }
-    b->stage_done = STAGE_SEEDED;
+    return 0;
+}
+
+int ma_seed_batch( ma_batch* b )
+{
+    if( !b || !b->d_roff )
+        return fail( "ma_seed_batch: no reads set" );
+    MA_BIND_DEVICE( b->device );
+    b->st.drop( ma_state::SEEDED );
+    if( seed_run( b ) )
+        return 1;
+    b->st.finish( ma_state::SEEDED );
     return 0;
 }

@@ -7,7 +7,7 @@ static int text_no_reads( ma_batch* b )
     b->n_reads = b->n_bases = 0;
     b->max_qlen = 0;
     batch_own_reads( b );
-    batch_reads_changed( b );
+    b->st.newReads( );
     MA_HIP( hipMemsetAsync( b->roff.p, 0, 8, b->stream ) );
     return 0;
 }
@@ -17,7 +17,7 @@ static int text_empty( ma_batch* b )
 {
     if( batch_wait( b ) )
         return 1;
-    b->txtSet = true;
+    b->st.finish( ma_state::NAMES );
     return 0;
 }
 
@@ -162,9 +162,9 @@ static int text_single_rest( ma_batch* b, TextFront& t, unsigned long long* h, c
     b->n_reads = h[ TXT_READS ];
     b->n_bases = h[ TXT_BASES ];
     b->max_qlen = (u32)h[ TXT_MAX_LEN ];
-    b->txtNameBytes = h[ TXT_NAME_BYTES ];
-    b->txtHasQual = t.kind == ma_text::KIND_FASTQ;
-    b->txtSet = true;
+    b->st.nameBytes = h[ TXT_NAME_BYTES ];
+    b->st.hasQual = t.kind == ma_text::KIND_FASTQ;
+    b->st.finish( ma_state::NAMES );
     if( n_reads )
         *n_reads = b->n_reads;
     return 0;
@@ -309,9 +309,9 @@ int ma_batch_set_mates_text( ma_batch* b, const char* text1, uint64_t n1, const 
     b->n_reads = 2 * h[ MT_PAIRS ];
     b->n_bases = h[ MT_BASES ];
     b->max_qlen = (u32)h[ MT_MAX_LEN ];
-    b->txtNameBytes = h[ MT_NAME_BYTES ];
-    b->txtHasQual = fastq;
-    b->txtSet = true;
+    b->st.nameBytes = h[ MT_NAME_BYTES ];
+    b->st.hasQual = fastq;
+    b->st.finish( ma_state::NAMES );
     if( n_pairs )
         *n_pairs = h[ MT_PAIRS ];
     if( consumed )
@@ -328,9 +328,9 @@ int ma_batch_read_counts( ma_batch* b, uint64_t* n_reads, uint64_t* n_bases, uin
     if( n_bases )
         *n_bases = b->d_roff ? b->n_bases : 0;
     if( n_name_bytes )
-        *n_name_bytes = b->txtSet ? b->txtNameBytes : 0;
+        *n_name_bytes = b->st.has( ma_state::NAMES ) ? b->st.nameBytes : 0;
     if( has_qual )
-        *has_qual = b->txtSet && b->txtHasQual ? 1 : 0;
+        *has_qual = b->st.has( ma_state::NAMES ) && b->st.hasQual ? 1 : 0;
     return 0;
 }
 
@@ -348,15 +348,15 @@ int ma_batch_get_reads( ma_batch* b, uint64_t* offsets, uint8_t* codes )
 
 int ma_batch_get_read_text( ma_batch* b, uint64_t* name_off, char* names, uint8_t* qual )
 {
-    if( !b || !b->d_roff || !b->txtSet )
+    if( !b || !b->d_roff || !b->st.has( ma_state::NAMES ) )
         return fail( "ma_batch_get_read_text: the reads have no names (ma_batch_set_read_text or ma_batch_set_reads_text)" );
-    if( qual && !b->txtHasQual )
+    if( qual && !b->st.hasQual )
         return fail( "ma_batch_get_read_text: the reads have no qualities" );
     MA_BIND_DEVICE( b->device );
     if( name_off )
         MA_HIP( hipMemcpyAsync( name_off, b->txtNameOff.p, ( b->n_reads + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
-    if( names && b->txtNameBytes )
-        MA_HIP( hipMemcpyAsync( names, b->txtNames.p, b->txtNameBytes, hipMemcpyDeviceToHost, b->stream ) );
+    if( names && b->st.nameBytes )
+        MA_HIP( hipMemcpyAsync( names, b->txtNames.p, b->st.nameBytes, hipMemcpyDeviceToHost, b->stream ) );
     if( qual && b->n_bases )
         MA_HIP( hipMemcpyAsync( qual, b->txtQual.p, b->n_bases, hipMemcpyDeviceToHost, b->stream ) );
     return batch_wait( b );

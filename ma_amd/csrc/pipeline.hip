@@ -96,6 +96,8 @@ static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0
 // the device deflate of the SAM texts into BGZF members: ma_sam_bgzf_batch (launch_deflate.h)
 #include "../host/ma_deflate_dev.h"
 #include "stage_deflate.h"
+// what of a batch is valid, and what a call takes away (every entry point: drop on entry, finish on success)
+#include "../host/ma_batch_state.h"
 
 // ------------------------------------------------------------------------------------------------
 // batch object
@@ -112,19 +114,14 @@ struct DeflateMembers
 {
     DevBuf off, bytes;
 };
-// z*: the text's BGZF members (ma_sam_bgzf_batch), valid while done and zDone: making the text again drops them
+// z: the text's BGZF members (ma_sam_bgzf_batch).  id: the text's product in the batch's state (ma_state::SAM or PAIR_SAM), where
+// its validity, its bytes and the members' counts are
 struct SamTextState
 {
+    const ma_state::Product id;
     DevBuf cnt, off, seqPos, text, stat;
-    bool done = false;
-    u64 bytes = 0;
     DeflateMembers z;
-    bool zDone = false;
-    u64 zMembers = 0, zBytes = 0;
 };
-
-// how far a batch's reads have come (ma_batch::stage_done), in order; ALIGNED: DP + MappingQuality, or lists handed in
-enum Stage { STAGE_NONE, STAGE_SEEDED, STAGE_EXTRACTED, STAGE_CHAINED, STAGE_ALIGNED, STAGE_PAIRED };
 
 struct ma_batch
 {
@@ -143,29 +140,23 @@ struct ma_batch
     DevBuf stage, smemA, smemB, segPool, segRead, segOff, segCnt, memsCnt, memsOff;
     DevBuf taskA, taskB, taskCnt, taskKey, taskKey2, taskPerm, taskPerm2, taskStage; // (taskStage: per-lane segments of an SMEM task) // area tasks of long reads (seed_tasks)
     u64 segPoolCap = 0, segPoolMin = 0;
-    bool segMarked = false; // the pool may hold segments that carry a position instead of rows (seeding.h: text mode); see seg_materialise
     // extraction
     DevBuf segSeedCnt, segSeedOff, seedOff, seedCnt, seeds, cubTmp;
-    u64 nSegs = 0, nSeeds = 0;
     // chaining
     DevBuf cWork, cMax, cMm, cA, cB, cOut, cSh1, cSh2, cVx, cVy, cMed, cInl, cBest, hpool, setTab, nsets, hsetOff,
         hsetFlat, hsetRead;
-    u64 hpoolCap = 0, nHsets = 0, nHseeds = 0;
+    u64 hpoolCap = 0;
     DevBuf socIn, socInCnt; // SoC queues swept elsewhere (ma_batch_set_soc_heap), carved by seed offset
     DevBuf preNmx, preSorted; // long reads: strips per read after k_soc_windows, which sorts k_sort_seeds_wave did
-    bool socGiven = false;
     // dp
     DevBuf jobs, info, ez, cigOff, cigPool, kswScratch, clsLists, opsCap, opsOff, ops, hdr, order, mqOrder, mqCnt;
     DevBuf outCnt, outOps, outAlnOff, outOpsOff, outAlns, outOpsPairs; // packed results (get_alns)
     DevBuf sortKey, sortKey2, sortVal2; // longest-job-first order of the DP job lists
     // pairing (ma_pair_batch): per pair its pick and sizes, the pairs left to the host and their round trip, the packed columns
     DevBuf pairPick, pairCnt, pairOps, pairOver, pairHostOff, pairHostLists, pairHostPick, pairMate, pairOther;
-    u64 pairRecs = 0, pairNOps = 0, pairOnHost = 0;
     // SAM text: the reads' names and qualities (ma_batch_set_read_text; dropped when reads are set), the single-end text per
     // read (ma_sam_batch) and the paired-end text per pair (ma_pair_sam_batch), each all of its own: one never touches the other
     DevBuf txtNames, txtNameOff, txtQual;
-    bool txtSet = false, txtHasQual = false;
-    u64 txtNameBytes = 0;
     // read text parsed on the device (ma_batch_set_reads_text, launch_text.h), reserved on first use: the text, the statistics of
     // the call, line feeds per workgroup, and per line its start, header flag | name bytes, bases (both scanned in place) and
     // per record its header line.  ma_batch_set_mates_text parses two texts: they share txtIn (the second at an aligned offset)
@@ -178,16 +169,14 @@ struct ma_batch
     // BGZF members inflated into txtIn (ma_batch_set_reads_bgzf, launch_bgzf.h): the compressed bytes and the member table; the
     // call's statistics follow the parse's in txtStat
     DevBuf bgzIn, bgzMembers;
-    SamTextState sam, pairSam;
+    SamTextState sam{ ma_state::SAM }, pairSam{ ma_state::PAIR_SAM };
     DeflateBufs zScratch; // of ma_sam_bgzf_batch, shared by both texts
     // small inversions (ma_inversions_batch, launch_inv.h): the statistics of the call, per MappingQuality slot its candidates, per
     // candidate its record, DP job, shape, window and result, and the FINAL lists the later stages see through mq_view
     DevBuf invStat, invSlotCnt, invSlotFirst, invCand, invJobs, invShapes, invWin, invEz, invCigOff, invCigPool, invCtr, invHdr;
     DevBuf finOff, finHdr, finOrder, finCnt;
     u64 invCandCap = 0, invWinCap = 0;
-    u64 invCands = 0, invJobsN = 0, invRecs = 0, invOps = 0;
-    bool invDone = false, invFinal = false;
-    u64 cigPoolCap = 0, cigPoolMin = 0, nOpsCap = 0, nJobSlots = 0;
+    u64 cigPoolCap = 0, cigPoolMin = 0, nOpsCap = 0;
     KswSide kswSide; // created on first use
     // double-buffered I/O (ma_batch_stage_reads / ma_batch_start_mapq_download): the next reads are uploaded into reads2 / roff2
     // and the packed results of the last step downloaded on ioStream while the batch's own stream runs kernels
@@ -197,7 +186,7 @@ struct ma_batch
     bool stagedPending = false, downPending = false;
     u64 stN = 0, stBases = 0;
     u32 stMaxQ = 0;
-    int stage_done = STAGE_NONE; // a Stage
+    ma_state::BatchState st; // what of all this is valid, and the counts that go with it
     bool timing = false;
     bool blocking = false; // batch_wait: sleep on an event instead of spinning
     hipEvent_t waitEv = nullptr;
@@ -210,8 +199,8 @@ struct ma_batch
 
 // The lists "after MappingQuality" as every later stage sees them -- pairing, both SAM texts, the packed download: read r's
 // records are hdr[ off[ r ] + order[ off[ r ] + k ] ], k < cnt[ r ]; slots = off[ n_reads ].  The MappingQuality arrays themselves,
-// or the final lists of a ma_inversions_batch that kept at least one record (launch_inv.h); setting reads, ma_dp_batch and
-// ma_batch_set_alignments put the view back (inv_reset).
+// or the final lists of a ma_inversions_batch that kept at least one record (launch_inv.h); whatever drops the inversions puts
+// the view back.
 struct MqView
 {
     const u64* off;
@@ -222,11 +211,10 @@ struct MqView
 };
 static MqView mq_view( const ma_batch* b )
 {
-    if( b->invFinal )
-        return MqView{ b->finOff.as<u64>( ), b->finHdr.as<AlnHeader>( ), b->finOrder.as<u32>( ), b->finCnt.as<u32>( ), b->nHsets + b->invRecs };
-    return MqView{ b->hsetOff.as<u64>( ), b->hdr.as<AlnHeader>( ), b->mqOrder.as<u32>( ), b->mqCnt.as<u32>( ), b->nHsets };
+    if( b->st.invFinal( ) )
+        return MqView{ b->finOff.as<u64>( ), b->finHdr.as<AlnHeader>( ), b->finOrder.as<u32>( ), b->finCnt.as<u32>( ), b->st.nHsets + b->st.invRecs };
+    return MqView{ b->hsetOff.as<u64>( ), b->hdr.as<AlnHeader>( ), b->mqOrder.as<u32>( ), b->mqCnt.as<u32>( ), b->st.nHsets };
 }
-static void inv_reset( ma_batch* b ); // launch_inv.h
 
 // Waits for the batch's stream.  Default: hipStreamSynchronize (the runtime spins: lowest latency, one host core busy).
 // With blocking waits (ma_batch_set_blocking_sync) the host thread sleeps on an interrupt-driven event instead: the mode for
@@ -244,26 +232,6 @@ static int batch_wait( ma_batch* b )
     MA_HIP( hipEventRecord( b->waitEv, b->stream ) );
     MA_HIP( hipEventSynchronize( b->waitEv ) );
     return 0;
-}
-
-// The alignment lists changed (ma_dp_batch, ma_batch_set_alignments; ma_inversions_batch, which also puts the stage back to
-// STAGE_ALIGNED): both SAM texts are of other records, and the list view goes back to the MappingQuality arrays.
-// ma_pair_batch is NOT one of them: it changes the picks only, so it drops pairSam alone and the single-end text stays.
-static void batch_results_changed( ma_batch* b )
-{
-    b->sam.done = b->pairSam.done = false;
-    inv_reset( b );
-}
-
-// The batch has new reads, however they came (host arrays, a staged upload, caller-owned device arrays, a text, a refused text):
-// no stage has run on them, they have no names (txtHasQual and txtNameBytes are only read behind txtSet), and every SAM text,
-// pair and inversion record is of other reads.
-static void batch_reads_changed( ma_batch* b )
-{
-    b->stage_done = STAGE_NONE;
-    b->txtSet = b->txtHasQual = false;
-    b->txtNameBytes = 0;
-    batch_results_changed( b );
 }
 
 static void batch_own_reads( ma_batch* b )
@@ -520,13 +488,13 @@ int ma_batch_use_staged_reads( ma_batch* b )
     MA_BIND_DEVICE( b->device );
     MA_HIP( hipEventSynchronize( b->evStaged ) );
     MA_HIP( hipEventRecord( b->evReadsFree, b->stream ) ); // what runs on the stream now is the last reader of the old buffer
+    b->st.newReads( );
     std::swap( b->reads, b->reads2 );
     std::swap( b->roff, b->roff2 );
     b->n_reads = b->stN;
     b->n_bases = b->stBases;
     b->max_qlen = b->stMaxQ;
     batch_own_reads( b );
-    batch_reads_changed( b );
     b->stagedPending = false;
     return 0;
 }
@@ -538,6 +506,7 @@ int ma_batch_set_reads( ma_batch* b, const uint8_t* codes, const uint64_t* offse
     MA_BIND_DEVICE( b->device );
     if( n > b->max_reads || offsets[ n ] > b->max_bases )
         return fail( "ma_batch_set_reads: batch capacity exceeded" );
+    b->st.newReads( );
     b->n_reads = n;
     b->n_bases = offsets[ n ];
     b->max_qlen = longest_read( offsets, n );
@@ -547,7 +516,6 @@ int ma_batch_set_reads( ma_batch* b, const uint8_t* codes, const uint64_t* offse
     if( batch_wait( b ) )
         return 1;
     batch_own_reads( b );
-    batch_reads_changed( b );
     return 0;
 }
 
@@ -570,19 +538,21 @@ int ma_batch_set_reads_device( ma_batch* b, const void* d_codes, const void* d_o
     if( !b || !d_offsets || ( n && !d_codes ) )
         return fail( "ma_batch_set_reads_device: null argument" );
     MA_BIND_DEVICE( b->device );
+    // the longest read first, from the caller's offsets (the counter block is its scratch: every stage's counters go, so the
+    // products go before it); the caller's arrays are installed last, so a failure up to there leaves the reads that were set
+    b->st.newReads( );
+    MA_HIP( hipMemsetAsync( b->ctr.p, 0, CTR_COUNT * 8, b->stream ) );
+    if( n )
+        hipLaunchKernelGGL( k_max_qlen, dim3( (unsigned)std::min<u64>( 256, ( n + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream, (const u64*)d_offsets, n,
+                            b->ctr.as<unsigned long long>( ) );
+    if( read_ctr( b ) )
+        return 1;
     b->n_reads = n;
     b->n_bases = n_bases;
     b->d_reads = (const uint8_t*)d_codes;
     b->d_roff = (const u64*)d_offsets;
     b->reads_external = true;
-    MA_HIP( hipMemsetAsync( b->ctr.p, 0, CTR_COUNT * 8, b->stream ) );
-    if( n )
-        hipLaunchKernelGGL( k_max_qlen, dim3( (unsigned)std::min<u64>( 256, ( n + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream, b->d_roff, n,
-                            b->ctr.as<unsigned long long>( ) );
-    if( read_ctr( b ) )
-        return 1;
     b->max_qlen = (u32)b->hctr[ 0 ];
-    batch_reads_changed( b );
     return 0;
 }
 
@@ -642,7 +612,7 @@ int ma_batch_set_segments( ma_batch* b, const uint64_t* seg_off, const ma_segmen
         return fail( "ma_batch_set_segments: no reads set or null argument" );
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads, ns = seg_off[ n ];
-    b->segMarked = false;
+    b->st.drop( ma_state::SEEDED );
     std::vector<u64> o;
     std::vector<u32> c, rd( ns + 1 );
     csr_parts( seg_off, n, o, c );
@@ -664,9 +634,8 @@ int ma_batch_set_segments( ma_batch* b, const uint64_t* seg_off, const ma_segmen
     MA_HIP( hipMemcpyAsync( b->ctr.as<unsigned long long>( ) + CTR_SEG_USED, &used, 8, hipMemcpyHostToDevice, b->stream ) );
     if( batch_wait( b ) )
         return 1; // the host vectors go out of scope
-    b->nSegs = ns;
-    b->nSeeds = b->nHsets = b->nHseeds = 0;
-    b->stage_done = STAGE_SEEDED;
+    b->st.nSegs = ns;
+    b->st.finish( ma_state::SEEDED );
     return 0;
 }
 
@@ -676,6 +645,7 @@ int ma_batch_set_seeds( ma_batch* b, const uint64_t* seed_off, const ma_seed* se
         return fail( "ma_batch_set_seeds: no reads set or null argument" );
     MA_BIND_DEVICE( b->device );
     const u64 n = b->n_reads, total = seed_off[ n ];
+    b->st.drop( ma_state::EXTRACTED );
     std::vector<u64> o;
     std::vector<u32> c;
     csr_parts( seed_off, n, o, c );
@@ -688,10 +658,8 @@ int ma_batch_set_seeds( ma_batch* b, const uint64_t* seed_off, const ma_seed* se
     MA_HIP( hipMemcpyAsync( b->seedCnt.p, c.data( ), ( n + 1 ) * 4, hipMemcpyHostToDevice, b->stream ) );
     if( batch_wait( b ) )
         return 1;
-    b->nSeeds = total;
-    b->nHsets = b->nHseeds = 0;
-    b->socGiven = false;
-    b->stage_done = STAGE_EXTRACTED;
+    b->st.nSeeds = total;
+    b->st.finish( ma_state::EXTRACTED );
     return 0;
 }
 
@@ -727,7 +695,7 @@ int ma_batch_set_soc_heap( ma_batch* b, const uint64_t* soc_off, const ma_soc* s
     MA_HIP( hipMemcpyAsync( b->socInCnt.p, c.data( ), ( n + 1 ) * 4, hipMemcpyHostToDevice, b->stream ) );
     if( batch_wait( b ) )
         return 1;
-    b->socGiven = true;
+    b->st.giveSocs( );
     return 0;
 }
 
@@ -736,10 +704,7 @@ int ma_batch_set_soc_heap( ma_batch* b, const uint64_t* soc_off, const ma_soc* s
 // without harmonized sets (as before ma_chain_batch) and otherwise usable.
 static int hsets_refuse( ma_batch* b, const std::string& what )
 {
-    b->nHsets = b->nHseeds = 0;
-    b->nJobSlots = 0;
-    if( b->stage_done > STAGE_EXTRACTED )
-        b->stage_done = STAGE_EXTRACTED;
+    b->st.drop( ma_state::CHAINED );
     return fail( "ma_batch_set_hsets: " + what );
 }
 static int hsets_check( ma_batch* b, const u64* roff, const uint64_t* hset_off, const uint64_t* hseed_off, const uint32_t* hset_soc, const ma_seed* hseeds )
@@ -802,6 +767,7 @@ int ma_batch_set_hsets( ma_batch* b, const uint64_t* hset_off, const uint64_t* h
         return 1;
     if( hsets_check( b, roff.data( ), hset_off, hseed_off, hset_soc, hseeds ) )
         return 1;
+    b->st.drop( ma_state::CHAINED );
     const u64 nh = hset_off[ n ];
     const u64 nhs = nh ? hseed_off[ nh ] : 0;
     std::vector<HSet> flat( nh + 1 );
@@ -827,9 +793,9 @@ int ma_batch_set_hsets( ma_batch* b, const uint64_t* hset_off, const uint64_t* h
     MA_HIP( hipMemcpyAsync( b->hsetOff.p, hset_off, ( n + 1 ) * 8, hipMemcpyHostToDevice, b->stream ) );
     if( batch_wait( b ) )
         return 1;
-    b->nHsets = nh;
-    b->nHseeds = nhs;
-    b->stage_done = STAGE_CHAINED;
+    b->st.nHsets = nh;
+    b->st.nHseeds = nhs;
+    b->st.finish( ma_state::CHAINED );
     return 0;
 }
 
@@ -848,10 +814,10 @@ int ma_batch_get_soc_heap( ma_batch* b, uint64_t* n_socs, uint64_t* soc_off, ma_
 static int get_socs( ma_batch* b, int heap_layout, uint64_t* n_socs, uint64_t* soc_off, ma_soc* socs, uint64_t* seed_off,
                      ma_seed* sorted_seeds )
 {
-    if( !b || b->stage_done < STAGE_EXTRACTED )
+    if( !b || !b->st.has( ma_state::EXTRACTED ) )
         return fail( "ma_batch_get_socs: run ma_extract_seeds_batch first" );
     MA_BIND_DEVICE( b->device );
-    const u64 n = b->n_reads, ts = b->nSeeds + 1;
+    const u64 n = b->n_reads, ts = b->st.nSeeds + 1;
     if( n_socs )
         *n_socs = 0;
     if( soc_off )
@@ -883,12 +849,12 @@ static int get_socs( ma_batch* b, int heap_layout, uint64_t* n_socs, uint64_t* s
         *n_socs = total;
     if( !soc_off && !socs && !seed_off && !sorted_seeds )
         return 0;
-    std::vector<ma_soc> hs( b->nSeeds + 1 );
-    std::vector<ma_seed> hw( b->nSeeds + 1 );
-    if( b->nSeeds )
+    std::vector<ma_soc> hs( b->st.nSeeds + 1 );
+    std::vector<ma_seed> hw( b->st.nSeeds + 1 );
+    if( b->st.nSeeds )
     {
-        MA_HIP( hipMemcpy( hs.data( ), dSocs.p, b->nSeeds * sizeof( ma_soc ), hipMemcpyDeviceToHost ) );
-        MA_HIP( hipMemcpy( hw.data( ), b->cWork.p, b->nSeeds * sizeof( ma_seed ), hipMemcpyDeviceToHost ) );
+        MA_HIP( hipMemcpy( hs.data( ), dSocs.p, b->st.nSeeds * sizeof( ma_soc ), hipMemcpyDeviceToHost ) );
+        MA_HIP( hipMemcpy( hw.data( ), b->cWork.p, b->st.nSeeds * sizeof( ma_seed ), hipMemcpyDeviceToHost ) );
     }
     u64 so = 0, sd = 0;
     for( u64 r = 0; r < n; r++ )
@@ -997,7 +963,7 @@ int ma_batch_counters( ma_batch* b, uint64_t out[ 8 ] )
     out[ 0 ] = b->hctr[ CTR_STEPS ];
     out[ 1 ] = b->hctr[ CTR_BLOCKS ];
     out[ 2 ] = b->hctr[ CTR_LF_STEPS ];
-    out[ 3 ] = b->nSeeds;
+    out[ 3 ] = b->st.nSeeds;
     out[ 4 ] = b->hctr[ CTR_CELLS ] + b->hctr[ CTR_N_1X1 ];
     out[ 5 ] = b->hctr[ CTR_KSW_JOBS ] + b->hctr[ CTR_N_1X1 ];
     out[ 6 ] = b->hctr[ CTR_SEQ_BYTES ];
@@ -1010,20 +976,20 @@ int ma_batch_counts( ma_batch* b, uint64_t* n_segments, uint64_t* n_seeds, uint6
 {
     if( ma_batch_sync( b ) )
         return 1;
-    if( b->stage_done >= STAGE_SEEDED && b->nSegs == 0 )
-        b->nSegs = b->hctr[ CTR_SEG_USED ];
+    if( b->st.has( ma_state::SEEDED ) && b->st.nSegs == 0 )
+        b->st.nSegs = b->hctr[ CTR_SEG_USED ];
     if( n_segments )
-        *n_segments = b->nSegs;
+        *n_segments = b->st.nSegs;
     if( n_seeds )
-        *n_seeds = b->nSeeds;
+        *n_seeds = b->st.nSeeds;
     if( n_hsets )
-        *n_hsets = b->nHsets;
+        *n_hsets = b->st.nHsets;
     if( n_hseeds )
-        *n_hseeds = b->nHseeds;
+        *n_hseeds = b->st.nHseeds;
     if( n_alignments )
-        *n_alignments = b->stage_done >= STAGE_ALIGNED ? mq_view( b ).slots : 0;
+        *n_alignments = b->st.has( ma_state::ALIGNED ) ? mq_view( b ).slots : 0;
     if( n_ops ) // exact: the ops of all alignments (the MappingQuality selection has at most as many) and of the inversion records
-        *n_ops = b->stage_done >= STAGE_ALIGNED ? b->hctr[ CTR_OPS_ALL ] + ( b->invFinal ? b->invOps : 0 ) : 0;
+        *n_ops = b->st.has( ma_state::ALIGNED ) ? b->hctr[ CTR_OPS_ALL ] + ( b->st.invFinal( ) ? b->st.invOps : 0 ) : 0;
     if( n_aligned_reads )
         *n_aligned_reads = b->hctr[ CTR_N_ALIGNED ];
     return 0;
@@ -1033,21 +999,21 @@ int ma_batch_counts( ma_batch* b, uint64_t* n_segments, uint64_t* n_seeds, uint6
 // segments out calls this first.  Not part of the aligned path: extraction takes the position as it is.
 static int seg_materialise( ma_batch* b, u64 ns )
 {
-    if( !b->segMarked || ns == 0 )
+    if( !b->st.segMarked || ns == 0 )
         return 0;
     hipLaunchKernelGGL( k_seg_materialise, dim3( (unsigned)( ( ns + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream, b->idx->v, b->d_reads, b->d_roff,
                         b->segRead.as<u32>( ), b->segPool.as<ma_segment>( ), ns );
     MA_HIP( hipGetLastError( ) );
     if( batch_wait( b ) )
         return 1;
-    b->segMarked = false;
+    b->st.markSegments( false );
     return 0;
 }
 
 // Downloads gather the per-read ranges (pools are in completion order) into read-order CSR arrays.
 int ma_batch_get_segments( ma_batch* b, uint64_t* seg_off, ma_segment* segs )
 {
-    if( !b || b->stage_done < STAGE_SEEDED )
+    if( !b || !b->st.has( ma_state::SEEDED ) )
         return fail( "ma_batch_get_segments: stage not run" );
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )
@@ -1082,7 +1048,7 @@ int ma_batch_get_segments( ma_batch* b, uint64_t* seg_off, ma_segment* segs )
 
 int ma_batch_get_seeds( ma_batch* b, uint64_t* seed_off, ma_seed* seeds )
 {
-    if( !b || b->stage_done < STAGE_EXTRACTED )
+    if( !b || !b->st.has( ma_state::EXTRACTED ) )
         return fail( "ma_batch_get_seeds: stage not run" );
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )
@@ -1090,14 +1056,14 @@ int ma_batch_get_seeds( ma_batch* b, uint64_t* seed_off, ma_seed* seeds )
     const u64 n = b->n_reads;
     std::vector<u64> off( n );
     std::vector<u32> cnt( n );
-    std::vector<ma_seed> pool( b->nSeeds );
+    std::vector<ma_seed> pool( b->st.nSeeds );
     if( n )
     {
         MA_HIP( hipMemcpy( off.data( ), b->seedOff.p, n * 8, hipMemcpyDeviceToHost ) );
         MA_HIP( hipMemcpy( cnt.data( ), b->seedCnt.p, n * 4, hipMemcpyDeviceToHost ) );
     }
-    if( b->nSeeds )
-        MA_HIP( hipMemcpy( pool.data( ), b->seeds.p, b->nSeeds * sizeof( ma_seed ), hipMemcpyDeviceToHost ) );
+    if( b->st.nSeeds )
+        MA_HIP( hipMemcpy( pool.data( ), b->seeds.p, b->st.nSeeds * sizeof( ma_seed ), hipMemcpyDeviceToHost ) );
     u64 o = 0;
     for( u64 r = 0; r < n; r++ )
     {
@@ -1115,22 +1081,22 @@ int ma_batch_get_seeds( ma_batch* b, uint64_t* seed_off, ma_seed* seeds )
 
 int ma_batch_get_hsets( ma_batch* b, uint64_t* hset_off, uint64_t* hseed_off, uint32_t* hset_soc, ma_seed* hseeds )
 {
-    if( !b || b->stage_done < STAGE_CHAINED )
+    if( !b || !b->st.has( ma_state::CHAINED ) )
         return fail( "ma_batch_get_hsets: stage not run" );
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )
         return 1;
-    const u64 n = b->n_reads, nh = b->nHsets;
+    const u64 n = b->n_reads, nh = b->st.nHsets;
     if( hset_off && n )
         MA_HIP( hipMemcpy( hset_off, b->hsetOff.p, ( n + 1 ) * 8, hipMemcpyDeviceToHost ) );
     if( hset_off && !n )
         hset_off[ 0 ] = 0;
     std::vector<HSet> flat( nh );
-    std::vector<ma_seed> pool( b->nHseeds );
+    std::vector<ma_seed> pool( b->st.nHseeds );
     if( nh )
         MA_HIP( hipMemcpy( flat.data( ), b->hsetFlat.p, nh * sizeof( HSet ), hipMemcpyDeviceToHost ) );
-    if( b->nHseeds )
-        MA_HIP( hipMemcpy( pool.data( ), b->hdense.p, b->nHseeds * sizeof( ma_seed ), hipMemcpyDeviceToHost ) );
+    if( b->st.nHseeds )
+        MA_HIP( hipMemcpy( pool.data( ), b->hdense.p, b->st.nHseeds * sizeof( ma_seed ), hipMemcpyDeviceToHost ) );
     u64 o = 0;
     for( u64 s = 0; s < nh; s++ )
     {
@@ -1151,14 +1117,14 @@ int ma_batch_get_hsets( ma_batch* b, uint64_t* hset_off, uint64_t* hseed_off, ui
 // async = the double-buffered form: the copies go to the I/O stream behind the pack kernels and nobody waits here
 static int get_alns( ma_batch* b, bool mq, uint64_t* aln_off, ma_alignment* alns, uint64_t* ops, bool async = false )
 {
-    if( !b || b->stage_done < STAGE_ALIGNED )
+    if( !b || !b->st.has( ma_state::ALIGNED ) )
         return fail( "ma_batch_get_alignments: stage not run" );
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )
         return 1;
     if( download_begin( b, async, "ma_batch_start_mapq_download" ) ) // (the packed arrays may be overwritten only behind it)
         return 1;
-    const u64 n = b->n_reads, nh = b->nHsets;
+    const u64 n = b->n_reads, nh = b->st.nHsets;
     if( aln_off )
         aln_off[ 0 ] = 0;
     if( n == 0 )
@@ -1171,7 +1137,7 @@ static int get_alns( ma_batch* b, bool mq, uint64_t* aln_off, ma_alignment* alns
     }
     // (the MappingQuality form serves the list view: the final lists after a ma_inversions_batch that kept records)
     const MqView V = mq_view( b );
-    const u64 invA = mq && b->invFinal ? b->invRecs : 0, invO = mq && b->invFinal ? b->invOps : 0;
+    const u64 invA = mq && b->st.invFinal( ) ? b->st.invRecs : 0, invO = mq && b->st.invFinal( ) ? b->st.invOps : 0;
     const u64 totalA = mq ? b->hctr[ CTR_ALN_MQ ] + invA : nh, totalO = mq ? b->hctr[ CTR_OPS_MQ ] + invO : b->hctr[ CTR_OPS_ALL ];
     if( b->outCnt.reserve( ( n + 2 ) * 8 ) || b->outOps.reserve( ( n + 2 ) * 8 ) || b->outAlnOff.reserve( ( n + 2 ) * 8 ) ||
         b->outOpsOff.reserve( ( n + 2 ) * 8 ) || b->outAlns.reserve( ( totalA + 1 ) * sizeof( ma_alignment ) ) ||
@@ -1229,12 +1195,12 @@ int ma_batch_get_mapq_alignments( ma_batch* b, uint64_t* aln_off, ma_alignment* 
 
 int ma_batch_get_dp_jobs( ma_batch* b, uint64_t* n_jobs, int32_t* shapes /* 8 x i32 per job */, uint64_t cap )
 {
-    if( !b || b->stage_done < STAGE_ALIGNED )
+    if( !b || !b->st.has( ma_state::ALIGNED ) )
         return fail( "ma_batch_get_dp_jobs: stage not run" );
     MA_BIND_DEVICE( b->device );
     if( ma_batch_sync( b ) )
         return 1;
-    const u64 nSlots = b->nJobSlots;
+    const u64 nSlots = b->st.nJobSlots;
     std::vector<DpJob> jobs( nSlots + 1 );
     std::vector<ma_ez> ez( nSlots + 1 );
     if( nSlots )

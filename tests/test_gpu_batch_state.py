@@ -1,9 +1,10 @@
-"""What a batch forgets, and when (ma_amd/csrc/pipeline.hip: batch_reads_changed, batch_results_changed).  Every form of "this
+"""What a batch forgets, and when (ma_amd/host/ma_batch_state.h, kept by ma_amd/csrc/pipeline.hip).  Every form of "this
 batch has new reads" -- the host arrays, the staged upload, caller-owned device arrays, a text, a refused text, mate texts, BGZF
 members -- puts a batch that has been through every stage back to the start: no stage output, no SAM text, no pairs, no names
 unless the form brings them, and the next pass computes what a fresh batch computes.  Every call that changes the alignment
 lists (ma_dp_batch, ma_batch_set_alignments, ma_inversions_batch) drops both SAM texts and the pairs; ma_pair_batch drops only
-the pairs' text."""
+the pairs' text.  An earlier stage run again, or its input handed in, drops every product of the later stages; a refused
+ma_batch_set_reads_device leaves the batch as it was."""
 import numpy as np
 import pytest
 
@@ -184,3 +185,67 @@ def test_empty_input(world):
         assert b.read_counts() == NO_READS
         b.align()
         b.sync()
+
+
+# ---- an earlier stage run again, or its input handed in: the products of the later stages go -------------------------------
+
+def refused_hsets(b):
+    import ma_amd
+    hset_off, hseed_off, soc, seeds = b.hsets()
+    bad = seeds.copy()
+    bad["q_start"][0] = 1000  # beyond its read of 100 bases
+    with pytest.raises(ma_amd.MaError, match="ma_batch_set_hsets: seed ends beyond its read of 100 bases"):
+        b.set_hsets(hset_off, hseed_off, soc, bad)
+
+
+# (name, the call, the stage calls that are left before full_pass's tail)
+EARLIER = [("seed", lambda b: b.seed(), ("extract", "chain", "dp")),
+           ("extract", lambda b: b.extract(), ("chain", "dp")),
+           ("chain", lambda b: b.chain(), ("dp",)),
+           ("set_segments", lambda b: b.set_segments(*b.segments()), ("extract", "chain", "dp")),
+           ("set_seeds", lambda b: b.set_seeds(*b.seeds()), ("chain", "dp")),
+           ("set_soc_heap", lambda b: b.set_soc_heap(*b.socs(heap=True)), ("chain", "dp")),
+           ("set_hsets", lambda b: b.set_hsets(*b.hsets()), ("dp",)),
+           ("set_hsets, refused", refused_hsets, ("chain", "dp"))]
+LATER_GONE = [(lambda b: b.sam_bytes(), "ma_batch_sam_counts: run ma_sam_batch first"),
+              (lambda b: b.pair_sam_bytes(), "ma_batch_pair_sam_counts: run ma_pair_sam_batch first"),
+              (lambda b: b.pair_counts(), "ma_batch_pair_counts: run ma_pair_batch first"),
+              (lambda b: b.sam_bgzf_counts(False), "ma_batch_sam_bgzf_counts: no SAM text to deflate (run ma_sam_batch first)"),
+              (lambda b: b.sam_bgzf_counts(True), "ma_batch_sam_bgzf_counts: no SAM text to deflate (run ma_pair_sam_batch first)"),
+              (lambda b: b.inversion_counts(), "ma_batch_inversion_counts: run ma_inversions_batch first")]
+
+
+@pytest.mark.parametrize("name,call,rest", EARLIER, ids=[e[0] for e in EARLIER])
+def test_an_earlier_stage_drops_the_later_products(world, name, call, rest):
+    """after a complete pass with the BGZF members of both texts, a stage run again or a stage input handed in leaves no SAM
+    text, no pairs, no members and no inversion counts: each getter raises the message it has for "never made".  The stages that
+    are left and the tail of the pass then compute the MappingQuality records of a fresh batch with the same reads, byte for
+    byte."""
+    b, reads, fresh, want = world
+    b.set_reads(fresh)
+    assert full_pass(b, fresh, False) == want["fresh"]
+    assert b.sam_bgzf(False) and b.sam_bgzf(True)
+    call(b)
+    for getter, message in LATER_GONE:
+        gone(lambda: getter(b), message)
+    for stage in rest:
+        getattr(b, stage)()
+    b.inversions()
+    b.pair()
+    assert b.sam() >= 0 and b.pair_sam() >= 0
+    assert tuple(x.tobytes() for x in b.mapq_alignments()) == want["fresh"]
+
+
+def test_a_refused_set_reads_device_keeps_the_reads(world):
+    """ma_batch_set_reads_device installs the caller's arrays last: a call it refuses (no offsets for n > 0 reads) leaves the reads,
+    the texts and the pairs of the batch as they were"""
+    import ma_amd
+    b, reads, fresh, want = world
+    b.set_reads(reads)
+    full_pass(b, reads, False)
+    before = b.read_counts(), b.sam_bytes(), b.pair_counts()
+    with pytest.raises(ma_amd.MaError) as e:
+        b.set_reads_device(0, 0, len(fresh), sum(len(r) for r in fresh))
+    assert str(e.value) == "ma_batch_set_reads_device: null argument"
+    assert (b.read_counts(), b.sam_bytes(), b.pair_counts()) == before
+    assert before[0]["reads"] == len(reads) and before[1] > 0
