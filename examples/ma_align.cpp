@@ -14,7 +14,8 @@
 // both files into runs of equally many records and the device parses, interleaves and reverse-complements them
 // (BatchAligner::executePairedTextSam, ma_batch_set_mates_text).  A single-end reads file that bgzip wrote (BGZF, told by its first
 // bytes) goes up compressed: BatchBgzfReader cuts it at member borders and the device inflates it in front of its parser
-// (BatchAligner::executeBgzfSam, ma_batch_set_reads_bgzf); plain gzip is not served with the flag.  The device serves four-line FASTQ and plain FASTA only; any other file ends the program with the library's message, which names the line -- there is no silent fallback.
+// (BatchAligner::executeBgzfSam, ma_batch_set_reads_bgzf); two BGZF files of a pair likewise (BatchPairedBgzfReader,
+// BatchAligner::executePairedBgzfSam, ma_batch_set_mates_bgzf); one BGZF file beside one that is not, and plain gzip, are not served with the flag.  The device serves four-line FASTQ and plain FASTA only; any other file ends the program with the library's message, which names the line -- there is no silent fallback.
 // With --bgzf-output, or an output name that ends in .gz, the output is BGZF (SamOptions::bBgzf; what bgzip writes: samtools, zcat
 // and gzip read it): on the device paths every batch's text is deflated where it was printed (ma_sam_bgzf_batch) and only its
 // members come down; the header, and with --host-sam every byte, goes through the host statement of the same rules
@@ -59,24 +60,29 @@ int main( int argc, char** argv )
             throw std::runtime_error( "--text-input serves input printed on the device (not with --host-sam: the host's writers need the reads)" );
         // a single-end reads file that starts with a BGZF member (what bgzip writes; told by its first 18 bytes, not by its name)
         // is inflated on the device; any other compressed file is not served with the flag
-        bool bBgzf = false;
-        if( bTextInput && !bPaired )
-        {
+        // with a mates file both files must be BGZF for that
+        const auto startsWithBgzf = []( const char* pPath ) {
             uint8_t aFirst[ ma_bgzf::MIN_PROBE_BYTES ];
-            std::ifstream xProbe( argv[ 2 ], std::ios::binary );
+            std::ifstream xProbe( pPath, std::ios::binary );
             xProbe.read( (char*)aFirst, sizeof( aFirst ) );
             ma_bgzf::Member xMember;
             const uint32_t uiReason = xProbe.gcount( ) == (std::streamsize)sizeof( aFirst ) ? ma_bgzf::header( aFirst, sizeof( aFirst ), 0, &xMember )
                                                                                              : (uint32_t)ma_bgzf::ERR_NOT_BGZF;
-            bBgzf = uiReason == ma_bgzf::OK || uiReason == ma_bgzf::ERR_TRUNCATED; // (truncated: the member goes on behind the 18 bytes)
-        }
+            return uiReason == ma_bgzf::OK || uiReason == ma_bgzf::ERR_TRUNCATED; // (truncated: the member goes on behind the 18 bytes)
+        };
+        const bool bBgzfReads = bTextInput && startsWithBgzf( argv[ 2 ] ), bBgzfMates = bTextInput && bPaired && startsWithBgzf( argv[ 5 ] );
+        const bool bBgzf = bPaired ? bBgzfReads && bBgzfMates : bBgzfReads;
+        if( bTextInput && bPaired && bBgzfReads != bBgzfMates )
+            throw std::runtime_error( std::string( "--text-input: " ) + argv[ bBgzfReads ? 2 : 5 ] + " is compressed (BGZF) and " +
+                                      argv[ bBgzfReads ? 5 : 2 ] +
+                                      " is not; the device inflates a pair of read files only when bgzip wrote both (run without the flag)" );
         for( int iFile : { 2, 5 } )
         {
             const std::string sReads = iFile < argc ? argv[ iFile ] : "";
-            if( bTextInput && !( iFile == 2 && bBgzf ) && sReads.size( ) >= 3 && sReads.compare( sReads.size( ) - 3, 3, ".gz" ) == 0 )
+            if( bTextInput && !bBgzf && sReads.size( ) >= 3 && sReads.compare( sReads.size( ) - 3, 3, ".gz" ) == 0 )
                 throw std::runtime_error( "--text-input: " + sReads +
-                                          " is compressed; the device parses plain text, and inflates single-end reads that bgzip wrote (BGZF), "
-                                          "but no plain gzip (run without the flag)" );
+                                          " is compressed; the device parses plain text, and inflates reads that bgzip wrote (BGZF; of a pair, "
+                                          "both files), but no plain gzip (run without the flag)" );
         }
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
@@ -92,7 +98,17 @@ int main( int argc, char** argv )
         FileReader xReader( xParams );
         std::shared_ptr<FileStream> pIn = bBgzf ? std::make_shared<StdFileStream>( argv[ 2 ] ) : fileStreamFromPath( argv[ 2 ] ); // (BGZF: its bytes as they are)
         const size_t uiBatch = 1000000; // reads per device batch
-        if( bTextInput && bPaired )
+        if( bBgzf && bPaired )
+        {
+            // the compressed paired path: the members of both files go to the device, which inflates both chains in one launch,
+            // parses, pairs and prints; what it leaves over of either text is the front of the reader's next batch
+            BatchPairedFileWriter xWriter( xParams, std::make_shared<PairedFileWriter>( xParams, std::string( argv[ 3 ] ), pPack ), pPack );
+            BatchPairedBgzfReader xBgzfReader( xParams );
+            auto pStreams = std::make_shared<PairedFileStream>( pIn, std::make_shared<StdFileStream>( argv[ 5 ] ) );
+            while( auto pMembers = xBgzfReader.execute( pStreams ) )
+                xWriter.execute( *xAligner.executePairedBgzfSam( pFM, pMembers, pPack ) );
+        }
+        else if( bTextInput && bPaired )
         {
             // the paired text path: the bytes of both files go to the device, which parses, reverse-complements the mates as the
             // parameter set says (bRevCompPairedReadMates), aligns, pairs and prints; one write per batch

@@ -9,7 +9,7 @@
 // Prints one JSON line.  bench.py runs it after its timed regions and reports it as config.boundary (never as `value`).
 //
 //   ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads]
-// (further legs, one per run: paired, pairtext, sam, sam-tags, sam-bgzf, text, bgzf, inversions -- see the comments at their blocks in main)
+// (further legs, one per run: paired, pairtext, pairbgzf, sam, sam-tags, sam-bgzf, text, bgzf, inversions -- see the comments at their blocks in main)
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_boundary_bench.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
@@ -234,11 +234,46 @@ static std::string prefetchLeg( const ParameterSetManager& xParams, std::shared_
     return sPrefetch;
 }
 
+#ifdef MA_WITH_ZLIB
+// a text as BGZF through zlib at the default level, 65 280 bytes of text per member as bgzip cuts them, the end-of-file marker behind
+static std::string bgzfOf( const std::string& sFastq )
+{
+    std::string sBgzf;
+    for( size_t uiAt = 0; uiAt <= sFastq.size( ); uiAt += 65280 ) // (the last turn writes the rest or the end-of-file marker)
+    {
+        const size_t uiText = std::min<size_t>( 65280, sFastq.size( ) - uiAt );
+        z_stream z;
+        memset( &z, 0, sizeof( z ) );
+        if( deflateInit2( &z, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY ) != Z_OK )
+            throw std::runtime_error( "deflateInit2" );
+        std::string sOut( deflateBound( &z, (uLong)uiText ) + 64, '\0' );
+        z.next_in = (Bytef*)( sFastq.data( ) + uiAt ), z.avail_in = (uInt)uiText;
+        z.next_out = (Bytef*)&sOut[ 0 ], z.avail_out = (uInt)sOut.size( );
+        if( deflate( &z, Z_FINISH ) != Z_STREAM_END )
+            throw std::runtime_error( "deflate" );
+        sOut.resize( z.total_out );
+        deflateEnd( &z );
+        const uint32_t uiCrc = (uint32_t)crc32( crc32( 0L, Z_NULL, 0 ), (const Bytef*)( sFastq.data( ) + uiAt ), (uInt)uiText );
+        auto le = [ & ]( uint32_t v, int nBytes ) {
+            for( int i = 0; i < nBytes; i++ )
+                sBgzf += (char)( ( v >> ( 8 * i ) ) & 0xff );
+        };
+        sBgzf += std::string( "\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0", 16 );
+        le( (uint32_t)sOut.size( ) + 25, 2 );
+        sBgzf += sOut;
+        le( uiCrc, 4 ), le( (uint32_t)uiText, 4 );
+        if( uiText == 0 )
+            break;
+    }
+    return sBgzf;
+}
+#endif
+
 int main( int argc, char** argv )
 {
     if( argc < 6 )
     {
-        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | pairtext [repeats] | sam [repeats] | sam-tags [repeats] | sam-bgzf [repeats] | text [repeats] | bgzf [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
+        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | pairtext [repeats] | pairbgzf [repeats] | sam [repeats] | sam-tags [repeats] | sam-bgzf [repeats] | text [repeats] | bgzf [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
         return 2;
     }
     try
@@ -249,7 +284,7 @@ int main( int argc, char** argv )
         maCheck( ma_set_device( atoi( argv[ 5 ] ) ) );
         maCheck( ma_host_bind_thread( atoi( argv[ 5 ] ), 0, nullptr ) ); // this thread and all it starts: the CPUs next to the GPU
         const unsigned uiHw = std::max( 1u, std::thread::hardware_concurrency( ) );
-        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "pairtext" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "sam-bgzf" ) && strcmp( argv[ 6 ], "text" ) && strcmp( argv[ 6 ], "bgzf" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
+        const int iGraphThreads = argc >= 7 && strcmp( argv[ 6 ], "paired" ) && strcmp( argv[ 6 ], "pairtext" ) && strcmp( argv[ 6 ], "pairbgzf" ) && strcmp( argv[ 6 ], "sam" ) && strcmp( argv[ 6 ], "sam-tags" ) && strcmp( argv[ 6 ], "sam-bgzf" ) && strcmp( argv[ 6 ], "text" ) && strcmp( argv[ 6 ], "bgzf" ) && strcmp( argv[ 6 ], "inversions" ) ? atoi( argv[ 6 ] ) : (int)std::min( 2048u, 8 * uiHw );
         std::shared_ptr<Pack> pPack;
         std::shared_ptr<FMIndex> pFM;
         double t0 = now( );
@@ -307,8 +342,10 @@ int main( int argc, char** argv )
             }
             return pMates;
         };
-        if( argc >= 7 && !strcmp( argv[ 6 ], "pairtext" ) )
+        const bool bPairBgzfLeg = argc >= 7 && !strcmp( argv[ 6 ], "pairbgzf" );
+        if( argc >= 7 && ( !strcmp( argv[ 6 ], "pairtext" ) || bPairBgzfLeg ) )
         {
+            // (pairbgzf: the same two texts written once as BGZF; see below, behind the lambdas both legs use)
             // ---- the paired text leg: the mates of the paired leg as TWO FASTQ texts in memory, as a sequencer writes them (R2 on
             // the other strand; seeded qualities 35 .. 126), files to SAM text through (a) BatchPairedTextReader ->
             // executePairedTextSam -- blocks of both texts cut into equally many records, parsed, interleaved and reverse-complemented
@@ -350,8 +387,11 @@ int main( int argc, char** argv )
                 vAligners.back( )->uiInflight = w == uiWorkers ? 3 : 1;
             }
             uint64_t uiBytesHost = 0, uiBytesText = 0;
+            std::string asGzPath[ 2 ]; // pairbgzf: (b) reads the two .gz files through GzFileStream
             auto host = [ & ]( std::string* pFile ) {
-                auto pStreams = std::make_shared<PairedFileStream>( std::make_shared<StringStream>( asFastq[ 0 ] ), std::make_shared<StringStream>( asFastq[ 1 ] ) );
+                auto pStreams = asGzPath[ 0 ].empty( )
+                                    ? std::make_shared<PairedFileStream>( std::make_shared<StringStream>( asFastq[ 0 ] ), std::make_shared<StringStream>( asFastq[ 1 ] ) )
+                                    : std::make_shared<PairedFileStream>( fileStreamFromPath( asGzPath[ 0 ] ), fileStreamFromPath( asGzPath[ 1 ] ) );
                 PairedFileReader xReader( xParams );
                 const double t = now( );
                 uiBytesHost = 0;
@@ -428,6 +468,118 @@ int main( int argc, char** argv )
                 }
                 return f;
             };
+            auto list = []( std::vector<double> v ) {
+                std::string sAll;
+                for( double f : v )
+                    sAll += ( sAll.empty( ) ? "" : ", " ) + std::to_string( f );
+                std::sort( v.begin( ), v.end( ) );
+                return "{\"median\": " + std::to_string( v[ v.size( ) / 2 ] ) + ", \"min\": " + std::to_string( v.front( ) ) +
+                       ", \"max\": " + std::to_string( v.back( ) ) + ", \"all\": [" + sAll + "]}";
+            };
+            if( bPairBgzfLeg )
+            {
+                // ---- the compressed paired leg: the two texts written once as BGZF (the bgzf leg's setup), files to SAM text through
+                // (a) BatchPairedBgzfReader -> executePairedBgzfSam -- both chains inflated by one launch, the rests handed back to
+                // the reader, so the set calls of consecutive batches are serial and everything behind them overlaps across the
+                // three workers --, (b) the two .gz files through GzFileStream -> PairedFileReader -> executePairedFlatSam -- what a
+                // compressed pair gets without it: gzread a byte at a time, one NucSeq per mate -- and (c) the pairtext leg's (a)
+                // on the uncompressed texts, the ceiling.  A warm-up of each keeps its text; the three must be the same bytes.  Then
+                // alternating, <repeats> times each; then (a) at other uiBatchBytes.  (Needs -DMA_WITH_ZLIB -lz.)
+#ifdef MA_WITH_ZLIB
+                const std::string asBgzf[ 2 ] = { bgzfOf( asFastq[ 0 ] ), bgzfOf( asFastq[ 1 ] ) };
+                for( int i = 0; i < 2; i++ )
+                {
+                    asGzPath[ i ] = std::string( argv[ 1 ] ) + ".boundary_bench_" + std::to_string( i + 1 ) + ".fq.gz";
+                    std::ofstream xOut( asGzPath[ i ], std::ios::binary );
+                    xOut.write( asBgzf[ i ].data( ), (std::streamsize)asBgzf[ i ].size( ) );
+                    if( !xOut )
+                        throw std::runtime_error( "cannot write " + asGzPath[ i ] );
+                }
+                uint64_t uiBytesBgzf = 0;
+                const size_t uiTextPerBatch = std::max<size_t>( 2, ( asFastq[ 0 ].size( ) + asFastq[ 1 ].size( ) ) / std::max<size_t>( uiMates, 1 ) * uiBatchReads );
+                auto bgzf = [ & ]( std::string* pFile, size_t uiBatchBytes ) {
+                    auto pStreams = std::make_shared<PairedFileStream>( std::make_shared<StringStream>( asBgzf[ 0 ] ), std::make_shared<StringStream>( asBgzf[ 1 ] ) );
+                    BatchPairedBgzfReader xReader( xParams );
+                    xReader.uiBatchBytes = uiBatchBytes;
+                    std::vector<std::pair<uint64_t, std::string>> vParts;
+                    std::mutex xParts;
+                    std::string sFailure;
+                    std::atomic<uint64_t> uiBytes{ 0 };
+                    const double t = now( );
+                    std::vector<std::thread> vT;
+                    for( size_t w = 0; w < uiWorkers; w++ )
+                        vT.emplace_back( [ &, w ]( ) {
+                            try
+                            {
+                                while( auto pMembers = xReader.execute( pStreams ) )
+                                {
+                                    auto pB = vAligners[ w ]->executePairedBgzfSamOn( pFM->pDev->p, pMembers );
+                                    uiBytes += pB->samBytes( );
+                                    if( pFile != nullptr )
+                                    {
+                                        const uint64_t uiFirst = pB->samBytes( ) > 1 ? strtoull( pB->samText( ) + 1, nullptr, 10 ) : 0; // "r<i>\t..."
+                                        std::lock_guard<std::mutex> xGuard( xParts );
+                                        vParts.emplace_back( uiFirst, std::string( pB->samText( ), pB->samBytes( ) ) );
+                                    }
+                                }
+                            }
+                            catch( const std::exception& rE )
+                            {
+                                std::lock_guard<std::mutex> xGuard( xParts );
+                                sFailure = rE.what( );
+                            }
+                        } );
+                    for( auto& rT : vT )
+                        rT.join( );
+                    const double f = now( ) - t;
+                    if( !sFailure.empty( ) )
+                        throw std::runtime_error( sFailure );
+                    uiBytesBgzf = uiBytes.load( );
+                    if( pFile != nullptr )
+                    {
+                        std::sort( vParts.begin( ), vParts.end( ), []( const auto& a, const auto& b ) { return a.first < b.first; } );
+                        pFile->clear( );
+                        for( const auto& rPart : vParts )
+                            *pFile += rPart.second;
+                    }
+                    return f;
+                };
+                std::string sFileBgzf, sFileGz, sFileText;
+                bgzf( &sFileBgzf, uiTextPerBatch ), host( &sFileGz ), text( &sFileText );
+                bool bEqual = sFileBgzf == sFileGz && sFileBgzf == sFileText && !sFileBgzf.empty( );
+                const uint64_t uiFileBytes = sFileText.size( );
+                std::string( ).swap( sFileBgzf ), std::string( ).swap( sFileGz ), std::string( ).swap( sFileText );
+                std::vector<double> vA, vB, vC;
+                for( int r = 0; r < iRepeats; r++ )
+                {
+                    vA.push_back( uiMates / bgzf( nullptr, uiTextPerBatch ) ), vB.push_back( uiMates / host( nullptr ) ), vC.push_back( uiMates / text( nullptr ) );
+                    bEqual = bEqual && uiBytesBgzf == uiFileBytes && uiBytesHost == uiFileBytes && uiBytesText == uiFileBytes;
+                }
+                // (a) at other sizes of the reader's batch: the set calls are serial, so a larger batch makes that section cheaper per read
+                std::string sSweep;
+                for( size_t uiDiv : { 8, 2, 1 } )
+                {
+                    std::vector<double> v;
+                    for( int r = 0; r < 3; r++ )
+                        v.push_back( uiMates / bgzf( nullptr, std::max<size_t>( 2, 2 * uiTextPerBatch / uiDiv ) ) );
+                    bEqual = bEqual && uiBytesBgzf == uiFileBytes;
+                    sSweep += ( sSweep.empty( ) ? "" : ", " ) + std::string( "{\"batch_bytes\": " ) + std::to_string( 2 * uiTextPerBatch / uiDiv ) +
+                              ", \"reads_per_s\": " + list( v ) + "}";
+                }
+                const bool bFaster = *std::min_element( vA.begin( ), vA.end( ) ) > *std::max_element( vB.begin( ), vB.end( ) );
+                printf( "{\"pairbgzf\": {\"mates\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_bytes\": %zu, \"workers\": %zu, "
+                        "\"paired_bgzf_reader_paired_bgzf_sam_reads_per_s\": %s, \"gz_paired_file_reader_paired_flat_sam_reads_per_s\": %s, "
+                        "\"paired_text_reader_paired_text_sam_reads_per_s\": %s, \"other_batch_bytes\": [%s], \"fastq_bytes\": %zu, \"bgzf_bytes\": %zu, "
+                        "\"sam_bytes\": %zu, \"equal\": %s, \"slowest_device_above_fastest_gz\": %s}}\n",
+                        uiMates, uiLen, iRepeats, uiTextPerBatch, uiWorkers, list( vA ).c_str( ), list( vB ).c_str( ), list( vC ).c_str( ), sSweep.c_str( ),
+                        asFastq[ 0 ].size( ) + asFastq[ 1 ].size( ), asBgzf[ 0 ].size( ) + asBgzf[ 1 ].size( ), (size_t)uiFileBytes, bEqual ? "true" : "false",
+                        bFaster ? "true" : "false" );
+                remove( asGzPath[ 0 ].c_str( ) ), remove( asGzPath[ 1 ].c_str( ) );
+                return bEqual && bFaster ? 0 : 1;
+#else
+                throw std::runtime_error( "the pairbgzf leg writes its files through zlib: build with -DMA_WITH_ZLIB -lz" );
+#endif
+            }
             // warm-up of both: these two runs keep their files, which must be the same bytes; the timed runs count theirs
             std::string sFileHost, sFileText;
             host( &sFileHost ), text( &sFileText );
@@ -440,14 +592,6 @@ int main( int argc, char** argv )
                 vD.push_back( uiMates / text( nullptr ) ), vH.push_back( uiMates / host( nullptr ) );
                 bEqual = bEqual && uiBytesHost == uiFileBytes && uiBytesText == uiFileBytes;
             }
-            auto list = []( std::vector<double> v ) {
-                std::string sAll;
-                for( double f : v )
-                    sAll += ( sAll.empty( ) ? "" : ", " ) + std::to_string( f );
-                std::sort( v.begin( ), v.end( ) );
-                return "{\"median\": " + std::to_string( v[ v.size( ) / 2 ] ) + ", \"min\": " + std::to_string( v.front( ) ) +
-                       ", \"max\": " + std::to_string( v.back( ) ) + ", \"all\": [" + sAll + "]}";
-            };
             printf( "{\"pairtext\": {\"mates\": %zu, \"read_len\": %zu, \"repeats\": %d, \"batch_reads\": %zu, \"workers\": %zu, "
                     "\"paired_text_reader_paired_text_sam_reads_per_s\": %s, \"paired_file_reader_paired_flat_sam_reads_per_s\": %s, "
                     "\"fastq_bytes\": %zu, \"sam_bytes\": %zu, \"equal\": %s}}\n",
@@ -776,33 +920,7 @@ int main( int argc, char** argv )
             if( bBgzfLeg )
             {
 #ifdef MA_WITH_ZLIB
-                std::string sBgzf;
-                for( size_t uiAt = 0; uiAt <= sFastq.size( ); uiAt += 65280 ) // (the last turn writes the rest or the end-of-file marker)
-                {
-                    const size_t uiText = std::min<size_t>( 65280, sFastq.size( ) - uiAt );
-                    z_stream z;
-                    memset( &z, 0, sizeof( z ) );
-                    if( deflateInit2( &z, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY ) != Z_OK )
-                        throw std::runtime_error( "deflateInit2" );
-                    std::string sOut( deflateBound( &z, (uLong)uiText ) + 64, '\0' );
-                    z.next_in = (Bytef*)( sFastq.data( ) + uiAt ), z.avail_in = (uInt)uiText;
-                    z.next_out = (Bytef*)&sOut[ 0 ], z.avail_out = (uInt)sOut.size( );
-                    if( deflate( &z, Z_FINISH ) != Z_STREAM_END )
-                        throw std::runtime_error( "deflate" );
-                    sOut.resize( z.total_out );
-                    deflateEnd( &z );
-                    const uint32_t uiCrc = (uint32_t)crc32( crc32( 0L, Z_NULL, 0 ), (const Bytef*)( sFastq.data( ) + uiAt ), (uInt)uiText );
-                    auto le = [ & ]( uint32_t v, int nBytes ) {
-                        for( int i = 0; i < nBytes; i++ )
-                            sBgzf += (char)( ( v >> ( 8 * i ) ) & 0xff );
-                    };
-                    sBgzf += std::string( "\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0", 16 );
-                    le( (uint32_t)sOut.size( ) + 25, 2 );
-                    sBgzf += sOut;
-                    le( uiCrc, 4 ), le( (uint32_t)uiText, 4 );
-                    if( uiText == 0 )
-                        break;
-                }
+                const std::string sBgzf = bgzfOf( sFastq );
                 const std::string sPath = std::string( argv[ 1 ] ) + ".boundary_bench.fq.gz";
                 {
                     std::ofstream xOut( sPath, std::ios::binary );

@@ -494,6 +494,54 @@ int ma_batch_set_mates_text( ma_batch*, const char* text1 /*host*/, uint64_t n1,
  *                            With ma_batch_enable_timing, ma_batch_kernel_ms [6] is the time of the two inflate kernels. */
 int ma_batch_set_reads_bgzf( ma_batch*, const char* head /*host, may be NULL*/, uint64_t n_head, const void* members /*host*/,
                              uint64_t n_bytes, uint64_t n_drop, uint64_t* n_reads );
+/* ---- compressed paired read text in: the two BGZF files of a paired-end run inflated on the device ----
+ * ma_batch_set_reads_bgzf's inflate in front of ma_batch_set_mates_text's parse: for each side i, T_i is head followed by what
+ * members inflate to, minus its last n_drop bytes, in the strict member form above; the call then is
+ * ma_batch_set_mates_text( T_1, T_2, rev_comp_mates ).  The rules and the order of the refusals are stated once in
+ * ma_amd/host/ma_mates_bgzf_dev.h (ma_bgzf::pairBgzfHost is the serial statement).  The member borders of two compressed files
+ * say nothing about record counts, so a caller cannot cut whole pairs: it cuts each stream into runs of whole records as for
+ * ma_batch_set_reads_bgzf, and carries what the device left over of either text into the next call's head.
+ *   ma_batch_set_mates_bgzf  side[i]: as the arguments of ma_batch_set_reads_bgzf (host memory; head / members may be NULL with
+ *                            their size 0).  Both chains are inflated by ONE launch of the inflate kernels over a joint member
+ *                            table; uploads, inflates, parses and waits: TWO read-backs (the line feeds of both texts, the
+ *                            inflate's verdict and the first and last byte of both texts in one copy; then the statistics, as
+ *                            ma_batch_set_mates_text's second).  Afterwards the batch is exactly as after
+ *                            ma_batch_set_mates_text( T_1, T_2 ): the same reads, names and qualities, *n_pairs = R and
+ *                            consumed[i] = offset in T_i of the first byte of record R; text_bytes[i] = |T_i|.  An empty T_i
+ *                            gives 0 pairs (the other text is still validated); records beyond R are validated, but neither
+ *                            counted nor checked against the capacity.  Refusals, in this order; each leaves the batch without
+ *                            reads and text and usable, *n_pairs = 0 and consumed = text_bytes = {0, 0} unless stated:
+ *                              "ma_batch_set_mates_bgzf: null argument"
+ *                              "ma_batch_set_mates_bgzf: text <1|2>: member <k> (byte <X>): <reason>"  k (0-based) and X count
+ *                                within that side's members: a bad header found on the host -- text 1's first, else text 2's
+ *                                first; nothing is launched -- else the lowest member of text 1 whose stream or trailer the
+ *                                device refuses, else the lowest of text 2.  A member that does not inflate wins over every
+ *                                refusal below: a text that did not inflate is not parsed
+ *                              "ma_batch_set_mates_bgzf: text <1|2>: n_drop is larger than the inflated part of the text"
+ *                              "ma_batch_set_mates_bgzf: text <1|2>: line <L> (byte <X>): <reason>"  ma_batch_set_mates_text's
+ *                                refusal, L and X counted in T_i.  (A T_i of 2 GiB or more gets its "too large" before
+ *                                anything is launched: behind a bad header, in front of everything else.)
+ *                              "ma_batch_set_mates_bgzf: the two texts differ in kind"
+ *                              "ma_batch_set_mates_bgzf: batch capacity exceeded"  *n_pairs = R
+ *                            With ma_batch_enable_timing, ma_batch_kernel_ms [6] is the time of this call's inflate kernels.
+ *   ma_batch_get_mates_rest  T_which[ consumed .. |T| ), the records beyond the last pair, which a streaming caller puts in front
+ *                            of the next call's head: *n_bytes, and the bytes with out != NULL -- a copy out of the batch's
+ *                            text buffer on its stream, no kernel; waits.  Valid from a successful ma_batch_set_mates_bgzf
+ *                            until the next call that sets reads in any form (ma_batch_set_reads, _set_reads_device,
+ *                            _use_staged_reads, _set_reads_text, _set_reads_bgzf, _set_mates_text, _set_mates_bgzf; not
+ *                            ma_batch_set_read_text, which replaces names and qualities only); otherwise it fails with
+ *                            "ma_batch_get_mates_rest: run ma_batch_set_mates_bgzf first". */
+typedef struct
+{
+    const char* head; /* host, may be NULL with n_head 0 */
+    uint64_t n_head;
+    const void* members; /* host, whole BGZF members */
+    uint64_t n_bytes;
+    uint64_t n_drop;
+} ma_bgzf_text;
+int ma_batch_set_mates_bgzf( ma_batch*, const ma_bgzf_text side[ 2 ], int32_t rev_comp_mates, uint64_t* n_pairs, uint64_t text_bytes[ 2 ],
+                             uint64_t consumed[ 2 ] );
+int ma_batch_get_mates_rest( ma_batch*, int32_t which /*0 | 1*/, uint64_t* n_bytes, char* out /*may be NULL: count only*/ );
 /* ---- compressed SAM text out: the text of a batch deflated on the device into BGZF members ----
  * The SAM text of the last ma_sam_batch / ma_pair_sam_batch is cut at fixed offsets -- member k holds text[65280 k ..
  * min(65280 (k+1), n)), so ceil(n / 65280) members and none for an empty text -- and every member is deflated by a wavefront
@@ -530,7 +578,7 @@ int ma_batch_counters( ma_batch*, uint64_t out[ 8 ] );
  * qlen, tlen, w, zdrop, flag, ez.zdropped, ez.max_q, ez.max_t (shapes may be NULL to only count) */
 int ma_batch_get_dp_jobs( ma_batch*, uint64_t* n_jobs, int32_t* shapes, uint64_t cap );
 /* per-kernel HIP-event times of the last stage calls in ms: [0] seeding [1] sa-lookup [2] chaining
- * [3] dp-jobs [4] ksw [5] stitch; [6] the inflate of the last ma_batch_set_reads_bgzf; [7] the deflate of the last ma_sam_bgzf_batch; requires ma_batch_enable_timing(b,1) */
+ * [3] dp-jobs [4] ksw [5] stitch; [6] the inflate of the last ma_batch_set_reads_bgzf / ma_batch_set_mates_bgzf; [7] the deflate of the last ma_sam_bgzf_batch; requires ma_batch_enable_timing(b,1) */
 int ma_batch_enable_timing( ma_batch*, int on );
 int ma_batch_kernel_ms( ma_batch*, float out[ 8 ] );
 /* host wall time in ms of the stage calls of the last ma_align_batch: [0] seed [1] extract [2] chain [3] dp (launches,

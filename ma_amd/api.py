@@ -42,6 +42,11 @@ class Params(C.Structure):
         return p
 
 
+class BgzfText(C.Structure):
+    """ma_bgzf_text: one side of ma_batch_set_mates_bgzf"""
+    _fields_ = [("head", C.c_void_p), ("n_head", C.c_uint64), ("members", C.c_void_p), ("n_bytes", C.c_uint64), ("n_drop", C.c_uint64)]
+
+
 SEGMENT_DT = np.dtype([("q_start", "<i8"), ("q_size", "<i8"), ("sa_start", "<i8"), ("sa_start_rc", "<i8"),
                        ("sa_size", "<i8")])
 SEED_DT = np.dtype([("q_start", "<i8"), ("len", "<i8"), ("r_start", "<i8"), ("delta", "<i8"), ("ambiguity", "<u4"),
@@ -433,6 +438,43 @@ class Batch:
         self.read_off, _ = self.reads(codes=False)
         self.n_bases = int(self.read_off[-1])
         return int(n.value), (int(consumed[0]), int(consumed[1]))
+
+    def set_mates_bgzf(self, members1, members2, heads=(b"", b""), drops=(0, 0), rev_comp=True):
+        """members1, members2: bytes of whole BGZF members of the two read files of a paired-end run.  Text i is heads[i] followed
+        by what its members inflate to, minus its last drops[i] bytes; both chains are inflated by one launch on the device and the
+        texts paired as set_mates_text() pairs them (ma_batch_set_mates_bgzf).  Returns (n_pairs, (consumed1, consumed2),
+        (text_bytes1, text_bytes2)); mates_rest() serves what of each text lies beyond the last pair.  A refusal raises MaError
+        and leaves the batch without reads; after "batch capacity exceeded" the exception's n_pairs is the number of pairs the
+        texts hold."""
+        bufs = [np.frombuffer(bytes(x) + b"\0", dtype=np.uint8) for x in (heads[0], members1, heads[1], members2)]
+        sides = (BgzfText * 2)()
+        for i in range(2):
+            sides[i].head, sides[i].n_head = bufs[2 * i].ctypes.data, len(bufs[2 * i]) - 1
+            sides[i].members, sides[i].n_bytes = bufs[2 * i + 1].ctypes.data, len(bufs[2 * i + 1]) - 1
+            sides[i].n_drop = int(drops[i])
+        n, consumed, size = C.c_uint64(), (C.c_uint64 * 2)(), (C.c_uint64 * 2)()
+        self.n, self.read_off, self.n_bases = 0, np.zeros(1, dtype=np.uint64), 0
+        try:
+            _chk(lib().ma_batch_set_mates_bgzf(self.h, sides, C.c_int32(1 if rev_comp else 0), C.byref(n), size, consumed))
+        except MaError as e:
+            e.n_pairs = int(n.value)
+            raise
+        self.n = 2 * int(n.value)
+        self.read_off, _ = self.reads(codes=False)
+        self.n_bases = int(self.read_off[-1])
+        return int(n.value), (int(consumed[0]), int(consumed[1])), (int(size[0]), int(size[1]))
+
+    def mates_rest(self):
+        """(rest1, rest2): the bytes of each text of the last set_mates_bgzf() behind its last paired record
+        (ma_batch_get_mates_rest); raises MaError once the batch has other reads, or none"""
+        out = []
+        for which in range(2):
+            n = C.c_uint64()
+            _chk(lib().ma_batch_get_mates_rest(self.h, C.c_int32(which), C.byref(n), None))
+            buf = np.zeros(n.value + 1, dtype=np.uint8)
+            _chk(lib().ma_batch_get_mates_rest(self.h, C.c_int32(which), C.byref(n), _ptr(buf)))
+            out.append(buf[:-1].tobytes())
+        return tuple(out)
 
     def read_counts(self):
         v = [C.c_uint64() for _ in range(3)]

@@ -28,10 +28,11 @@ static int text_refuse( u64 line, u64 byte, u32 reason, const char* who = "ma_ba
     ma_text::messageOf( msg, sizeof( msg ), who, line, byte, reason );
     return fail( msg );
 }
-static int mates_refuse( u32 refusal, u32 text, u64 line, u64 byte, u32 reason )
+// who: the call's name ("ma_batch_set_mates_text", "ma_batch_set_mates_bgzf")
+static int mates_refuse( const char* who, u32 refusal, u32 text, u64 line, u64 byte, u32 reason )
 {
     char msg[ 256 ];
-    ma_text::messageMates( msg, sizeof( msg ), refusal, text, line, byte, reason );
+    ma_text::messageMatesOf( msg, sizeof( msg ), who, refusal, text, line, byte, reason );
     return fail( msg );
 }
 
@@ -170,6 +171,9 @@ static int text_single_rest( ma_batch* b, TextFront& t, unsigned long long* h, c
     return 0;
 }
 
+static int text_mates_rest( ma_batch* b, TextFront t[ 2 ], const bool parsed[ 2 ], const u64 hostKey[ 2 ], unsigned long long* h, int32_t rev_comp_mates,
+                            const char* who, uint64_t* n_pairs, uint64_t consumed[ 2 ] ); // (behind ma_batch_set_mates_text)
+
 extern "C" {
 
 int ma_batch_set_reads_text( ma_batch* b, const char* text, uint64_t n, uint64_t* n_reads )
@@ -220,7 +224,7 @@ int ma_batch_set_mates_text( ma_batch* b, const char* text1, uint64_t n1, const 
     // the other text is validated all the same (a violation in text 1 wins over text 2's)
     const u64 hostKey[ 2 ] = { text_host_key( text1, n1 ), text_host_key( text2, n2 ) };
     if( hostKey[ 0 ] != ma_text::NO_VIOLATION )
-        return batch_wait( b ) || mates_refuse( ma_text::MATES_LINE, 1, 0, 0, (u32)( hostKey[ 0 ] & 0xffu ) );
+        return batch_wait( b ) || mates_refuse( "ma_batch_set_mates_text", ma_text::MATES_LINE, 1, 0, 0, (u32)( hostKey[ 0 ] & 0xffu ) );
     const bool parsed[ 2 ] = { n1 > 0, n2 > 0 && hostKey[ 1 ] == ma_text::NO_VIOLATION };
     const u64 at2 = ( n1 + 255 ) & ~(u64)255; // text 2 behind text 1 in the one upload buffer
     if( b->txtNameOff.reserve( ( b->max_reads + 1 ) * 8 ) || b->txtIn.reserve( at2 + ( parsed[ 1 ] ? n2 : 0 ) + 64 ) ||
@@ -245,6 +249,22 @@ int ma_batch_set_mates_text( ma_batch* b, const char* text1, uint64_t n1, const 
         if( batch_wait( b ) )
             return 1;
     }
+    return text_mates_rest( b, t, parsed, hostKey, h, rev_comp_mates, "ma_batch_set_mates_text", n_pairs, consumed );
+}
+} // extern "C"
+
+// The rest of a parse of two texts behind the read-back of their line feeds into h (h[ i * TXT_WORDS + TXT_FEEDS ]; kind, first
+// and last of a parsed text are set): the per-line kernels of each text, k_text_mates_plan / _stat / _emit, the read-back of the
+// mates statistics into h and the batch's new state.  parsed / hostKey: as ma_batch_set_mates_text decides them; the statistics
+// are the 2 * TXT_WORDS + MT_WORDS words at the front of b->txtStat; who: the call's name in a refusal.  The TXT_* words of a
+// text that is NOT parsed are not read here or by the mates kernels (its hostKey or its emptiness speaks for it), and they
+// differ by caller: all zero from ma_batch_set_mates_text, which never counts such a text, and k_text_count's from
+// ma_batch_set_mates_bgzf, which counts every text before it knows the first byte.
+static int text_mates_rest( ma_batch* b, TextFront t[ 2 ], const bool parsed[ 2 ], const u64 hostKey[ 2 ], unsigned long long* h, int32_t rev_comp_mates,
+                            const char* who, uint64_t* n_pairs, uint64_t consumed[ 2 ] )
+{
+    unsigned long long* const mstat = b->txtStat.as<unsigned long long>( ) + 2 * TXT_WORDS;
+    const u64 n1 = t[ 0 ].n, n2 = t[ 1 ].n;
     u64 most = ~0ull; // pairs at most: a FASTQ record has four lines, a FASTA record two or more
     for( int i = 0; i < 2; i++ )
     {
@@ -304,7 +324,7 @@ int ma_batch_set_mates_text( ma_batch* b, const char* text1, uint64_t n1, const 
             return 1;
         if( h[ MT_REFUSAL ] == ma_text::MATES_CAPACITY && n_pairs )
             *n_pairs = h[ MT_PAIRS ]; // (what a caller sizes the next batch object by)
-        return mates_refuse( (u32)h[ MT_REFUSAL ], (u32)h[ MT_TEXT ], h[ MT_VIOLATION ] >> 8, h[ MT_BYTE ], (u32)( h[ MT_VIOLATION ] & 0xffu ) );
+        return mates_refuse( who, (u32)h[ MT_REFUSAL ], (u32)h[ MT_TEXT ], h[ MT_VIOLATION ] >> 8, h[ MT_BYTE ], (u32)( h[ MT_VIOLATION ] & 0xffu ) );
     }
     b->n_reads = 2 * h[ MT_PAIRS ];
     b->n_bases = h[ MT_BASES ];
@@ -318,6 +338,8 @@ int ma_batch_set_mates_text( ma_batch* b, const char* text1, uint64_t n1, const 
         consumed[ 0 ] = h[ MT_CONSUMED ], consumed[ 1 ] = h[ MT_CONSUMED + 1 ];
     return 0;
 }
+
+extern "C" {
 
 int ma_batch_read_counts( ma_batch* b, uint64_t* n_reads, uint64_t* n_bases, uint64_t* n_name_bytes, int32_t* has_qual )
 {

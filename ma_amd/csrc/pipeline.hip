@@ -1322,4 +1322,7 @@ int ma_debug_seed_prof( unsigned long long* out )
 
 #include "launch_bgzf.h"
 
+#include "../host/ma_mates_bgzf_dev.h"
+#include "launch_mates_bgzf.h"
+
 #include "launch_deflate.h"

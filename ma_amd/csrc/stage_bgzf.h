@@ -11,15 +11,17 @@
 //                   ma_bgzf::crcCombine in six shuffle steps.  A kernel of its own and not part of the lanes of k_bgzf_inflate:
 //                   there the CRC would lengthen the one dependent chain per member that sets the kernel's time (a member is
 //                   decoded by ONE lane), here 64 lanes share a member's bytes.  Also leaves the text's first and last byte for
-//                   the parser's front (BGZ_FIRST, BGZ_LAST).
+//                   the parser's front (BGZ_FIRST, BGZ_LAST), of each text.
+// ma_batch_set_mates_bgzf runs both over ONE member table, text 1's members in front of text 2's: a member's uiDeflate and uiOut
+// say where its bytes are and where its text goes, so neither kernel knows of the two texts -- but for the ends k_bgzf_crc leaves.
 // A violation is ma_bgzf::key( member, reason ), the lowest wins (atomicMin, one per wavefront).
 
 enum : int // the statistics block of an inflate (u64 words), behind the parse's TXT_WORDS
 {
     BGZ_VIOLATION = 0, // lowest ma_bgzf::key( member, reason ) (all ones: none)
     BGZ_FIRST = 1, // the text's first ...
-    BGZ_LAST = 2, // ... and last byte
-    BGZ_WORDS = 4
+    BGZ_LAST = 2, // ... and last byte; ma_batch_set_mates_bgzf's second text: BGZ_FIRST + 2, BGZ_LAST + 2
+    BGZ_WORDS = 6
 };
 static constexpr u32 BGZF_LANES = 64;
 
@@ -59,8 +61,13 @@ __global__ __launch_bounds__( BGZF_LANES ) void k_bgzf_inflate( const uint8_t* d
         atomicMin( bstat + BGZ_VIOLATION, (unsigned long long)key );
 }
 
-// whole: the call's text T (head + members - drop) of n bytes, for its first and last byte
-__global__ __launch_bounds__( 256 ) void k_bgzf_crc( const ma_bgzf::Member* members, u64 nMembers, const uint8_t* text, const uint8_t* whole, u64 n,
+// the call's texts T (head + members - drop) of n bytes each, for their first and last bytes (a single text: n[ 1 ] = 0)
+struct BgzfWhole
+{
+    const uint8_t* p[ 2 ];
+    u64 n[ 2 ];
+};
+__global__ __launch_bounds__( 256 ) void k_bgzf_crc( const ma_bgzf::Member* members, u64 nMembers, const uint8_t* text, BgzfWhole whole,
                                                      unsigned long long* bstat )
 {
     const u64 m = (u64)blockIdx.x * ( 256 / BGZF_LANES ) + ( threadIdx.x / BGZF_LANES ); // (the same for a whole wavefront)
@@ -83,9 +90,14 @@ __global__ __launch_bounds__( 256 ) void k_bgzf_crc( const ma_bgzf::Member* memb
         if( lane == 0 && crc != M.uiCrc )
             atomicMin( bstat + BGZ_VIOLATION, (unsigned long long)ma_bgzf::key( m, ma_bgzf::ERR_CRC ) );
     }
-    if( blockIdx.x == 0 && threadIdx.x == 0 && n > 0 )
+    if( blockIdx.x == 0 && threadIdx.x < 2 ) // (no indexing of the argument by the lane: it stays in registers)
     {
-        bstat[ BGZ_FIRST ] = whole[ 0 ];
-        bstat[ BGZ_LAST ] = whole[ n - 1 ];
+        const uint8_t* const p = threadIdx.x ? whole.p[ 1 ] : whole.p[ 0 ];
+        const u64 n = threadIdx.x ? whole.n[ 1 ] : whole.n[ 0 ];
+        if( n > 0 )
+        {
+            bstat[ BGZ_FIRST + 2 * threadIdx.x ] = p[ 0 ];
+            bstat[ BGZ_LAST + 2 * threadIdx.x ] = p[ n - 1 ];
+        }
     }
 }

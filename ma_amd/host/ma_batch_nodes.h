@@ -244,10 +244,12 @@ class BatchTextReader : public libMS::Module<TextBatch, true, FileStream>
 // and the members behind that one are carried as they are.  No batch waits for anything the device makes of the one before it.
 // At the end of the file the rest is the batch, uiDrop = 0.  A chunk without a record start grows.  A stream that is not BGZF
 // -- plain gzip has no size field in its header -- throws with the reason's text, which names GzFileStream.  No zlib.
-class BatchBgzfReader : public libMS::Module<BgzfBatch, true, FileStream>
+// (The cut of ONE stream is BgzfStreamCutter: BatchBgzfReader has one, BatchPairedBgzfReader one per file.)
+struct BgzfStreamCutter
 {
     std::string sCarry, sHeadCarry; // compressed bytes and text behind the last cut (guarded by the stream's lock)
     char cKind = '\0'; // the first byte of the file's text
+    uint64_t uiCompressed = 0, uiText = 0; // of the members handed out so far: the stream's running ISIZE-to-compressed ratio
 
     [[noreturn]] static void refuse( FileStream& rStream, const std::string& sWhat, uint32_t uiReason )
     {
@@ -262,35 +264,18 @@ class BatchBgzfReader : public libMS::Module<BgzfBatch, true, FileStream>
         if( uiReason != ma_bgzf::OK )
             refuse( rStream, "the member at byte " + std::to_string( rM.uiIn ) + " of a chunk", uiReason );
     }
-
-  public:
-    size_t uiBatchBytes = 16u << 20; // of the compressed file
-    BatchBgzfReader( const ParameterSetManager& )
-    {}
-    // the text of a batch, inflated on the host (tests, and callers without a device)
-    static std::string textOf( const BgzfBatch& rBatch )
+    // the members of rBatch are handed out
+    void count( const std::string& rData )
     {
-        ma_bgzf::Result xResult;
-        const uint8_t* const pData = (const uint8_t*)rBatch.sMembers.data( );
-        char aMessage[ 320 ];
-        if( ma_bgzf::inflateHost( pData, rBatch.sMembers.size( ), nullptr, &xResult ) == 0 )
-        {
-            std::string sText( xResult.uiBytes, '\0' );
-            if( ma_bgzf::inflateHost( pData, rBatch.sMembers.size( ), (uint8_t*)&sText[ 0 ], &xResult ) == 0 && rBatch.uiDrop <= sText.size( ) )
-            {
-                sText.resize( sText.size( ) - rBatch.uiDrop );
-                return rBatch.sHead + sText;
-            }
-        }
-        ma_bgzf::message( aMessage, sizeof( aMessage ), xResult.uiMember, xResult.uiByte, xResult.uiReason );
-        throw std::runtime_error( aMessage );
+        ma_bgzf::Result xWalk;
+        ma_bgzf::inflateHost( (const uint8_t*)rData.data( ), rData.size( ), nullptr, &xWalk );
+        uiCompressed += rData.size( ), uiText += xWalk.uiBytes;
     }
-    virtual std::shared_ptr<BgzfBatch> execute( std::shared_ptr<FileStream> pStream ) override
+    // The next batch of the stream, whose lock the caller holds: about uiWant compressed bytes, the carried ones included.
+    // False: the end of the file, nothing is left.
+    bool cut( const std::shared_ptr<FileStream>& pStream, size_t uiWant, BgzfBatch* pRet )
     {
-        auto pRet = std::make_shared<BgzfBatch>( );
         std::string& rData = pRet->sMembers;
-        const size_t uiWant = std::max<size_t>( uiBatchBytes, 1 );
-        std::lock_guard<std::mutex> xLock( pStream->xMutex );
         rData.reserve( sCarry.size( ) + uiWant );
         rData.swap( sCarry );
         sCarry.clear( );
@@ -374,7 +359,8 @@ class BatchBgzfReader : public libMS::Module<BgzfBatch, true, FileStream>
             }
             sCarry.assign( rData, uiKeep, std::string::npos );
             rData.resize( uiKeep );
-            return pRet;
+            count( rData );
+            return true;
         }
         if( uiWalked != rData.size( ) ) // (never at the end of the file: a truncated member is refused there)
         {
@@ -384,7 +370,41 @@ class BatchBgzfReader : public libMS::Module<BgzfBatch, true, FileStream>
         bool bText = !pRet->sHead.empty( );
         for( const ma_bgzf::Member& rM : vMembers )
             bText = bText || rM.uiIsize > 0;
-        if( !bText )
+        count( rData );
+        return bText;
+    }
+};
+class BatchBgzfReader : public libMS::Module<BgzfBatch, true, FileStream>
+{
+    BgzfStreamCutter xCutter;
+
+  public:
+    size_t uiBatchBytes = 16u << 20; // of the compressed file
+    BatchBgzfReader( const ParameterSetManager& )
+    {}
+    // the text of a batch, inflated on the host (tests, and callers without a device)
+    static std::string textOf( const BgzfBatch& rBatch )
+    {
+        ma_bgzf::Result xResult;
+        const uint8_t* const pData = (const uint8_t*)rBatch.sMembers.data( );
+        char aMessage[ 320 ];
+        if( ma_bgzf::inflateHost( pData, rBatch.sMembers.size( ), nullptr, &xResult ) == 0 )
+        {
+            std::string sText( xResult.uiBytes, '\0' );
+            if( ma_bgzf::inflateHost( pData, rBatch.sMembers.size( ), (uint8_t*)&sText[ 0 ], &xResult ) == 0 && rBatch.uiDrop <= sText.size( ) )
+            {
+                sText.resize( sText.size( ) - rBatch.uiDrop );
+                return rBatch.sHead + sText;
+            }
+        }
+        ma_bgzf::message( aMessage, sizeof( aMessage ), xResult.uiMember, xResult.uiByte, xResult.uiReason );
+        throw std::runtime_error( aMessage );
+    }
+    virtual std::shared_ptr<BgzfBatch> execute( std::shared_ptr<FileStream> pStream ) override
+    {
+        auto pRet = std::make_shared<BgzfBatch>( );
+        std::lock_guard<std::mutex> xLock( pStream->xMutex );
+        if( !xCutter.cut( pStream, std::max<size_t>( uiBatchBytes, 1 ), pRet.get( ) ) )
             return nullptr; // end of file (module.h:688-695)
         return pRet;
     }
@@ -501,6 +521,82 @@ class BatchPairedTextReader : public libMS::Module<MatesTextBatch, true, PairedF
                 rText.resize( uiCut );
             }
         }
+        return pRet;
+    }
+};
+
+// BatchBgzfReader for mate pairs, the source of BatchAligner::executePairedBgzfSam: the COMPRESSED bytes of the two BGZF files of a
+// paired-end run.  Each stream is cut as BatchBgzfReader cuts its stream (BgzfStreamCutter: whole members, only the last ones
+// inflated to find the last record start, the bytes behind the cut dropped and carried).  The member borders of two files say
+// nothing about record counts, and equal counts cannot be had on the host without inflating everything, so the two texts of a
+// batch hold whatever they hold: the device pairs min( R1, R2 ) records and the batch hands back what it left over of either
+// text (MatesBgzfBatch::handBack, two strings: a test drives it with ma_bgzf::pairBgzfHost).  Batch k + 1's head of stream i is
+// rest_i( k ) followed by the bytes dropped at batch k's cut, so execute( ) for batch k + 1 waits, under the pair stream's lock,
+// until batch k's rests are back: the set calls of consecutive batches are serial, everything behind them overlaps.  A batch
+// destroyed without having handed back releases the wait, and that execute( ) and every later one throw.
+// THE CARRY STAYS BOUNDED although one stream may pack more records into a compressed byte than the other: each stream is
+// asked for only as many compressed bytes as bring ITS text, head included, to uiBatchBytes / 2, by the stream's running
+// ISIZE-to-compressed ratio (the first batch, with no ratio yet, takes what it needs for one record start).  The stream that
+// is ahead then reads little or nothing until the other has caught up.  The pair stream ends when a stream has nothing left:
+// the one with fewer records is at its end, the other's surplus was dropped by the device, as PairedFileReader drops it
+// (fileReader.h:590-600).  A stream that is not BGZF throws BatchBgzfReader's message.
+class BatchPairedBgzfReader : public libMS::Module<MatesBgzfBatch, true, PairedFileStream>
+{
+    BgzfStreamCutter axCutter[ 2 ]; // (guarded by the pair stream's lock)
+    const std::shared_ptr<MatesRestLink> pLink = std::make_shared<MatesRestLink>( );
+    bool bDone = false; // one of the streams has ended
+
+  public:
+    // of text, both streams together.  Measured, not the single-end default: the set calls of consecutive batches are serial and
+    // an inflate costs about the same for few members as for many, so a larger batch is cheaper per read (1 M mates of 150 bp,
+    // three workers: 0.51 M reads/s at 20 MB, 1.76 M at 82 MB, 2.42 M at 164 MB; profiles/pair_bgzf_device.md)
+    size_t uiBatchBytes = 160u << 20;
+    BatchPairedBgzfReader( const ParameterSetManager& )
+    {}
+    virtual std::shared_ptr<MatesBgzfBatch> execute( std::shared_ptr<PairedFileStream> pStreams ) override
+    {
+        const std::shared_ptr<FileStream> apStream[ 2 ] = { pStreams->first, pStreams->second };
+        std::lock_guard<std::mutex> xLock( pStreams->xMutex );
+        {
+            std::unique_lock<std::mutex> xWait( pLink->xMutex );
+            pLink->xCondition.wait( xWait, [ & ] { return !pLink->bPending; } );
+            if( pLink->bAbandoned )
+                throw std::runtime_error( "BatchPairedBgzfReader: a batch was destroyed without handing back its rests (its worker failed, or the "
+                                          "caller dropped it): the records behind it cannot be paired" );
+            for( int i = 0; i < 2; i++ )
+            {
+                axCutter[ i ].sHeadCarry.insert( 0, pLink->asRest[ i ] );
+                pLink->asRest[ i ].clear( );
+            }
+        }
+        if( bDone )
+            return nullptr;
+        auto pRet = std::make_shared<MatesBgzfBatch>( );
+        const size_t uiTarget = std::max<size_t>( uiBatchBytes / 2, 1 );
+        for( int i = 0; i < 2; i++ )
+        {
+            BgzfStreamCutter& rCutter = axCutter[ i ];
+            const size_t uiHead = rCutter.sHeadCarry.size( ), uiNeed = uiTarget > uiHead ? uiTarget - uiHead : 0;
+            const size_t uiWant = rCutter.uiText == 0 ? 1 : (size_t)( (double)uiNeed * (double)rCutter.uiCompressed / (double)rCutter.uiText );
+            BgzfBatch xSide;
+            const size_t uiHeadCut = uiNeed == 0 ? BatchTextReader::lastRecordStart( rCutter.sHeadCarry ) : 0;
+            if( uiHeadCut > 0 )
+            {
+                // this stream is ahead: its batch is the whole records of what it carries, and nothing is read
+                xSide.sHead.assign( rCutter.sHeadCarry, 0, uiHeadCut );
+                rCutter.sHeadCarry.erase( 0, uiHeadCut );
+            }
+            else if( !rCutter.cut( apStream[ i ], std::max<size_t>( uiWant, 1 ), &xSide ) )
+                bDone = true; // nothing is left of this stream: the shorter file ends the pair stream
+            pRet->asHead[ i ].swap( xSide.sHead );
+            pRet->asMembers[ i ].swap( xSide.sMembers );
+            pRet->auiDrop[ i ] = xSide.uiDrop;
+        }
+        if( bDone )
+            return nullptr; // (module.h:688-695)
+        std::lock_guard<std::mutex> xOut( pLink->xMutex );
+        pLink->bPending = true;
+        pRet->pLink = pLink;
         return pRet;
     }
 };

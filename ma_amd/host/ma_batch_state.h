@@ -15,7 +15,8 @@
 //   an early `return 1` in between needs no bookkeeping: the batch is left at "X and what depends on it are gone"
 //
 //   call                                          drops on entry                      establishes on success
-//   every form of new reads                       everything (newReads)               the reads; a text form: NAMES
+//   every form of new reads                       everything (newReads)               the reads; a text form: NAMES;
+//                                                                                     ma_batch_set_mates_bgzf: the mates' rest
 //   ma_batch_set_read_text                        NAMES: both texts and members       NAMES
 //   ma_seed_batch, ma_batch_set_segments          SEEDED and later                    SEEDED
 //   ma_extract_seeds_batch, ma_batch_set_seeds    EXTRACTED and later (socGiven too)  EXTRACTED
@@ -105,6 +106,13 @@ struct BatchState
     // NAMES
     bool hasQual = false;
     uint64_t nameBytes = 0;
+    // the reads came from ma_batch_set_mates_bgzf: the two inflated texts are still in the text buffer, and ma_batch_get_mates_rest
+    // serves what of each lies beyond the last pair (offset and bytes).  No product: nothing depends on it; every form of new
+    // reads takes it away (newReads: ma_batch_set_reads, _set_reads_device, _use_staged_reads, _set_reads_text, _set_reads_bgzf,
+    // _set_mates_text, _set_mates_bgzf, refused or not).  ma_batch_set_read_text does not: it replaces names and qualities, not
+    // the reads, and does not touch the text buffer the rest lies in
+    bool matesRest = false;
+    uint64_t restAt[ 2 ] = { 0, 0 }, restBytes[ 2 ] = { 0, 0 };
     // SEEDED: segments; the pool may hold segments that carry a position instead of rows (seeding.h: text mode)
     uint64_t nSegs = 0;
     bool segMarked = false;
@@ -168,6 +176,15 @@ struct BatchState
     {
         drop( NAMES );
         drop( SEEDED );
+        matesRest = false;
+        restAt[ 0 ] = restAt[ 1 ] = restBytes[ 0 ] = restBytes[ 1 ] = 0;
+    }
+    // ma_batch_set_mates_bgzf on success, behind finish( NAMES ): where in the text buffer the records beyond the last pair are
+    void keepMatesRest( const uint64_t at[ 2 ], const uint64_t bytes[ 2 ] )
+    {
+        matesRest = true;
+        restAt[ 0 ] = at[ 0 ], restAt[ 1 ] = at[ 1 ];
+        restBytes[ 0 ] = bytes[ 0 ], restBytes[ 1 ] = bytes[ 1 ];
     }
     // finish: p is valid; a stage brings the stages before it
     void finish( Product p )

@@ -5,7 +5,8 @@
 //   - inflateHost( ) below runs the same routine serially: the statement of the rules the CPU tests (tests/emul/bgzf_dev_test.cpp)
 //     compare with zlib, and the GPU tests with the kernels; BatchBgzfReader (ma_batch_nodes.h) inflates the last members of a
 //     chunk with it to find its cut;
-//   - libma_amd.so words a refusal with errorText( ) / message( ).
+//   - libma_amd.so words a refusal with errorText( ) / message( ), ma_batch_set_mates_bgzf with messageMates( ); that call's
+//     own rules -- two such chains, paired -- are in ma_mates_bgzf_dev.h.
 // No zlib, no containers, no strings.
 //
 // BGZF (what bgzip and htslib write) is a chain of independent gzip members of at most 64 KiB of text each, every one with its
@@ -133,6 +134,12 @@ inline void message( char* pOut, size_t uiCap, uint64_t uiMember, uint64_t uiByt
 {
     snprintf( pOut, uiCap, "ma_batch_set_reads_bgzf: member %llu (byte %llu): %s", (unsigned long long)uiMember, (unsigned long long)uiByte,
               errorText( uiReason ) );
+}
+// "ma_batch_set_mates_bgzf: text <1|2>: member <k> (byte <X>): <reason>": k and X count within that text's members
+inline void messageMates( char* pOut, size_t uiCap, uint32_t uiText, uint64_t uiMember, uint64_t uiByte, uint32_t uiReason )
+{
+    snprintf( pOut, uiCap, "ma_batch_set_mates_bgzf: text %u: member %llu (byte %llu): %s", (unsigned)uiText, (unsigned long long)uiMember,
+              (unsigned long long)uiByte, errorText( uiReason ) );
 }
 // violations are ordered by member, then by reason
 MA_BGZF_HD uint64_t key( uint64_t uiMember, uint32_t uiReason )

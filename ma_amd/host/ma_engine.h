@@ -490,6 +490,46 @@ class Engine
         endRun( R, t0, [ & ]( char* p, size_t c ) { snprintf( p, c, "%zu + %zu bytes of mate text, %llu pairs, h2d+parse", uiBytes1, uiBytes2, (unsigned long long)nPairs ); } );
         return pRes;
     }
+    // runMatesText for a batch of two BGZF-compressed files: text i is aSide[ i ]'s head followed by what its members inflate to,
+    // minus its last n_drop bytes (ma_batch_set_mates_bgzf).  The two texts need not hold equally many records: directly after
+    // the set call succeeded -- once, also when the call ran twice for the capacity -- and before the stages, rOnRest gets what
+    // of either text lies beyond the last pair (ma_batch_get_mates_rest): the front of the caller's next heads.  The member
+    // headers are walked here as well, for the size of the texts the device batch is sized by.
+    template <typename ON_REST>
+    std::shared_ptr<BatchResult> runMatesBgzf( const ma_bgzf_text aSide[ 2 ], bool bRevCompMates, uint32_t uiSamOptions, bool bInversions, ON_REST&& rOnRest )
+    {
+        auto pRes = beginRun( false, true, true, uiSamOptions );
+        BatchResult& R = *pRes;
+        auto t0 = std::chrono::steady_clock::now( );
+        size_t uiBytes = 0;
+        for( int i = 0; i < 2; i++ )
+        {
+            ma_bgzf::Result xWalk;
+            ma_bgzf::inflateHost( (const uint8_t*)aSide[ i ].members, aSide[ i ].n_bytes, nullptr, &xWalk ); // (a bad header: the library refuses it by name)
+            uiBytes += aSide[ i ].n_head + xWalk.uiBytes - std::min<uint64_t>( aSide[ i ].n_drop, xWalk.uiBytes );
+        }
+        uint64_t aConsumed[ 2 ], aTextBytes[ 2 ];
+        const uint64_t nPairs = setText( uiBytes, 2, [ & ]( uint64_t* pPairs ) {
+            return ma_batch_set_mates_bgzf( pBatch, aSide, bRevCompMates ? 1 : 0, pPairs, aTextBytes, aConsumed );
+        } );
+        std::string asRest[ 2 ];
+        for( int i = 0; i < 2; i++ )
+        {
+            uint64_t n = 0;
+            engineCheck( ma_batch_get_mates_rest( pBatch, i, &n, nullptr ) );
+            asRest[ i ].resize( n );
+            if( n )
+                engineCheck( ma_batch_get_mates_rest( pBatch, i, &n, &asRest[ i ][ 0 ] ) );
+        }
+        rOnRest( asRest[ 0 ], asRest[ 1 ] );
+        R.uiReads = 2 * nPairs;
+        R.fH2D = secondsSince( t0 );
+        t0 = runStages( R, bInversions );
+        engineCheck( ma_batch_counts( pBatch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &R.uiAlignedReads ) );
+        fetchPairSam( R, uiSamOptions );
+        endRun( R, t0, [ & ]( char* p, size_t c ) { snprintf( p, c, "%zu bytes of compressed mate text, %llu pairs, h2d+inflate+parse", uiBytes, (unsigned long long)nPairs ); } );
+        return pRes;
+    }
 
   private:
     // uiBytes of text that rSet puts into pBatch (it returns the library's status and the reads it found)

@@ -19,7 +19,9 @@
 #include "ma_engine.h"
 #include <algorithm>
 #include <cmath>
+#include <condition_variable>
 #include <limits>
+#include <mutex>
 #include <tuple>
 #include <cstdint>
 #include <cstdio>
@@ -1517,6 +1519,48 @@ class MatesTextBatch : public libMS::Container
   public:
     std::string sText1, sText2;
 };
+// What a batch of two compressed mate files hands back to its reader: the records of either text beyond the batch's last pair
+// (ma_batch_get_mates_rest), which are the front of the next batch's heads.  The reader's next execute( ) waits for them; a
+// batch that is destroyed without having handed them back -- its worker threw, or the caller dropped it -- releases that wait
+// and makes that execute( ) throw.  Knows no device: two strings.
+struct MatesRestLink
+{
+    std::mutex xMutex;
+    std::condition_variable xCondition;
+    bool bPending = false, bAbandoned = false; // a batch is out and its rests are not back; a batch went without handing back
+    std::string asRest[ 2 ];
+};
+// The same out of two BGZF-compressed files (BatchPairedBgzfReader of ma_batch_nodes.h): text i is asHead[ i ] followed by what
+// the whole members of asMembers[ i ] inflate to, minus its last auiDrop[ i ] bytes -- what BatchAligner::executePairedBgzfSam
+// hands to ma_batch_set_mates_bgzf.  The two texts need not hold equally many records: handBack( ) returns what the device left
+// over, once, directly after the device call succeeded.
+class MatesBgzfBatch : public libMS::Container
+{
+  public:
+    std::string asHead[ 2 ], asMembers[ 2 ];
+    uint64_t auiDrop[ 2 ] = { 0, 0 };
+    std::shared_ptr<MatesRestLink> pLink; // the link back to the reader (none: nobody waits)
+    bool bHandedBack = false;
+
+    void handBack( const std::string& sRest1, const std::string& sRest2 )
+    {
+        if( pLink == nullptr || bHandedBack )
+            return;
+        std::lock_guard<std::mutex> xLock( pLink->xMutex );
+        pLink->asRest[ 0 ] = sRest1, pLink->asRest[ 1 ] = sRest2;
+        pLink->bPending = false;
+        bHandedBack = true;
+        pLink->xCondition.notify_all( );
+    }
+    ~MatesBgzfBatch( )
+    {
+        if( pLink == nullptr || bHandedBack )
+            return;
+        std::lock_guard<std::mutex> xLock( pLink->xMutex );
+        pLink->bPending = false, pLink->bAbandoned = true;
+        pLink->xCondition.notify_all( );
+    }
+};
 
 // Phase times of a throughput run (seconds, summed over the device batches; the phases of different batches overlap when
 // several are in flight, so their sum can exceed the wall time)
@@ -2035,6 +2079,35 @@ class BatchAligner
         return withEngine( pIndex, [ & ]( detail::Engine& rEngine ) {
             return rEngine.runMatesText( pTexts->sText1.data( ), pTexts->sText1.size( ), pTexts->sText2.data( ), pTexts->sText2.size( ),
                                          xParams.bRevCompPairedReadMates, samOptionBits( xParams.xSam ), xP.search_inversions != 0 );
+        } );
+    }
+    // executePairedTextSam for mates that still are the COMPRESSED bytes of their two BGZF files (BatchPairedBgzfReader): the
+    // device inflates both chains of members in one launch and goes on as for the texts (ma_batch_set_mates_bgzf).  What the
+    // device leaves over of either text goes back to the batch's reader directly after that call (MatesBgzfBatch::handBack), so
+    // the reader's next batch waits for the inflate and the parse of this one, not for its alignment.  Not with the NGMLR tag
+    // emulation.
+    std::shared_ptr<AlignedBatch> executePairedBgzfSam( std::shared_ptr<FMIndex> pFM_index, std::shared_ptr<MatesBgzfBatch> pBatch,
+                                                        std::shared_ptr<Pack> pPack )
+    {
+        if( xParams.xSam.bEmulateNgmlrTags )
+            throw std::runtime_error( "BatchAligner::executePairedBgzfSam: not with the NGMLR tag emulation (use executePaired and "
+                                      "PairedFileWriter)" );
+        nameContigs( *pFM_index->pDev, *pPack );
+        return executePairedBgzfSamOn( pFM_index->pDev->p, pBatch );
+    }
+    // (the contigs of pIndex are named already)
+    std::shared_ptr<AlignedBatch> executePairedBgzfSamOn( const ma_index* pIndex, std::shared_ptr<MatesBgzfBatch> pBatch )
+    {
+        if( !servesPairSam( ) )
+            throw std::runtime_error( "BatchAligner::executePairedBgzfSam: not with the NGMLR tag emulation (use executePairedFlat and "
+                                      "BatchPairedFileWriter)" );
+        ma_bgzf_text aSide[ 2 ];
+        for( int i = 0; i < 2; i++ )
+            aSide[ i ] = ma_bgzf_text{ pBatch->asHead[ i ].data( ), pBatch->asHead[ i ].size( ), pBatch->asMembers[ i ].data( ), pBatch->asMembers[ i ].size( ),
+                                       pBatch->auiDrop[ i ] };
+        return withEngine( pIndex, [ & ]( detail::Engine& rEngine ) {
+            return rEngine.runMatesBgzf( aSide, xParams.bRevCompPairedReadMates, samOptionBits( xParams.xSam ), xP.search_inversions != 0,
+                                         [ & ]( const std::string& sRest1, const std::string& sRest2 ) { pBatch->handBack( sRest1, sRest2 ); } );
         } );
     }
 

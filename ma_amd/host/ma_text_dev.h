@@ -426,15 +426,22 @@ struct PairResult
     uint32_t uiText, uiReason; // MATES_LINE: 1 or 2, and the reason
     uint64_t uiLine, uiByte; // MATES_LINE: 0-based line, offset of its first byte
 };
-// "ma_batch_set_mates_text: text <1|2>: line <L> (byte <X>): <reason>" and the two other refusals; uiLine is 0-based here
-inline void messageMates( char* pOut, size_t uiCap, uint32_t uiRefusal, uint32_t uiText, uint64_t uiLine, uint64_t uiByte, uint32_t uiReason )
+// "<who>: text <1|2>: line <L> (byte <X>): <reason>" and the two other refusals; uiLine is 0-based here.  (ma_batch_set_mates_bgzf
+// words a refusal of its inflated texts with it.)
+inline void messageMatesOf( char* pOut, size_t uiCap, const char* pWho, uint32_t uiRefusal, uint32_t uiText, uint64_t uiLine, uint64_t uiByte,
+                            uint32_t uiReason )
 {
     if( uiRefusal == MATES_LINE )
-        snprintf( pOut, uiCap, "ma_batch_set_mates_text: text %u: line %llu (byte %llu): %s", (unsigned)uiText, (unsigned long long)( uiLine + 1 ),
+        snprintf( pOut, uiCap, "%s: text %u: line %llu (byte %llu): %s", pWho, (unsigned)uiText, (unsigned long long)( uiLine + 1 ),
                   (unsigned long long)uiByte, errorText( uiReason ) );
     else
-        snprintf( pOut, uiCap, "ma_batch_set_mates_text: %s",
+        snprintf( pOut, uiCap, "%s: %s", pWho,
                   uiRefusal == MATES_KIND ? "the two texts differ in kind" : uiRefusal == MATES_CAPACITY ? "batch capacity exceeded" : "no error" );
+}
+// "ma_batch_set_mates_text: text <1|2>: line <L> (byte <X>): <reason>" ...
+inline void messageMates( char* pOut, size_t uiCap, uint32_t uiRefusal, uint32_t uiText, uint64_t uiLine, uint64_t uiByte, uint32_t uiReason )
+{
+    messageMatesOf( pOut, uiCap, "ma_batch_set_mates_text", uiRefusal, uiText, uiLine, uiByte, uiReason );
 }
 // offset of the first byte of record uiRecord of an ACCEPTED text with the line starts parseHost left in pStart (n if the text
 // has no such record)
