@@ -25,6 +25,9 @@ static __device__ unsigned long long g_chain_prof[ 16 ];
 #define CH_ADD( i, a, b )
 #endif
 
+// draws a table holds: two RANSAC runs of 100 iterations with their retries (run_ransac) stay inside it
+#define MA_RNG_TAB 256
+
 struct ChainParams
 {
     u32 max_num_soc, min_num_soc;
@@ -43,6 +46,13 @@ struct ChainParams
     double max_delta_dist;
     u32 rng_ring[ 31 ]; // glibc random() state after srand(seed) (310 discards done)
     u32 libm_probe; // ma_params::libm_probe: 0 = off (the product), else every libm result is nudged (see LibmProbe)
+    // the first rng_tab_n draws out of rng_ring (fill_rand_table; 0: no table): every read starts from the same ring, so its
+    // k-th draw is the same number, and a read's generator is a counter into this table (GlibcRand).  The table (with a copy of
+    // the ring behind it, MA_RNG_TAB_WORDS) lies in memory of its own (on the device: a buffer of the batch), not in this
+    // struct: kernel arguments indexed by a lane's counter, or pointed to from a lane's generator, are copied to every lane's
+    // scratch
+    u32 rng_tab_n = 0;
+    const u32* rng_tab = nullptr;
 };
 
 struct SoCEntry // tuple<SoCOrder, it, it> (soc.h:26-90, 192)
@@ -81,23 +91,70 @@ struct ChainScratch
     Shadow* sh2; // n
     double* vX; // 3n
     double* vY; // 3n
-    double* med; // 3n
+    double* med; // 6n (the medians' copy of vY, then dx | dy of the line fit)
     i32* inl; // 3n
     i32* best; // 3n
 };
 
-struct GlibcRand // glibc stdlib/random_r.c, TYPE_3: r[i] = r[i-3] + r[i-31], output >> 1
+// The same thirteen arrays as ONE block per read (short reads, k_chain_list): a read of n seeds at seed offset `off` owns
+// [off * MA_CHAIN_SCRATCH_B, (off + n) * MA_CHAIN_SCRATCH_B) of one buffer, its arrays back to back in it, the 8-byte types
+// first -- a read of three seeds touches ten 128-byte lines instead of thirteen slices in thirteen allocations.  Seed offsets
+// of different reads are disjoint ranges, so the blocks are; every array starts at a multiple of 8 bytes (of 4: best).
+#define MA_CHAIN_SCRATCH_B                                                                                                       \
+    ( 4 * sizeof( ma_seed ) + sizeof( SoCEntry ) + sizeof( RefMinMax ) + 2 * sizeof( Shadow ) + ( 3 + 3 + 6 ) * sizeof( double ) + \
+      ( 3 + 3 ) * sizeof( i32 ) )
+MA_HD ChainScratch chain_scratch_carve( uint8_t* base, u64 off, u32 n )
+{
+    static_assert( sizeof( ma_seed ) % 8 == 0 && sizeof( SoCEntry ) % 8 == 0 && sizeof( RefMinMax ) % 8 == 0 && sizeof( Shadow ) % 8 == 0 &&
+                       MA_CHAIN_SCRATCH_B % 8 == 0,
+                   "the arrays of a block follow each other without padding" );
+    ChainScratch C;
+    uint8_t* p = base + off * MA_CHAIN_SCRATCH_B;
+    const u64 m = n;
+    C.work = (ma_seed*)p, p += m * sizeof( ma_seed );
+    C.setA = (ma_seed*)p, p += m * sizeof( ma_seed );
+    C.setB = (ma_seed*)p, p += m * sizeof( ma_seed );
+    C.outA = (ma_seed*)p, p += m * sizeof( ma_seed );
+    C.maxima = (SoCEntry*)p, p += m * sizeof( SoCEntry );
+    C.mm = (RefMinMax*)p, p += m * sizeof( RefMinMax );
+    C.sh1 = (Shadow*)p, p += m * sizeof( Shadow );
+    C.sh2 = (Shadow*)p, p += m * sizeof( Shadow );
+    C.vX = (double*)p, p += 3 * m * sizeof( double );
+    C.vY = (double*)p, p += 3 * m * sizeof( double );
+    C.med = (double*)p, p += 6 * m * sizeof( double );
+    C.inl = (i32*)p, p += 3 * m * sizeof( i32 );
+    C.best = (i32*)p;
+    return C;
+}
+
+// glibc stdlib/random_r.c, TYPE_3: r[i] = r[i-3] + r[i-31], output >> 1.  With a table of the ring's first nTab draws
+// (ChainParams::rng_tab) the generator is a counter into it and leaves its ring alone: no copy of the ring per read, no
+// read-modify-write of it per draw.  The draw behind the table rebuilds the ring by replaying the table's draws and goes on.
+struct GlibcRand
 {
     u32 ring[ 31 ];
     i32 f, b;
+    const u32* tab = nullptr;
+    const u32* seed = nullptr;
+    u32 nTab = 0, k = 0;
     MA_HD void init( const u32* st )
     {
         for( int i = 0; i < 31; i++ )
             ring[ i ] = st[ i ];
         f = 3;
         b = 0;
+        nTab = 0;
     }
-    MA_HD i32 next( )
+    // table: n draws, then the 31 words of the ring they came out of (fill_rand_table) -- in memory of its own, so that no
+    // pointer into a kernel's arguments has to be kept
+    MA_HD void init( const u32* st, const u32* table, u32 n )
+    {
+        if( n == 0 )
+            init( st );
+        else
+            tab = table, seed = table + n, nTab = n, k = 0;
+    }
+    MA_HD i32 step( )
     {
         ring[ f ] += ring[ b ];
         const u32 res = ring[ f ] >> 1;
@@ -107,7 +164,31 @@ struct GlibcRand // glibc stdlib/random_r.c, TYPE_3: r[i] = r[i-3] + r[i-31], ou
             b = 0;
         return (i32)res;
     }
+    MA_HD i32 next( )
+    {
+        if( k < nTab )
+            return (i32)tab[ k++ ];
+        if( nTab != 0 )
+        {
+            const u32 n = nTab;
+            init( seed );
+            for( u32 i = 0; i < n; i++ )
+                step( );
+        }
+        return step( );
+    }
 };
+// the first n draws out of `ring` (the state after srand) and the ring itself behind them: n + 31 words -- ChainParams::rng_tab
+#define MA_RNG_TAB_WORDS( n ) ( ( n ) + 31 )
+MA_HD void fill_rand_table( const u32* ring, u32* tab, u32 n )
+{
+    GlibcRand g;
+    g.init( ring );
+    for( u32 i = 0; i < n; i++ )
+        tab[ i ] = (u32)g.step( );
+    for( u32 i = 0; i < 31; i++ )
+        tab[ n + i ] = ring[ i ];
+}
 
 // Sensitivity probe for the four libm functions the stage decides with (tan, sin, atan, log): the reference evaluates them
 // with glibc, the device with ocml, and the two differ in the last bit for ~13 % of the arguments
@@ -956,7 +1037,7 @@ MA_HD u32 chain_read( const IndexView& X, const ChainParams& P, const ChainScrat
         nmx0 = soc_sweep( X, P, C.work, nSeeds, qlen, C.maxima, C.mm, (KeyIdx*)C.sh1, C.setA );
     u32 nmx = nmx0;
     GlibcRand rng;
-    rng.init( P.rng_ring );
+    rng.init( P.rng_ring, P.rng_tab, P.rng_tab_n );
     LibmProbe lp{ P.libm_probe, 0 };
     u32 nsets = 0;
     u32 numTries = 0, socIndex = 0, repeat = 0;
@@ -1089,6 +1170,74 @@ MA_HD u32 chain_read( const IndexView& X, const ChainParams& P, const ChainScrat
     atomicAdd( &g_chain_prof[ 11 ], (unsigned long long)numTries );
     atomicAdd( &g_chain_prof[ 12 ], (unsigned long long)nSeeds );
 #endif
+    return nsets;
+}
+
+// chain_read for a read of AT MOST ONE seed, in closed form (k_chain_split answers such reads without a lane of k_chain; no
+// queue, no pre-swept strips).  What chain_read does with one seed, step by step:
+//   sweep    one window holding the seed; it becomes a strip iff (double)len >= fMinLen (soc_windows), and the rebuild over the
+//            re-sorted seeds (soc_rebuild) finds the same seed again
+//   loop     one turn: ++numTries > max_num_soc ends it at max_num_soc == 0; the tests against lastHarm / bestSoC compare with
+//            zero and never fire; a reverse-strand seed is un-mirrored, harmonize_one copies the one seed; the two harm_score_min*
+//            tests on curHarm = len; apply_filters keeps the one seed; emit writes set 0 (soc 0 on either strand) and the seed
+//            at the start of the read's private region; `repeat` stays 1 only below switch_qlen with curHarm within the tolerance
+//            of lastHarm = 0
+//   tail     the repeat / nsets-- loop
+// tests/emul/chain_split_test.cpp holds this against chain_read over the parameter grid.
+MA_HD u32 chain_read_one( const IndexView& X, const ChainParams& P, const ma_seed* seeds, u32 nSeeds, u32 qlen, const ChainOut& O, u32& err )
+{
+    if( nSeeds == 0 )
+        return 0;
+    ma_seed s = seeds[ 0 ];
+    double fMinLen = mmax( (double)P.harm_score_min_rel * (double)(u64)qlen, (double)(u64)P.harm_score_min );
+    if( P.genome_size_disable >= X.n )
+        fMinLen = 0;
+    const u64 len = (u64)s.len;
+    if( !( (double)len >= fMinLen ) || P.max_num_soc == 0 )
+        return 0;
+    const bool heur = !P.disable_heuristics;
+    const bool pastMin = heur && 1 > P.min_num_soc; // numTries == 1
+    if( s.on_forward == 0 )
+        s.r_start = (i64)( X.n - (u64)s.r_start - 1 );
+    if( pastMin && len < (u64)P.harm_score_min )
+        return 0;
+    if( heur && (double)len < (double)(u64)qlen * P.harm_score_min_rel )
+        return 0;
+    if( O.set_cap > 0 )
+    {
+        u64 off;
+        if( O.local && O.local_cap >= 1 )
+        {
+            off = MA_HSET_LOCAL;
+            O.local[ 0 ] = s;
+        }
+        else
+        {
+            off = bump_alloc( O.pool_used, 1 );
+            if( off + 1 <= O.pool_cap )
+                O.pool[ off ] = s;
+            else
+                err |= MA_ERR_SEED_OVERFLOW;
+        }
+        O.sets[ 0 ].off = off;
+        O.sets[ 0 ].cnt = 1;
+        O.sets[ 0 ].soc = 0;
+    }
+    else
+        err |= MA_ERR_SCRATCH_OVERFLOW;
+    u32 nsets = 1, repeat = 1;
+    const u64 switchQ = (u64)P.switch_qlen;
+    if( pastMin && (u64)qlen < switchQ && switchQ != 0 )
+    {
+        const double tol = (double)(u64)qlen * P.score_diff_tol;
+        if( !( (double)len + tol >= 0.0 && (double)len - tol <= 0.0 ) )
+            repeat = 0;
+    }
+    else
+        repeat = 0;
+    if( heur )
+        for( u32 ui = 0; ui < repeat && nsets > P.min_num_soc; ui++ )
+            nsets--;
     return nsets;
 }
 } // namespace ma

@@ -24,6 +24,23 @@ static ChainParams chain_params( const ma_params& P )
     C.libm_probe = (u32)P.libm_probe;
     return C;
 }
+// the table of the ring's first draws (ChainParams::rng_tab) on the device: filled next to the ring, uploaded when the batch has
+// none for this srand seed yet -- it depends on nothing else
+static int chain_rand_table( ma_batch* b, ChainParams& C )
+{
+    if( !b->rngTabValid || b->rngTabSeed != (u32)b->P.srand_seed )
+    {
+        if( b->cRng.reserve( MA_RNG_TAB_WORDS( MA_RNG_TAB ) * 4 ) )
+            return 1;
+        fill_rand_table( C.rng_ring, b->rngTabHost, MA_RNG_TAB );
+        MA_HIP( hipMemcpyAsync( b->cRng.p, b->rngTabHost, MA_RNG_TAB_WORDS( MA_RNG_TAB ) * 4, hipMemcpyHostToDevice, b->stream ) );
+        b->rngTabSeed = (u32)b->P.srand_seed;
+        b->rngTabValid = true;
+    }
+    C.rng_tab = b->cRng.as<u32>( );
+    C.rng_tab_n = MA_RNG_TAB;
+    return 0;
+}
 
 // Lanes of a wavefront that get a read / a seed set in the one-item-per-lane kernels (k_chain, k_dp_enum, k_stitch).
 // Their lanes run long data-dependent loops (std::sort emulation, RANSAC, the walk over the seeds of an alignment), so
@@ -31,10 +48,15 @@ static ChainParams chain_params( const ma_params& P )
 // of 1 M short reads fills the machine with full waves; a batch of 20 k long reads is only 313 full waves on 1024
 // SIMDs, each serialising 64 lanes (50 kb reads: k_chain 545 ms).  Fewer items per wave spread the same lanes over
 // ~4 waves per SIMD.
+static u32 lanes_forced( )
+{
+    const char* e = getenv( "MA_LANES_PER_WAVE" ); // tuning hook
+    return e ? (u32)std::min( 64, std::max( 1, atoi( e ) ) ) : 0;
+}
 static u32 lanes_per_wave( u64 items )
 {
-    if( const char* e = getenv( "MA_LANES_PER_WAVE" ) ) // tuning hook
-        return (u32)std::min( 64, std::max( 1, atoi( e ) ) );
+    if( const u32 f = lanes_forced( ) )
+        return f;
     if( items >= 131072 )
         return 64; // >= 2 full waves per SIMD: measured no gain from thinner waves (10 kb x 200 k reads)
     const u64 waves = 256ull * 4 * 4;
@@ -56,12 +78,28 @@ int ma_chain_batch( ma_batch* b )
     const u64 ts = b->st.nSeeds + 1;
     const u32 set_cap = 2 * (u32)b->P.max_num_soc;
     b->hpoolCap = 3 * ts + 1024;
-    if( b->cWork.reserve( ts * sizeof( ma_seed ) ) || b->cMax.reserve( ts * sizeof( SoCEntry ) ) ||
-        b->cMm.reserve( ts * sizeof( RefMinMax ) ) || b->cA.reserve( ts * sizeof( ma_seed ) ) ||
-        b->cB.reserve( ts * sizeof( ma_seed ) ) || b->cOut.reserve( ts * sizeof( ma_seed ) ) ||
-        b->cSh1.reserve( ts * sizeof( Shadow ) ) || b->cSh2.reserve( ts * sizeof( Shadow ) ) ||
-        b->cVx.reserve( 3 * ts * 8 ) || b->cVy.reserve( 3 * ts * 8 ) || b->cMed.reserve( 6 * ts * 8 ) ||
-        b->cInl.reserve( 3 * ts * 4 ) || b->cBest.reserve( 3 * ts * 4 ) ||
+    // long reads (thousands of seeds per read): the sweep's two std::sort calls run as wave-cooperative kernels on arrays in
+    // LDS, the window sweep between them and the rest of the stage stay one read per lane (MA_CHAIN_WAVE_SORT=0: all in k_chain)
+    const bool waveSortOn = []( ) { // (read on every call: the tests switch it inside one process)
+        const char* e = getenv( "MA_CHAIN_WAVE_SORT" );
+        return !e || atoi( e ) != 0;
+    }( );
+    const bool waveSort = waveSortOn && !b->st.socGiven && b->max_qlen > 254 && b->st.nSeeds >= 64;
+    // short reads: reads of at most one seed are answered by k_chain_split, the others run as a list on scratch packed per read
+    // (MA_CHAIN_SPLIT=0: every read a lane of k_chain on the thirteen arrays, as for long reads)
+    const bool split = !waveSort && !b->st.socGiven && []( ) {
+        const char* e = getenv( "MA_CHAIN_SPLIT" );
+        return !e || atoi( e ) != 0;
+    }( );
+    if( split ? b->cPack.reserve( ts * MA_CHAIN_SCRATCH_B )
+               : ( b->cWork.reserve( ts * sizeof( ma_seed ) ) || b->cMax.reserve( ts * sizeof( SoCEntry ) ) ||
+                   b->cMm.reserve( ts * sizeof( RefMinMax ) ) || b->cA.reserve( ts * sizeof( ma_seed ) ) ||
+                   b->cB.reserve( ts * sizeof( ma_seed ) ) || b->cOut.reserve( ts * sizeof( ma_seed ) ) ||
+                   b->cSh1.reserve( ts * sizeof( Shadow ) ) || b->cSh2.reserve( ts * sizeof( Shadow ) ) ||
+                   b->cVx.reserve( 3 * ts * 8 ) || b->cVy.reserve( 3 * ts * 8 ) || b->cMed.reserve( 6 * ts * 8 ) ||
+                   b->cInl.reserve( 3 * ts * 4 ) || b->cBest.reserve( 3 * ts * 4 ) ) )
+        return 1;
+    if( ( split && b->cList.reserve( ( n + 1 ) * 4 ) ) ||
         b->hpool.reserve( b->hpoolCap * sizeof( ma_seed ) ) || b->hlocal.reserve( ( 3 * ts + 16 ) * sizeof( ma_seed ) ) ||
         b->hseedCnt.reserve( ( n + 2 ) * 8 ) || b->hseedOff.reserve( ( n + 2 ) * 8 ) ||
         b->setTab.reserve( n * set_cap * sizeof( HSet ) ) ||
@@ -70,6 +108,8 @@ int ma_chain_batch( ma_batch* b )
     ChainKernelArgs A;
     A.X = b->idx->v;
     A.P = chain_params( b->P );
+    if( chain_rand_table( b, A.P ) )
+        return 1;
     A.n_reads = (u32)n;
     A.roff = b->d_roff;
     A.seed_off = b->seedOff.as<u64>( );
@@ -99,13 +139,8 @@ int ma_chain_batch( ma_batch* b )
     A.queue_cnt = b->st.socGiven ? b->socInCnt.as<u32>( ) : nullptr;
     A.pre_nmx = nullptr;
     A.pre_sorted = nullptr;
-    // long reads (thousands of seeds per read): the sweep's two std::sort calls run as wave-cooperative kernels on arrays in
-    // LDS, the window sweep between them and the rest of the stage stay one read per lane (MA_CHAIN_WAVE_SORT=0: all in k_chain)
-    const bool waveSortOn = []( ) { // (read on every call: the tests switch it inside one process)
-        const char* e = getenv( "MA_CHAIN_WAVE_SORT" );
-        return !e || atoi( e ) != 0;
-    }( );
-    const bool waveSort = waveSortOn && !b->st.socGiven && b->max_qlen > 254 && b->st.nSeeds >= 64;
+    A.list = split ? b->cList.as<u32>( ) : nullptr;
+    A.pack = split ? b->cPack.as<uint8_t>( ) : nullptr;
     {
         EvTimer t( b, 2 );
         A.lanes = lanes_per_wave( n );
@@ -143,7 +178,16 @@ int ma_chain_batch( ma_batch* b )
             A.pre_nmx = b->preNmx.as<u32>( );
             A.pre_sorted = b->preSorted.as<u32>( );
         }
-        hipLaunchKernelGGL( k_chain, dim3( (unsigned)( ( n + A.lanes - 1 ) / A.lanes ) ), dim3( 64 ), 0, b->stream, A );
+        if( split )
+        {
+            MA_HIP( hipMemsetAsync( b->cList.p, 0, 4, b->stream ) );
+            hipLaunchKernelGGL( k_chain_split, dim3( (unsigned)( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream, A );
+            // (reads per wavefront from the list's length, on the device: chain_list_lanes)
+            A.lanes = lanes_forced( );
+            hipLaunchKernelGGL( k_chain_list, dim3( (unsigned)chain_list_blocks( n, A.lanes ) ), dim3( 64 ), 0, b->stream, A );
+        }
+        else
+            hipLaunchKernelGGL( k_chain, dim3( (unsigned)( ( n + A.lanes - 1 ) / A.lanes ) ), dim3( 64 ), 0, b->stream, A );
     }
     MA_HIP( hipGetLastError( ) );
     // CSR of sets per read: widen counts to u64 via a scan over u32->u64 transform

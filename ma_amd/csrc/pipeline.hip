@@ -148,6 +148,11 @@ struct ma_batch
     u64 hpoolCap = 0;
     DevBuf socIn, socInCnt; // SoC queues swept elsewhere (ma_batch_set_soc_heap), carved by seed offset
     DevBuf preNmx, preSorted; // long reads: strips per read after k_soc_windows, which sorts k_sort_seeds_wave did
+    DevBuf cPack, cList; // short reads: the thirteen scratch arrays as one block per read; the reads with two or more seeds
+    DevBuf cRng; // the first draws of the RANSAC generator (ChainParams::rng_tab), uploaded once per srand seed from rngTabHost
+    u32 rngTabHost[ MA_RNG_TAB_WORDS( MA_RNG_TAB ) ];
+    u32 rngTabSeed = 0;
+    bool rngTabValid = false;
     // dp
     DevBuf jobs, info, ez, cigOff, cigPool, kswScratch, clsLists, opsCap, opsOff, ops, hdr, order, mqOrder, mqCnt;
     DevBuf outCnt, outOps, outAlnOff, outOpsOff, outAlns, outOpsPairs; // packed results (get_alns)
@@ -902,7 +907,7 @@ int ma_align_batch( ma_batch* b )
             MA_ROW( taskB ), MA_ROW( taskCnt ), MA_ROW( taskKey ), MA_ROW( taskKey2 ), MA_ROW( taskPerm ), MA_ROW( taskPerm2 ),
             MA_ROW( segSeedCnt ), MA_ROW( segSeedOff ), MA_ROW( seedOff ), MA_ROW( seedCnt ), MA_ROW( seeds ), MA_ROW( cubTmp ), MA_ROW( cWork ),
             MA_ROW( cMax ), MA_ROW( cMm ), MA_ROW( cA ), MA_ROW( cB ), MA_ROW( cOut ), MA_ROW( cSh1 ), MA_ROW( cSh2 ), MA_ROW( cVx ), MA_ROW( cVy ),
-            MA_ROW( cMed ), MA_ROW( cInl ), MA_ROW( cBest ), MA_ROW( hpool ), MA_ROW( setTab ), MA_ROW( nsets ), MA_ROW( hsetOff ),
+            MA_ROW( cMed ), MA_ROW( cInl ), MA_ROW( cBest ), MA_ROW( cPack ), MA_ROW( cList ), MA_ROW( hpool ), MA_ROW( setTab ), MA_ROW( nsets ), MA_ROW( hsetOff ),
             MA_ROW( hsetFlat ), MA_ROW( hsetRead ), MA_ROW( jobs ), MA_ROW( info ), MA_ROW( ez ), MA_ROW( cigOff ), MA_ROW( cigPool ),
             MA_ROW( kswScratch ), MA_ROW( clsLists ), MA_ROW( opsCap ), MA_ROW( opsOff ), MA_ROW( ops ), MA_ROW( hdr ), MA_ROW( order ),
             MA_ROW( mqOrder ), MA_ROW( mqCnt ), MA_ROW( outCnt ), MA_ROW( outOps ), MA_ROW( outAlnOff ), MA_ROW( outOpsOff ), MA_ROW( outAlns ),

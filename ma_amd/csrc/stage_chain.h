@@ -32,7 +32,7 @@ struct ChainKernelArgs
     u32 set_cap;
     u32* nsets; // per read
     unsigned long long* ctr;
-    u32 lanes; // reads per wavefront (lanes_per_wave)
+    u32 lanes; // reads per wavefront (lanes_per_wave); k_chain_list: a forced value or 0 (chain_list_lanes)
     // optional: the SoC queues were swept elsewhere (ma_batch_set_soc_heap); carved by seed offset like the scratch
     const ma_soc* queue;
     const u32* queue_cnt;
@@ -40,15 +40,42 @@ struct ChainKernelArgs
     // k_soc_windows): strips per read, and which of a read's two sorts the wave kernel did (bit 0 delta, bit 1 reference)
     const u32* pre_nmx;
     const u32* pre_sorted;
+    // optional (short reads, k_chain_split / k_chain_list): list[ 0 ] = reads with two or more seeds, their indices behind it;
+    // pack = the scratch as one block per read (chain_scratch_carve), instead of the thirteen arrays above
+    u32* list;
+    uint8_t* pack;
 };
 
-__global__ void __launch_bounds__( 64 ) __attribute__( ( amdgpu_waves_per_eu( 4, 4 ) ) ) k_chain( ChainKernelArgs A )
+// where read r's sets and their seeds go
+__device__ __forceinline__ ChainOut chain_out_of( const ChainKernelArgs& A, u32 r, u64 off, u32 n )
 {
-    const u32 r = blockIdx.x * A.lanes + threadIdx.x;
-    if( threadIdx.x >= A.lanes || r >= A.n_reads )
-        return;
-    const u64 off = A.seed_off[ r ];
-    const u32 n = A.seed_cnt[ r ];
+    ChainOut O;
+    O.pool = A.hpool;
+    O.pool_cap = A.hpool_cap;
+    O.pool_used = &A.ctr[ CTR_HSEED_USED ];
+    O.sets = A.sets + (u64)r * A.set_cap;
+    O.set_cap = A.set_cap;
+    O.local = A.hlocal + 3 * off; // seed ranges of different reads are disjoint (but not ordered by read)
+    O.local_cap = 3 * n;
+    return O;
+}
+// the lane of k_chain / k_chain_list: read r (n seeds at `off`) on the scratch C
+__device__ __forceinline__ void chain_lane( const ChainKernelArgs& A, u32 r, u64 off, u32 n, const ChainScratch& C )
+{
+    if( A.pre_nmx == nullptr )
+        for( u32 i = 0; i < n; i++ )
+            C.work[ i ] = A.seeds[ off + i ];
+    const ChainOut O = chain_out_of( A, r, off, n );
+    u32 err = 0;
+    const u32 qlen = (u32)( A.roff[ r + 1 ] - A.roff[ r ] );
+    const u32 ns = chain_read( A.X, A.P, C, n, qlen, O, err, A.queue ? A.queue + off : nullptr, A.queue ? A.queue_cnt[ r ] : 0,
+                               A.pre_nmx != nullptr, A.pre_nmx ? A.pre_nmx[ r ] : 0, A.pre_sorted ? ( A.pre_sorted[ r ] & 2u ) != 0 : false );
+    A.nsets[ r ] = ns < A.set_cap ? ns : A.set_cap;
+    if( err )
+        atomicOr( (unsigned long long*)&A.ctr[ CTR_ERR ], (unsigned long long)err );
+}
+__device__ __forceinline__ ChainScratch chain_scratch_arrays( const ChainKernelArgs& A, u64 off )
+{
     ChainScratch C;
     C.work = A.work + off;
     C.maxima = A.maxima + off;
@@ -63,24 +90,89 @@ __global__ void __launch_bounds__( 64 ) __attribute__( ( amdgpu_waves_per_eu( 4,
     C.med = A.med + 6 * off;
     C.inl = A.inl + 3 * off;
     C.best = A.best + 3 * off;
-    if( A.pre_nmx == nullptr )
-        for( u32 i = 0; i < n; i++ )
-            C.work[ i ] = A.seeds[ off + i ];
-    ChainOut O;
-    O.pool = A.hpool;
-    O.pool_cap = A.hpool_cap;
-    O.pool_used = &A.ctr[ CTR_HSEED_USED ];
-    O.sets = A.sets + (u64)r * A.set_cap;
-    O.set_cap = A.set_cap;
-    O.local = A.hlocal + 3 * off; // seed ranges of different reads are disjoint (but not ordered by read)
-    O.local_cap = 3 * n;
-    u32 err = 0;
-    const u32 qlen = (u32)( A.roff[ r + 1 ] - A.roff[ r ] );
-    const u32 ns = chain_read( A.X, A.P, C, n, qlen, O, err, A.queue ? A.queue + off : nullptr, A.queue ? A.queue_cnt[ r ] : 0,
-                               A.pre_nmx != nullptr, A.pre_nmx ? A.pre_nmx[ r ] : 0, A.pre_sorted ? ( A.pre_sorted[ r ] & 2u ) != 0 : false );
-    A.nsets[ r ] = ns < A.set_cap ? ns : A.set_cap;
-    if( err )
-        atomicOr( (unsigned long long*)&A.ctr[ CTR_ERR ], (unsigned long long)err );
+    return C;
+}
+
+// every read a lane: long reads behind the wave kernels, strips given from outside, MA_CHAIN_SPLIT=0
+__global__ void __launch_bounds__( 64 ) __attribute__( ( amdgpu_waves_per_eu( 4, 4 ) ) ) k_chain( ChainKernelArgs A )
+{
+    const u32 r = blockIdx.x * A.lanes + threadIdx.x;
+    if( threadIdx.x >= A.lanes || r >= A.n_reads )
+        return;
+    const u64 off = A.seed_off[ r ];
+    chain_lane( A, r, off, A.seed_cnt[ r ], chain_scratch_arrays( A, off ) );
+}
+
+// Short reads: a read of at most one seed costs chain_read a handful of copies, but as a lane of k_chain it waits out the
+// RANSAC runs and sorts of its wave's other lanes.  k_chain_split answers those reads on the spot (chain_read_one) and lists
+// the others, one ballot and one atomic per wave; the list's order does not matter, every output is indexed by read.
+// k_chain_list runs chain_read over the list, on scratch packed per read.
+__global__ void __launch_bounds__( 256 ) k_chain_split( ChainKernelArgs A )
+{
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    bool multi = false;
+    if( r < A.n_reads )
+    {
+        const u32 n = A.seed_cnt[ r ];
+        if( n >= 2 )
+            multi = true;
+        else
+        {
+            const u64 off = A.seed_off[ r ];
+            const ChainOut O = chain_out_of( A, r, off, n );
+            u32 err = 0;
+            const u32 ns = chain_read_one( A.X, A.P, A.seeds + off, n, (u32)( A.roff[ r + 1 ] - A.roff[ r ] ), O, err );
+            A.nsets[ r ] = ns < A.set_cap ? ns : A.set_cap;
+            if( err )
+                atomicOr( (unsigned long long*)&A.ctr[ CTR_ERR ], (unsigned long long)err );
+        }
+    }
+    const unsigned long long m = __ballot( multi );
+    if( m == 0 )
+        return;
+    const int lane = threadIdx.x & 63, leader = __ffsll( m ) - 1;
+    u32 base = 0;
+    if( lane == leader )
+        base = atomicAdd( &A.list[ 0 ], (u32)__popcll( m ) );
+    base = (u32)__shfl( (int)base, leader, 64 );
+    if( multi ) // (at most n_reads entries: every read is listed once)
+        A.list[ 1 + base + (u32)__popcll( m & ( ( 1ull << lane ) - 1 ) ) ] = r;
+}
+// The list's length stays on the device: a read-back between the two kernels would stall the stream, and the stage has none
+// before this point.  So k_chain_list computes its reads per wavefront from list[ 0 ] by lanes_per_wave's rule, and the host
+// launches the blocks the longest possible list (every read) would need under that rule; those beyond the list end at once.
+__host__ __device__ inline u32 chain_list_lanes( u64 items, u32 forced )
+{
+    if( forced != 0 )
+        return forced;
+    if( items >= 131072 )
+        return 64;
+    const u64 per = ( items + 4095 ) / 4096; // <= 32
+    return (u32)( per < 1 ? 1 : per );
+}
+// blocks of ceil( len / chain_list_lanes( len ) ) lists of len <= n reads: at most 4096 (and at most len) below 131072 reads
+static inline u64 chain_list_blocks( u64 n, u32 forced )
+{
+    if( forced != 0 )
+        return ( n + forced - 1 ) / forced;
+    const u64 thin = n < 4096 ? n : 4096, full = ( n + 63 ) / 64;
+    return thin > full ? thin : full;
+}
+#ifndef MA_CHAIN_LIST_WPE
+#define MA_CHAIN_LIST_WPE 4
+#endif
+__global__ void __launch_bounds__( 64 ) __attribute__( ( amdgpu_waves_per_eu( MA_CHAIN_LIST_WPE, MA_CHAIN_LIST_WPE ) ) )
+k_chain_list( ChainKernelArgs A )
+{
+    const u32 len = A.list[ 0 ];
+    const u32 lanes = chain_list_lanes( len, A.lanes );
+    const u32 i = blockIdx.x * lanes + threadIdx.x;
+    if( threadIdx.x >= lanes || i >= len )
+        return;
+    const u32 r = A.list[ 1 + i ];
+    const u64 off = A.seed_off[ r ];
+    const u32 n = A.seed_cnt[ r ];
+    chain_lane( A, r, off, n, chain_scratch_carve( A.pack, off, n ) );
 }
 
 // ---- long reads: the two big sorts of the sweep as wave-cooperative kernels (wave_sort.h), the window sweep between them
