@@ -229,7 +229,15 @@ int ma_stream_destroy( const ma_index*, void* hip_stream );
 /* stage INPUTS from the host: a module of this library takes over in the middle of a chain whose earlier stages ran
  * elsewhere (e.g. the reference's BinarySeeding followed by the MI355X StripOfConsideration).  Reads must be set; each
  * call replaces the output of the preceding stage (CSR offsets per read, records as the get functions return them). */
-int ma_batch_set_segments( ma_batch*, const uint64_t* seg_off /*n+1*/, const ma_segment* segs ); /* -> ma_extract_seeds_batch */
+/* Segments from elsewhere (layout of ma_batch_get_segments): the segments of read r are segs[seg_off[r] .. seg_off[r+1]).
+ * -> ma_extract_seeds_batch.  Contract, checked on the host before anything is uploaded: seg_off starts at 0 and never
+ * decreases; q_start, q_size, sa_start and sa_size are not negative; sa_size >= 1; sa_start >= 1 and sa_start + sa_size <= n + 1,
+ * n the length of the doubled text (the BWT has the rows 0 .. n; row 0 is the sentinel's, and no interval of the seeding starts
+ * there: FMIndex::init_interval, fMIndex.h:772); q_start + q_size + 1 <= the length of the read (q_size is the seed's length
+ * minus 1).  Any row range inside these limits is legal, whether the seeding could have found it or not.  sa_start_rc is not
+ * read and not checked.  A violation fails the call with "ma_batch_set_segments: ..." naming the read and the segment; the batch
+ * then holds no segments (as before ma_seed_batch) and stays usable. */
+int ma_batch_set_segments( ma_batch*, const uint64_t* seg_off /*n+1*/, const ma_segment* segs );
 int ma_batch_set_seeds( ma_batch*, const uint64_t* seed_off /*n+1*/, const ma_seed* seeds ); /* -> ma_chain_batch */
 /* Harmonized seed sets from elsewhere (layout of ma_batch_get_hsets): the sets of read r are hset_off[r] .. hset_off[r+1], the
  * seeds of set s are hseeds[hseed_off[s] .. hseed_off[s+1]), hset_soc[s] is its xStats.index_of_strip.  -> ma_dp_batch.

@@ -572,7 +572,9 @@ class Batch:
         return hoff, soff, soc, seeds[: int(soff[-1])]
 
     def set_segments(self, off, segs):
-        """Segments from elsewhere (CSR per read, the layout of segments()) -> extract()."""
+        """Segments from elsewhere (CSR per read, the layout of segments()) -> extract().  ma_batch_set_segments checks them on
+        the host and raises MaError("ma_batch_set_segments: ...") for a decreasing offset array, a negative field, an empty
+        interval, rows outside 1 .. n or a segment beyond its read; the batch then holds no segments and stays usable."""
         off = np.ascontiguousarray(off, dtype=np.uint64)
         segs = np.ascontiguousarray(np.concatenate([segs, np.zeros(1, dtype=SEGMENT_DT)]))
         _chk(lib().ma_batch_set_segments(self.h, _ptr(off), _ptr(segs)))

@@ -45,7 +45,7 @@ int ma_extract_seeds_batch( ma_batch* b )
         unsigned long long* c = b->ctr.as<unsigned long long>( );
         hipLaunchKernelGGL( k_seed_rows, dim3( (unsigned)( ( ns + 255 ) / 256 ) ), dim3( 256 ), 0, b->stream,
                             b->segPool.as<ma_segment>( ), b->segSeedOff.as<u64>( ), ns, b->seedRow.as<i64>( ),
-                            b->seedSeg.as<u32>( ) );
+                            b->seedSeg.as<u32>( ), c );
         const u64 lanes = std::min<u64>( 256ull * 2048, ( total + 255 ) / 256 * 256 );
         hipLaunchKernelGGL( k_lf_walk, dim3( (unsigned)( lanes / 256 ) ), dim3( 256 ), 0, b->stream, b->idx->v,
                             b->seedRow.as<i64>( ), b->seedSteps.as<u32>( ), total, c + CTR_NEXT_SEED );

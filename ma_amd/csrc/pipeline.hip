@@ -611,12 +611,65 @@ static void csr_parts( const uint64_t* off, u64 n, std::vector<u64>& o, std::vec
     c[ n ] = 0;
 }
 
+// What ma_extract_seeds_batch relies on in segments handed in (include/ma_amd.h): checked on the host, before anything is
+// uploaded -- a decreasing seg_off would make the loop below write beyond `rd`, a negative sa_size becomes a huge seed count in
+// k_seg_seed_counts, a row beyond n an out-of-bounds read of k_lf_walk, a segment beyond its read an underflow of delta in
+// k_seed_final.  A negative sa_start is the pool's own "this segment carries its position" form (seeding.h: text mode), which no
+// getter returns and no caller may hand in.  sa_start_rc is not read by extraction and not checked: the MEMs seeding and the
+// reference's SAInterval::do_for_difference (fMIndex.h:145-148) set it to -1.  A refusal is the early return of
+// ma_batch_state.h: the batch is left without segments (as before ma_seed_batch) and otherwise usable.
+static int segments_refuse( ma_batch* b, const std::string& what )
+{
+    b->st.drop( ma_state::SEEDED );
+    return fail( "ma_batch_set_segments: " + what );
+}
+static int segments_check( ma_batch* b, const u64* roff, const uint64_t* seg_off, const ma_segment* segs )
+{
+    const u64 n = b->n_reads, rows = b->idx->v.n + 1; // rows 0 .. n of the BWT; row 0 is the sentinel's
+    if( seg_off[ 0 ] != 0 )
+        return segments_refuse( b, "seg_off does not start at 0" );
+    for( u64 r = 0; r < n; r++ )
+        if( seg_off[ r + 1 ] < seg_off[ r ] )
+            return segments_refuse( b, "seg_off decreases at read " + std::to_string( r ) );
+    if( seg_off[ n ] > 0xffffffffull )
+        return segments_refuse( b, "more than 2^32 - 1 segments" );
+    if( seg_off[ n ] && !segs )
+        return fail( "ma_batch_set_segments: null argument" );
+    for( u64 r = 0; r < n; r++ )
+    {
+        const u64 qlen = roff[ r + 1 ] - roff[ r ];
+        for( u64 k = seg_off[ r ]; k < seg_off[ r + 1 ]; k++ )
+        {
+            const ma_segment& x = segs[ k ];
+            const std::string where = " (read " + std::to_string( r ) + ", segment " + std::to_string( k - seg_off[ r ] ) + ")";
+            if( x.q_start < 0 || x.q_size < 0 || x.sa_start < 0 || x.sa_size < 0 )
+                return segments_refuse( b, "negative field" + where );
+            if( x.sa_size < 1 )
+                return segments_refuse( b, "empty interval" + where );
+            // no interval of the seeding starts at row 0: FMIndex::init_interval starts at L2[c] + 1 (fMIndex.h:772)
+            if( x.sa_start < 1 || (u64)x.sa_start > rows || (u64)x.sa_size > rows - (u64)x.sa_start )
+                return segments_refuse( b, "interval outside rows 1 .. " + std::to_string( rows - 1 ) + where );
+            if( (u64)x.q_start > qlen || (u64)x.q_size >= qlen - (u64)x.q_start )
+                return segments_refuse( b, "segment ends beyond its read of " + std::to_string( qlen ) + " bases" + where );
+        }
+    }
+    return 0;
+}
+
 int ma_batch_set_segments( ma_batch* b, const uint64_t* seg_off, const ma_segment* segs )
 {
-    if( !b || !b->d_roff || !seg_off || ( seg_off[ b->n_reads ] && !segs ) )
+    if( !b || !b->d_roff || !seg_off )
         return fail( "ma_batch_set_segments: no reads set or null argument" );
     MA_BIND_DEVICE( b->device );
-    const u64 n = b->n_reads, ns = seg_off[ n ];
+    const u64 n = b->n_reads;
+    // the reads' lengths: the offsets live on the device, however the reads were set (as in ma_batch_set_hsets)
+    std::vector<u64> roff( n + 1, 0 );
+    MA_HIP( hipMemcpyAsync( roff.data( ), b->d_roff, ( n + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
+    if( batch_wait( b ) )
+        return 1;
+    if( segments_check( b, roff.data( ), seg_off, segs ) )
+        return 1;
+    const u64 ns = seg_off[ n ];
     b->st.drop( ma_state::SEEDED );
     std::vector<u64> o;
     std::vector<u32> c, rd( ns + 1 );

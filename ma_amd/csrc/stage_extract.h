@@ -37,11 +37,16 @@ __global__ void k_read_seed_ranges( const u64* seg_off, const u32* seg_cnt, cons
 //                the next seed from a wave-aggregated queue: no divergence over the (unbounded, mean 16) steps a
 //                row needs until it hits a sampled row
 //  k_seed_final  one lane per seed: sampled SA value, strand, contig, delta
-__global__ void k_seed_rows( const ma_segment* pool, const u64* seg_seed_off, u64 n_pool, i64* row, u32* seg_of )
+__global__ void k_seed_rows( const ma_segment* pool, const u64* seg_seed_off, u64 n_pool, i64* row, u32* seg_of,
+                             unsigned long long* ctr )
 {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if( i >= n_pool )
         return;
+    // the stage's own counters start at 0 on EVERY run: a second ma_extract_seeds_batch on the same segments would find the
+    // queue of k_lf_walk at its end -- no lane takes a seed, k_seed_final reads rows nobody walked -- and double the steps
+    if( i == 0 )
+        ctr[ CTR_NEXT_SEED ] = 0, ctr[ CTR_LF_STEPS ] = 0;
     const u64 o = seg_seed_off[ i ], cnt = seg_seed_off[ i + 1 ] - o;
     if( cnt == 0 )
         return;

@@ -9,6 +9,10 @@
 //           harmonized seed sets for the reads of a MACASE01 file, in the layout of ma_batch_get_hsets / ma_batch_set_hsets: the
 //           sets of read r are hset_off[r] .. hset_off[r + 1], the seeds of set s are hseed_off[s] .. hseed_off[s + 1] (records
 //           in ma_seed layout, positions on the doubled text), hset_soc[s] is its index_of_strip (writer: tests/nw_sets.py)
+// EXSEGS01: magic[8] | u64 n_reads | u64 n_segs | u64 seg_off[n_reads + 1]
+//           | { i64 q_start, i64 q_size, i64 sa_start, i64 sa_start_rc, i64 sa_size }[n_segs]
+//           segments for the reads of a MACASE01 file, in the layout of ma_batch_get_segments / ma_batch_set_segments: the segments
+//           of read r are seg_off[r] .. seg_off[r + 1] (records in ma_segment layout; writer: tests/extract_lists.py)
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -119,6 +123,40 @@ inline NwSetsFile readNwSets( const char* sPath )
     for( uint64_t i = 0; i < nSets; i++ )
         if( s.hseedOff[ i + 1 ] < s.hseedOff[ i ] )
             throw std::runtime_error( "sets file: hseed_off decreases" );
+    return s;
+}
+
+struct SegsRecord
+{
+    int64_t q_start, q_size, sa_start, sa_start_rc, sa_size;
+};
+struct SegsFile
+{
+    std::vector<uint64_t> segOff;
+    std::vector<SegsRecord> segs;
+};
+
+inline SegsFile readSegs( const char* sPath )
+{
+    FILE* f = fopen( sPath, "rb" );
+    if( !f )
+        throw std::runtime_error( std::string( "cannot open " ) + sPath );
+    char magic[ 8 ];
+    dumpfmt::rd( f, magic, 8 );
+    if( memcmp( magic, "EXSEGS01", 8 ) )
+        throw std::runtime_error( "bad segments magic" );
+    const uint64_t nReads = dumpfmt::rdv<uint64_t>( f ), nSegs = dumpfmt::rdv<uint64_t>( f );
+    SegsFile s;
+    s.segOff.resize( nReads + 1 );
+    s.segs.resize( nSegs );
+    dumpfmt::rd( f, s.segOff.data( ), 8 * ( nReads + 1 ) );
+    dumpfmt::rd( f, s.segs.data( ), sizeof( SegsRecord ) * nSegs );
+    fclose( f );
+    if( s.segOff[ 0 ] != 0 || s.segOff[ nReads ] != nSegs )
+        throw std::runtime_error( "segments file: offsets and counts disagree" );
+    for( uint64_t i = 0; i < nReads; i++ )
+        if( s.segOff[ i + 1 ] < s.segOff[ i ] )
+            throw std::runtime_error( "segments file: seg_off decreases" );
     return s;
 }
 
