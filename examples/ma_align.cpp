@@ -2,7 +2,7 @@
 // `maCMD -x <genome> -i <reads> [-m <mates>] -o <out.sam> -p <preset>` needs from the hot path.  Not a re-implementation
 // of cmdMa.cpp: no option parsing beyond the four arguments, no thread pool (the batches are the parallelism).
 //
-//   ma_align [--host-sam] [--ngmlr-tags] [--text-input] [--bgzf-output] <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam[.gz]|stdout> [preset] [mates.fa|fq[.gz]]
+//   ma_align [--host-sam] [--ngmlr-tags] [--text-input] [--bgzf-output] [--genome-text] <genome.fa | index prefix> <reads.fa|fq[.gz]> <out.sam[.gz]|stdout> [preset] [mates.fa|fq[.gz]]
 //
 // Single-end input is printed on the device (BatchAligner::executeFlatSam: the SAM text is what comes down) whenever the
 // options are ones the device serves -- with --ngmlr-tags ("Emulate NGMLR's tag output") and with "Detect Small Inversions"
@@ -20,9 +20,14 @@
 // and gzip read it): on the device paths every batch's text is deflated where it was printed (ma_sam_bgzf_batch) and only its
 // members come down; the header, and with --host-sam every byte, goes through the host statement of the same rules
 // (ma_bgzf::deflateHost).  The file inflates to the bytes of the run without the option.
+// With --genome-text a FASTA genome is not walked on the host either: buildIndexFromFastaText (ma_genome.h) sends the file up in
+// chunks, the device parses contigs, codes and holes (ma_genome_append_text) and fills the hole bases with the draws of srand( 1 ),
+// the seed the program gives libc without the flag.  The output is the same bytes.  With an index prefix in place of a FASTA file
+// the flag has no effect (the index files are loaded) and the program says so on stderr.
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_align.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
+#include "ma_genome.h"
 #include <cstdio>
 
 using namespace libMA;
@@ -30,22 +35,23 @@ typedef libMS::ContainerVector<std::shared_ptr<NucSeq>> ReadVec;
 
 int main( int argc, char** argv )
 {
-    bool bHostSam = false, bNgmlrTags = false, bTextInput = false, bBgzfOutput = false;
+    bool bHostSam = false, bNgmlrTags = false, bTextInput = false, bBgzfOutput = false, bGenomeText = false;
     for( int i = 1; i < argc; i++ )
         if( std::string( argv[ i ] ) == "--host-sam" || std::string( argv[ i ] ) == "--ngmlr-tags" || std::string( argv[ i ] ) == "--text-input" ||
-            std::string( argv[ i ] ) == "--bgzf-output" )
+            std::string( argv[ i ] ) == "--bgzf-output" || std::string( argv[ i ] ) == "--genome-text" )
         {
-            ( std::string( argv[ i ] ) == "--host-sam"     ? bHostSam
-              : std::string( argv[ i ] ) == "--ngmlr-tags" ? bNgmlrTags
-              : std::string( argv[ i ] ) == "--text-input" ? bTextInput
-                                                           : bBgzfOutput ) = true;
+            ( std::string( argv[ i ] ) == "--host-sam"      ? bHostSam
+              : std::string( argv[ i ] ) == "--ngmlr-tags"  ? bNgmlrTags
+              : std::string( argv[ i ] ) == "--text-input"  ? bTextInput
+              : std::string( argv[ i ] ) == "--genome-text" ? bGenomeText
+                                                            : bBgzfOutput ) = true;
             for( int j = i; j + 1 < argc; j++ )
                 argv[ j ] = argv[ j + 1 ];
             argc--, i--;
         }
     if( argc < 4 )
     {
-        fprintf( stderr, "usage: ma_align [--host-sam] [--ngmlr-tags] [--text-input] [--bgzf-output] <genome.fa | index prefix> <reads> <out.sam[.gz]|stdout> [preset] [mates]\n" );
+        fprintf( stderr, "usage: ma_align [--host-sam] [--ngmlr-tags] [--text-input] [--bgzf-output] [--genome-text] <genome.fa | index prefix> <reads> <out.sam[.gz]|stdout> [preset] [mates]\n" );
         return 2;
     }
     try
@@ -88,11 +94,18 @@ int main( int argc, char** argv )
         std::shared_ptr<FMIndex> pFM;
         const std::string sGenome = argv[ 1 ];
         if( std::ifstream( sGenome + ".bwt" ).good( ) )
+        {
+            if( bGenomeText )
+                fprintf( stderr, "ma_align: --genome-text has no effect: %s is an index prefix, its files are loaded\n", sGenome.c_str( ) );
             loadIndex( sGenome, pPack, pFM ); // the reference's own index files (or storeIndex output)
+        }
         else
         {
             srand( 1 );
-            buildIndexFromFasta( sGenome, pPack, pFM ); // suffix sort on the GPU
+            if( bGenomeText )
+                buildIndexFromFastaText( sGenome, pPack, pFM, 1 ); // the FASTA text read on the device, the draws of srand( 1 )
+            else
+                buildIndexFromFasta( sGenome, pPack, pFM ); // suffix sort on the GPU
         }
         BatchAligner xAligner( xParams );
         FileReader xReader( xParams );

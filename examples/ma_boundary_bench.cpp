@@ -13,7 +13,10 @@
 //
 // build: g++ -std=c++17 -O2 [-DMA_WITH_ZLIB] -Iinclude -Ima_amd/host examples/ma_boundary_bench.cpp -Lma_amd -lma_amd [-lz] -lpthread
 #include "ma_batch_nodes.h"
+#include "ma_genome.h"
 #include <atomic>
+#include <random>
+#include <unistd.h>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -269,11 +272,144 @@ static std::string bgzfOf( const std::string& sFastq )
 }
 #endif
 
+// ma_boundary_bench genome <bases> [device] [repeats] [chunk MiB]: the wall time from a FASTA file to a usable index, host path
+// (buildIndexFromFasta: FileReader + the base loop of buildIndex, then upload + suffix sort) against device text path
+// (buildIndexFromFastaText: ma_genome_append_text per chunk, then fill + suffix sort) on one synthetic multi-contig genome with N
+// runs, written from a seed to <TMPDIR or /tmp>/ma_boundary_bench.genome.<pid>.fa and removed afterwards.  The two steps of each
+// path are timed apart; the repeats alternate between the paths.
+static int genomeLeg( int argc, char** argv )
+{
+    const uint64_t uiBases = strtoull( argv[ 2 ], NULL, 10 );
+    const int iDevice = argc >= 4 ? atoi( argv[ 3 ] ) : 0, iRepeats = argc >= 5 ? atoi( argv[ 4 ] ) : 3;
+    const uint64_t uiChunk = ( argc >= 6 ? strtoull( argv[ 5 ], NULL, 10 ) : 256 ) << 20;
+    maCheck( ma_set_device( iDevice ) );
+    maCheck( ma_host_bind_thread( iDevice, 0, nullptr ) );
+    const char* pTmp = getenv( "TMPDIR" );
+    const std::string sPath = std::string( pTmp ? pTmp : "/tmp" ) + "/ma_boundary_bench.genome." + std::to_string( getpid( ) ) + ".fa";
+    uint64_t uiFileBytes = 0, uiHoleBases = 0;
+    {
+        // 24 contigs of falling size, lines of 60, an N run of 10 - 50 000 every ~2 Mnt and at both ends of every contig
+        std::mt19937_64 rng( 20261021 );
+        FILE* f = fopen( sPath.c_str( ), "wb" );
+        if( !f )
+            throw std::runtime_error( "cannot write " + sPath );
+        std::string sLine;
+        const int nContigs = 24;
+        uint64_t uiLeft = uiBases;
+        for( int c = 0; c < nContigs && uiLeft; c++ )
+        {
+            const uint64_t uiLen = c + 1 == nContigs ? uiLeft : std::max<uint64_t>( 1, std::min<uint64_t>( uiLeft, uiBases / 12 * ( nContigs - c ) / nContigs ) );
+            uiLeft -= uiLen;
+            fprintf( f, ">chr%d synthetic contig of %llu bases\n", c + 1, (unsigned long long)uiLen );
+            uint64_t uiHole = std::min<uint64_t>( uiLen / 4, 10000 ); // hole bases to go; the contig starts in a run
+            uint64_t uiNext = rng( ) % 2000000;
+            for( uint64_t at = 0; at < uiLen; at += 60 )
+            {
+                const size_t uiLine = (size_t)std::min<uint64_t>( 60, uiLen - at );
+                sLine.resize( uiLine );
+                uint64_t r = 0;
+                for( size_t k = 0; k < uiLine; k++ )
+                {
+                    if( ( k & 31 ) == 0 )
+                        r = rng( );
+                    if( at + k + 10000 >= uiLen && uiLen > 40000 )
+                        uiHole = std::max<uint64_t>( uiHole, 1 ); // ... and ends in one
+                    if( uiHole == 0 && uiNext == 0 )
+                        uiHole = 10 + rng( ) % 50000, uiNext = 1 + rng( ) % 4000000;
+                    if( uiHole )
+                        sLine[ k ] = 'N', uiHole--, uiHoleBases++;
+                    else
+                        sLine[ k ] = "ACGT"[ ( r >> ( 2 * ( k & 31 ) ) ) & 3 ], uiNext--;
+                }
+                fwrite( sLine.data( ), 1, uiLine, f );
+                fputc( '\n', f );
+            }
+        }
+        uiFileBytes = (uint64_t)ftell( f );
+        fclose( f );
+    }
+    std::vector<double> vHostText, vHostSort, vDevText, vDevSort;
+    size_t uiHoles = 0, uiContigs = 0;
+    for( int r = 0; r < iRepeats; r++ )
+    {
+        {
+            std::shared_ptr<Pack> pPack = std::make_shared<Pack>( );
+            std::shared_ptr<FMIndex> pFM;
+            srand( 1 );
+            double t0 = now( );
+            // the two halves of buildIndexFromFasta + buildIndex, timed apart
+            ParameterSetManager xParameters;
+            FileReader xReader( xParameters );
+            auto pStream = fileStreamFromPath( sPath );
+            std::vector<std::shared_ptr<NucSeq>> vContigs;
+            while( auto pContig = xReader.execute( pStream ) )
+                vContigs.push_back( pContig );
+            std::vector<uint64_t> vLens;
+            std::vector<uint8_t> vCat;
+            packContigs( vContigs, pPack, vLens, vCat );
+            vHostText.push_back( now( ) - t0 );
+            t0 = now( );
+            auto pDev = std::make_shared<DeviceIndex>( );
+            maCheck( ma_index_build( (int32_t)vLens.size( ), vLens.data( ), vCat.data( ), &pDev->p ) );
+            vHostSort.push_back( now( ) - t0 );
+            uiHoles = pPack->vHoles.size( ), uiContigs = vLens.size( );
+        }
+        {
+            std::shared_ptr<Pack> pPack;
+            std::shared_ptr<FMIndex> pFM;
+            double t0 = now( );
+            auto pGenome = readFastaText( sPath, uiChunk );
+            vDevText.push_back( now( ) - t0 );
+            t0 = now( );
+            buildIndexFromGenomeText( pGenome, pPack, pFM, 1 );
+            vDevSort.push_back( now( ) - t0 );
+            if( pPack->vHoles.size( ) != uiHoles || pPack->vNames.size( ) != uiContigs )
+                throw std::runtime_error( "the two paths disagree on the contigs or holes" );
+        }
+    }
+    remove( sPath.c_str( ) );
+    auto list = []( const std::vector<double>& v ) {
+        std::string s = "[";
+        for( size_t i = 0; i < v.size( ); i++ )
+            s += ( i ? ", " : "" ) + std::to_string( v[ i ] );
+        return s + "]";
+    };
+    auto sums = []( std::vector<double> a, const std::vector<double>& b ) { // file to index, per repetition
+        for( size_t i = 0; i < a.size( ); i++ )
+            a[ i ] += b[ i ];
+        return a;
+    };
+    auto median = []( std::vector<double> v ) {
+        std::sort( v.begin( ), v.end( ) );
+        return v[ v.size( ) / 2 ];
+    };
+    printf( "{\"leg\": \"genome\", \"bases\": %llu, \"file_bytes\": %llu, \"contigs\": %zu, \"holes\": %zu, \"hole_bases\": %llu, \"chunk_bytes\": %llu, "
+            "\"host_text_s\": %s, \"host_upload_sort_s\": %s, \"device_text_s\": %s, \"device_fill_sort_s\": %s, "
+            "\"host_text_bytes_per_s\": %.0f, \"device_text_bytes_per_s\": %.0f, \"host_total_median_s\": %.3f, \"device_total_median_s\": %.3f}\n",
+            (unsigned long long)uiBases, (unsigned long long)uiFileBytes, uiContigs, uiHoles, (unsigned long long)uiHoleBases, (unsigned long long)uiChunk,
+            list( vHostText ).c_str( ), list( vHostSort ).c_str( ), list( vDevText ).c_str( ), list( vDevSort ).c_str( ),
+            (double)uiFileBytes / median( vHostText ), (double)uiFileBytes / median( vDevText ), median( sums( vHostText, vHostSort ) ),
+            median( sums( vDevText, vDevSort ) ) );
+    return 0;
+}
+
 int main( int argc, char** argv )
 {
+    if( argc >= 3 && !strcmp( argv[ 1 ], "genome" ) )
+    {
+        try
+        {
+            return genomeLeg( argc, argv );
+        }
+        catch( const std::exception& rE )
+        {
+            fprintf( stderr, "ma_boundary_bench genome: %s\n", rE.what( ) );
+            return 1;
+        }
+    }
     if( argc < 6 )
     {
-        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | pairtext [repeats] | pairbgzf [repeats] | sam [repeats] | sam-tags [repeats] | sam-bgzf [repeats] | text [repeats] | bgzf [repeats] | inversions [repeats] [inverted reads per mille]]\n" );
+        fprintf( stderr, "usage: ma_boundary_bench <index prefix> <reads> <read length> <preset> <device> [graph threads | paired [repeats] | pairtext [repeats] | pairbgzf [repeats] | sam [repeats] | sam-tags [repeats] | sam-bgzf [repeats] | text [repeats] | bgzf [repeats] | inversions [repeats] [inverted reads per mille]]\n       ma_boundary_bench genome <bases> [device] [repeats] [chunk MiB]\n" );
         return 2;
     }
     try

@@ -161,6 +161,49 @@ int ma_index_sizes( const ma_index*, uint64_t* n_words, uint64_t* n_sa, uint64_t
 int ma_index_download( const ma_index*, uint32_t* bwt_words, int64_t* sa, uint64_t L2[ 5 ], int64_t* primary,
                        uint8_t* pac, uint64_t* contig_starts, uint64_t* contig_lens );
 
+/* ---- the genome's FASTA text read on the device (replaces Pack::vAppendFASTA, pack.cpp:510-537 + vAppendSequence, pack.h:586-698,
+ * for files; the rules are ma_amd/host/ma_genome_dev.h) ----
+ * A genome object takes the text of one or more FASTA files in chunks and keeps the codes (1 byte per base, hole bases -- N and
+ * every other letter that is not A C G T -- as 4) on the device, the contig table (name up to the first blank, start, length,
+ * number of holes) and the holes (start on the forward strand, length; a run of hole bases inside one contig) on the host.
+ * ma_genome_append_text: `text` is a chunk of the file in host memory (page-locked memory uploads fastest), n_bytes < 2 GiB, in the
+ *   strict FASTA form of ma_batch_set_reads_text ("\n" or "\r\n" line ends, '>' header lines, non-empty base lines, every record
+ *   has bases).  The call consumes whole lines only -- up to and including the chunk's last "\n" -- and says in *consumed how
+ *   many bytes that was; the caller carries the rest into its next call.  With end_of_file != 0 an unterminated last line is
+ *   consumed too and the file is closed: the next call starts another file with a header.  A chunk after a file's first may
+ *   begin with base lines; they continue the open contig.  A chunk without any "\n" and end_of_file == 0 consumes 0 bytes.
+ *   It uploads, parses and waits: THREE read-backs per call (the line feeds, which size the per-line work; the sums and the
+ *   refusal, which size the lists; the chunk's contig names, starts and holes) -- one call per 256 MiB of text, not per record.
+ *   A refusal leaves the object exactly as it was (*consumed = 0) and usable:
+ *     "ma_genome_append_text: line <L> (byte <X>): <reason>"   the lowest offending line, L (1-based) and X counted over
+ *                                                              everything consumed so far plus this chunk; reasons as
+ *                                                              ma_batch_set_reads_text's
+ *     "ma_genome_append_text: a genome is FASTA"               an '@' where a header is due
+ *     "ma_genome_append_text: genome capacity exceeded (<B> bases)"   B: what the genome would hold after the chunk
+ *     "ma_genome_append_text: too large"                       n_bytes of 2 GiB or more (judged on n_bytes, before the chunk is
+ *                                                              looked at)
+ *     "ma_genome_append_text: the index was already built"
+ *     "ma_genome_append_text: a genome as BGZF or gzip is not served (plain FASTA text only)"   the bytes 1f 8b where a header is due
+ *   Not served, and refused by these rules: BGZF / gzip bytes and FASTQ genomes.
+ * ma_genome_build_index: fills the hole bases -- the k-th in text order becomes rand( ) & 3 of the k-th draw after
+ *   srand( srand_seed ) of glibc, drawn from the library's own generator (libc's state is not touched) --, builds the index as
+ *   ma_index_build_device does (sampling interval 32) and sets its contig names and holes: ma_sam_batch, ma_pair_sam_batch and
+ *   MA_SAM_NGMLR_TAGS work on it with no further call.  Once per genome; fails on a genome without contigs or whose last contig
+ *   has no bases yet.  The getters keep serving afterwards, and ma_genome_get_codes then shows the filled bases.
+ *   The hole bases are filled before the sort: if the sort then fails (out of memory, say), the genome counts as built and the call
+ *   cannot be tried again on it -- read the file into a new genome object.
+ * ma_genome_create: device < 0 means the calling thread's current device; a device that does not exist fails here.
+ * Getters: any pointer may be NULL.  name_off: n_contigs + 1 offsets into names. */
+typedef struct ma_genome ma_genome;
+int ma_genome_create( int device, uint64_t max_bases, ma_genome** out );
+int ma_genome_append_text( ma_genome*, const char* text /*host*/, uint64_t n_bytes, int32_t end_of_file, uint64_t* consumed );
+int ma_genome_counts( const ma_genome*, uint64_t* n_contigs, uint64_t* n_bases, uint64_t* n_name_bytes, uint64_t* n_holes, uint64_t* n_hole_bases );
+int ma_genome_get_contigs( const ma_genome*, uint64_t* name_off /*n+1*/, char* names, uint64_t* starts, uint64_t* lens, uint64_t* n_holes );
+int ma_genome_get_holes( const ma_genome*, uint64_t* start, uint64_t* len );
+int ma_genome_get_codes( const ma_genome*, uint64_t from, uint64_t n, uint8_t* codes ); /* 4 = a hole base not filled yet */
+int ma_genome_build_index( ma_genome*, uint32_t srand_seed, ma_index** out );
+int ma_genome_destroy( ma_genome* );
+
 /* Pack::vExtract (pack.h:1440-1450, vExtractSubsection 1147-1236) for n ranges [begin[i], end[i]) of the doubled
  * text; codes 0..3 back to back in out (host). Replaces the reference extraction SmallInversions does
  * (smallInversions.h:207). */

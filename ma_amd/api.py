@@ -181,7 +181,7 @@ class Index:
 
     @staticmethod
     def build(contigs):
-        """GPU index construction from N-free contigs (list of uint8 code arrays)."""
+        """GPU index construction from N-free contigs (list of uint8 code arrays); a FASTA text with N: build_text."""
         lens = np.array([len(c) for c in contigs], dtype=np.uint64)
         cat = np.ascontiguousarray(np.concatenate([np.asarray(c, dtype=np.uint8) for c in contigs]))
         h = C.c_void_p()
@@ -194,6 +194,19 @@ class Index:
         h = C.c_void_p()
         _chk(lib().ma_index_build_device(C.c_int32(len(lens)), _ptr(lens), C.c_void_p(int(d_codes_ptr)), C.byref(h)))
         return Index(h)
+
+    @staticmethod
+    def build_text(data, seed=1):
+        """GPU index construction from a whole FASTA text held as bytes, holes (N and the other IUPAC letters) included: Genome
+        reads the text on the device, build_index fills the hole bases with the draws of srand(seed) and sets the index's contig
+        names and holes."""
+        data = bytes(data)
+        g = Genome(max(len(data), 1))
+        try:
+            g.append_text(data, end_of_file=True)
+            return g.build_index(seed)
+        finally:
+            g.close()
 
     def sizes(self):
         nw, ns, rl, nc = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_int32()
@@ -291,6 +304,68 @@ class Index:
     def close(self):
         if self.h:
             lib().ma_index_destroy(self.h)
+            self.h = None
+
+
+class Genome:
+    """A genome being read from FASTA text on the device (ma_genome*): codes of 1 byte per base on the device (hole bases -- N and
+    every letter that is not A C G T -- as 4 until build_index fills them), the contig table and the holes."""
+
+    def __init__(self, max_bases, device=None):
+        self.h = C.c_void_p()
+        _chk(lib().ma_genome_create(C.c_int(-1 if device is None else int(device)), C.c_uint64(int(max_bases)), C.byref(self.h)))
+
+    def append_text(self, data, end_of_file=False):
+        """Appends the whole lines of a chunk of the file (bytes); returns how many bytes were consumed -- up to and including the
+        chunk's last line feed, or all of them with end_of_file.  The caller carries the rest into its next call.  A refusal
+        (MaError) leaves the genome as it was."""
+        data = bytes(data)
+        buf = np.frombuffer(data + b"\0", dtype=np.uint8)
+        consumed = C.c_uint64(0)
+        _chk(lib().ma_genome_append_text(self.h, _ptr(buf), C.c_uint64(len(data)), C.c_int32(1 if end_of_file else 0), C.byref(consumed)))
+        return consumed.value
+
+    def counts(self):
+        v = [C.c_uint64() for _ in range(5)]
+        _chk(lib().ma_genome_counts(self.h, *[C.byref(x) for x in v]))
+        return dict(zip(("contigs", "bases", "name_bytes", "holes", "hole_bases"), (x.value for x in v)))
+
+    def contigs(self):
+        """dict: names (list of bytes), starts, lens, n_holes (uint64 arrays)"""
+        c = self.counts()
+        nc = c["contigs"]
+        off = np.zeros(nc + 1, dtype=np.uint64)
+        names = np.zeros(c["name_bytes"] + 1, dtype=np.uint8)
+        starts, lens, nh = (np.zeros(nc, dtype=np.uint64) for _ in range(3))
+        _chk(lib().ma_genome_get_contigs(self.h, _ptr(off), _ptr(names), _ptr(starts), _ptr(lens), _ptr(nh)))
+        raw = names.tobytes()
+        return dict(names=[raw[int(off[i]):int(off[i + 1])] for i in range(nc)], starts=starts, lens=lens, n_holes=nh)
+
+    def holes(self):
+        """(starts, lens): the runs of hole bases, each inside one contig, in text order"""
+        n = self.counts()["holes"]
+        st, ln = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        _chk(lib().ma_genome_get_holes(self.h, _ptr(st), _ptr(ln)))
+        return st, ln
+
+    def codes(self, start=0, n=None):
+        """codes [start, start + n) of the genome (uint8; 4 = a hole base not filled yet)"""
+        if n is None:
+            n = self.counts()["bases"] - start
+        out = np.zeros(max(int(n), 1), dtype=np.uint8)
+        _chk(lib().ma_genome_get_codes(self.h, C.c_uint64(int(start)), C.c_uint64(int(n)), _ptr(out)))
+        return out[:int(n)]
+
+    def build_index(self, seed=1):
+        """Fills the hole bases (the k-th becomes rand() & 3 of the k-th draw after srand(seed)) and builds the index, contig names
+        and holes set.  Once per genome."""
+        h = C.c_void_p()
+        _chk(lib().ma_genome_build_index(self.h, C.c_uint32(int(seed) & 0xffffffff), C.byref(h)))
+        return Index(h)
+
+    def close(self):
+        if self.h:
+            lib().ma_genome_destroy(self.h)
             self.h = None
 
 

@@ -90,6 +90,8 @@ static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0
 
 #include "../host/ma_text_dev.h"
 #include "stage_text.h"
+#include "../host/ma_genome_dev.h"
+#include "stage_genome.h"
 
 #include "../host/ma_bgzf_dev.h"
 #include "stage_bgzf.h"
@@ -1377,6 +1379,7 @@ int ma_debug_seed_prof( unsigned long long* out )
 #include "launch_inv.h"
 
 #include "launch_text.h"
+#include "launch_genome.h"
 
 #include "launch_bgzf.h"
 

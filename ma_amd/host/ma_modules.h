@@ -320,13 +320,11 @@ inline void loadIndex( const std::string& sPrefix, std::shared_ptr<Pack>& pPack,
     pFM->pDev = pDev;
 }
 
-// Builds the index on the GPU from N-free contigs (codes 0..3).
-inline void buildIndex( const std::vector<std::shared_ptr<NucSeq>>& vContigs, std::shared_ptr<Pack>& pPack,
-                        std::shared_ptr<FMIndex>& pFM )
+// The base loop of buildIndex, which needs no device: the contigs' codes back to back in `cat` with every N replaced, their
+// lengths in `lens`, and names, starts, lengths, holes and holes per contig in *pPack.
+inline void packContigs( const std::vector<std::shared_ptr<NucSeq>>& vContigs, const std::shared_ptr<Pack>& pPack, std::vector<uint64_t>& lens,
+                         std::vector<uint8_t>& cat )
 {
-    std::vector<uint64_t> lens;
-    std::vector<uint8_t> cat;
-    pPack = std::make_shared<Pack>( );
     uint64_t off = 0;
     for( auto& c : vContigs )
     {
@@ -359,6 +357,16 @@ inline void buildIndex( const std::vector<std::shared_ptr<NucSeq>>& vContigs, st
         pPack->vLengths.push_back( c->length( ) );
         off += c->length( );
     }
+}
+
+// Builds the index on the GPU from contigs (codes 0..3; an N, code 4, becomes rand( ) & 3 and its run a hole).
+inline void buildIndex( const std::vector<std::shared_ptr<NucSeq>>& vContigs, std::shared_ptr<Pack>& pPack,
+                        std::shared_ptr<FMIndex>& pFM )
+{
+    std::vector<uint64_t> lens;
+    std::vector<uint8_t> cat;
+    pPack = std::make_shared<Pack>( );
+    packContigs( vContigs, pPack, lens, cat );
     auto pDev = std::make_shared<DeviceIndex>( );
     maCheck( ma_index_build( (int32_t)lens.size( ), lens.data( ), cat.data( ), &pDev->p ) );
     pPack->pDev = pDev;
