@@ -281,6 +281,18 @@ int ma_stream_destroy( const ma_index*, void* hip_stream );
  * read and not checked.  A violation fails the call with "ma_batch_set_segments: ..." naming the read and the segment; the batch
  * then holds no segments (as before ma_seed_batch) and stays usable. */
 int ma_batch_set_segments( ma_batch*, const uint64_t* seg_off /*n+1*/, const ma_segment* segs );
+/* Seeds from elsewhere (layout of ma_batch_get_seeds): the seeds of read r are seeds[seed_off[r] .. seed_off[r+1]), in the order the
+ * sweep's first sort is to see them, as ExtractSeeds leaves them (segment.h:89-113, stripOfConsideration.h:41-53, 97-112): a match
+ * at position p of the doubled text (n = 2 F) has r_start = p, on_forward = 1 if p < F, and is mirrored to r_start = n - 1 - p,
+ * on_forward = 0 otherwise.  -> ma_chain_batch.  Contract, checked on the host before anything is uploaded: seed_off starts at 0
+ * and never decreases; no field is negative; len >= 1; q_start + len <= the length of the read; on_forward is 0 or 1; r_start < F;
+ * the match stays inside the doubled text (forward: r_start + len <= n; mirrored: len <= r_start + 1); delta is the value
+ * ExtractSeeds computes for the seed, r_start + (length of the read - q_start) + (length of the read + 1) * index of r_start's
+ * contig, which the sweep reads as stored (stripOfConsideration.cpp:33, 81).  A seed MAY cross a contig border or the junction
+ * of the strands: the reference's extraction checks neither, the seeding finds such matches, and the stage takes them as the
+ * reference does (the DP stage answers a set that bridges contigs with the empty alignment).  Duplicated and nested seeds are
+ * legal.  A violation fails the call with "ma_batch_set_seeds: ..." naming the read and the seed; the batch then holds no seeds
+ * and no strips (as before ma_extract_seeds_batch) and stays usable. */
 int ma_batch_set_seeds( ma_batch*, const uint64_t* seed_off /*n+1*/, const ma_seed* seeds ); /* -> ma_chain_batch */
 /* Harmonized seed sets from elsewhere (layout of ma_batch_get_hsets): the sets of read r are hset_off[r] .. hset_off[r+1], the
  * seeds of set s are hseeds[hseed_off[s] .. hseed_off[s+1]), hset_soc[s] is its xStats.index_of_strip.  -> ma_dp_batch.
@@ -294,7 +306,11 @@ int ma_batch_set_hsets( ma_batch*, const uint64_t* hset_off /*n+1*/, const uint6
                         const uint32_t* hset_soc, const ma_seed* hseeds ); /* -> ma_dp_batch */
 /* A SoC queue per read that was swept elsewhere (SoCPriorityQueue soc.h:96-420 as StripOfConsideration::execute returns
  * it, stripOfConsideration.cpp:162-173): sorted_seeds = its pSeeds (re-sorted by reference position), socs = its vMaxima
- * array (layout of ma_batch_get_soc_heap).  -> ma_chain_batch, which then runs Harmonization::execute only. */
+ * array (layout of ma_batch_get_soc_heap).  -> ma_chain_batch, which then runs Harmonization::execute only.  Contract, checked on
+ * the host before anything is uploaded: sorted_seeds keep the contract of ma_batch_set_seeds; soc_off starts at 0 and never
+ * decreases; a read has no more strips than seeds; begin <= end <= the read's number of seeds and n_seeds == end - begin for
+ * every strip (acc_len and ambiguity are the queue's keys and taken as given).  A violation fails the call with
+ * "ma_batch_set_soc_heap: ..." naming the read and the strip or seed; the batch then holds no seeds and no strips and stays usable. */
 int ma_batch_set_soc_heap( ma_batch*, const uint64_t* soc_off /*n+1*/, const ma_soc* socs, const uint64_t* seed_off /*n+1*/,
                            const ma_seed* sorted_seeds );
 /* MappingQuality::execute (mappingQuality.cpp:11-131) alone: alignments that were computed elsewhere (e.g. by the

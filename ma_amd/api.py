@@ -655,7 +655,11 @@ class Batch:
         _chk(lib().ma_batch_set_segments(self.h, _ptr(off), _ptr(segs)))
 
     def set_seeds(self, off, seeds):
-        """Extracted seeds from elsewhere (CSR per read) -> chain()."""
+        """Extracted seeds from elsewhere (CSR per read, the layout of seeds(): reverse-strand seeds mirrored onto forward
+        positions) -> chain().  ma_batch_set_seeds checks them on the host and raises MaError("ma_batch_set_seeds: ...") for a
+        decreasing offset array, a negative field, an empty seed, a seed beyond its read or the doubled text, an on_forward other
+        than 0 / 1, an r_start outside the forward text or a delta that is not ExtractSeeds'; the batch then holds no seeds and
+        stays usable."""
         off = np.ascontiguousarray(off, dtype=np.uint64)
         seeds = np.ascontiguousarray(np.concatenate([seeds, np.zeros(1, dtype=SEED_DT)]))
         _chk(lib().ma_batch_set_seeds(self.h, _ptr(off), _ptr(seeds)))
@@ -685,7 +689,9 @@ class Batch:
         return soff, socs[: int(n.value)], doff, seeds[: c["seeds"]]
 
     def set_soc_heap(self, soc_off, socs, seed_off, seeds):
-        """SoC queues swept elsewhere (layout of socs(heap=True)) -> chain() only harmonizes."""
+        """SoC queues swept elsewhere (layout of socs(heap=True)) -> chain() only harmonizes.  The seeds are held to the contract
+        of set_seeds, the strips to begin <= end <= the read's seed count and n_seeds == end - begin: MaError("ma_batch_set_soc_heap:
+        ...") otherwise, and the batch then holds no seeds and no strips."""
         soc_off = np.ascontiguousarray(soc_off, dtype=np.uint64)
         seed_off = np.ascontiguousarray(seed_off, dtype=np.uint64)
         socs = np.ascontiguousarray(np.concatenate([socs, np.zeros(1, dtype=SOC_DT)]))

@@ -25,6 +25,13 @@ static __device__ unsigned long long g_chain_prof[ 16 ];
 #define CH_ADD( i, a, b )
 #endif
 
+// branch census of the host tests (tests/emul/harm_census.cpp defines both before it includes this file and counts by name);
+// nothing in every other build
+#ifndef CH_HIT
+#define CH_HIT( name )
+#define CH_HIT_IF( cond, name )
+#endif
+
 // draws a table holds: two RANSAC runs of 100 iterations with their retries (run_ransac) stay inside it
 #define MA_RNG_TAB 256
 
@@ -171,6 +178,7 @@ struct GlibcRand
         if( nTab != 0 )
         {
             const u32 n = nTab;
+            CH_HIT( rng_past_table );
             init( seed );
             for( u32 i = 0; i < n; i++ )
                 step( );
@@ -221,6 +229,7 @@ struct LibmProbe
 
 MA_HD bool soc_less( const SoCEntry& a, const SoCEntry& b ) // SoCOrder::operator< (soc.h:71-76)
 {
+    CH_HIT_IF( a.accLen == b.accLen && a.amb != b.amb, soc_tie_by_ambiguity );
     if( a.accLen == b.accLen )
         return a.amb > b.amb;
     return a.accLen < b.accLen;
@@ -310,12 +319,14 @@ MA_HD void soc_push_no_overlap( const ma_seed* s, SoCEntry* mx, u32& nmx, SoCEnt
     while( nmx > 0 && mx[ nmx - 1 ].e > itS )
     {
         SoCEntry& back = mx[ nmx - 1 ];
+        CH_HIT( push_overlap );
         if( soc_less( back, cur ) )
         {
             const u32 bb = back.b;
             soc_sum( s, pre, bb, itS, back );
             back.b = bb;
             back.e = itS;
+            CH_HIT_IF( back.accLen < minScore || back.accLen == 0, push_overlap_back_dropped );
             if( back.accLen < minScore || back.accLen == 0 )
                 nmx--;
         }
@@ -324,6 +335,8 @@ MA_HD void soc_push_no_overlap( const ma_seed* s, SoCEntry* mx, u32& nmx, SoCEnt
             const u32 be = back.e;
             soc_sum( s, pre, be, itE, cur );
             itS = be;
+            CH_HIT( push_overlap_cur_cut );
+            CH_HIT_IF( cur.accLen < minScore || cur.accLen == 0, push_overlap_cur_dropped );
             if( cur.accLen < minScore || cur.accLen == 0 )
                 return;
         }
@@ -407,6 +420,8 @@ MA_HD u32 soc_windows( const IndexView& X, const ChainParams& P, ma_seed* s, u32
     if( P.genome_size_disable >= X.n )
         fMinLen = 0;
     const u64 strip = P.soc_width != 0 ? (u64)P.soc_width : ( (u64)P.match * (u64)qlen - (u64)P.gap ) / (u64)P.extend;
+    CH_HIT_IF( P.soc_width != 0, win_soc_width );
+    CH_HIT_IF( fMinLen > 0, win_min_len_live );
     CH_T( c0 );
     if( sortedByDelta )
         ;
@@ -442,12 +457,15 @@ MA_HD u32 soc_windows( const IndexView& X, const ChainParams& P, ma_seed* s, u32
             const u64 lim = (u64)s[ S ].delta + strip;
             while( E != n && lim >= (u64)s[ E ].delta && cidS == cidE )
             {
+                CH_HIT_IF( lim == (u64)s[ E ].delta && E != S, win_delta_at_limit );
                 E++;
                 if( E != n )
                     cidE = cache.get( X, (u64)s[ E ].r_start );
             }
+            CH_HIT_IF( E != n && lim >= (u64)s[ E ].delta && cidS != cidE, win_contig_stop );
             // the window holds seed S at least (E == S passes both tests), so E > S: the running sums of the reference
             cur.accLen = pl[ E ] - pl[ S ], cur.amb = pa[ E ] - pa[ S ], cur.cnt = E - S;
+            CH_HIT_IF( !( (double)cur.accLen >= fMinLen ), win_below_min_len );
             if( (double)cur.accLen >= fMinLen )
                 soc_push_no_overlap( s, mx, nmx, cur, S, E, (u64)fMinLen, pre );
             S++;
@@ -459,6 +477,7 @@ MA_HD u32 soc_windows( const IndexView& X, const ChainParams& P, ma_seed* s, u32
         const i64 cidS = cache.get( X, (u64)s[ S ].r_start );
         while( E != n && (u64)s[ S ].delta + strip >= (u64)s[ E ].delta && cidS == cidE )
         {
+            CH_HIT_IF( (u64)s[ S ].delta + strip == (u64)s[ E ].delta && E != S, win_delta_at_limit );
             cur.amb += s[ E ].ambiguity;
             cur.cnt++;
             cur.accLen += (u64)s[ E ].len;
@@ -466,6 +485,8 @@ MA_HD u32 soc_windows( const IndexView& X, const ChainParams& P, ma_seed* s, u32
             if( E != n )
                 cidE = cache.get( X, (u64)s[ E ].r_start );
         }
+        CH_HIT_IF( E != n && (u64)s[ S ].delta + strip >= (u64)s[ E ].delta && cidS != cidE, win_contig_stop );
+        CH_HIT_IF( !( (double)cur.accLen >= fMinLen ), win_below_min_len );
         if( (double)cur.accLen >= fMinLen )
             soc_push_no_overlap( s, mx, nmx, cur, S, E, (u64)fMinLen );
         cur.amb -= s[ S ].ambiguity;
@@ -676,6 +697,7 @@ MA_HD_OUTLINE void run_ransac( const double* X, const double* Y, u32 nPts, doubl
                 if( iter > 1000 )
                     break;
                 iterations++;
+                CH_HIT_IF( s1 == s0, ransac_same_point_retry );
             } while( s1 == s0 );
             iterations--;
         }
@@ -713,6 +735,8 @@ MA_HD_OUTLINE void run_ransac( const double* X, const double* Y, u32 nPts, doubl
                 haveModel = true;
                 const double w = (double)nIn / (double)nPts;
                 double pNo = 1 - w * w; // pow(w, 2.0)
+                CH_HIT_IF( pNo < 2.220446049250313e-16, ransac_pno_clamped );
+                CH_HIT_IF( nIn == 0, ransac_zero_inliers );
                 pNo = mmax( 2.220446049250313e-16, pNo );
                 pNo = mmin( 1 - 2.220446049250313e-16, pNo );
                 k = lp( log( 1 - 0.99 ) ) / lp( log( pNo ) );
@@ -724,8 +748,11 @@ MA_HD_OUTLINE void run_ransac( const double* X, const double* Y, u32 nPts, doubl
         if( iterations > 100 )
             break;
     }
+    CH_HIT_IF( fMAD == 0, ransac_mad_zero );
+    CH_HIT_IF( iterations > 100, ransac_iteration_limit );
     if( !haveModel )
     {
+        CH_HIT( ransac_no_model );
         outAngle = NAN;
         outIntercept = NAN;
         return;
@@ -776,6 +803,7 @@ MA_HD_OUTLINE u32 linesweep( Shadow* sh, u32 n, Shadow* ends, const ma_seed* see
     for( u32 k = 0; k < n; k++ )
     {
         const Shadow t = sh[ k ];
+        CH_HIT_IF( k > 0 && sh[ k - 1 ].a == t.a && sh[ k - 1 ].b == t.b, sweep_equal_shadows );
         if( x < t.b )
         {
             ends[ ne++ ] = t;
@@ -784,13 +812,17 @@ MA_HD_OUTLINE u32 linesweep( Shadow* sh, u32 n, Shadow* ends, const ma_seed* see
         else
         {
             const double fD = delta_distance( seeds[ t.seed ], fAngle, rStart, lp );
+            CH_HIT( sweep_shadowed );
+            CH_HIT_IF( !( fD == fD ), sweep_nan_distance );
             u32 pos = ne;
             bool closer = true;
             while( pos > 0 && ends[ pos - 1 ].b >= t.b )
             {
                 const double fO = delta_distance( seeds[ ends[ pos - 1 ].seed ], fAngle, rStart, lp );
+                CH_HIT_IF( fO == fD, sweep_equal_distance );
                 if( fO <= fD )
                 {
+                    CH_HIT( sweep_not_closer );
                     closer = false;
                     break;
                 }
@@ -798,6 +830,7 @@ MA_HD_OUTLINE u32 linesweep( Shadow* sh, u32 n, Shadow* ends, const ma_seed* see
             }
             if( closer )
             {
+                CH_HIT_IF( ne > 1 && ends[ ne - 2 ].b >= t.b, sweep_pops_several );
                 while( ne > 0 && ends[ ne - 1 ].b >= t.b )
                     ne--;
                 ends[ ne++ ] = t;
@@ -851,6 +884,9 @@ MA_HD_OUTLINE u32 harmonize_one( ma_seed* S, u32 n, ma_seed* out, const ChainScr
                     S[ m ] = S[ i ];
                 m++;
             }
+        CH_HIT_IF( m < n, harm_outliers_removed );
+        CH_HIT_IF( m == 0, harm_all_removed_undefined );
+        CH_HIT_IF( !( fAngle == fAngle ), harm_nan_model );
         n = m;
         for( u32 i = 0; i < n; i++ )
         {
@@ -876,6 +912,8 @@ MA_HD_OUTLINE u32 harmonize_one( ma_seed* S, u32 n, ma_seed* out, const ChainScr
         CH_ADD( 8, h3, h4 );
         if( n3 <= 1 )
         {
+            CH_HIT( harm_middle_seed );
+            CH_HIT_IF( 3 * n < np, harm_middle_seed_after_removal );
             out[ 0 ] = S[ n / 2 ];
             return 1;
         }
@@ -919,10 +957,14 @@ MA_HD void apply_filters( const ChainParams& P, ma_seed* I, u32 n, u32& outBegin
         gap *= (u64)P.extend;
         if( gap > 0 )
             gap += (u64)P.gap;
+        CH_HIT_IF( gap > (u64)P.sv_penalty && P.sv_penalty != 0, filt_gap_capped );
+        CH_HIT_IF( gap > 100 && P.sv_penalty == 0, filt_gap_uncapped );
         if( gap > (u64)P.sv_penalty && P.sv_penalty != 0 )
             gap = (u64)P.sv_penalty;
+        CH_HIT_IF( iScore == (i64)gap && gap > 0, filt_score_equals_gap );
         if( iScore < (i64)gap )
         {
+            CH_HIT( filt_score_below_gap );
             iScore = 0;
             lastStart = p;
         }
@@ -936,6 +978,9 @@ MA_HD void apply_filters( const ChainParams& P, ma_seed* I, u32 n, u32& outBegin
         }
     }
     u32 end = n;
+    CH_HIT_IF( n > 1 && optE + 1 == n, filt_range_ends_at_last );
+    CH_HIT_IF( n > 1 && optE + 2 == n, filt_range_ends_one_before_last );
+    CH_HIT_IF( optS > 0, filt_range_starts_later );
     if( optE != n )
         if( ++optE != n )
             end = optE;
@@ -962,8 +1007,12 @@ MA_HD void apply_filters( const ChainParams& P, ma_seed* I, u32 n, u32& outBegin
             if( ad < 0 )
                 ad = -ad;
             const double diff = (double)( ad * 2 ) / ( (double)toPre + (double)toPost );
+            CH_HIT_IF( !( diff == diff ), art_diff_nan );
+            CH_HIT_IF( diff < P.max_delta_dist && (u64)toPre == (u64)P.min_delta_dist, art_at_min_delta_dist );
             if( diff < P.max_delta_dist && (u64)toPre > (u64)P.min_delta_dist )
             {
+                CH_HIT( art_triggered );
+                CH_HIT_IF( pre + 1 != cen, art_run_keeps_pre );
                 R[ cen ].len = 0;
                 cen++;
             }
@@ -1078,7 +1127,10 @@ MA_HD u32 chain_read( const IndexView& X, const ChainParams& P, const ChainScrat
     while( nmx > 0 )
     {
         if( ++numTries > P.max_num_soc )
+        {
+            CH_HIT( loop_try_limit );
             break;
+        }
         // pop (soc.h:240-284)
         const u32 thisSoc = socIndex++;
         u32 nIn = 0;
@@ -1092,13 +1144,22 @@ MA_HD u32 chain_read( const IndexView& X, const ChainParams& P, const ChainScrat
         u64 curSoC = 0;
         for( u32 i = 0; i < nIn; i++ )
             curSoC += (u64)C.setA[ i ].len;
+        CH_HIT_IF( !heur, loop_heuristics_off );
+        CH_HIT_IF( heur && numTries <= P.min_num_soc && numTries > 1, loop_strip_exempt );
+        CH_HIT_IF( heur && numTries > P.min_num_soc && (u64)qlen == switchQ, loop_qlen_at_switch );
         if( heur && numTries > P.min_num_soc )
         {
             if( (u64)qlen > switchQ && switchQ != 0 )
                 if( lastHarm > curSoC )
+                {
+                    CH_HIT( loop_skip_soc_below_last_harm );
                     continue;
+                }
             if( (double)bestSoC * P.soc_score_decrease_tol > (double)curSoC && P.soc_score_decrease_tol > 0 )
+            {
+                CH_HIT( loop_break_soc_decrease );
                 break;
+            }
         }
         bestSoC = mmax( bestSoC, curSoC );
         // extractStrand(false) (seed.h:405-420) + un-mirror (harmonization.cpp:437-442)
@@ -1129,15 +1190,26 @@ MA_HD u32 chain_read( const IndexView& X, const ChainParams& P, const ChainScrat
             curHarm += (u64)C.outA[ i ].len;
         for( u32 i = 0; i < nOutR; i++ )
             curHarm += (u64)outB[ i ].len;
+        CH_HIT_IF( nF > 0 && nR > 0, loop_both_strands_in_strip );
         if( heur && numTries > P.min_num_soc )
             if( curHarm < (u64)P.harm_score_min )
+            {
+                CH_HIT( loop_skip_harm_score_min );
                 continue;
+            }
         if( heur )
             if( (double)curHarm < (double)(u64)qlen * P.harm_score_min_rel )
+            {
+                CH_HIT( loop_skip_harm_score_min_rel );
                 continue;
+            }
         if( heur && numTries > P.min_num_soc && (u64)qlen > switchQ && switchQ != 0 )
             if( lastHarm > curHarm )
+            {
+                CH_HIT( loop_skip_harm_below_last );
                 continue;
+            }
+        CH_HIT_IF( nOutR > 0 && thisSoc != 0, loop_reverse_set_of_later_strip );
         if( nOutF > 0 )
         {
             repeat++;
@@ -1154,12 +1226,18 @@ MA_HD u32 chain_read( const IndexView& X, const ChainParams& P, const ChainScrat
             if( !( (double)curHarm + tol >= (double)lastHarm && (double)curHarm - tol <= (double)lastHarm ) )
                 repeat = 0;
             if( repeat >= P.max_score_lookahead && P.max_score_lookahead != 0 )
+            {
+                CH_HIT( loop_break_lookahead );
                 break;
+            }
         }
         else
             repeat = 0;
         lastHarm = curHarm;
     }
+    CH_HIT_IF( nsets == O.set_cap && nsets > 0, loop_set_cap_filled );
+    CH_HIT_IF( heur && repeat > 0 && nsets > P.min_num_soc, tail_pops_sets );
+    CH_HIT_IF( heur && repeat > 0 && nsets > P.min_num_soc && nsets - P.min_num_soc < repeat, tail_stops_at_min_num_soc );
     if( heur )
         for( u32 ui = 0; ui < repeat && nsets > P.min_num_soc; ui++ )
             nsets--;

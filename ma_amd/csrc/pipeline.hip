@@ -100,6 +100,7 @@ static_assert( CTR_COUNT == 96 && KSW_N_NEXT % 2 == 0 && KSW_N_NEXT_BIG % 2 == 0
 #include "stage_deflate.h"
 // what of a batch is valid, and what a call takes away (every entry point: drop on entry, finish on success)
 #include "../host/ma_batch_state.h"
+#include "../host/ma_seed_contract.h"
 
 // ------------------------------------------------------------------------------------------------
 // batch object
@@ -699,13 +700,29 @@ int ma_batch_set_segments( ma_batch* b, const uint64_t* seg_off, const ma_segmen
     return 0;
 }
 
-int ma_batch_set_seeds( ma_batch* b, const uint64_t* seed_off, const ma_seed* seeds )
+// What ma_chain_batch relies on in seeds handed in (include/ma_amd.h, ../host/ma_seed_contract.h): checked on the host, before
+// anything is uploaded.  A refusal is the early return of ma_batch_state.h: the batch is left without seeds and strips (as before
+// ma_extract_seeds_batch) and otherwise usable.
+static int seeds_check( ma_batch* b, const char* fn, const uint64_t* seed_off, const ma_seed* seeds )
 {
-    if( !b || !b->d_roff || !seed_off || ( seed_off[ b->n_reads ] && !seeds ) )
-        return fail( "ma_batch_set_seeds: no reads set or null argument" );
+    const u64 n = b->n_reads;
+    std::vector<u64> roff( n + 1, 0 );
+    MA_HIP( hipMemcpyAsync( roff.data( ), b->d_roff, ( n + 1 ) * 8, hipMemcpyDeviceToHost, b->stream ) );
+    if( batch_wait( b ) )
+        return 1;
+    const std::string what = ma_contract::seeds_violation( seed_off, seeds, n, roff.data( ), b->idx->h_cstart.data( ), b->idx->h_cstart.size( ),
+                                                           b->idx->v.F );
+    return what.empty( ) ? 0 : fail( std::string( fn ) + ": " + what );
+}
+
+static int set_seeds( ma_batch* b, const char* fn, const uint64_t* seed_off, const ma_seed* seeds )
+{
     MA_BIND_DEVICE( b->device );
-    const u64 n = b->n_reads, total = seed_off[ n ];
+    const u64 n = b->n_reads;
     b->st.drop( ma_state::EXTRACTED );
+    if( seeds_check( b, fn, seed_off, seeds ) )
+        return 1;
+    const u64 total = seed_off[ n ];
     std::vector<u64> o;
     std::vector<u32> c;
     csr_parts( seed_off, n, o, c );
@@ -723,6 +740,16 @@ int ma_batch_set_seeds( ma_batch* b, const uint64_t* seed_off, const ma_seed* se
     return 0;
 }
 
+int ma_batch_set_seeds( ma_batch* b, const uint64_t* seed_off, const ma_seed* seeds )
+{
+    if( !b || !b->d_roff || !seed_off )
+        return fail( "ma_batch_set_seeds: no reads set or null argument" );
+    // (a seed_off that decreases is the check's to name; seeds may be null only where there are none)
+    if( !seeds && seed_off[ 0 ] == 0 && seed_off[ b->n_reads ] != 0 )
+        return fail( "ma_batch_set_seeds: no reads set or null argument" );
+    return set_seeds( b, "ma_batch_set_seeds", seed_off, seeds );
+}
+
 // A SoC queue per read that was swept elsewhere -- the reference's StripOfConsideration in a mixed graph -- as input of
 // ma_chain_batch, which then only harmonizes: sorted_seeds = the read's seeds as rectangularSoC left them (pSeeds of the
 // SoCPriorityQueue), socs = its array vMaxima (score triple + seed range), both CSR per read (the layout
@@ -734,10 +761,15 @@ int ma_batch_set_soc_heap( ma_batch* b, const uint64_t* soc_off, const ma_soc* s
     const u64 n = b->n_reads;
     if( ( soc_off[ n ] && !socs ) || ( seed_off[ n ] && !sorted_seeds ) )
         return fail( "ma_batch_set_soc_heap: null argument" );
-    for( u64 r = 0; r < n; r++ )
-        if( soc_off[ r + 1 ] - soc_off[ r ] > seed_off[ r + 1 ] - seed_off[ r ] )
-            return fail( "ma_batch_set_soc_heap: a read has more strips than seeds" );
-    if( ma_batch_set_seeds( b, seed_off, sorted_seeds ) )
+    {
+        const std::string what = ma_contract::socs_violation( soc_off, socs, seed_off, n );
+        if( !what.empty( ) )
+        {
+            b->st.drop( ma_state::EXTRACTED );
+            return fail( "ma_batch_set_soc_heap: " + what );
+        }
+    }
+    if( set_seeds( b, "ma_batch_set_soc_heap", seed_off, sorted_seeds ) )
         return 1;
     const u64 total = seed_off[ n ];
     std::vector<ma_soc> q( total + 1 ); // the strips of read r at its SEED offset: the carving every chain scratch uses

@@ -9,6 +9,9 @@
 //           harmonized seed sets for the reads of a MACASE01 file, in the layout of ma_batch_get_hsets / ma_batch_set_hsets: the
 //           sets of read r are hset_off[r] .. hset_off[r + 1], the seeds of set s are hseed_off[s] .. hseed_off[s + 1] (records
 //           in ma_seed layout, positions on the doubled text), hset_soc[s] is its index_of_strip (writer: tests/nw_sets.py)
+// CHSEED01: magic[8] | u64 n_reads | u64 n_seeds | u64 seed_off[n_reads + 1] | { seed record as in NWSETS01 }[n_seeds]
+//           seeds for the reads of a MACASE01 file as ExtractSeeds leaves them (reverse-strand seeds mirrored onto forward
+//           positions), in the order the chain stage's first sort is to see them (writer: tests/harm_sets.py)
 // EXSEGS01: magic[8] | u64 n_reads | u64 n_segs | u64 seg_off[n_reads + 1]
 //           | { i64 q_start, i64 q_size, i64 sa_start, i64 sa_start_rc, i64 sa_size }[n_segs]
 //           segments for the reads of a MACASE01 file, in the layout of ma_batch_get_segments / ma_batch_set_segments: the segments
@@ -123,6 +126,37 @@ inline NwSetsFile readNwSets( const char* sPath )
     for( uint64_t i = 0; i < nSets; i++ )
         if( s.hseedOff[ i + 1 ] < s.hseedOff[ i ] )
             throw std::runtime_error( "sets file: hseed_off decreases" );
+    return s;
+}
+
+// CHSEED01: seeds for the reads of a MACASE01 file, in the layout of ma_batch_get_seeds / ma_batch_set_seeds (records as NWSETS01's)
+struct ChainSeedsFile
+{
+    std::vector<uint64_t> seedOff;
+    std::vector<NwSetsSeed> seeds;
+};
+
+inline ChainSeedsFile readChainSeeds( const char* sPath )
+{
+    FILE* f = fopen( sPath, "rb" );
+    if( !f )
+        throw std::runtime_error( std::string( "cannot open " ) + sPath );
+    char magic[ 8 ];
+    dumpfmt::rd( f, magic, 8 );
+    if( memcmp( magic, "CHSEED01", 8 ) )
+        throw std::runtime_error( "bad seeds magic" );
+    const uint64_t nReads = dumpfmt::rdv<uint64_t>( f ), nSeeds = dumpfmt::rdv<uint64_t>( f );
+    ChainSeedsFile s;
+    s.seedOff.resize( nReads + 1 );
+    s.seeds.resize( nSeeds );
+    dumpfmt::rd( f, s.seedOff.data( ), 8 * ( nReads + 1 ) );
+    dumpfmt::rd( f, s.seeds.data( ), sizeof( NwSetsSeed ) * nSeeds );
+    fclose( f );
+    if( s.seedOff[ 0 ] != 0 || s.seedOff[ nReads ] != nSeeds )
+        throw std::runtime_error( "seeds file: offsets and counts disagree" );
+    for( uint64_t i = 0; i < nReads; i++ )
+        if( s.seedOff[ i + 1 ] < s.seedOff[ i ] )
+            throw std::runtime_error( "seeds file: seed_off decreases" );
     return s;
 }
 

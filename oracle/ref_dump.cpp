@@ -17,6 +17,8 @@
 //                                                      -> SmallInversions / PairedReads lists (+ SAM of the (Paired)FileWriter)
 //   ref_dump nwsets <case> <preset> <sets file> <out> [match mismatch gap extend gap2 extend2]
 //                                                      -> NeedlemanWunsch + MappingQuality on GIVEN harmonized sets (NWSETS01)
+//   ref_dump chainseeds <case> <preset> <srand_seed> <seeds file> <out> [name=value ...]
+//                                                      -> StripOfConsiderationSeeds + Harmonization on GIVEN seeds (CHSEED01)
 #include "ma/container/fMIndex.h"
 #include "ma/container/pack.h"
 #include "ma/module/binarySeeding.h"
@@ -232,6 +234,91 @@ static int cmdNwSets( const char* sCase, const char* sPreset, const char* sSets,
                      (unsigned long long)pA->uiEndOnQuery, (long long)pA->iScore, (int)pA->bSecondary,
                      (int)pA->bSupplementary, pA->fMappingQuality );
         fflush( f ); // (a case the reference dies on shows as the last read of the file)
+    }
+    fclose( f );
+    return 0;
+}
+
+// StripOfConsiderationSeeds::execute + Harmonization::execute on seeds handed in (CHSEED01, dump_format.h): the Seeds container is
+// built from the file as ExtractSeeds leaves it -- strand, ambiguity, mirrored position and the stored delta, which the sweep reads
+// (stripOfConsideration.cpp:33, 81) --, srand( seed ) precedes every read's harmonization as in cmdPipe; the HARM lines are
+// cmdPipe's.  name=value arguments set fields of the selected parameter set before the modules are constructed.
+static bool setChainParameter( ParameterSetManager& xParams, const std::string& sName, const char* sValue )
+{
+    auto p = xParams.getSelected( );
+    if( sName == "max_num_soc" )
+        p->xMaxNumSoC->set( atoi( sValue ) );
+    else if( sName == "min_num_soc" )
+        p->xMinNumSoC->set( atoi( sValue ) );
+    else if( sName == "harm_score_min" )
+        p->xHarmScoreMin->set( atoi( sValue ) );
+    else if( sName == "harm_score_min_rel" )
+        p->xHarmScoreMinRel->set( atof( sValue ) );
+    else if( sName == "max_score_lookahead" )
+        p->xMaxScoreLookahead->set( atoi( sValue ) );
+    else if( sName == "switch_qlen" )
+        p->xSwitchQlen->set( atoi( sValue ) );
+    else if( sName == "min_delta_dist" )
+        p->xMinDeltaDist->set( atoi( sValue ) );
+    else if( sName == "max_delta_dist" )
+        p->xMaxDeltaDist->set( atof( sValue ) );
+    else if( sName == "soc_score_decrease_tol" )
+        p->xSoCScoreDecreaseTolerance->set( atof( sValue ) );
+    else if( sName == "score_diff_tol" )
+        p->xScoreDiffTolerance->set( atof( sValue ) );
+    else if( sName == "disable_heuristics" )
+        p->xDisableHeuristics->set( atoi( sValue ) != 0 );
+    else if( sName == "soc_width" )
+        p->xSoCWidth->set( atoi( sValue ) );
+    else if( sName == "genome_size_disable" )
+        p->xGenomeSizeDisable->set( atoi( sValue ) );
+    else
+        return false; // (sv_penalty among them: applyFilters reads the library's own copy of the global parameters)
+    return true;
+}
+static int cmdChainSeeds( const char* sCase, const char* sPreset, unsigned uiSeed, const char* sSeeds, const char* sOut, int iNumParams,
+                          char** pParams )
+{
+    CaseFile c = readCase( sCase );
+    ChainSeedsFile s = readChainSeeds( sSeeds );
+    if( s.seedOff.size( ) != c.reads.size( ) + 1 )
+        throw std::runtime_error( "seeds file and case differ in their number of reads" );
+    RefIndex idx = buildIndex( c );
+    ParameterSetManager xParams;
+    selectPreset( xParams, sPreset );
+    for( int i = 0; i < iNumParams; i++ )
+    {
+        const char* sEq = strchr( pParams[ i ], '=' );
+        if( !sEq || !setChainParameter( xParams, std::string( pParams[ i ], sEq - pParams[ i ] ), sEq + 1 ) )
+            throw std::runtime_error( std::string( "cannot set " ) + pParams[ i ] );
+    }
+    StripOfConsiderationSeeds xSoc( xParams );
+    Harmonization xHarm( xParams );
+    FILE* f = fopen( sOut, "w" );
+    for( size_t i = 0; i < c.reads.size( ); i++ )
+    {
+        auto pQ = mkSeq( c.reads[ i ] );
+        pQ->sName = "r" + std::to_string( i );
+        fprintf( f, "R %zu %zu\n", i, c.reads[ i ].size( ) );
+        fflush( f ); // (a case the reference dies on shows as the last read of the file)
+        auto pSeeds = std::make_shared<Seeds>( );
+        for( uint64_t j = s.seedOff[ i ]; j < s.seedOff[ i + 1 ]; j++ )
+        {
+            const NwSetsSeed& x = s.seeds[ j ];
+            Seed xSeed( (nucSeqIndex)x.q_start, (nucSeqIndex)x.len, (nucSeqIndex)x.r_start, x.ambiguity, x.on_forward != 0 );
+            xSeed.uiDelta = (nucSeqIndex)x.delta;
+            pSeeds->push_back( xSeed );
+        }
+        auto pSocs = xSoc.execute( pSeeds, pQ, idx.pPack );
+        srand( uiSeed );
+        auto pHarm = xHarm.execute( pSocs, pQ, idx.pFM );
+        fprintf( f, "HARM %zu\n", pHarm->size( ) );
+        for( auto& pS : *pHarm )
+        {
+            fprintf( f, "h %u %zu\n", pS->xStats.index_of_strip, pS->size( ) );
+            dumpSeeds( f, "g", *pS );
+        }
+        fflush( f );
     }
     fclose( f );
     return 0;
@@ -599,6 +686,8 @@ int main( int argc, char** argv )
     }
     if( argc >= 6 && !strcmp( argv[ 1 ], "nwsets" ) )
         return cmdNwSets( argv[ 2 ], argv[ 3 ], argv[ 4 ], argv[ 5 ] );
+    if( argc >= 7 && !strcmp( argv[ 1 ], "chainseeds" ) ) // chainseeds <case> <preset> <seed> <seeds file> <out> [name=value ...]
+        return cmdChainSeeds( argv[ 2 ], argv[ 3 ], (unsigned)atoi( argv[ 4 ] ), argv[ 5 ], argv[ 6 ], argc - 7, argv + 7 );
     if( argc >= 6 && !strcmp( argv[ 1 ], "pipe" ) )
         return cmdPipe( argv[ 2 ], argv[ 3 ], (unsigned)atoi( argv[ 4 ] ), argv[ 5 ] );
     if( argc >= 6 && !strcmp( argv[ 1 ], "sam" ) )
@@ -641,6 +730,6 @@ int main( int argc, char** argv )
                 aSc[ i ] = atoi( argv[ 5 + i ] );
         return cmdKsw( argv[ 2 ], argv[ 3 ], argc >= 5 && !strcmp( argv[ 4 ], "dirty" ), aSc );
     }
-    fprintf( stderr, "usage: ref_dump index|pipe|sam|f4|nwsets|read|ext|ksw ...\n" );
+    fprintf( stderr, "usage: ref_dump index|pipe|sam|f4|nwsets|chainseeds|read|ext|ksw ...\n" );
     return 2;
 }

@@ -198,6 +198,27 @@ def refused_hsets(b):
         b.set_hsets(hset_off, hseed_off, soc, bad)
 
 
+def refused_seeds(b):
+    import ma_amd
+    off, seeds = b.seeds()
+    bad = seeds.copy()
+    bad["delta"][0] += 1
+    with pytest.raises(ma_amd.MaError, match="ma_batch_set_seeds: delta is [0-9]+, ExtractSeeds computes [0-9]+ \\(read 0, seed 0\\)"):
+        b.set_seeds(off, bad)
+    gone(b.chain, "ma_chain_batch: run ma_extract_seeds_batch first")
+
+
+def refused_soc_heap(b):
+    import ma_amd
+    soc_off, socs, seed_off, seeds = b.socs(heap=True)
+    assert len(socs)
+    bad = socs.copy()
+    bad["end"][0] = 10 ** 6
+    with pytest.raises(ma_amd.MaError, match="ma_batch_set_soc_heap: strip outside the read's [0-9]+ seeds \\(read 0, strip 0\\)"):
+        b.set_soc_heap(soc_off, bad, seed_off, seeds)
+    gone(b.chain, "ma_chain_batch: run ma_extract_seeds_batch first")
+
+
 # (name, the call, the stage calls that are left before full_pass's tail)
 EARLIER = [("seed", lambda b: b.seed(), ("extract", "chain", "dp")),
            ("extract", lambda b: b.extract(), ("chain", "dp")),
@@ -206,7 +227,9 @@ EARLIER = [("seed", lambda b: b.seed(), ("extract", "chain", "dp")),
            ("set_seeds", lambda b: b.set_seeds(*b.seeds()), ("chain", "dp")),
            ("set_soc_heap", lambda b: b.set_soc_heap(*b.socs(heap=True)), ("chain", "dp")),
            ("set_hsets", lambda b: b.set_hsets(*b.hsets()), ("dp",)),
-           ("set_hsets, refused", refused_hsets, ("chain", "dp"))]
+           ("set_hsets, refused", refused_hsets, ("chain", "dp")),
+           ("set_seeds, refused", refused_seeds, ("extract", "chain", "dp")),
+           ("set_soc_heap, refused", refused_soc_heap, ("extract", "chain", "dp"))]
 LATER_GONE = [(lambda b: b.sam_bytes(), "ma_batch_sam_counts: run ma_sam_batch first"),
               (lambda b: b.pair_sam_bytes(), "ma_batch_pair_sam_counts: run ma_pair_sam_batch first"),
               (lambda b: b.pair_counts(), "ma_batch_pair_counts: run ma_pair_batch first"),
@@ -249,3 +272,59 @@ def test_a_refused_set_reads_device_keeps_the_reads(world):
     assert str(e.value) == "ma_batch_set_reads_device: null argument"
     assert (b.read_counts(), b.sam_bytes(), b.pair_counts()) == before
     assert before[0]["reads"] == len(reads) and before[1] > 0
+
+
+def test_refused_seeds_and_strips_name_the_read_and_the_record(world):
+    """Every clause of the contract of ma_batch_set_seeds / ma_batch_set_soc_heap (include/ma_amd.h; the clauses one by one on the
+    host: test_seed_contract_host.py) through the library: the call fails with the message, the batch holds no seeds and no
+    strips afterwards, and the same batch then takes the seeds as they were and chains them to the sets of the fused path."""
+    import ma_amd
+    b, reads, fresh, want = world
+    b.set_reads(fresh)
+    b.seed(), b.extract(), b.chain()
+    b.sync()
+    sets = tuple(x.tobytes() for x in b.hsets())
+    off, seeds = b.seeds()
+    soc_off, socs, seed_off, sorted_seeds = b.socs(heap=True)
+    r = int(np.nonzero(np.diff(off.astype(np.int64)) >= 2)[0][0])  # a read of two seeds at least
+    k = int(off[r])
+    qlen = len(fresh[r])
+
+    def seeds_with(field, value, at=k):
+        bad = seeds.copy()
+        bad[field][at] = value
+        return off, bad
+
+    assert off[-2] > 0
+    bad_off = off.copy()
+    bad_off[-1] = off[-2] - 1
+    cases = [(lambda: (bad_off, seeds), "seed_off decreases at read %d" % (len(off) - 2)),
+             (lambda: seeds_with("q_start", -1), "negative field (read %d, seed 0)" % r),
+             (lambda: seeds_with("len", 0, k + 1), "empty seed (read %d, seed 1)" % r),
+             (lambda: seeds_with("len", qlen + 1), "seed ends beyond its read of %d bases (read %d, seed 0)" % (qlen, r)),
+             (lambda: seeds_with("on_forward", 2), "on_forward is neither 0 nor 1 (read %d, seed 0)" % r),
+             (lambda: seeds_with("r_start", 20000), "r_start outside the forward text of 20000 bases (read %d, seed 0)" % r)]
+    for make, message in cases:
+        with pytest.raises(ma_amd.MaError) as e:
+            b.set_seeds(*make())
+        assert str(e.value) == "ma_batch_set_seeds: " + message
+        gone(b.chain, "ma_chain_batch: run ma_extract_seeds_batch first")
+        gone(lambda: b.socs(), "ma_batch_get_socs: run ma_extract_seeds_batch first")
+    bad = socs.copy()
+    bad["n_seeds"][0] += 1
+    with pytest.raises(ma_amd.MaError) as e:
+        b.set_soc_heap(soc_off, bad, seed_off, sorted_seeds)
+    assert str(e.value) == "ma_batch_set_soc_heap: n_seeds is not end - begin (read 0, strip 0)"
+    gone(b.chain, "ma_chain_batch: run ma_extract_seeds_batch first")
+    with pytest.raises(ma_amd.MaError) as e:  # the seeds of a strip call are held to the seeds' contract, under the call's name
+        b.set_soc_heap(soc_off, socs, *seeds_with("delta", 0))
+    assert str(e.value).startswith("ma_batch_set_soc_heap: delta is 0, ExtractSeeds computes ")
+    # recovery on the same batch, both ways in
+    b.set_seeds(off, seeds)
+    b.chain()
+    b.sync()
+    assert tuple(x.tobytes() for x in b.hsets()) == sets
+    b.set_soc_heap(soc_off, socs, seed_off, sorted_seeds)
+    b.chain()
+    b.sync()
+    assert tuple(x.tobytes() for x in b.hsets()) == sets
