@@ -1,6 +1,8 @@
 // ksw_launch.h -- persistent-wave driver around ksw_wave_core: every 64-thread workgroup (= one
 // wavefront) pulls DP job slots from an atomic counter until none are left.  Also the kernel classes of the DP jobs (KSW_CLS_*), the
-// one router that assigns them (ksw_route_job), the sizing of the launches (KswSizing) and the launches themselves (ksw_run_all).
+// one router that assigns them (ksw_route_job), the job population the launches are sized for (KswSizing), the table of a stage's
+// launches (KswLaunch rows in issue order inside a KswStagePlan: kernel, job list, queue, lane, waves, LDS, scratch), the pure function
+// that plans it (ksw_plan_stage) and the loop that reads the two environment hooks, plans, and issues the rows (ksw_run_all).
 #pragma once
 #include "internal.h"
 #include "ksw_wave.h"
@@ -568,49 +570,56 @@ inline void ksw_size_route( KswSizing& S, const KswRoute& R )
     }
 }
 
-// Plans the launch: fills WS (without base) and returns waves + dynamic LDS bytes
-struct KswPlan
+// ---- The launches of one DP stage as a table: ksw_plan_stage writes it (no HIP call: tests/emul/dp_plan_test.cpp runs it on the
+// CPU), ksw_run_all issues it row by row.  A row names its kernel by family and instantiation and its pointers by index.
+enum : int
 {
-    KswWaveScratch ws;
-    u32 waves;
-    u32 lds_bytes;
+    KSW_FAM_PK = 0, // k_ksw_pk<S>; inst = the class, KSW_CLS_PK0 .. PK3
+    KSW_FAM_EXT, // k_ksw_ext<R>; inst = R
+    KSW_FAM_GRP, // k_ksw_grp<G, 1, LEFT>; inst = the class, KSW_CLS_GRP2_L .. GRP4_R
+    KSW_FAM_BAND4, // k_ksw_band<.., 4>, the narrow band; inst = 1 left, 0 right
+    KSW_FAM_BAND1, // k_ksw_band<.., 1>, the band of 120; inst = 1 left, 0 right
+    KSW_FAM_LDS // k_ksw; inst = the class, KSW_CLS_LDS
 };
-inline KswPlan ksw_plan( const KswSizing& S, u64 nJobs, u64 scratch_budget_bytes )
+// A counter of a row is a word of `next` (KSW_NX_*) or one of KSW_CT_*; a list is lists + index * list_stride, the index a class (its jobs)
+// or one of KSW_LIST_*.
+enum : int
 {
-    KswPlan P;
-    memset( &P, 0, sizeof( P ) );
-    auto al = []( u64 x ) { return ( x + 255 ) / 256 * 256; };
-    P.ws.state_cap = al( S.state );
-    P.ws.h_cap = al( S.h );
-    P.ws.p_cap = al( S.p );
-    P.ws.cig_cap = S.cig;
-    const u64 ldsNeed = P.ws.state_cap + P.ws.h_cap;
-    P.ws.use_lds = ldsNeed <= 64 * 1024 ? 1 : 0;
-    P.lds_bytes = P.ws.use_lds ? (u32)ldsNeed : 0;
-    P.ws.stride = al( ( P.ws.use_lds ? 0 : P.ws.state_cap + P.ws.h_cap ) + P.ws.p_cap + al( S.cig * 4 ) );
-    u64 waves = 256ull * 16; // 16 single-wave workgroups per CU
-    if( P.ws.use_lds )
-    {
-        const u64 perCu = ( 160 * 1024 ) / ( ldsNeed ? ldsNeed : 1 );
-        waves = 256ull * ( perCu > 16 ? 16 : ( perCu < 1 ? 1 : perCu ) );
-    }
-    if( waves > nJobs )
-        waves = nJobs;
-    if( P.ws.stride * waves > scratch_budget_bytes )
-        waves = scratch_budget_bytes / ( P.ws.stride ? P.ws.stride : 1 );
-    if( waves < 1 )
-        waves = 1;
-    P.waves = (u32)waves;
-    return P;
-}
-
-// Launches every class that has jobs.  `next` = KSW_N_NEXT zeroed counters (KSW_NX_*), `nextBig` = KSW_N_NEXT_BIG more.  `lists`
-// (device, or null) holds the job slots of class k at lists + k * list_stride, SZ.cls[k] entries, and room for the jobs
-// the extension kernels hand back at lists + KSW_N_CLASSES * list_stride (counted in *nRedo); without lists every
-// launch scans nSlots and there are no extension-kernel classes.
-//
+    KSW_NONE = -1, // no counter, no list: null
+    KSW_CT_BIG = KSW_N_NEXT, // + k: word k of `nextBig`
+    KSW_CT_NREDO = KSW_N_NEXT + KSW_N_NEXT_BIG, // *nRedo
+    KSW_LIST_REDO = KSW_N_CLASSES, // the jobs handed back to the exact kernels
+    KSW_LIST_REDOL = KSW_N_CLASSES + 1 // the long jobs the band of 120 handed back, when they have a stream of their own
+};
+struct KswLaunch
+{
+    int family = 0, inst = 0; // KSW_FAM_*
+    int lane = 0; // 0 .. 3: stream and scratch region (KswSide)
+    u32 waves = 0; // grid (0: nothing planned)
+    u32 lds = 0; // dynamic LDS bytes of the launch (register kernels: reversed query of ITS longest job)
+    int queue = KSW_NONE; // counter: the launch's job queue
+    int list = KSW_NONE; // list: its jobs (KSW_NONE: it scans the slots)
+    int nDev = KSW_NONE; // counter: KswJobs::nDev
+    KswJobs jb = { }; // n, mode, cls, tier, pSplit, qSplit; of the kernels that take no KswJobs: n (list and nDev: set from the indices when launching)
+    u64 stride = 0, p_cap = 0; // scratch bytes per wave, direction bytes among them
+    int out1 = KSW_NONE, out2 = KSW_NONE; // lists: where the kernel appends the jobs it hands back (narrow band: hands on to k_ksw_ext<1> / <2>) ...
+    u32 nOut1 = 0, nOut2 = 0; // ... the entries there before the launch (narrow band) ...
+    int outCtr = KSW_NONE; // ... counter: of the appended ones
+    int nMore = KSW_NONE; // counter: jobs the narrow band appended to the list (k_ksw_ext)
+    KswWaveScratch ws = { }; // k_ksw (base: set when launching)
+};
+#define KSW_MAX_LAUNCHES 27 // exact kernels 4 x (huge tier, own, handed back, handed back by the band of 120), band 2 + 2, k_ksw_grp 4, k_ksw_ext 2, k_ksw
+struct KswStagePlan
+{
+    KswLaunch launch[ KSW_MAX_LAUNCHES ]; // in issue order
+    int n = 0;
+    u64 laneBase[ 4 ] = { }, total = 0; // byte offsets of the lanes' scratch regions; bytes of all four
+    bool laneUsed[ 4 ] = { true, false, false, false }; // lanes 1 .. 3: fork from and join the batch's stream
+    int bandAfter = -1; // after this row the event `band` is recorded and lane 3 waits for it (-1: no such event)
+    u32 ldsPk = 0, ldsLds = 0; // LDS limit to set on the k_ksw_pk instantiations / on k_ksw (0: the default of 48 KB is enough)
+};
 // Scratch: every wave owns `stride` bytes (direction bytes + cigar of the job it is working on) of one allocation that
-// the launches, which run back to back on one stream, share.  Each launch is sized for ITS class: the classes differ
+// the launches of a lane, which run back to back on one stream, share.  Each launch is sized for ITS class: the classes differ
 // by orders of magnitude (gap between two seeds: KBs; end extension of a 50 kb read: 27 MB), and one stride for all
 // would cut every launch down to the few hundred waves the largest job allows -- less than one wave per SIMD
 // (50 kb reads: DP stage 2.4 s -> see DESIGN.md 3.6).  A class whose own largest job still does not leave room for a
@@ -627,19 +636,11 @@ inline u64 ksw_scratch_budget( )
     const char* e = getenv( "MA_KSW_SCRATCH_MB" ); // (read on every call: the tests switch it inside one process)
     return e && atoi( e ) > 0 ? (u64)atoi( e ) << 20 : 24ull << 30;
 }
-#define KSW_SCRATCH_BUDGET ksw_scratch_budget( )
-struct KswLaunchPlan
-{
-    u64 p_cap = 0, stride = 0;
-    u32 waves = 0;
-    u32 lds = 0; // dynamic LDS bytes of the launch (register kernels: reversed query of ITS longest job)
-    int tier = 0; // KswJobs::tier
-    u64 region = 0; // byte offset of the launch's scratch region
-};
-inline KswLaunchPlan ksw_plan_launch( u64 p, u64 cigWords, u64 jobs, u64 wantWaves, u64 budget )
+// scratch and waves of a launch whose waves each work on one job of up to p direction bytes and cigWords cigar words
+inline KswLaunch ksw_plan_launch( u64 p, u64 cigWords, u64 jobs, u64 wantWaves, u64 budget )
 {
     auto al = []( u64 x ) { return ( x + 255 ) / 256 * 256; };
-    KswLaunchPlan L;
+    KswLaunch L;
     L.p_cap = al( p );
     L.stride = al( L.p_cap + al( cigWords * 4 ) );
     u64 waves = std::max<u64>( 1, std::min<u64>( wantWaves, jobs ) );
@@ -647,6 +648,24 @@ inline KswLaunchPlan ksw_plan_launch( u64 p, u64 cigWords, u64 jobs, u64 wantWav
         waves = std::max<u64>( 1, budget / L.stride );
     L.waves = (u32)waves;
     return L;
+}
+// ... of k_ksw: state and H of the longest job in LDS, or with the direction bytes in the wave's scratch
+inline KswLaunch ksw_plan( const KswSizing& S, u64 nJobs, u64 budget )
+{
+    auto al = []( u64 x ) { return ( x + 255 ) / 256 * 256; };
+    const u64 state = al( S.state ), h = al( S.h ), ldsNeed = state + h;
+    const bool useLds = ldsNeed <= 64 * 1024;
+    u64 waves = 256ull * 16; // 16 single-wave workgroups per CU
+    if( useLds )
+    {
+        const u64 perCu = ( 160 * 1024 ) / ( ldsNeed ? ldsNeed : 1 );
+        waves = 256ull * ( perCu > 16 ? 16 : ( perCu < 1 ? 1 : perCu ) );
+    }
+    KswLaunch P = ksw_plan_launch( ( useLds ? 0 : ldsNeed ) + al( S.p ), S.cig, nJobs, waves, budget );
+    P.p_cap = al( S.p );
+    P.lds = useLds ? (u32)ldsNeed : 0;
+    P.ws = KswWaveScratch{ nullptr, P.stride, state, h, P.p_cap, S.cig, useLds ? 1u : 0u };
+    return P;
 }
 // Streams of one DP stage.  The kernel classes of a stage are independent of each other, and each is a persistent launch
 // that ends in a tail -- a few waves still working on their last jobs while the rest of the machine idles.  On ONE stream
@@ -658,7 +677,7 @@ struct KswSide
 {
     hipStream_t stream[ 3 ] = { nullptr, nullptr, nullptr };
     hipEvent_t fork = nullptr, join[ 3 ] = { nullptr, nullptr, nullptr };
-    hipEvent_t band = nullptr; // the long jobs' band kernels are done: their handed-back jobs start on lane 3 (ksw_run_all)
+    hipEvent_t band = nullptr; // the long jobs' band kernels are done: their handed-back jobs start on lane 3 (KswStagePlan::bandAfter)
     bool ready( ) const
     {
         return stream[ 0 ] && stream[ 1 ] && stream[ 2 ];
@@ -668,32 +687,21 @@ struct KswSide
 // LDS bytes of a job's query window (ksw_q_lds) up to which it runs in the class's first tier: the register kernels'
 // minimum per-wave LDS, so that 16 waves take 96 KB of a CU's 160 KB and the extension kernels' waves still fit beside them
 #define KSW_Q_SPLIT KSW_REG_LDS
-// the instantiations a launch picks from by a run-time index: exact class k, list k of the wavefront-sharing classes, direction
-template <typename FETCH> auto ksw_pk_kernel( int k ) -> decltype( &k_ksw_pk<FETCH, KSW_S0> )
-{
-    return k == KSW_CLS_PK0 ? k_ksw_pk<FETCH, KSW_S0>
-                            : ( k == KSW_CLS_PK1 ? k_ksw_pk<FETCH, KSW_S1> : ( k == KSW_CLS_PK2 ? k_ksw_pk<FETCH, KSW_S2> : k_ksw_pk<FETCH, KSW_S3> ) );
-}
-template <typename FETCH> auto ksw_grp_kernel( int cls ) -> decltype( &k_ksw_grp<FETCH, 2, 1, true> )
-{
-    return cls == KSW_CLS_GRP2_L ? k_ksw_grp<FETCH, 2, 1, true>
-                                 : ( cls == KSW_CLS_GRP2_R ? k_ksw_grp<FETCH, 2, 1, false> : ( cls == KSW_CLS_GRP4_L ? k_ksw_grp<FETCH, 4, 1, true> : k_ksw_grp<FETCH, 4, 1, false> ) );
-}
-template <typename FETCH, int G> auto ksw_band_kernel( bool left ) -> decltype( &k_ksw_band<FETCH, true, G> )
-{
-    return left ? k_ksw_band<FETCH, true, G> : k_ksw_band<FETCH, false, G>;
-}
-template <typename FETCH>
-int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizing& SZ, DevBuf& scratch,
-                 unsigned int* next, KswOut O, hipStream_t stream, u32* lists = nullptr, u64 list_stride = 0,
-                 unsigned int* nRedo = nullptr, unsigned int* nextBig = nullptr, const KswSide* side = nullptr )
+
+// Plans every launch of a stage whose job population is SZ.  `lists`: there are per-class job lists (without them every launch scans
+// nSlots and there are no extension-kernel classes); `nextBig`: there are queues for huge tiers; side3 / side2 / sideBand: KswSide has
+// all three streams / stream[ 2 ] / the event `band`; B: scratch budget of one launch (ksw_scratch_budget); perCu: waves per CU of
+// the persistent launches.
+inline KswStagePlan ksw_plan_stage( const KswSizing& SZ, const KswScoring& SC, u32 nSlots, bool lists, bool nextBig, bool side3, bool side2, bool sideBand,
+                                    u64 B, u64 perCu )
 {
     auto al = []( u64 x ) { return ( x + 255 ) / 256 * 256; };
+    KswStagePlan P;
     u64 nJobs = 0;
     for( int k = 0; k < KSW_N_CLASSES; k++ )
         nJobs += SZ.cls[ k ];
     if( nJobs == 0 )
-        return 0;
+        return P;
     u64 nGrp = 0;
     for( int k = 0; k < KSW_GRP_LISTS; k++ )
         nGrp += SZ.cls[ KSW_CLS_GRP0 + k ];
@@ -702,10 +710,7 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
     const u64 nBand = SC.grp >= 1000 ? SZ.cls[ KSW_CLS_NARROW_L ] + SZ.cls[ KSW_CLS_NARROW_R ] : 0;
     const u64 nBandL = SZ.cls[ KSW_CLS_BANDL_L ] + SZ.cls[ KSW_CLS_BANDL_R ]; // long jobs on the band of 120; those that fail go to `redo`
     const u64 nExt = SZ.cls[ KSW_CLS_EXT1 ] + SZ.cls[ KSW_CLS_EXT2 ] + nGrp + nBandL;
-    const bool conc = side && side->ready( ) && lists; // classes on their own streams
-    u64 perCu = 32; // waves per CU of the persistent ksw launches (MA_KSW_WAVES_PER_CU: tuning hook)
-    if( const char* e = getenv( "MA_KSW_WAVES_PER_CU" ) )
-        perCu = (u64)std::max( 1, atoi( e ) );
+    const bool conc = side3 && lists; // classes on their own streams
     const u64 wantWaves = 256ull * perCu;
     // Concurrent launches each own a scratch region, so each asks only for the waves that can be RESIDENT (registers:
     // k_ksw_pk<1> 74 VGPRs = 6 waves per SIMD, <2> 99, <3> 122, <5> 128 = 4; the extension kernels 7 / 4): a persistent wave
@@ -713,34 +718,26 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
     const u64 resident[ KSW_CLS_GRP0 ] = { 256 * 24, 256 * 16, 256 * 16, 256 * 16, 0, 256 * 28, 256 * 16 };
     auto wantOf = [ & ]( int k ) { return conc ? std::min<u64>( wantWaves, resident[ k ] ) : wantWaves; };
     // budgets of the scratch regions: lane 0 / 1 / 2 (sequential launches of a lane share its region)
-    const u64 B = KSW_SCRATCH_BUDGET; // one reading per call
     const u64 budgetOf[ KSW_CLS_GRP0 ] = { conc ? B / 3 : B, conc ? B / 3 : B, conc ? B / 3 : B, conc ? 5 * B / 12 : B, B, conc ? B / 4 : B, conc ? B / 4 : B };
     auto ldsOf = []( u64 qBytes ) { return std::max<u32>( (u32)( ( ( std::min<u64>( qBytes, 150000 + 64 ) + 15 ) / 16 ) * 16 ), KSW_REG_LDS ); };
-    // launch plans of the register kernels, in three banks: the classes' own launches (pass 0: KSW_CLS_PK0 .. PK3 exact,
-    // KSW_CLS_EXT1 / EXT2 extension), the exact classes' second pass over the jobs handed back, their huge tiers
-    enum : int
-    {
-        LP_CLS = 0, // + class
-        LP_REDO = KSW_CLS_GRP0, // + k
-        LP_BIG = LP_REDO + 4, // + k
-        LP_N = LP_BIG + 4
-    };
-    KswLaunchPlan LP[ LP_N ];
-    u64 pSplit[ 4 ] = { 0, 0, 0, 0 };
+    // ---- sizes.  Register kernels: the classes' own launches (KSW_CLS_PK0 .. PK3 exact, KSW_CLS_EXT1 / EXT2 extension), the exact
+    // classes' huge tiers, their second pass over the jobs handed back (RD: the same plan for the four), and the one over the long
+    // jobs the band of 120 handed back (LPR).  Lanes: sequential mode, one region for all launches (+ one for the huge tiers when
+    // they have a stream); concurrent mode, lane 0 = extension classes, handed-back jobs, LDS kernel; lane 1 = KSW_CLS_PK3;
+    // lane 2 = KSW_CLS_PK0 .. PK2; lane 3 = huge tiers.
+    KswLaunch own[ KSW_CLS_GRP0 ], big[ 4 ], RD, LPR, LG, LBL, LL;
     // k_ksw_grp: fixed scratch per wave (KSW_GRP_ROWS direction rows; the cigars stay in LDS), 5 waves per SIMD
-    KswLaunchPlan LG;
     if( nGrp )
     {
         const u64 sets = ( SZ.cls[ KSW_CLS_NARROW_L ] + 1 ) / ( SC.grp >= 1000 ? 4 : 2 ) + ( SZ.cls[ KSW_CLS_NARROW_R ] + 1 ) / ( SC.grp >= 1000 ? 4 : 2 ) +
                          ( SZ.cls[ KSW_CLS_GRP2_L ] + 1 ) / 2 + ( SZ.cls[ KSW_CLS_GRP2_R ] + 1 ) / 2 + ( SZ.cls[ KSW_CLS_GRP4_L ] + 3 ) / 4 + ( SZ.cls[ KSW_CLS_GRP4_R ] + 3 ) / 4;
         LG = ksw_plan_launch( (u64)KSW_GRP_ROWS * 128, 0, sets, std::min<u64>( wantWaves, 256 * 20 ), conc ? B / 4 : B );
     }
-    KswLaunchPlan LBL; // k_ksw_band<.., 1>: KSW_BANDL_ROWS direction rows per wave, 5 waves per SIMD
+    // LBL: k_ksw_band<.., 1>, KSW_BANDL_ROWS direction rows per wave, 5 waves per SIMD.
     // The few long jobs the band hands back (0.1 % of a 10 kb batch, and the long ones among them: queries AND targets of thousands of
     // bases) take tens of ms each in k_ksw_pk<5>.  Behind the extension kernels on the batch's stream they were a tail of their own
     // (10 kb: 38 of 161 ms); with streams they get their own list and start on lane 3 the moment the band kernels are done.
-    const bool ownRedo = nBandL && conc && side->band;
-    KswLaunchPlan LPR;
+    const bool ownRedo = nBandL && conc && sideBand;
     if( nBandL )
     {
         // rows for the largest job of the batch, but no more than leave a full set of waves their scratch: the few larger jobs are handed
@@ -755,6 +752,7 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
     {
         LPR = ksw_plan_launch( SZ.pRedo ? SZ.pRedo : SZ.p, SZ.cigRedo ? SZ.cigRedo : SZ.cig, std::min<u64>( nBandL / 4 + 64, 256 * 8 ), wantWaves, B / 4 );
         LPR.lds = ldsOf( std::min<u64>( SZ.qlen, SZ.cigRedo ? SZ.cigRedo : SZ.qlen ) + 48 );
+        LPR.lane = 3;
     }
     for( int k = 0; k < KSW_CLS_GRP0; k++ )
     {
@@ -765,17 +763,18 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
         const u64 cg = SZ.cigc[ k ] ? SZ.cigc[ k ] : SZ.cig;
         // (the narrow band hands on a few per cent of its jobs: the extension kernels' waves are planned for their own jobs plus a
         // sixteenth of the band's -- more of them would only wait their turn)
-        LP[ k ] = ksw_plan_launch( pk, cg, SZ.cls[ k ] + ( isExt && nBand ? nBand / 16 + 64 : 0 ), wantOf( k ), budgetOf[ k ] );
+        own[ k ] = ksw_plan_launch( pk, cg, SZ.cls[ k ] + ( isExt && nBand ? nBand / 16 + 64 : 0 ), wantOf( k ), budgetOf[ k ] );
         if( isExt )
         {
-            LP[ k ].lds = KSW_EXT_LDS;
+            own[ k ].lds = KSW_EXT_LDS;
+            own[ k ].nMore = nBand ? KSW_NX_BAND_EXT + ( k - KSW_CLS_EXT1 ) : KSW_NONE;
             continue;
         }
         // LDS bytes of the longest query of the class (ksw_q_lds <= round16( qlen ) + 32; qlen + tlen + 2 <= cigc[k])
         const u64 qMaxK = std::min<u64>( SZ.qlen, SZ.cigc[ k ] ? SZ.cigc[ k ] : SZ.qlen ) + 48;
-        LP[ k ].lds = ldsOf( qMaxK );
+        own[ k ].lds = ldsOf( qMaxK );
         const u64 full = std::min<u64>( wantOf( k ), SZ.cls[ k ] );
-        const bool fewWaves = LP[ k ].waves < full && LP[ k ].waves < 256 * 16;
+        const bool fewWaves = own[ k ].waves < full && own[ k ].waves < 256 * 16;
         // The reversed query of a job lives in LDS, sized for the longest job of the LAUNCH: one 49 kb end extension in a
         // class of 10^5 gap fills would leave 3 waves per CU to all of them (this, not the tails, held the exact kernels of the
         // 50 kb workload at a fifth of the issue rate).  Jobs whose query or direction matrix does not leave room for a full
@@ -796,48 +795,40 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
         }
         if( nextBig && ( splitP || splitQ ) )
         {
-            LP[ LP_BIG + k ] = LP[ k ]; // the huge jobs: what the small tier leaves
-            LP[ LP_BIG + k ].tier = 2;
+            big[ k ] = own[ k ]; // the huge jobs: what the small tier leaves
+            big[ k ].jb.tier = 2;
             if( conc ) // their region is a fixed quarter of the budget (a region that follows the largest job of every batch
                        // would be re-allocated -- seconds, device-wide -- whenever a later batch brings a larger one)
-                LP[ LP_BIG + k ].waves = (u32)std::max<u64>( 1, std::min<u64>( std::min<u32>( LP[ LP_BIG + k ].waves, KSW_SIDE_WAVES ),
-                                                                        ( B / 4 ) / std::max<u64>( LP[ LP_BIG + k ].stride, 1 ) ) );
+                big[ k ].waves = (u32)std::max<u64>( 1, std::min<u64>( std::min<u32>( big[ k ].waves, KSW_SIDE_WAVES ), ( B / 4 ) / std::max<u64>( big[ k ].stride, 1 ) ) );
             const u64 cgSmall = splitP ? std::min<u64>( cg, pSmall / 16 + 3 ) : cg;
-            LP[ k ] = ksw_plan_launch( pSmall, cgSmall, SZ.cls[ k ], wantOf( k ), budgetOf[ k ] );
-            LP[ k ].tier = 1;
-            LP[ k ].lds = ldsOf( std::min<u64>( qMaxK, KSW_Q_SPLIT ) );
-            pSplit[ k ] = pSmall;
+            own[ k ] = ksw_plan_launch( pSmall, cgSmall, SZ.cls[ k ], wantOf( k ), budgetOf[ k ] );
+            own[ k ].jb.tier = 1;
+            own[ k ].lds = ldsOf( std::min<u64>( qMaxK, KSW_Q_SPLIT ) );
+            own[ k ].jb.pSplit = big[ k ].jb.pSplit = pSmall;
         }
     }
     if( nExt )
-        for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
-        {
-            // (the band of 120 proves nearly all of its jobs: a quarter of them as waves of the second pass is plenty)
-            LP[ LP_REDO + k ] = ksw_plan_launch( SZ.pRedo ? SZ.pRedo : SZ.p, SZ.cigRedo ? SZ.cigRedo : SZ.cig,
-                                           std::min<u64>( nExt, 256 * 4 ) + std::min<u64>( nBandL / 4, 256 * 12 ), wantWaves, conc ? B / 4 : B );
-            LP[ LP_REDO + k ].lds = ldsOf( std::min<u64>( SZ.qlen, SZ.cigRedo ? SZ.cigRedo : SZ.qlen ) + 48 );
-        }
-    KswPlan plan = ksw_plan( SZ, SZ.cls[ KSW_CLS_LDS ] ? SZ.cls[ KSW_CLS_LDS ] : 1, conc ? B / 4 : B );
-    // scratch regions.  Sequential mode: one region for all launches (+ one for the huge tiers when they have a stream).
-    // Concurrent mode: lane 0 = extension classes, handed-back jobs, LDS kernel; lane 1 = KSW_CLS_PK3; lane 2 = KSW_CLS_PK0 .. PK2;
-    // lane 3 = huge tiers.
-    auto laneOf = [ & ]( int i ) -> int {
-        if( !conc )
-            return i >= LP_BIG && side && side->stream[ 2 ] ? 3 : 0;
-        if( i >= LP_BIG )
-            return 3;
-        if( i == LP_CLS + KSW_CLS_PK3 )
-            return 1;
-        if( i <= LP_CLS + KSW_CLS_PK2 )
-            return 2;
-        return 0;
-    };
-    u64 needLane[ 4 ] = { std::max<u64>( std::max<u64>( SZ.cls[ KSW_CLS_LDS ] ? plan.ws.stride * plan.waves : 0, LG.stride * LG.waves ), LBL.stride * LBL.waves ), 0, 0, 0 };
-    for( int i = 0; i < LP_N; i++ )
-        if( LP[ i ].waves )
-            needLane[ laneOf( i ) ] = std::max<u64>( needLane[ laneOf( i ) ], LP[ i ].stride * LP[ i ].waves );
-    if( ownRedo )
-        needLane[ 3 ] = std::max<u64>( needLane[ 3 ], LPR.stride * LPR.waves );
+    {
+        // (the band of 120 proves nearly all of its jobs: a quarter of them as waves of the second pass is plenty)
+        RD = ksw_plan_launch( SZ.pRedo ? SZ.pRedo : SZ.p, SZ.cigRedo ? SZ.cigRedo : SZ.cig, std::min<u64>( nExt, 256 * 4 ) + std::min<u64>( nBandL / 4, 256 * 12 ),
+                              wantWaves, conc ? B / 4 : B );
+        RD.lds = ldsOf( std::min<u64>( SZ.qlen, SZ.cigRedo ? SZ.cigRedo : SZ.qlen ) + 48 );
+    }
+    if( SZ.cls[ KSW_CLS_LDS ] )
+        LL = ksw_plan( SZ, SZ.cls[ KSW_CLS_LDS ], conc ? B / 4 : B );
+    for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
+        own[ k ].lane = !conc ? 0 : ( k == KSW_CLS_PK3 ? 1 : 2 ), big[ k ].lane = conc || side2 ? 3 : 0;
+    // ---- scratch regions: a lane's region holds the largest of its launches
+    u64 needLane[ 4 ] = { 0, 0, 0, 0 };
+    u32 ldsMax = std::max( RD.lds, LPR.lds );
+    auto need = [ & ]( const KswLaunch& L ) { needLane[ L.lane ] = std::max<u64>( needLane[ L.lane ], L.stride * L.waves ); };
+    for( const KswLaunch* L : { &LL, &LG, &LBL, &LPR, &RD, own + KSW_CLS_EXT1, own + KSW_CLS_EXT2 } )
+        need( *L );
+    for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
+    {
+        need( own[ k ] ), need( big[ k ] );
+        ldsMax = std::max( ldsMax, std::max( own[ k ].lds, big[ k ].lds ) );
+    }
     // the per-wave scratch follows the largest jobs of the batch, which vary a lot from batch to batch for long
     // reads: once it is in the GB range take the whole budget so that later batches never re-allocate mid-step
     if( !conc && needLane[ 0 ] > ( 2ull << 30 ) )
@@ -849,155 +840,178 @@ int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizi
         needLane[ 2 ] = std::max<u64>( needLane[ 2 ], B / 3 );
         needLane[ 3 ] = std::max<u64>( needLane[ 3 ], B / 4 );
     }
-    u64 laneBase[ 4 ], total = 0;
     for( int l = 0; l < 4; l++ )
     {
-        laneBase[ l ] = total;
-        total += al( needLane[ l ] );
+        P.laneBase[ l ] = P.total;
+        P.total += al( needLane[ l ] );
     }
-    if( scratch.reserve( total ) )
-        return 1;
-    u32 ldsMax = LPR.lds;
-    for( int i = 0; i < LP_N; i++ )
-        if( i != LP_CLS + KSW_CLS_EXT1 && i != LP_CLS + KSW_CLS_EXT2 )
-            ldsMax = std::max( ldsMax, LP[ i ].lds );
-    if( ldsMax > 48 * 1024 )
-        for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
-            MA_HIP( hipFuncSetAttribute( (const void*)ksw_pk_kernel<FETCH>( k ), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsMax ) );
-    uint8_t* base = scratch.as<uint8_t>( );
-    u32* redo = lists ? lists + (u64)KSW_N_CLASSES * list_stride : nullptr;
-    u32* redoL = lists ? lists + (u64)( KSW_N_CLASSES + 1 ) * list_stride : nullptr; // (ownRedo: the long jobs the band of 120 handed back)
-    hipStream_t laneStream[ 4 ] = { stream, conc ? side->stream[ 0 ] : stream, conc ? side->stream[ 1 ] : stream,
-                                    side && side->stream[ 2 ] ? side->stream[ 2 ] : stream };
-    bool laneUsed[ 4 ] = { true, false, false, false };
-    for( int i = 0; i < LP_N; i++ )
-        if( LP[ i ].waves && laneStream[ laneOf( i ) ] != stream )
-            laneUsed[ laneOf( i ) ] = true;
+    P.ldsPk = ldsMax > 48 * 1024 ? ldsMax : 0;
+    P.ldsLds = LL.lds > 48 * 1024 ? LL.lds : 0;
+    // ---- the rows, in issue order
+    auto push = [ & ]( const KswLaunch& L ) {
+        if( L.waves == 0 )
+            return;
+        P.laneUsed[ L.lane ] = true;
+        P.launch[ P.n++ ] = L;
+    };
+    // a launch of exact class k over its own list (the class's launch or its huge tier) or over a list of handed-back jobs (second pass)
+    auto pushExact = [ & ]( KswLaunch L, int k, int queue, int list ) {
+        const bool ownList = list == k, redoL = list == KSW_LIST_REDOL;
+        L.family = k == KSW_CLS_LDS ? KSW_FAM_LDS : KSW_FAM_PK, L.inst = L.jb.cls = k, L.queue = queue;
+        L.list = lists ? list : KSW_NONE;
+        L.nDev = redoL ? KSW_NX_N_REDOL : KSW_CT_NREDO;
+        L.jb.n = redoL ? 0u : ( lists ? (u32)SZ.cls[ k ] : nSlots );
+        L.jb.mode = !ownList ? 2 : ( lists ? 0 : 1 );
+        L.jb.pSplit = redoL ? 0 : own[ k ].jb.pSplit;
+        L.jb.qSplit = k == KSW_CLS_LDS ? 0 : KSW_Q_SPLIT; // (k_ksw takes all the jobs of its class)
+        push( L );
+    };
+    // a launch of an extension class over its list, on `waves` waves
+    auto pushExt = [ & ]( KswLaunch L, int family, int inst, int cls, int queue, u64 waves, int out1, int outCtr ) {
+        L.family = family, L.inst = inst, L.list = cls, L.queue = queue, L.out1 = out1, L.outCtr = outCtr;
+        L.jb.n = (u32)SZ.cls[ cls ];
+        L.waves = (u32)std::max<u64>( 1, waves );
+        if( family != KSW_FAM_EXT )
+            L.p_cap = 0; // (only k_ksw_ext takes it: the others' scratch is direction rows alone)
+        push( L );
+    };
+    // longest jobs first: the huge tiers, then the wide classes; the extension kernels' small jobs fill the tails
+    for( int k = KSW_CLS_PK3; k >= KSW_CLS_PK0; k-- )
+        pushExact( big[ k ], k, KSW_CT_BIG + k, k );
+    if( conc )
+        for( int k = KSW_CLS_PK3; k >= KSW_CLS_PK0; k-- )
+            pushExact( own[ k ], k, KSW_NX_CLS + k, k );
+    for( int k = 0; k < 2; k++ ) // the long extensions on the band of 120 first: they are the longest jobs of lane 0
+        if( SZ.cls[ KSW_CLS_BANDL + k ] )
+            pushExt( LBL, KSW_FAM_BAND1, k == 0, KSW_CLS_BANDL + k, KSW_NX_BANDL + k, std::min<u64>( LBL.waves, SZ.cls[ KSW_CLS_BANDL + k ] ),
+                     ownRedo ? KSW_LIST_REDOL : KSW_LIST_REDO, ownRedo ? KSW_NX_N_REDOL : KSW_CT_NREDO );
+    // The jobs handed back are drained by k_ksw_pk alone (these rows and the last four): a long-band job of class KSW_CLS_LDS that is
+    // handed back is run by no second-pass launch -- no row reads KSW_LIST_REDO / REDOL with cls == KSW_CLS_LDS.
     if( ownRedo )
-        laneUsed[ 3 ] = true;
-    const bool forked = laneUsed[ 1 ] || laneUsed[ 2 ] || laneUsed[ 3 ];
+    {
+        P.bandAfter = P.n - 1;
+        for( int k = KSW_CLS_PK3; k >= KSW_CLS_PK0; k-- )
+            pushExact( LPR, k, KSW_NX_REDOL + k, KSW_LIST_REDOL );
+    }
+    // the short extensions, several per wavefront (lane 0 of the streams, like the other extension kernels); longest first
+    for( int k = 0; k < KSW_GRP_LISTS; k++ )
+    {
+        const int cls = KSW_CLS_GRP0 + k;
+        const u64 nk = SZ.cls[ cls ], Gk = k < 2 && SC.grp >= 1000 ? 4u : ( k < 4 ? 2u : 4u ), waves = std::min<u64>( LG.waves, ( nk + Gk - 1 ) / Gk );
+        KswLaunch L = LG;
+        L.out2 = KSW_CLS_EXT2, L.nOut1 = (u32)SZ.cls[ KSW_CLS_EXT1 ], L.nOut2 = (u32)SZ.cls[ KSW_CLS_EXT2 ]; // (the narrow band's)
+        if( nk && k >= 2 )
+            pushExt( LG, KSW_FAM_GRP, cls, cls, KSW_NX_GRP + k, waves, KSW_LIST_REDO, KSW_CT_NREDO );
+        else if( nk && SC.grp >= 1000 ) // (without the narrow band its two lists stay empty)
+            pushExt( L, KSW_FAM_BAND4, k == 0, cls, KSW_NX_GRP + k, waves, KSW_CLS_EXT1, KSW_NX_BAND_EXT );
+    }
+    for( int c = KSW_CLS_EXT1; c <= KSW_CLS_EXT2; c++ ) // k_ksw_ext<1>, k_ksw_ext<2>
+        if( own[ c ].waves )
+            pushExt( own[ c ], KSW_FAM_EXT, c - KSW_CLS_EXT1 + 1, c, KSW_NX_CLS + c, own[ c ].waves, KSW_LIST_REDO, KSW_CT_NREDO );
+    if( !conc )
+        for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
+            pushExact( own[ k ], k, KSW_NX_CLS + k, k );
+    pushExact( LL, KSW_CLS_LDS, KSW_NX_CLS + KSW_CLS_LDS, KSW_CLS_LDS ); // k_ksw (a handed-back job always fits a register kernel)
+    for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
+        pushExact( RD, k, KSW_NX_REDO + k, KSW_LIST_REDO ); // on the batch's stream, behind the extension kernels that fill the list
+    return P;
+}
+
+// the instantiations a launch picks from by a run-time index: exact class k, list k of the wavefront-sharing classes, direction
+template <typename FETCH> auto ksw_pk_kernel( int k ) -> decltype( &k_ksw_pk<FETCH, KSW_S0> )
+{
+    return k == KSW_CLS_PK0 ? k_ksw_pk<FETCH, KSW_S0>
+                            : ( k == KSW_CLS_PK1 ? k_ksw_pk<FETCH, KSW_S1> : ( k == KSW_CLS_PK2 ? k_ksw_pk<FETCH, KSW_S2> : k_ksw_pk<FETCH, KSW_S3> ) );
+}
+template <typename FETCH> auto ksw_grp_kernel( int cls ) -> decltype( &k_ksw_grp<FETCH, 2, 1, true> )
+{
+    return cls == KSW_CLS_GRP2_L ? k_ksw_grp<FETCH, 2, 1, true>
+                                 : ( cls == KSW_CLS_GRP2_R ? k_ksw_grp<FETCH, 2, 1, false> : ( cls == KSW_CLS_GRP4_L ? k_ksw_grp<FETCH, 4, 1, true> : k_ksw_grp<FETCH, 4, 1, false> ) );
+}
+template <typename FETCH, int G> auto ksw_band_kernel( bool left ) -> decltype( &k_ksw_band<FETCH, true, G> )
+{
+    return left ? k_ksw_band<FETCH, true, G> : k_ksw_band<FETCH, false, G>;
+}
+// Launches every class that has jobs.  `next` = KSW_N_NEXT zeroed counters (KSW_NX_*), `nextBig` = KSW_N_NEXT_BIG more (or null).
+// `lists` (device, or null) holds the job slots of class k at lists + k * list_stride, SZ.cls[k] entries, and room for the jobs the
+// kernels hand back at lists + KSW_LIST_REDO * list_stride (counted in *nRedo) and lists + KSW_LIST_REDOL * list_stride; `side`
+// (or null): the streams the classes fork to.
+template <typename FETCH>
+int ksw_run_all( const FETCH& F, const KswScoring& SC, u32 nSlots, const KswSizing& SZ, DevBuf& scratch, unsigned int* next, KswOut O, hipStream_t stream,
+                 u32* lists, u64 list_stride, unsigned int* nRedo, unsigned int* nextBig, const KswSide* side )
+{
+    u64 perCu = 32; // waves per CU of the persistent ksw launches (MA_KSW_WAVES_PER_CU: tuning hook)
+    if( const char* e = getenv( "MA_KSW_WAVES_PER_CU" ) )
+        perCu = (u64)std::max( 1, atoi( e ) );
+    const bool side3 = side && side->ready( );
+    const KswStagePlan P = ksw_plan_stage( SZ, SC, nSlots, lists != nullptr, nextBig != nullptr, side3, side && side->stream[ 2 ], side && side->band,
+                                           ksw_scratch_budget( ), perCu ); // one reading of the hooks per call
+    if( P.n == 0 )
+        return 0;
+    if( scratch.reserve( P.total ) )
+        return 1;
+    if( P.ldsPk )
+        for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
+            MA_HIP( hipFuncSetAttribute( (const void*)ksw_pk_kernel<FETCH>( k ), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.ldsPk ) );
+    if( P.ldsLds )
+        MA_HIP( hipFuncSetAttribute( (const void*)k_ksw<FETCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.ldsLds ) );
+    hipStream_t laneStream[ 4 ] = { stream, side3 ? side->stream[ 0 ] : stream, side3 ? side->stream[ 1 ] : stream,
+                                    side && side->stream[ 2 ] ? side->stream[ 2 ] : stream }; // (lanes 1 and 2 have rows only when there are lists, too)
+    const bool forked = P.laneUsed[ 1 ] || P.laneUsed[ 2 ] || P.laneUsed[ 3 ];
     if( forked )
     {
         MA_HIP( hipEventRecord( side->fork, stream ) );
         for( int l = 1; l < 4; l++ )
-            if( laneUsed[ l ] )
+            if( P.laneUsed[ l ] )
                 MA_HIP( hipStreamWaitEvent( laneStream[ l ], side->fork, 0 ) );
     }
-    // pass 0: the classes' own jobs; pass 1: whatever the extension kernel handed back (usually nothing); pass 2: the huge
-    // tier of a class that was split
-    auto launchPk = [ & ]( int pass, int k ) {
-        const int i = pass == 0 ? LP_CLS + k : ( pass == 1 ? LP_REDO + k : LP_BIG + k );
-        const KswLaunchPlan& L = LP[ i ];
-        if( L.waves == 0 )
-            return;
-        KswJobs JB;
-        JB.list = pass == 1 ? redo : ( lists ? lists + (u64)k * list_stride : nullptr );
-        JB.n = lists ? (u32)SZ.cls[ k ] : nSlots;
-        JB.nDev = nRedo;
-        JB.mode = pass == 1 ? 2 : ( lists ? 0 : 1 );
-        JB.cls = k;
-        JB.tier = pass == 1 ? 0 : L.tier;
-        JB.pSplit = pSplit[ k ];
-        JB.qSplit = KSW_Q_SPLIT;
-        unsigned int* nx = pass == 0 ? next + KSW_NX_CLS + k : ( pass == 1 ? next + KSW_NX_REDO + k : nextBig + k );
-        hipStream_t st = laneStream[ laneOf( i ) ];
-        uint8_t* sbase = base + laneBase[ laneOf( i ) ];
-        hipLaunchKernelGGL( ksw_pk_kernel<FETCH>( k ), dim3( L.waves ), dim3( 64 ), L.lds, st, F, SC, JB, nx, sbase, L.stride, L.p_cap, L.lds, O );
-    };
-    // longest jobs first: the huge tiers, then the wide classes; the extension kernels' small jobs fill the tails
-    for( int k = KSW_CLS_PK3; k >= KSW_CLS_PK0; k-- )
-        launchPk( 2, k );
-    if( conc )
-        for( int k = KSW_CLS_PK3; k >= KSW_CLS_PK0; k-- )
-            launchPk( 0, k );
-    if( nBandL ) // the long extensions on the band of 120 first: they are the longest jobs of lane 0
-        for( int k = 0; k < 2; k++ )
-        {
-            const u32 nk = (u32)SZ.cls[ KSW_CLS_BANDL + k ];
-            if( nk == 0 )
-                continue;
-            const u32* lk = lists + (u64)( KSW_CLS_BANDL + k ) * list_stride;
-            const u32 waves = (u32)std::max<u64>( 1, std::min<u64>( LBL.waves, nk ) );
-            uint8_t* sb = base + laneBase[ 0 ];
-            hipLaunchKernelGGL( ( ksw_band_kernel<FETCH, 1>( k == 0 ) ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + KSW_NX_BANDL + k, sb, LBL.stride, O,
-                                ownRedo ? redoL : redo, 0u, (u32*)nullptr, 0u, ownRedo ? next + KSW_NX_N_REDOL : nRedo );
-        }
-    if( ownRedo )
+    auto listAt = [ & ]( int i ) -> u32* { return lists && i != KSW_NONE ? lists + (u64)i * list_stride : nullptr; };
+    auto ctrAt = [ & ]( int w ) -> unsigned int* { return w == KSW_NONE ? nullptr : ( w < KSW_CT_BIG ? next + w : ( w < KSW_CT_NREDO ? nextBig + ( w - KSW_CT_BIG ) : nRedo ) ); };
+    for( int i = 0; i < P.n; i++ )
     {
-        MA_HIP( hipEventRecord( side->band, stream ) );
-        MA_HIP( hipStreamWaitEvent( laneStream[ 3 ], side->band, 0 ) );
-        for( int k = KSW_CLS_PK3; k >= KSW_CLS_PK0; k-- )
+        const KswLaunch& L = P.launch[ i ];
+        const dim3 grid( L.waves ), block( 64 );
+        hipStream_t st = laneStream[ L.lane ];
+        uint8_t* sb = scratch.as<uint8_t>( ) + P.laneBase[ L.lane ];
+        unsigned int* const queue = ctrAt( L.queue );
+        KswJobs JB = L.jb;
+        JB.list = listAt( L.list );
+        JB.nDev = ctrAt( L.nDev );
+        KswWaveScratch WS = L.ws;
+        WS.base = sb;
+        switch( L.family )
         {
-            KswJobs JB;
-            JB.list = redoL;
-            JB.n = 0;
-            JB.nDev = next + KSW_NX_N_REDOL;
-            JB.mode = 2;
-            JB.cls = k;
-            JB.tier = 0;
-            JB.pSplit = 0;
-            JB.qSplit = KSW_Q_SPLIT;
-            uint8_t* sb = base + laneBase[ 3 ];
-            hipLaunchKernelGGL( ksw_pk_kernel<FETCH>( k ), dim3( LPR.waves ), dim3( 64 ), LPR.lds, laneStream[ 3 ], F, SC, JB, next + KSW_NX_REDOL + k, sb,
-                                LPR.stride, LPR.p_cap, LPR.lds, O );
+        case KSW_FAM_PK:
+            hipLaunchKernelGGL( ksw_pk_kernel<FETCH>( L.inst ), grid, block, L.lds, st, F, SC, JB, queue, sb, L.stride, L.p_cap, L.lds, O );
+            break;
+        case KSW_FAM_EXT:
+            hipLaunchKernelGGL( ( L.inst == 1 ? k_ksw_ext<FETCH, 1> : k_ksw_ext<FETCH, 2> ), grid, block, L.lds, st, F, SC, JB.list, JB.n, queue, sb, L.stride, L.p_cap,
+                                L.lds, O, listAt( L.out1 ), ctrAt( L.outCtr ), ctrAt( L.nMore ) );
+            break;
+        case KSW_FAM_GRP:
+            hipLaunchKernelGGL( ksw_grp_kernel<FETCH>( L.inst ), grid, block, 0, st, F, SC, JB.list, JB.n, queue, sb, L.stride, O, listAt( L.out1 ), ctrAt( L.outCtr ) );
+            break;
+        case KSW_FAM_BAND4:
+            hipLaunchKernelGGL( ( ksw_band_kernel<FETCH, 4>( L.inst != 0 ) ), grid, block, 0, st, F, SC, JB.list, JB.n, queue, sb, L.stride, O, listAt( L.out1 ), L.nOut1,
+                                listAt( L.out2 ), L.nOut2, ctrAt( L.outCtr ) );
+            break;
+        case KSW_FAM_BAND1:
+            hipLaunchKernelGGL( ( ksw_band_kernel<FETCH, 1>( L.inst != 0 ) ), grid, block, 0, st, F, SC, JB.list, JB.n, queue, sb, L.stride, O, listAt( L.out1 ), L.nOut1,
+                                listAt( L.out2 ), L.nOut2, ctrAt( L.outCtr ) );
+            break;
+        case KSW_FAM_LDS:
+            hipLaunchKernelGGL( k_ksw<FETCH>, grid, block, L.lds, st, F, SC, JB, queue, WS, L.lds, O );
+            break;
+        }
+        if( i == P.bandAfter )
+        {
+            MA_HIP( hipEventRecord( side->band, stream ) );
+            MA_HIP( hipStreamWaitEvent( laneStream[ 3 ], side->band, 0 ) );
         }
     }
-    if( nGrp ) // the short extensions, several per wavefront (lane 0 of the streams, like the other extension kernels); longest first
-        for( int k = 0; k < KSW_GRP_LISTS; k++ )
-        {
-            const u32 nk = (u32)SZ.cls[ KSW_CLS_GRP0 + k ];
-            if( nk == 0 )
-                continue;
-            const u32* lk = lists + (u64)( KSW_CLS_GRP0 + k ) * list_stride;
-            const u32 Gk = k < 2 && SC.grp >= 1000 ? 4u : ( k < 4 ? 2u : 4u );
-            const u32 waves = (u32)std::max<u64>( 1, std::min<u64>( LG.waves, ( nk + Gk - 1 ) / Gk ) );
-            uint8_t* sb = base + laneBase[ 0 ];
-            u32* const ext1 = lists + (u64)KSW_CLS_EXT1 * list_stride;
-            u32* const ext2 = lists + (u64)KSW_CLS_EXT2 * list_stride;
-            if( k >= 2 )
-                hipLaunchKernelGGL( ksw_grp_kernel<FETCH>( KSW_CLS_GRP0 + k ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + KSW_NX_GRP + k, sb,
-                                    LG.stride, O, redo, nRedo );
-            else if( SC.grp >= 1000 ) // (without the narrow band its two lists stay empty)
-                hipLaunchKernelGGL( ( ksw_band_kernel<FETCH, 4>( k == 0 ) ), dim3( waves ), dim3( 64 ), 0, stream, F, SC, lk, nk, next + KSW_NX_GRP + k, sb, LG.stride, O,
-                                    ext1, (u32)SZ.cls[ KSW_CLS_EXT1 ], ext2, (u32)SZ.cls[ KSW_CLS_EXT2 ], next + KSW_NX_BAND_EXT );
-        }
-    for( int e = 0; e < 2; e++ ) // k_ksw_ext<1>, k_ksw_ext<2>
-    {
-        const int c = KSW_CLS_EXT1 + e;
-        if( !( SZ.cls[ c ] || nBand ) )
-            continue;
-        const auto kernel = e == 0 ? k_ksw_ext<FETCH, 1> : k_ksw_ext<FETCH, 2>;
-        hipLaunchKernelGGL( kernel, dim3( LP[ LP_CLS + c ].waves ), dim3( 64 ), KSW_EXT_LDS, stream, F, SC, lists + (u64)c * list_stride, (u32)SZ.cls[ c ],
-                            next + KSW_NX_CLS + c, base + laneBase[ 0 ], LP[ LP_CLS + c ].stride, LP[ LP_CLS + c ].p_cap, KSW_EXT_LDS, O, redo, nRedo,
-                            nBand ? next + KSW_NX_BAND_EXT + e : nullptr );
-    }
-    if( !conc )
-        for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
-            launchPk( 0, k );
-    if( SZ.cls[ KSW_CLS_LDS ] ) // a handed-back job always fits a register kernel
-    {
-        KswJobs JB;
-        JB.list = lists ? lists + (u64)KSW_CLS_LDS * list_stride : nullptr;
-        JB.n = lists ? (u32)SZ.cls[ KSW_CLS_LDS ] : nSlots;
-        JB.nDev = nRedo;
-        JB.mode = lists ? 0 : 1;
-        JB.cls = KSW_CLS_LDS;
-        JB.tier = 0;
-        JB.pSplit = 0;
-        JB.qSplit = 0;
-        plan.ws.base = base + laneBase[ 0 ];
-        if( plan.lds_bytes > 48 * 1024 )
-            MA_HIP( hipFuncSetAttribute( (const void*)k_ksw<FETCH>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)plan.lds_bytes ) );
-        hipLaunchKernelGGL( k_ksw<FETCH>, dim3( plan.waves ), dim3( 64 ), plan.lds_bytes, stream, F, SC, JB, next + KSW_NX_CLS + KSW_CLS_LDS,
-                            plan.ws, plan.lds_bytes, O );
-    }
-    if( nExt )
-        for( int k = KSW_CLS_PK0; k <= KSW_CLS_PK3; k++ )
-            launchPk( 1, k ); // on the batch's stream, behind the extension kernels that fill the list
     if( forked )
         for( int l = 1; l < 4; l++ )
-            if( laneUsed[ l ] )
+            if( P.laneUsed[ l ] )
             {
                 MA_HIP( hipEventRecord( side->join[ l - 1 ], laneStream[ l ] ) );
                 MA_HIP( hipStreamWaitEvent( stream, side->join[ l - 1 ], 0 ) );

@@ -153,7 +153,7 @@ static int ksw_bytes_launch( const FETCH& F, const KswScoring& SC, uint64_t n, c
     O.cig_words = nullptr;
     O.cig_chunk = 0; // dense pool: cigar_off[n] is the total
     return ksw_run_all( F, SC, (u32)n, S, scratch, (unsigned int*)( ctr + PC_NEXT ), O, stream, lists, n, (unsigned int*)( ctr + PC_N_REDO ),
-                        (unsigned int*)( ctr + PC_NEXT_BIG ) );
+                        (unsigned int*)( ctr + PC_NEXT_BIG ), nullptr );
 }
 
 // ma_ksw_batch's kernels (every ez field, no early stop) over jobs that are in device memory already: the DP of the pipeline's
